@@ -24,8 +24,13 @@ barrier + device synchronisation on both sides, MAX over ranks per region; `valu
 Prints ONE JSON line (rank 0). Extra objects: `roofline` (the dominant kernel: algorithmic FLOP per launch / its
 average in-chain duration, measured live with the dispatch's own start/stop events), `roofline_step` (whole
 update vs the FP32 peak, the binding roofline per SURVEY.md section 8d), `roofline_hbm` (the HBM view north_star
-asks for), `kernels`, `cpu_baseline` (the unmodified reference when it is mounted, else the oracle port; 1M-row
-host buffer, 4 threads and all cores), `alt` (the other hidden-layer setting of SURVEY.md D1).
+asks for), `kernels`, `cpu_baseline` (the oracle port of the reference arithmetic; 4 threads and all cores), `alt` (the other
+hidden-layer setting of SURVEY.md D1).
+
+`--dump-outputs DIR` writes, after the headline configuration's timed regions and before anything else runs on its
+engine, what a caller of the timed path holds after the last timed update: DIR/stats.npy (the 14 tb_info statistics,
+float64) and DIR/online.npy, DIR/target.npy (the parameter arenas, float32). Every input is seeded, so the same
+arguments give the same arrays from run to run.
 """
 import argparse
 import json
@@ -39,7 +44,7 @@ for p in (ROOT, PKG):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-FP32_PEAK_TFLOPS = 157.3  # /opt/skills/guides/MI355X_MICROARCH.md (vector == f32 MFMA)
+FP32_PEAK_TFLOPS = 157.3  # MI355X spec (vector == f32 MFMA)
 HBM_PEAK_GBS = 8000.0     # spec; 6290 measured float4 copy
 
 O, A, B = 376, 17, 256
@@ -283,42 +288,23 @@ def _cpu_fill(bufs, n_rows):
 
 
 def cpu_baseline_child(hidden, n_rows=CPU_ROWS, warm=50, timed=300, budget_s=12.0):
-    """The reference CPU path beside the GPU number (BASELINE.md section 3 / SURVEY.md 8d): the UNMODIFIED reference
-    (`create_alg` -> DSAC_V2, `create_buffer` -> ReplayBuffer, imported in place through oracle/ref_loader.py) when
-    /root/reference is mounted -- kind "reference"; otherwise (the GPU box) the oracle port of the same arithmetic,
-    pinned bit-exact against it in tests/test_oracle_vs_reference.py -- kind "port". Timed loop =
+    """The reference CPU path beside the GPU number (BASELINE.md section 3 / SURVEY.md 8d): the oracle port of the
+    reference arithmetic, pinned to the reference's recorded vectors in tests/test_oracle_vs_reference.py -- kind "port". Timed loop =
     sample_batch(B) + local_update, `warm` warm-up + up to `timed` updates, every loop bounded by budget_s, at 4 torch
     threads (the reference's own setting, utils/init_args.py:14) and at os.cpu_count() threads (skipped when one
     update at that thread count takes longer than 2 s: an over-subscribed container)."""
     import numpy as np
     import torch
-    from oracle import ref_loader
+    from oracle.dsact_oracle import DsactOracle, ReplayOracle, default_config, draw_noise
 
-    use_ref = ref_loader.reference_available()
-    if use_ref:
-        ref_loader.import_reference()
-        from utils.initialization import create_alg, create_buffer   # the reference's own factories
+    torch.manual_seed(0)
+    orc = DsactOracle(default_config(O, A, hidden))
+    buf = ReplayOracle(O, A, n_rows)
+    _cpu_fill(buf.buf, n_rows)
+    buf.size = n_rows
 
-        kw = ref_loader.reference_kwargs(O, A, tuple(hidden), buffer_max_size=n_rows, replay_batch_size=B)
-        torch.manual_seed(0)
-        alg = create_alg(**kw)
-        buf = create_buffer(**kw)
-        _cpu_fill(buf.buf, n_rows)
-        buf.size, buf.ptr = n_rows, 0
-
-        def step(it):
-            alg.local_update(buf.sample_batch(B), it)
-    else:
-        from oracle.dsact_oracle import DsactOracle, ReplayOracle, default_config, draw_noise
-
-        torch.manual_seed(0)
-        orc = DsactOracle(default_config(O, A, hidden))
-        buf = ReplayOracle(O, A, n_rows)
-        _cpu_fill(buf.buf, n_rows)
-        buf.size = n_rows
-
-        def step(it):
-            orc.local_update(buf.sample_batch(B), draw_noise(B, A), it)
+    def step(it):
+        orc.local_update(buf.sample_batch(B), draw_noise(B, A), it)
     legs = {}
     ncpu = os.cpu_count() or 4
     it = 0
@@ -372,13 +358,12 @@ def cpu_baseline_child(hidden, n_rows=CPU_ROWS, warm=50, timed=300, budget_s=12.
         legs[threads] = {"value": sorted(reps)[1], "updates": n_all, "seconds": dt_all, "warmup": nw,
                          "repeats": [round(v, 2) for v in reps], "min": min(reps), "max": max(reps)}
     v4 = legs[4]
-    who = ("unmodified reference (create_alg -> DSAC_V2, create_buffer -> ReplayBuffer)" if use_ref else
-           "oracle port of the reference arithmetic (the reference is not mounted on this box)")
+    who = "oracle port of the reference arithmetic"
     try:
         e2e = e2e_cpu(hidden)
     except Exception as ex:   # informational leg
         e2e = {"error": repr(ex)}
-    return {"value": v4.get("value"), "unit": "steps/s", "cores": 4, "kind": "reference" if use_ref else "port",
+    return {"value": v4.get("value"), "unit": "steps/s", "cores": 4, "kind": "port",
             "repeats": v4.get("repeats"), "min": v4.get("min"), "max": v4.get("max"),
             "all_cores": dict(legs[ncpu], cores=ncpu), "e2e": e2e,
             "sample": "%s: sample_batch(256) + local_update, hidden %s, %d-row host buffer (SURVEY 8d recipe; 1M rows = minutes of first-touch page faults in this sandbox), %s warm-up + "
@@ -544,14 +529,12 @@ def e2e_gpu_grouped(hidden, device, interval=8, iters=1600, warm=160):
 
 
 def e2e_cpu(hidden, budget_s=10.0):
-    """the same loop on the host cores: the UNMODIFIED reference trainer (its own factories, CPU nets) where
-    /root/reference is mounted -- kind "reference"; elsewhere our loop around the oracle port of the update and a CPU
-    container for acting -- kind "port". A handful of iterations: one CPU update is ~20 ms."""
+    """the same loop on the host cores: our loop around the oracle port of the update and a CPU container for acting --
+    kind "port". A handful of iterations: one CPU update is ~20 ms."""
     import tempfile
 
     import numpy as np
     import torch
-    from oracle import ref_loader
 
     torch.set_num_threads(4)
     kw = e2e_kwargs(hidden, B, algorithm="DSAC_V2", buffer_name="replay_buffer", use_gpu=False, enable_cuda=False,
@@ -559,49 +542,31 @@ def e2e_cpu(hidden, budget_s=10.0):
     d = tempfile.mkdtemp()
     os.makedirs(os.path.join(d, "apprfunc"), exist_ok=True)
     kw["save_folder"] = d
-    if ref_loader.reference_available():
-        from oracle.trainer_trajectory import install_writer_stub
+    import plugin
+    from dsac_v2_hip import ApproxContainer
+    from oracle.dsact_oracle import DsactOracle, ReplayOracle, default_config, draw_noise
 
-        ref_loader.import_reference()
-        install_writer_stub()
-        from training.evaluator import create_evaluator
-        from training.off_sampler import create_sampler
-        from training.trainer import create_trainer
-        from utils.initialization import create_alg, create_buffer
+    torch.manual_seed(0)
+    orc = DsactOracle(default_config(O, A, hidden))
 
-        torch.manual_seed(0)
-        alg = create_alg(**kw)
-        sampler, buf = create_sampler(**kw), create_buffer(**kw)
-        ev = create_evaluator(**dict(kw, max_episode_steps=20))
-        trainer = create_trainer(alg, sampler, buf, ev, **kw)
-        trainer.iteration = 1          # iteration 0 would evaluate and checkpoint
-        kind = "reference"
-    else:
-        import plugin
-        from dsac_v2_hip import ApproxContainer
-        from oracle.dsact_oracle import DsactOracle, ReplayOracle, default_config, draw_noise
+    class PortAlg:
+        networks = ApproxContainer(**dict(kw, algorithm="DSAC_V2_HIP"))
 
-        torch.manual_seed(0)
-        orc = DsactOracle(default_config(O, A, hidden))
+        def local_update(self, data, it):
+            return orc.local_update(data, draw_noise(B, A), it)
 
-        class PortAlg:
-            networks = ApproxContainer(**dict(kw, algorithm="DSAC_V2_HIP"))
+    class PortBuffer:
+        r = ReplayOracle(O, A, kw["buffer_max_size"])
+        size = property(lambda self: self.r.size)
+        add_batch = lambda self, s: self.r.add_batch(s)
+        sample_batch = lambda self, n: self.r.sample_batch(n)
+        __get_RAM__ = lambda self: 0.0
 
-            def local_update(self, data, it):
-                return orc.local_update(data, draw_noise(B, A), it)
-
-        class PortBuffer:
-            r = ReplayOracle(O, A, kw["buffer_max_size"])
-            size = property(lambda self: self.r.size)
-            add_batch = lambda self, s: self.r.add_batch(s)
-            sample_batch = lambda self, n: self.r.sample_batch(n)
-            __get_RAM__ = lambda self: 0.0
-
-        alg, buf = PortAlg(), PortBuffer()
-        sampler = plugin.create_sampler(**dict(kw, algorithm="DSAC_V2_HIP"))
-        trainer = plugin.create_trainer(alg, sampler, buf, None, **dict(kw, save_folder=None))
-        trainer.iteration = 1
-        kind = "port"
+    alg, buf = PortAlg(), PortBuffer()
+    sampler = plugin.create_sampler(**dict(kw, algorithm="DSAC_V2_HIP"))
+    trainer = plugin.create_trainer(alg, sampler, buf, None, **dict(kw, save_folder=None))
+    trainer.iteration = 1
+    kind = "port"
     t0 = time.perf_counter()
     trainer.step(); trainer.iteration += 1
     one = time.perf_counter() - t0
@@ -876,6 +841,32 @@ def profile_kernels_pipe(e, first_it, n_steps, reps=10, skip=2):
     return [(n, acc[n] / cnt[n], blocks[n]) for n in order], per_update
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(e, stats, out_dir):
+    """--dump-outputs DIR: what a caller of the timed path holds after its last update -- the 14 tb_info statistics
+    (float64) and the online / target parameter arenas (float32, arena order). An arena that would take the total past
+    DUMP_BYTES is replaced by a fixed sample: the elements at the sorted indices np.random.default_rng(0).choice draws.
+    Inputs (nets, ring, index table, device noise) are seeded, so the same arguments give the same arrays on every run."""
+    import numpy as np
+    from dsact.engine import STAT_KEYS
+
+    os.makedirs(out_dir, exist_ok=True)
+    e.sync()
+    arrays = {"stats": np.array([stats[k] for k in STAT_KEYS], np.float64)}
+    arenas = {"online": e.online, "target": e.target}
+    budget = (DUMP_BYTES - 64 * 1024) // len(arenas)   # (64 KB reserved for the statistics and the .npy headers)
+    for name, t in arenas.items():
+        a = t.detach().cpu().numpy().astype(np.float32)
+        if a.nbytes > budget:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, budget // 4, replace=False))]
+        arrays[name] = a
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def self_spawn(args):
     """`python bench.py --gpus N` without a torch.distributed environment: re-execute under torch.distributed.run with N
     ranks on this node. Never measures fewer GPUs than were asked for."""
@@ -917,7 +908,11 @@ def main():
                     help="launcher check without GPUs: the ranks rendezvous over gloo, all-reduce one tensor and rank 0 prints the line")
     ap.add_argument("--cpu-baseline-only", action="store_true", help="internal: print the cpu_baseline object and exit")
     ap.add_argument("--dp-eager", action="store_true", help="data-parallel leg through torch.distributed eagerly instead of the graph-captured native RCCL path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed regions, write the last update's tb_info statistics and parameter arenas as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.dump_outputs and args.cnn_only:
+        ap.error("--dump-outputs covers the headline workload; it cannot be combined with --cnn-only")
     if args.headline_only:
         args.no_alt = args.no_cpu_baseline = True
     steps, warmup = int(args.steps), int(args.warmup)
@@ -1008,6 +1003,7 @@ def main():
     if use_dp and getattr(dp, "native", False) and not getattr(measure, "dp_graph", True):
         dp_mode = "EAGER launches + ncclAllReduce on the library-owned RCCL communicator (the hipGraph capture of the data-parallel update FAILED on this runtime: see stderr)"
     stats = e.read_stats()
+    dumped = dump_outputs(e, stats, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     finite = all(v == v and abs(v) < 1e30 for v in stats.values())
     updates_per_s = steps / wall
     value = updates_per_s * world  # batch-B gradient-step equivalents per second over the whole job
@@ -1038,6 +1034,8 @@ def main():
         "regions_ms": [round(1000.0 * r, 4) for r in regions],
         "finite_stats": finite,
     }
+    if dumped:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "after_iteration": warmup + steps * len(regions) - 1}
     if rank == 0:
         per_gpu_steps = updates_per_s
         out["roofline_step"] = {

@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE ONLY -- CPU restatement (torch fp32) of the DSAC-T off-policy update.
 
 This file is the *oracle* for the MI355X-native hot path. It restates, op for op, what the
-reference (Jingliang-Duan/DSAC-v2, mounted read-only at /root/reference) computes in
+reference (Jingliang-Duan/DSAC-v2) computes in
 
     dsac_v2.py:150-206   DSAC_V2.__compute_gradient
     dsac_v2.py:208-216   __q_evaluate
@@ -14,7 +14,7 @@ reference (Jingliang-Duan/DSAC-v2, mounted read-only at /root/reference) compute
     training/replay_buffer.py:58-90                ring write + uniform index draw + gather
 
 Pinning: `tests/test_oracle_vs_reference.py` runs this restatement next to the unmodified
-reference (imported through oracle/ref_loader.py, only possible where /root/reference is mounted)
+reference (imported through oracle/ref_loader.py from a checkout named by DSACT_REFERENCE_ROOT)
 on the same seeded nets / minibatch / torch RNG stream and requires equality of every loss, stat,
 gradient and post-update parameter; `oracle/make_golden.py` stores reference outputs as fixtures
 under tests/golden/ so the same pin holds on the GPU box where the reference is absent.

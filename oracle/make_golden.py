@@ -1,10 +1,10 @@
 """TEST INFRASTRUCTURE ONLY -- generates tests/golden/*.npz by running the UNMODIFIED reference
-(/root/reference, imported through oracle/ref_loader.py) in this container.
+(a checkout named by DSACT_REFERENCE_ROOT, imported through oracle/ref_loader.py).
 
     python oracle/make_golden.py
 
 The fixtures are small (tiny nets) so they can be committed; they pin oracle/dsact_oracle.py to the
-reference on boxes where /root/reference is absent (the GPU box). Each file records the torch / numpy
+reference wherever the reference is absent. Each file records the torch / numpy
 versions the reference ran under.
 
 What is stored per case (`step_<name>.npz`):

@@ -1,15 +1,13 @@
 """TEST INFRASTRUCTURE ONLY -- loader for the *unmodified* reference (Jingliang-Duan/DSAC-v2).
 
-Imports `/root/reference/dsac_v2.py` (and friends) in THIS container, where the reference is
-mounted read-only, by injecting stub modules for the two packages the reference imports at
-module scope but that are not installed here (`gym`, `tensorboard`).
-Nothing under /root/reference is copied or modified.
+Imports `dsac_v2.py` (and friends) from a reference checkout named by the DSACT_REFERENCE_ROOT
+environment variable, by injecting stub modules for the two packages the reference imports at
+module scope but that may not be installed (`gym`, `tensorboard`).
+Nothing in the reference checkout is copied or modified.
 
-Used for two things only:
-  * `oracle/make_golden.py` -- generate golden input/output vectors committed under tests/golden/
-  * `tests/test_oracle_vs_reference.py` -- pin the restatement in `oracle/dsact_oracle.py`
-    against the live reference (skipped automatically where /root/reference is absent,
-    e.g. on the GPU box).
+Used only to generate the vectors committed under tests/golden/ (`oracle/make_golden.py`,
+`oracle/reference_vectors.py`, `oracle/trainer_trajectory.py`); the tests compare against those
+files and never need the reference.
 
 Never imported by the product (`dsac-v2_amd/`), `bench.py` or `__graft_entry__.py`.
 """
@@ -17,11 +15,11 @@ import os
 import sys
 import types
 
-REFERENCE_ROOT = os.environ.get("DSACT_REFERENCE_ROOT", "/root/reference")
+REFERENCE_ROOT = os.environ.get("DSACT_REFERENCE_ROOT", "")
 
 
 def reference_available() -> bool:
-    return os.path.isfile(os.path.join(REFERENCE_ROOT, "dsac_v2.py"))
+    return bool(REFERENCE_ROOT) and os.path.isfile(os.path.join(REFERENCE_ROOT, "dsac_v2.py"))
 
 
 def _stub(name):
@@ -102,7 +100,7 @@ def install_stubs():
 def import_reference():
     """Returns the reference's `dsac_v2` module (unmodified code, run in place)."""
     if not reference_available():
-        raise RuntimeError("reference not mounted at %s" % REFERENCE_ROOT)
+        raise RuntimeError("no reference checkout: set DSACT_REFERENCE_ROOT (now %r)" % REFERENCE_ROOT)
     install_stubs()
     if REFERENCE_ROOT not in sys.path:
         sys.path.insert(0, REFERENCE_ROOT)

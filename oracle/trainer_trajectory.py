@@ -3,7 +3,7 @@
 `run_reference()` drives the reference's own `create_env -> init_args -> create_alg -> create_sampler -> create_buffer
 -> create_evaluator -> create_trainer -> train()` (example_train/main.py:156-170, training/trainer.py:15-158) in place,
 on CPU, through the gym / tensorboard stubs of oracle/ref_loader.py and the synthetic Pendulum of tests/envs, and
-records everything observable about the loop from OUTSIDE the reference's code (nothing under /root/reference is edited;
+records everything observable about the loop from OUTSIDE the reference's code (nothing in the reference checkout is edited;
 the hooks wrap `np.random.randint`, `torch.save`, the stub `SummaryWriter` and two bound methods of the objects the
 reference's factories returned):
 

@@ -1,5 +1,5 @@
 """The oracle restatement vs the golden vectors generated from the unmodified reference
-(oracle/make_golden.py). Runs anywhere (no GPU, no /root/reference needed)."""
+(oracle/make_golden.py). Runs anywhere (no GPU, no reference checkout needed)."""
 import json
 import os
 

@@ -8,6 +8,7 @@ import torch
 
 from dsact.layout import ArenaLayout
 from oracle import ref_loader
+from oracle import reference_vectors as rv
 from oracle.dsact_oracle import DsactOracle, default_config
 
 
@@ -47,24 +48,22 @@ def test_layout_of_the_separated_std_type():
         assert torch.equal(torch.as_strided(fp, shape, strides, off), orc.state_dict()["policy." + name]), name
 
 
-@pytest.mark.skipif(not ref_loader.reference_available(), reason="reference not mounted")
 def test_container_with_separated_std_matches_the_reference_module():
-    """same seed -> same initial state_dict (keys, order, values); forward of the stand-alone CPU module == reference's"""
+    """same seed -> same initial state_dict (keys, order, values) as the reference's container; forward of the stand-alone
+    CPU module == the reference's (tests/golden/oracle_vs_reference.npz, oracle/reference_vectors.py::container_case)"""
     from dsac_v2_hip import ApproxContainer
 
-    ref = ref_loader.import_reference()
-    O, A, hid = 24, 6, (64, 64)
-    kw = ref_loader.reference_kwargs(O, A, hid, policy_std_type="mlp_separated")
-    torch.manual_seed(3)
-    theirs = ref.ApproxContainer(**kw)
-    torch.manual_seed(3)
-    ours = ApproxContainer(**kw)
-    sd, osd = theirs.state_dict(), ours.state_dict()
-    assert list(sd.keys()) == list(osd.keys())
-    assert all(torch.equal(sd[k], osd[k]) for k in sd)
-    assert [n for n, _ in theirs.policy.named_parameters()] == [n for n, _ in ours.policy.named_parameters()]
-    obs = torch.randn(5, O)
-    assert torch.equal(theirs.policy(obs), ours.policy(obs))
+    gold = rv.load()
+    want = lambda k: gold("container:mlp_separated", k)
+    kw = ref_loader.reference_kwargs(*rv.CONTAINER_SHAPE, policy_std_type="mlp_separated")
+    got = rv.container_case(ApproxContainer, "mlp_separated", kw)
+    assert list(got["init/keys"]) == [str(k) for k in want("init/keys")]
+    assert list(got["init/shapes"]) == [str(k) for k in want("init/shapes")]
+    np.testing.assert_array_equal(got["init/sample"], want("init/sample"))
+    np.testing.assert_array_equal(got["init/sum"], want("init/sum"))
+    assert list(got["names"]) == [str(n) for n in want("names")]
+    # same torch build on the same kind of host => bit-exact; elsewhere the last ulps may differ
+    np.testing.assert_allclose(got["policy_out"], want("policy_out"), rtol=1e-6, atol=1e-7)
 
 
 def test_unsupported_combinations_are_refused():

@@ -1,10 +1,10 @@
 """Row a4 (OffSerialTrainer.step / train, training/trainer.py:60-152): the training LOOP against the unmodified reference.
 
-  * CPU, where /root/reference is mounted: the reference's own algorithm and replay buffer are plugged into
-    HipOffSerialTrainer + HipOffSampler + HipEvaluator and the run is compared with the reference's loop driven by its
-    own factories (oracle/trainer_trajectory.py::run_reference) -- same seed, same env. With the arithmetic identical
-    on both sides the loop logic must agree EXACTLY: replay indices, ring size/ptr, the ordered (tag, step, value) list
-    of every scalar written, checkpoint file names and their order, evaluation returns, every update's tb_info.
+  * CPU: the reference's algorithm and replay buffer, restated (OracleAlg / OracleBuffer: the oracle update and ring), are
+    plugged into HipOffSerialTrainer + HipOffSampler + HipEvaluator and the run is compared with the trajectory the
+    reference's own loop recorded (oracle/trainer_trajectory.py::run_reference, tests/golden/trainer_trajectory*.json) --
+    same seed, same env. The loop logic must agree EXACTLY: replay indices, ring size/ptr, the ordered (tag, step) list of
+    every scalar written, checkpoint file names and their order, evaluation iterations; the numbers to a 1e-5 gate.
   * `-m gpu`: the whole HIP stack (DSAC_V2_HIP + HipReplayBuffer + HIP acting forward, strict_rng) against the committed
     trajectory tests/golden/trainer_trajectory.json the reference produced: indices / cadence / file names exactly,
     statistics and evaluation returns at the parity gates of DESIGN section 5.
@@ -18,9 +18,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import ref_loader
-from oracle.trainer_trajectory import (ENVS, GOLDEN, TIME_TAGS, TRAINER_CASE, VARIANTS, Hooks, run_reference, tb_floats, variant_case,
-                                       variant_golden)
+from oracle.trainer_trajectory import ENVS, GOLDEN, TIME_TAGS, VARIANTS, Hooks, tb_floats, variant_case, variant_golden
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.join(os.path.dirname(HERE), "dsac-v2_amd")
@@ -103,32 +101,103 @@ def check_cadence(got, want):
     assert got["samples"] == want["samples"] and len(got["tb_info"]) == len(want["tb_info"])
 
 
-@pytest.mark.skipif(not ref_loader.reference_available(), reason="reference not mounted")
+class OracleAlg:
+    """the reference's DSAC_V2 as create_alg builds it, restated: the container draws its initial weights from the torch
+    generator in the reference's construction order (dsac_v2_hip.ApproxContainer, pinned to the reference's module in
+    tests/test_std_*.py), the update is the oracle (pinned to the reference in tests/test_oracle_vs_reference.py), whose noise
+    draws consume the torch generator as the reference's local_update does. `networks` follows every update, so the sampler,
+    the evaluator and the checkpoints see what they would see with the reference's algorithm."""
+
+    def __init__(self, kw):
+        from dsac_v2_hip import ApproxContainer
+        from oracle.dsact_oracle import TB_KEYS, DsactOracle, default_config
+
+        self.networks = ApproxContainer(**kw)
+        A = int(kw["action_dim"])
+        if kw.get("value_func_type") == "CNN":
+            from oracle.dsact_oracle_cnn import DsactCnnOracle, cnn_config
+
+            cfg, cls = cnn_config(kw["obsv_dim"], A, kw["value_conv_type"]), DsactCnnOracle
+        else:
+            cfg = default_config(kw["obsv_dim"], A, kw["value_hidden_sizes"], policy_hidden=list(kw["policy_hidden_sizes"]),
+                                 value_act=kw["value_hidden_activation"], policy_act=kw["policy_hidden_activation"],
+                                 value_out_act=kw["value_output_activation"], policy_out_act=kw["policy_output_activation"],
+                                 act_dist=kw["policy_act_distribution"], policy_std_type=kw.get("policy_std_type", "mlp_shared"))
+            cls = DsactOracle
+        cfg["act_high"], cfg["act_low"] = np.asarray(kw["action_high_limit"], np.float32), np.asarray(kw["action_low_limit"], np.float32)
+        rng = torch.get_rng_state()   # the oracle draws its own initial parameters before loading these: not a draw the reference makes
+        self.orc = cls(cfg, state_dict=self.networks.state_dict())
+        torch.set_rng_state(rng)
+        self.act_dim, self.time_key = A, TB_KEYS[-1]
+
+    def local_update(self, data, it):
+        from oracle.dsact_oracle import draw_noise
+
+        tb = self.orc.local_update(data, draw_noise(int(data["obs"].shape[0]), self.act_dim), it)
+        self.networks.load_state_dict(self.orc.state_dict())
+        tb.setdefault(self.time_key, 0.0)
+        return tb
+
+
+class OracleBuffer:
+    """the reference ReplayBuffer as create_buffer builds it (the oracle ring; image rows for the CNN case)"""
+
+    def __init__(self, kw):
+        from oracle.dsact_oracle import ReplayOracle
+
+        shape = kw["obsv_dim"] if isinstance(kw["obsv_dim"], tuple) else (int(kw["obsv_dim"]),)
+        N = int(kw["buffer_max_size"])
+        self.r = ReplayOracle(1, int(kw["action_dim"]), N)
+        for k in ("obs", "obs2"):
+            self.r.buf[k] = np.zeros((N,) + tuple(shape), np.float32)
+
+    size = property(lambda self: self.r.size)
+    ptr = property(lambda self: self.r.ptr)
+
+    def add_batch(self, samples):
+        self.r.add_batch(samples)
+
+    def sample_batch(self, n):
+        return self.r.sample_batch(n)
+
+    def __get_RAM__(self):
+        return 0.0
+
+
+def check_numbers(got, want, tol):
+    """statistics, evaluation returns and logged values of two runs of the same loop (wall-clock and RAM values excepted);
+    tol: relative gate -- the recorded run is the reference's arithmetic, this one the oracle's restatement of it, on another
+    host's float32 accumulation order"""
+    for it, (g, w) in enumerate(zip(got["tb_info"], want["tb_info"])):
+        if g is not None:
+            np.testing.assert_allclose(g, w, rtol=tol, atol=tol, err_msg="update %d" % it)
+    assert [e[0] for e in got["evals"]] == [e[0] for e in want["evals"]]
+    np.testing.assert_allclose([e[1] for e in got["evals"]], [e[1] for e in want["evals"]], rtol=tol)
+    for g, w in zip(got["scalars"], want["scalars"]):
+        if g[0] in TIME_TAGS or g[0] == RAM_TAG:
+            continue
+        assert abs(g[2] - w[2]) <= tol * max(1.0, abs(w[2])), (g, w)
+
+
+TOL = 1e-5
+
+
 def test_trainer_loop_equals_the_reference_loop_exactly(tmp_path):
-    ref_loader.import_reference()
+    """our loop (HipOffSerialTrainer + HipOffSampler + HipEvaluator) around the reference's algorithm and replay buffer, restated
+    (OracleAlg / OracleBuffer), against the trajectory the reference's own loop recorded (tests/golden/trainer_trajectory.json):
+    the loop logic must agree EXACTLY -- replay indices, ring size/ptr, the ordered (tag, step) list of every scalar written,
+    checkpoint file names and their order, evaluation iterations -- and the numbers to the restatement's gate."""
     for p in (PKG, ENVS):
         if p not in sys.path:
-            sys.path.append(p)      # AFTER the reference root: `training`, `utils` stay the reference's packages
-    import plugin
-
-    plugin.install()
-    want = run_reference(str(tmp_path / "ref"))
-    # --- the same run with OUR loop around the reference's algorithm and buffer (arithmetic identical on both sides)
-    from utils.initialization import create_alg, create_buffer
-
-    kw = derived_kwargs(TRAINER_CASE, str(tmp_path / "hip"))
-    alg = create_alg(**kw)
-    # the reference builds sampler, buffer, evaluator in this order (example_train/main.py:160-168); run_hip_loop builds
-    # the sampler and the evaluator (both draw a container from the torch generator), the buffer draws nothing
-    buffer = create_buffer(**kw)
+            sys.path.append(p)
+    want = json.load(open(GOLDEN))
+    # (DSAC_V2_HIP: the sampler and evaluator build dsac_v2_hip.ApproxContainer by the reference's rule, as in the -m gpu test)
+    kw = derived_kwargs(dict(want["case"], algorithm="DSAC_V2_HIP"), str(tmp_path / "hip"))
+    alg = OracleAlg(kw)
+    buffer = OracleBuffer(kw)
     got = run_hip_loop(kw, alg, buffer)
     check_cadence(got, want)
-    assert got["tb_info"] == want["tb_info"]
-    assert got["evals"] == want["evals"]
-    for g, w in zip(got["scalars"], want["scalars"]):
-        if g[0] in TIME_TAGS:
-            continue
-        assert g[2] == w[2] or (g[0] == RAM_TAG), (g, w)
+    check_numbers(got, want, TOL)
     # the trainer's post-training CSV export exists for every tag the reference wrote
     tags = {s[0] for s in want["scalars"]}
     assert len(os.listdir(tmp_path / "hip" / "data")) == len(tags)
@@ -170,27 +239,23 @@ class _GroupedRefBuffer:
         return [self._buf.sample_batch(batch_size) for _ in range(n)]
 
 
-@pytest.mark.skipif(not ref_loader.reference_available(), reason="reference not mounted")
 @pytest.mark.parametrize("variant", sorted(VARIANTS))
 def test_grouped_updates_follow_the_reference_loop_exactly(tmp_path, variant):
     """sample_interval = K (training/trainer.py:63-66): HipOffSerialTrainer.train() issues the updates between two sampler
     calls as groups (sample_batches + local_update_group) cut at every iteration with a log / evaluation / checkpoint. Around
-    the reference's own arithmetic that must be the reference loop to the last bit: index draws, ring state, every scalar,
-    checkpoint names, evaluation returns, and the tb_info of every update a group can report (its last)."""
-    ref_loader.import_reference()
+    the reference's arithmetic (restated: OracleAlg / OracleBuffer) that must be the loop the reference recorded
+    (tests/golden/trainer_trajectory_<variant>.json): index draws, ring state, every scalar, checkpoint names and evaluation
+    iterations exactly; evaluation returns, logged values and the tb_info of every update a group can report (its last) to the
+    restatement's gate."""
     for p in (PKG, ENVS):
         if p not in sys.path:
             sys.path.append(p)
-    import plugin
-
-    plugin.install()
+    want = json.load(open(variant_golden(variant)))
     case = variant_case(variant)
-    want = run_reference(str(tmp_path / "ref"), case)
-    from utils.initialization import create_alg, create_buffer
-
-    kw = derived_kwargs(case, str(tmp_path / "hip"))
-    alg = _GroupedRefAlg(create_alg(**kw))
-    buffer = _GroupedRefBuffer(create_buffer(**kw))
+    assert want["case"] == json.loads(json.dumps(case))
+    kw = derived_kwargs(dict(case, algorithm="DSAC_V2_HIP"), str(tmp_path / "hip"))
+    alg = _GroupedRefAlg(OracleAlg(kw))
+    buffer = _GroupedRefBuffer(OracleBuffer(kw))
     got = run_hip_loop(kw, alg, buffer)
     assert got["groups"], "no group was issued"
     K = case["sample_interval"]
@@ -204,25 +269,8 @@ def test_grouped_updates_follow_the_reference_loop_exactly(tmp_path, variant):
         assert 8 in sizes               # whole groups of 8 between events
     # indices: the reference trainer draws per iteration, ours per group -- the same calls in the same order
     check_cadence(got, want)
-    for g, w in zip(got["tb_info"], want["tb_info"]):
-        assert g is None or g == w
     assert sum(g is not None for g in got["tb_info"]) >= len(want["tb_info"]) // K
-    assert got["evals"] == want["evals"]
-    for g, w in zip(got["scalars"], want["scalars"]):
-        if g[0] in TIME_TAGS:
-            continue
-        assert g[2] == w[2] or (g[0] == RAM_TAG), (g, w)
-
-
-def test_committed_trajectory_is_what_the_reference_produces_here(tmp_path):
-    """the fixtures the GPU tests compare against are regenerated where the reference is mounted"""
-    if not ref_loader.reference_available():
-        pytest.skip("reference not mounted")
-    for path, case in [(GOLDEN, None)] + [(variant_golden(v), variant_case(v)) for v in sorted(VARIANTS)]:
-        want = json.load(open(path))
-        got = run_reference(str(tmp_path / os.path.basename(path)), case)
-        check_cadence(got, want)
-        assert got["tb_info"] == want["tb_info"] and got["evals"] == want["evals"]
+    check_numbers(got, want, TOL)
 
 
 @pytest.mark.gpu
