@@ -1,0 +1,186 @@
+// dsact_act_batch.h -- the vectorised sampler's acting forward: policy(obs) + the action distribution's sample() for n
+// observation rows per call (training/off_sampler.py:46-56 over N environments, networks/mlp.py:79-100,
+// utils/act_distribution_cls.py:32-42 and :82-115), reading the live policy weights from the parameter arena on the
+// handle's stream.
+//
+// Launch shape: one launch per layer, each a grid of (feature slice x row tile) workgroups; the output layer's launch also
+// draws the action and its log-probability. Why not the one-launch hand-off of k_act_mlp (dsact_act.h): a dependent kernel
+// boundary on the same stream costs ~1.5 us on the MI355X, the same order as one in-launch hop, and
+// with n rows every layer hands over n x width values instead of one row -- a hop's price grows with the bytes a consumer
+// reads, a boundary's does not. Why not one workgroup per row block: the whole 3 x 256 Humanoid policy (0.94 MB) through
+// one CU took ~40 us (dsact_act.h); here a hidden layer's weights are split into 32-feature slices (a 256-wide layer: 8
+// workgroups per row tile, each streaming 32 KB), so even n <= 32 spreads a layer over several CUs.
+//
+// Arithmetic: plain fp32 FMAs on the VALU, staged through LDS in 128-wide K chunks (the next chunk's loads are in flight
+// while the current one is multiplied). At n <= 1024 and widths <= 1024 a layer is <= 1 GFMA: MFMA throughput buys nothing
+// measurable against the launch boundaries, and a VALU dot product fixes the order of every sum: output (r, f) is
+// fmaf(W[f][k], x[r][k], acc) for k = 0 .. K-1 in order, then + bias -- the same instructions whatever n is and wherever row
+// r sits in its tile (rows never share a sum, padding only ever adds exact zeros after the last term). A row's action
+// and log-probability are therefore bitwise independent of the batch around it. The sampling epilogue is tanh_gauss_fwd of
+// dsact_math.h (the closed form k_act_mlp and the host acting path use; half range 0 selects the plain Gaussian), and the
+// log-probability is summed over the action dimensions in order, as dsact_host_act.h's head() does.
+#pragma once
+#include "dsact_kernels.h"
+
+namespace dsact {
+
+constexpr int kActBatchCap = 1024;   // rows per launch; dsact_act_sample_batch chunks above it
+constexpr int kAbKC = 128;           // K chunk of the hidden layers staged in LDS (a layer is a chain of chunk round trips)
+
+// one hidden layer: Y[r][f] = act(sum_k W[f][k] X[r][xoff + k] + b[f]) for r < n, f < N. half > 0: a twin-trunk layer
+// (policy_std_type "mlp_separated"): features >= half are the second trunk's and read inputs [K, 2K) (xoff = K)
+struct ActBatchHidden {
+  const float* X; int ldx;
+  const float* W; const float* b;
+  int K, N, half;
+  float* Y; int ldy;
+  int n, act;
+};
+
+// the output layer (2A <= 64 features) + the sample: action[r][d], logp[r]
+struct ActBatchOut {
+  const float* X; int ldx;
+  const float* W; const float* b;
+  int K, A, n;
+  int out_act, out_n;                  // policy_output_activation and the outputs it applies to (2A, or A: mean half only)
+  const float* eps;                    // [n][A] standard-normal draws
+  const float* scale; const float* center;   // action half range / centre (0 / 0: GaussDistribution)
+  float lo_ls, hi_ls;
+  float* action; float* logp;          // [n][A], [n]
+};
+
+#ifdef DSACT_ACT_BATCH_DEFINE   // the kernels themselves: csrc/dsact_tu_act_batch.hip; other units see the declarations
+// 32 rows x 32 features per workgroup; thread (tr, tf) = (tid / 16, tid % 16) owns rows tr, tr + 16 and features tf, tf + 16.
+// grid: x = feature slices (per trunk), y = row tiles
+__global__ void __launch_bounds__(256) k_act_batch_hidden(ActBatchHidden a) {
+  __shared__ float xs[32][kAbKC + 1];
+  __shared__ float ws[32][kAbKC + 1];
+  const int tid = threadIdx.x, tf = tid & 15, tr = tid >> 4;
+  const int seg_n = a.half > 0 ? a.half : a.N;
+  const int tps = (seg_n + 31) / 32;
+  const int seg = (int)blockIdx.x / tps;
+  const int f0 = seg * seg_n + ((int)blockIdx.x % tps) * 32;
+  const int f_end = min(f0 + 32, (seg + 1) * seg_n);
+  const int r0 = (int)blockIdx.y * 32;
+  const float* X = a.X + (seg ? a.K : 0);
+  // staging: element e = tid + 256 q of a chunk is row e / kAbKC, column e % kAbKC (a wave: one 256-byte row segment per load)
+  constexpr int QH = 32 * kAbKC / 256;
+  float xr[QH], wr[QH];
+  auto load = [&](int k0) {
+#pragma unroll
+    for (int q = 0; q < QH; ++q) {
+      const int e = tid + 256 * q, rr = e / kAbKC, k = k0 + e % kAbKC;
+      xr[q] = (r0 + rr < a.n && k < a.K) ? X[(size_t)(r0 + rr) * a.ldx + k] : 0.f;
+      wr[q] = (f0 + rr < f_end && k < a.K) ? a.W[(size_t)(f0 + rr) * a.K + k] : 0.f;
+    }
+  };
+  load(0);
+  float c00 = 0.f, c01 = 0.f, c10 = 0.f, c11 = 0.f;   // c<row i><feature j>
+  for (int k0 = 0; k0 < a.K; k0 += kAbKC) {
+    __syncthreads();   // the previous chunk's reads are done
+#pragma unroll
+    for (int q = 0; q < QH; ++q) {
+      const int e = tid + 256 * q;
+      xs[e / kAbKC][e % kAbKC] = xr[q];
+      ws[e / kAbKC][e % kAbKC] = wr[q];
+    }
+    __syncthreads();
+    if (k0 + kAbKC < a.K) load(k0 + kAbKC);   // (block-uniform) the next chunk's loads fly while this one is multiplied
+#pragma unroll 16
+    for (int kk = 0; kk < kAbKC; ++kk) {
+      const float x0 = xs[tr][kk], x1 = xs[tr + 16][kk], w0 = ws[tf][kk], w1 = ws[tf + 16][kk];
+      c00 = fmaf(w0, x0, c00); c01 = fmaf(w1, x0, c01);
+      c10 = fmaf(w0, x1, c10); c11 = fmaf(w1, x1, c11);
+    }
+  }
+  const float c[2][2] = {{c00, c01}, {c10, c11}};
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int r = r0 + tr + 16 * i;
+    if (r >= a.n) continue;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int f = f0 + tf + 16 * j;
+      if (f >= f_end) continue;
+      float hv, gd;
+      act_fwd_grad(a.act, c[i][j] + a.b[f], hv, gd);
+      a.Y[(size_t)r * a.ldy + f] = hv;
+    }
+  }
+}
+
+// 8 rows x 64 outputs (mean | raw log-std, 2A <= 64) per workgroup; thread (tr, tf) = (tid / 32, tid % 32) owns row tr and
+// outputs tf, tf + 32. grid: x = row tiles
+__global__ void __launch_bounds__(256) k_act_batch_out(ActBatchOut a) {
+  constexpr int KC = 64;   // (the 64-row weight tile at 128 columns runs out of scalar registers)
+  __shared__ float xs[8][KC + 1];
+  __shared__ float ws[64][KC + 1];
+  __shared__ float raw[8][65];
+  __shared__ float lps[8][33];
+  const int tid = threadIdx.x, tf = tid & 31, tr = tid >> 5;
+  const int r0 = (int)blockIdx.x * 8, N = 2 * a.A;
+  constexpr int QX = 8 * KC / 256, QW = 64 * KC / 256;   // staging as in k_act_batch_hidden
+  float xr[QX], wr[QW];
+  auto load = [&](int k0) {
+#pragma unroll
+    for (int q = 0; q < QX; ++q) {
+      const int e = tid + 256 * q, rr = e / KC, k = k0 + e % KC;
+      xr[q] = (r0 + rr < a.n && k < a.K) ? a.X[(size_t)(r0 + rr) * a.ldx + k] : 0.f;
+    }
+#pragma unroll
+    for (int q = 0; q < QW; ++q) {
+      const int e = tid + 256 * q, rr = e / KC, k = k0 + e % KC;
+      wr[q] = (rr < N && k < a.K) ? a.W[(size_t)rr * a.K + k] : 0.f;
+    }
+  };
+  load(0);
+  float c0 = 0.f, c1 = 0.f;
+  for (int k0 = 0; k0 < a.K; k0 += KC) {
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < QX; ++q) { const int e = tid + 256 * q; xs[e / KC][e % KC] = xr[q]; }
+#pragma unroll
+    for (int q = 0; q < QW; ++q) { const int e = tid + 256 * q; ws[e / KC][e % KC] = wr[q]; }
+    __syncthreads();
+    if (k0 + KC < a.K) load(k0 + KC);
+#pragma unroll 16
+    for (int kk = 0; kk < KC; ++kk) {
+      const float x = xs[tr][kk];
+      c0 = fmaf(ws[tf][kk], x, c0);
+      c1 = fmaf(ws[tf + 32][kk], x, c1);
+    }
+  }
+  // (mean | raw log-std) of this row after policy_output_activation (networks/mlp.py:15-20)
+  const float c[2] = {c0, c1};
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int f = tf + 32 * j;
+    if (f < N) {
+      float z = c[j] + a.b[f];
+      if (a.out_act && f < a.out_n) z = out_act_fwd(a.out_act, z);
+      raw[tr][f] = z;
+    }
+  }
+  __syncthreads();
+  // the sample, one (row, action dimension) per thread: tanh_gauss_fwd term for term
+  const int r = r0 + tr, d = tf;
+  if (r < a.n && d < a.A) {
+    const TanhGaussFwd g = tanh_gauss_fwd(raw[tr][d], raw[tr][a.A + d], a.eps[(size_t)r * a.A + d], a.scale[d], a.center[d],
+                                          a.lo_ls, a.hi_ls);
+    a.action[(size_t)r * a.A + d] = g.a;
+    lps[tr][d] = g.lp;
+  }
+  __syncthreads();
+  // Independent(..., 1): the log-probability summed over the action dimensions, in order
+  if (tid < 8 && r0 + tid < a.n) {
+    float lp = 0.0f;
+    for (int q = 0; q < a.A; ++q) lp += lps[tid][q];
+    a.logp[r0 + tid] = lp;
+  }
+}
+#else
+__global__ void k_act_batch_hidden(ActBatchHidden a);
+__global__ void k_act_batch_out(ActBatchOut a);
+#endif
+
+}  // namespace dsact

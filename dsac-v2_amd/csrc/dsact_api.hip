@@ -20,6 +20,7 @@
 #include "dsact_chain.h"
 #include "dsact_fat.h"
 #include "dsact_act.h"
+#include "dsact_act_batch.h"
 #include "dsact_host_act.h"
 #include "dsact_conv.h"
 
@@ -298,6 +299,12 @@ struct dsact_handle {
   int act_threads = 0;                  // 0: not calibrated yet; DSACT_HOST_ACT_THREADS forces a count
   float act_scale_h[32] = {0}, act_center_h[32] = {0};   // host copies of act_scale / act_center (act_dim <= 32 on this path)
   double act_host_us = 0.0, act_copy_wait_us = 0.0;
+  // batched acting forward (dsact_act_batch.h), allocated by the first dsact_act_sample_batch: pinned staging of a chunk's
+  // (obs | eps) rows, its device copy, two activation buffers, and the mapped host block the output launch writes
+  // (action | logp) into
+  float* ab_stage = nullptr; float* ab_in = nullptr; float* ab_h[2] = {nullptr, nullptr};
+  float* ab_out_host = nullptr; float* ab_out_dev = nullptr;
+  unsigned long long ab_calls = 0;
   unsigned long long act_host_calls = 0, act_copies = 0;
   bool env_no_conv_dx_mfma = false;     // DSACT_NO_CONV_DX_MFMA: the 16-channel layer's data gradient with k_conv_dx_block (A/B)
   bool fwd_merge = false;               // launches A and B as one (batch <= 256)
@@ -3572,6 +3579,10 @@ int dsact_destroy(dsact_handle* h) {
   }
   if (h->handoff_host) hipHostFree(h->handoff_host);
   if (h->act_h) hipFree(h->act_h);
+  if (h->ab_stage) hipHostFree(h->ab_stage);
+  if (h->ab_out_host) hipHostFree(h->ab_out_host);
+  if (h->ab_in) hipFree(h->ab_in);
+  for (int i = 0; i < 2; ++i) if (h->ab_h[i]) hipFree(h->ab_h[i]);
   if (h->pol_host) hipHostFree(h->pol_host);
   if (h->pol_ev) hipEventDestroy(h->pol_ev);
   free(h->act_buf);
@@ -5062,6 +5073,7 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "graph_steps")) *value = (double)h->graph_steps;
   else if (!strcmp(name, "pipe_graph")) *value = h->pipe_graph ? 1.0 : 0.0;   // the captured graphs are the pipelined ones
   else if (!strcmp(name, "state_invalid")) *value = h->state_invalid ? 1.0 : 0.0;
+  else if (!strcmp(name, "act_batch_calls")) *value = (double)h->ab_calls;   // dsact_act_sample_batch chunks launched on the GPU
   else if (!strcmp(name, "act_fast")) *value = act_fast_ok(h) ? 1.0 : 0.0;     // dsact_act_sample / the one-launch acting forward serve this handle
   else if (!strcmp(name, "graph_cache")) *value = (double)h->graph_cache.size();   // inactive captured graphs kept by dsact_run_group
   else if (!strcmp(name, "graph_noise_table")) *value = h->graph_noise_table ? 1.0 : 0.0;
@@ -5146,6 +5158,75 @@ int dsact_act_sample(dsact_handle* h, const float* obs_host, const float* eps_ho
   for (int d = 0; d < A; ++d) { action_host[d] = out[d]; lp += out[A + d]; }   // Independent(..., 1): sum over the action dimensions
   *logp_host = lp;
   return DSACT_OK;
+}
+
+// dsact_act_sample for n observation rows (dsact_act_batch.h): per chunk of <= kActBatchCap rows ONE copy of (obs | eps) to the
+// device, one launch per policy layer on the handle's stream (behind every enqueued update: the live weights), the sample in
+// the output layer's epilogue written into mapped host memory, ONE stream synchronisation
+static bool is_device_ptr(const void* p) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // (pageable host memory)
+  return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
+}
+int dsact_act_sample_batch(dsact_handle* h, const float* obs, int32_t n, const float* eps, float* action_host, float* logp_host) {
+  if (!h || !obs || !eps || !action_host || !logp_host || n < 1) return DSACT_E_INVALID;
+  if (!h->online) return fail(h, DSACT_E_STATE, "arenas not bound");
+  if (!h->limits_set) return fail(h, DSACT_E_STATE, "action limits not set (dsact_set_action_limits)");
+  if (h->cnn) return fail(h, DSACT_E_INVALID, "dsact_act_sample_batch serves MLP policies (CNN: dsact_policy_forward)");
+  if (h->A > 32) return fail(h, DSACT_E_INVALID, "dsact_act_sample_batch serves act_dim <= 32");
+  HIPCHK(h, hipSetDevice(h->device));
+  TRY(check_handoff(h));
+  const int O = h->O, A = h->A, R = kActBatchCap;
+  if (!h->ab_in) {
+    HIPCHK(h, hipHostMalloc((void**)&h->ab_stage, (size_t)R * (O + A) * sizeof(float), hipHostMallocDefault));
+    HIPCHK(h, hipMalloc((void**)&h->ab_in, (size_t)R * (O + A) * sizeof(float)));
+    for (int i = 0; i < 2; ++i) HIPCHK(h, hipMalloc((void**)&h->ab_h[i], (size_t)R * kMaxWidth * sizeof(float)));
+    HIPCHK(h, hipHostMalloc((void**)&h->ab_out_host, (size_t)R * (A + 1) * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(h, hipHostGetDevicePointer((void**)&h->ab_out_dev, h->ab_out_host, 0));
+  }
+  const bool obs_dev = is_device_ptr(obs), eps_dev = is_device_ptr(eps);
+  const float* base = net_params(h, N_POL);
+  const NetDesc& d = h->pd;
+  for (int s = 0; s < n; s += R) {
+    const int m = n - s < R ? n - s : R;
+    float* in_obs = h->ab_in;
+    float* in_eps = h->ab_in + (size_t)m * O;
+    // (obs | eps) of this chunk: host rows through the pinned stage in one copy, device rows copied on the stream
+    if (!obs_dev) memcpy(h->ab_stage, obs + (size_t)s * O, (size_t)m * O * sizeof(float));
+    if (!eps_dev) memcpy(h->ab_stage + (size_t)m * O, eps + (size_t)s * A, (size_t)m * A * sizeof(float));
+    if (!obs_dev && !eps_dev) {
+      HIPCHK(h, hipMemcpyAsync(h->ab_in, h->ab_stage, (size_t)m * (O + A) * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    } else {
+      HIPCHK(h, hipMemcpyAsync(in_obs, obs_dev ? obs + (size_t)s * O : h->ab_stage, (size_t)m * O * sizeof(float), hipMemcpyDefault, h->stream));
+      HIPCHK(h, hipMemcpyAsync(in_eps, eps_dev ? eps + (size_t)s * A : h->ab_stage + (size_t)m * O, (size_t)m * A * sizeof(float),
+                               hipMemcpyDefault, h->stream));
+    }
+    const float* X = in_obs;
+    int ldx = O;
+    for (int l = 0; l < h->Lp; ++l) {
+      ActBatchHidden a;
+      a.X = X; a.ldx = ldx; a.W = base + d.w_off[l]; a.b = base + d.b_off[l];
+      a.K = d.in[l]; a.N = d.out[l]; a.half = 0;
+      if (d.nblk == 2 && l > 0) { a.K = d.in[l] / 2; a.half = d.out[l] / 2; }   // two (H x Hprev) blocks
+      a.Y = h->ab_h[l & 1]; a.ldy = d.out[l]; a.n = m; a.act = h->cfg.policy_act;
+      const int seg_n = a.half > 0 ? a.half : a.N;
+      const dim3 grid((unsigned)((a.half > 0 ? 2 : 1) * ((seg_n + 31) / 32)), (unsigned)((m + 31) / 32));
+      TRY(launch(h, "act_batch_hidden", k_act_batch_hidden, grid, dim3(256), 0, a));
+      X = a.Y; ldx = a.ldy;
+    }
+    ActBatchOut o;
+    o.X = X; o.ldx = ldx; o.W = base + d.w_off[h->Lp]; o.b = base + d.b_off[h->Lp];
+    o.K = d.in[h->Lp]; o.A = A; o.n = m;
+    o.out_act = h->cfg.policy_out_act; o.out_n = h->cfg.policy_std_param ? A : 2 * A;
+    o.eps = in_eps; o.scale = h->act_scale; o.center = h->act_center; o.lo_ls = h->cfg.min_log_std; o.hi_ls = h->cfg.max_log_std;
+    o.action = h->ab_out_dev; o.logp = h->ab_out_dev + (size_t)m * A;
+    TRY(launch(h, "act_batch_out", k_act_batch_out, dim3((unsigned)((m + 7) / 8)), dim3(256), 0, o));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->ab_calls++;
+    memcpy(action_host + (size_t)s * A, h->ab_out_host, (size_t)m * A * sizeof(float));
+    memcpy(logp_host + s, h->ab_out_host + (size_t)m * A, (size_t)m * sizeof(float));
+  }
+  return check_handoff(h);
 }
 
 int dsact_policy_forward(dsact_handle* h, const float* obs_host, int32_t n, float* logits_host) {

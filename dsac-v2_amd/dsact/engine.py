@@ -532,6 +532,32 @@ class DsactEngine:
         if rc != 0:
             self._chk(rc)
 
+    def act_sample_batch(self, obs, eps):
+        """dsact_act_sample_batch: (action float32[N, A], logp float32[N]) of the policy's action distribution sampled for N
+        observation rows with the caller's N(0,1) draws eps[N, A] (row i: torch.randn(N, A)[i]). obs / eps: numpy / CPU
+        tensors, or CUDA tensors on this engine's GPU (passed by device address, as load_batch does)"""
+        torch = self.torch
+        n = int(np.prod(np.shape(obs))) // self.obs_dim
+        srcs = [self._src(obs, n * self.obs_dim), self._src(eps, n * self.act_dim)]
+        if any(isinstance(k, torch.Tensor) for _, k in srcs):
+            torch.cuda.current_stream(self.device).synchronize()   # the producers of the CUDA sources have finished
+        act = np.empty((n, self.act_dim), np.float32)
+        lp = np.empty(n, np.float32)
+        self._chk(self._lib.dsact_act_sample_batch(self._h, srcs[0][0], n, srcs[1][0], _ffi.fptr(act), _ffi.fptr(lp)))
+        return act, lp
+
+    def act_sample_batch_addr(self, obs_addr: int, n: int, eps_addr: int, act_addr: int, logp_addr: int):
+        """dsact_act_sample_batch on plain integer addresses (the vectorised sampler's per-step call; results land in the
+        caller's rows). A second binding of the same symbol whose pointer arguments are void*."""
+        f = getattr(self, "_act_batch_addr_fn", None)
+        if f is None:
+            f = self._lib["dsact_act_sample_batch"]    # a fresh function object: its argtypes are its own
+            f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+            self._act_batch_addr_fn = f
+        rc = f(self._h, obs_addr, n, eps_addr, act_addr, logp_addr)
+        if rc != 0:
+            self._chk(rc)
+
     def policy_forward(self, obs) -> np.ndarray:
         obs = _f32(obs).reshape(-1, self.obs_dim)
         n = obs.shape[0]

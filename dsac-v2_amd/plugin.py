@@ -4,6 +4,9 @@ training/trainer.py:155-158): the drop-in surface of this repository.
     create_alg(algorithm="DSAC_V2_HIP", **kw)          -> module dsac_v2_hip, class DSAC_V2_HIP
     create_buffer(buffer_name="hip_replay_buffer", **kw) -> module training.hip_replay_buffer,
                                                             class HipReplayBuffer
+    create_sampler(**kw)                                 -> training.hip_sampler.HipOffSampler, or with
+                                                            sampler_name="hip_vec_off_sampler"
+                                                            training.hip_vec_sampler.HipVecOffSampler
     create_trainer(alg, sampler, buffer, evaluator, **kw) -> training.hip_trainer.HipOffSerialTrainer
 """
 import importlib
@@ -65,6 +68,13 @@ def create_env(**kwargs):
 
 
 def create_sampler(**kwargs):
+    """sampler_name="hip_vec_off_sampler": the vectorised sampler (training/hip_vec_sampler.py; N = vector_env_num
+    environments in lockstep). Every other name -- or none -- is the one-environment HipOffSampler, whatever
+    vector_env_num says (the reference's CNN examples pass it and step one environment)."""
+    if kwargs.get("sampler_name") == "hip_vec_off_sampler":
+        from training.hip_vec_sampler import HipVecOffSampler
+
+        return HipVecOffSampler(**kwargs)
     from training.hip_sampler import HipOffSampler
 
     return HipOffSampler(**kwargs)

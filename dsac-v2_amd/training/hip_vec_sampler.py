@@ -1,0 +1,231 @@
+"""HipVecOffSampler -- N environments stepped in lockstep, all N actions from ONE batched acting call per step
+(`plugin.create_sampler(sampler_name="hip_vec_off_sampler", vector_env_num=N, ...)`).
+
+The reference parses `vector_env_num` / `vector_env_type` and never uses them (example_train/
+dsacv2_cnn_carracing_offasync.py:37-38); its OffSampler (training/off_sampler.py:12-101) steps one environment. Here the
+per-step host costs -- the acting call, the N(0,1) draw, clipping, the stores -- are paid once per N transitions.
+
+Transitions are STEP-MAJOR: sample() runs S / N lockstep steps (S = batch_size_per_sampler, or sample_batch_size; a
+multiple of N), and transition t * N + i is environment i's transition of step t. Replay ring rows and replay indices --
+and so a training run's trajectory -- follow this order.
+
+Per environment the semantics are HipOffSampler's (training/hip_sampler.py): the action is clipped to that environment's
+action_space, the reward is multiplied by reward_scale, a `TimeLimit.truncated` step is stored as non-terminal, and an
+environment that ends (terminal or truncated) is reset on its own while the others go on. Environment i is
+`envs[i]`, or `create_env(**kwargs)` seeded with `seed + i` (environment 0 thus gets what HipOffSampler's environment
+gets). The throw-away ApproxContainer HipOffSampler builds is built here too, so the torch generator is consumed the same.
+
+Acting routes (per sample(), one per lockstep step):
+  * N == 1: HipOffSampler itself -- the run is bitwise HipOffSampler's;
+  * attached MLP policy, N >= hip_vec_gpu_min_envs (or hip_vec_act="gpu"): dsact_act_sample_batch, ONE GPU call for the
+    N rows with ONE torch.randn(N, A) draw (csrc/dsact_act_batch.h);
+  * attached MLP policy below the threshold (or hip_vec_act="host"): dsact_act_sample per row (the host acting forward
+    HipOffSampler uses), the N rows of ONE torch.randn(N, A) draw as their eps;
+  * CNN policies and unattached containers: the module forward over the [N, ...] batch plus create_action_distributions
+    and its sample() (which consumes the generator as one torch.randn(N, A) draw does).
+A row's action depends only on its observation and its eps row: environment i's trajectory does not depend on how many
+environments run beside it (given the same draws).
+
+Exploration noise is not supported (as in HipOffSampler).
+"""
+import time
+
+import numpy as np
+import torch
+
+from training.hip_sampler import SAMPLER_TIME_KEY, HipOffSampler, SampleBatch, _container, _reset
+
+__all__ = ["HipVecOffSampler", "DEFAULT_GPU_MIN_ENVS"]
+
+# the crossover of the batched GPU call and N per-row host calls on the Humanoid policy
+DEFAULT_GPU_MIN_ENVS = 32
+
+
+class HipVecOffSampler:
+    def __init__(self, index=0, **kwargs):
+        from plugin import create_env
+
+        envs = kwargs.get("envs")
+        n = kwargs.get("vector_env_num")
+        if envs is not None:
+            envs = list(envs)
+            if n is not None and int(n) != len(envs):
+                raise ValueError("vector_env_num=%s but %d environments were passed" % (n, len(envs)))
+            n = len(envs)
+        n = int(n) if n is not None else 1
+        if n < 1:
+            raise ValueError("vector_env_num must be >= 1 (got %d)" % n)
+        self.n_envs = n
+        self.sample_batch_size = kwargs["batch_size_per_sampler"] if "batch_size_per_sampler" in kwargs \
+            else kwargs["sample_batch_size"]
+        if self.sample_batch_size % n:
+            raise ValueError("the sample batch size %d is not a multiple of vector_env_num %d" % (self.sample_batch_size, n))
+        if kwargs.get("noise_params") is not None:
+            raise NotImplementedError("exploration noise is not part of the DSAC-T path (default None)")
+        self.act_mode = kwargs.get("hip_vec_act", "auto")
+        if self.act_mode not in ("auto", "gpu", "host"):
+            raise ValueError("hip_vec_act must be 'auto', 'gpu' or 'host' (got %r)" % (self.act_mode,))
+        self.gpu_min_envs = int(kwargs.get("hip_vec_gpu_min_envs", DEFAULT_GPU_MIN_ENVS))
+        if n == 1:
+            # the single-environment sampler as it is: same environment, same container, same per-step calls
+            one = dict(kwargs)
+            one.pop("envs", None)
+            if envs is not None:
+                one["env"] = envs[0]
+            self._single = HipOffSampler(index, **one)
+            return
+        self._single = None
+        seed = kwargs.get("seed")
+        if envs is None:
+            envs = []
+            for i in range(n):
+                kw_i = dict(kwargs)
+                if seed is not None:
+                    kw_i["seed"] = seed + i
+                envs.append(create_env(**kw_i))
+        if seed is not None:
+            for i, e in enumerate(envs):
+                if hasattr(e, "seed"):
+                    e.seed(seed + i)   # (HipOffSampler seeds its environment with the plain seed: environment 0 here)
+        self.envs = envs
+        first = [_reset(e) for e in envs]
+        self.obs_shape = np.shape(first[0][0])
+        self.obs_dim = int(np.prod(self.obs_shape))
+        self.obs = np.empty((n, self.obs_dim), np.float32)
+        self.obs[...] = [np.reshape(o, -1) for o, _ in first]
+        self.infos = [i for _, i in first]
+        # the reference's own throw-away container (off_sampler.py:19-23), built for its use of the torch generator
+        self.networks = kwargs.get("networks")
+        if self.networks is None and "algorithm" in kwargs:
+            self.networks = _container(**kwargs)
+        self.action_type = kwargs.get("action_type", "continu")
+        self.reward_scale = kwargs.get("reward_scale", 1)
+        self.total_sample_number = 0
+        # per-environment action limits as [N, A] rows: the clip is two ufunc calls over the N actions of a step
+        self.low = np.stack([np.asarray(e.action_space.low, np.float32).reshape(-1) for e in envs])
+        self.high = np.stack([np.asarray(e.action_space.high, np.float32).reshape(-1) for e in envs])
+        self._fast_ok = {}
+
+    # HipOffSampler's surface (the trainer assigns `networks`, the evaluator reads the sample count)
+    def __getattr__(self, name):
+        single = self.__dict__.get("_single")
+        if single is not None:
+            return getattr(single, name)
+        raise AttributeError(name)
+
+    def __setattr__(self, name, value):
+        single = self.__dict__.get("_single")
+        if single is not None and name != "_single" and not hasattr(type(self), name):   # (a wrapped sample() stays here)
+            setattr(single, name, value)
+        else:
+            object.__setattr__(self, name, value)
+
+    def load_state_dict(self, state_dict):
+        self.networks.load_state_dict(state_dict)
+
+    def get_total_sample_number(self):
+        return self.total_sample_number
+
+    def _engine(self):
+        """the engine behind an ATTACHED MLP policy (dsact_act_sample_batch serves every one), else None"""
+        pol = getattr(self.networks, "policy", None)
+        eng = getattr(pol, "_engine", None)
+        if eng is None or self.action_type != "continu" or getattr(eng, "conv_type", None):
+            return None
+        if type(pol).__name__ != "HipStochaPolicy":
+            return None
+        return eng
+
+    def route(self):
+        """'single' | 'gpu' | 'host' | 'module': how the next sample() acts (see the module docstring)"""
+        if self._single is not None:
+            return "single"
+        eng = self._engine()
+        if eng is None:
+            return "module"
+        if self.act_mode == "gpu" or (self.act_mode == "auto" and self.n_envs >= self.gpu_min_envs):
+            return "gpu"
+        ok = self._fast_ok.get(id(eng))
+        if ok is None:   # the library's own gate of dsact_act_sample (act_fast_ok)
+            try:
+                ok = eng.debug_get("act_fast") == 1.0
+            except Exception:
+                ok = False
+            self._fast_ok[id(eng)] = ok
+        return "host" if ok else "gpu"
+
+    def sample(self):
+        if self._single is not None:
+            return self._single.sample()
+        t0 = time.perf_counter()
+        self.total_sample_number += self.sample_batch_size
+        route = self.route()
+        N, S, O = self.n_envs, self.sample_batch_size, self.obs_dim
+        eng = self._engine() if route in ("gpu", "host") else None
+        if eng is not None:
+            A = eng.act_dim
+            eng.note_torch_writes(self.networks.policy.parameters())   # (weights written with torch ops since the last call)
+        else:
+            A = self.low.shape[1]
+        obs_b, obs2_b = np.empty((S, O), np.float32), np.empty((S, O), np.float32)
+        act_b, clip_b = np.empty((S, A), np.float32), np.empty((S, A), np.float32)
+        rew_b, done_b, logp_b = np.empty(S, np.float32), np.empty(S, np.float32), np.empty(S, np.float32)
+        rew64 = np.empty(N, np.float64)
+        eps_t = torch.empty(N, A)
+        eps_a = eps_t.data_ptr()
+        envs, low, high, scale = self.envs, self.low, self.high, self.reward_scale
+        maximum, minimum = np.maximum, np.minimum
+        flat = len(self.obs_shape) == 1
+        batch = SampleBatch()
+        infos = self.infos
+        obs_b[0:N] = self.obs
+        for t in range(S // N):
+            r0, r1 = t * N, (t + 1) * N
+            ob, ac, lp = obs_b[r0:r1], act_b[r0:r1], logp_b[r0:r1]
+            if route == "module":
+                obs_t = torch.from_numpy(ob.reshape((N,) + tuple(self.obs_shape)))
+                with torch.no_grad():
+                    logits = self.networks.policy(obs_t)
+                    dist = self.networks.create_action_distributions(logits)
+                    action, logp = dist.sample()
+                ac[...] = action.detach().cpu().numpy().reshape(N, A)
+                lp[...] = logp.detach().cpu().numpy().reshape(N)
+            else:
+                torch.randn(N, A, out=eps_t)   # ONE draw per lockstep step, row i for environment i
+                if route == "gpu":
+                    eng.act_sample_batch_addr(ob.ctypes.data, N, eps_a, ac.ctypes.data, lp.ctypes.data)
+                else:
+                    act_into = eng.act_sample_addr
+                    for i in range(N):
+                        act_into(ob[i].ctypes.data, eps_a + 4 * A * i, ac[i].ctypes.data, lp[i:i + 1].ctypes.data)
+            cl = clip_b[r0:r1]
+            minimum(maximum(ac, low, out=cl), high, out=cl)
+            steps = [e.step(cl[i]) for i, e in enumerate(envs)]
+            obs2 = obs2_b[r0:r1]
+            obs2[...] = [np.reshape(s[0], -1) for s in steps]
+            truncs = [bool(s[3].get("TimeLimit.truncated", False)) for s in steps]
+            dones = [bool(s[2]) and not tr for s, tr in zip(steps, truncs)]   # time-outs are stored as non-terminal (off_sampler.py:70-73)
+            np.multiply(np.asarray([s[1] for s in steps], np.float64), scale, out=rew64)
+            rew_b[r0:r1] = rew64
+            done_b[r0:r1] = dones
+            next_infos = []
+            for i, s in enumerate(steps):
+                ni = s[3]
+                ni["TimeLimit.truncated"] = truncs[i]
+                next_infos.append(ni)
+                if flat:
+                    batch.append((ob[i], infos[i], ac[i], float(rew64[i]), obs2[i], dones[i], lp[i], ni))
+                else:
+                    batch.append((ob[i].reshape(self.obs_shape), infos[i], ac[i], float(rew64[i]),
+                                  obs2[i].reshape(self.obs_shape), dones[i], lp[i], ni))
+            # the next step's observations: this step's, with every environment that ended reset on its own
+            nxt = obs_b[r1:r1 + N] if r1 < S else self.obs
+            nxt[...] = obs2
+            infos = next_infos
+            for i, e in enumerate(envs):
+                if dones[i] or truncs[i]:
+                    o, infos[i] = _reset(e)
+                    nxt[i] = np.reshape(o, -1)
+        self.infos = infos
+        batch.packed = (obs_b, act_b, rew_b, obs2_b, done_b, logp_b)
+        return batch, {SAMPLER_TIME_KEY: (time.perf_counter() - t0) * 1000}

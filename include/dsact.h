@@ -376,6 +376,16 @@ int dsact_policy_forward(dsact_handle* h, const float* obs_host, int32_t n, floa
  * does, and mean + std * eps is bit for bit what Normal.sample() returns). action[A], logp[1] on the host; MLP policies
  * (DSACT_E_INVALID otherwise -- the caller then takes dsact_policy_forward and samples itself). Synchronous. */
 int dsact_act_sample(dsact_handle* h, const float* obs_host, const float* eps_host, float* action_host, float* logp_host);
+/* dsact_act_sample for N environments stepped in lockstep (the vectorised sampler, training/hip_vec_sampler.py): the
+ * reference's per-step acting (training/off_sampler.py:46-56) for n observation rows at once -- policy(obs) on the live
+ * weights, read on the handle's stream behind every enqueued update, then TanhGaussDistribution.sample() or
+ * GaussDistribution.sample() (utils/act_distribution_cls.py) in the output layer's epilogue with the caller's
+ * standard-normal draws eps[n*A] (row i: torch.randn(N, A)[i]). action[n*A] and logp[n] (summed over the action
+ * dimensions) on the host. obs[n*O] / eps[n*A] may be host or device pointers (as for dsact_load_batch). A row's results
+ * are bitwise independent of n and of its position in the batch. Any n >= 1 (chunked inside the call); MLP policies with
+ * act_dim <= 32 (DSACT_E_INVALID for CNN policies). Synchronous. */
+int dsact_act_sample_batch(dsact_handle* h, const float* obs, int32_t n, const float* eps, float* action_host,
+                           float* logp_host);
 
 #ifdef __cplusplus
 }
