@@ -199,6 +199,15 @@ struct dsact_handle {
   // replay ring
   long long cap = 0, ptr = 0, size = 0;
   float *rb_obs = nullptr, *rb_obs2 = nullptr, *rb_act = nullptr, *rb_rew = nullptr, *rb_done = nullptr, *rb_logp = nullptr;
+  // coded image ring (dsact_buffer_create_coded): rb_obs / rb_obs2 stay null, the image columns are byte codes into a table
+  uint8_t* rb_code = nullptr;      // [2][cap][O]: obs codes, then obs2 codes
+  float* code_book = nullptr;      // [256] device copy of the table (entries >= n_codes unused)
+  int n_codes = 0;
+  CodeMiss* code_miss = nullptr;   // device record of values missing from the table
+  int* miss_host = nullptr;        // mapped host word raised by the encoder (polled without a sync: check_codes)
+  int* miss_dev = nullptr;
+  bool miss_seen = false;          // miss_rec holds the device record (read once, after a drain)
+  CodeMiss miss_rec = {};
   float* stage_dev = nullptr;  // device staging for ring writes
   size_t stage_rows = 0;
   float* stage_pin[2] = {nullptr, nullptr};   // pinned host staging, two slots: dsact_buffer_add returns without a sync
@@ -1512,9 +1521,8 @@ NoiseArgs noise_args(const dsact_handle* h);
 
 // step_it >= -1: fused step flow (bookkeeping for iteration step_it, or the device iteration when use_dev; device
 // noise; weight repack) rides in the same launch; -2: plain staging
-int enqueue_gather_img(dsact_handle* h, const float* src_obs, const float* src_obs2, const int* table, int rows,
-                       int use_dev, bool with_scalars, float* img0, float* img2, int n_rows,
-                       long long step_it = -2, int advance = 0) {
+ImgGatherArgs img_gather_args(dsact_handle* h, const float* src_obs, const float* src_obs2, const int* table, int rows,
+                              int use_dev, bool with_scalars, float* img0, float* img2, int n_rows, long long step_it, int advance) {
   ImgGatherArgs a;
   memset(&a, 0, sizeof(a));
   if (step_it >= -1) {
@@ -1526,12 +1534,37 @@ int enqueue_gather_img(dsact_handle* h, const float* src_obs, const float* src_o
   a.idx_table = table; a.idx_rows = rows; a.use_dev = use_dev; a.host_row = 0; a.st = h->st;
   a.img0 = img0; a.img2 = img2; a.Xa0 = h->Xc[C_Q1C]; a.Xa1 = h->Xc[C_Q2C]; a.rew = h->rew; a.done = h->done;
   a.B = n_rows; a.C = h->cfg.img_c; a.HW = h->cfg.img_h * h->cfg.img_w; a.A = h->A; a.F = h->F; a.ldx = h->ldx;
+  return a;
+}
+
+int enqueue_gather_img(dsact_handle* h, const float* src_obs, const float* src_obs2, const int* table, int rows,
+                       int use_dev, bool with_scalars, float* img0, float* img2, int n_rows,
+                       long long step_it = -2, int advance = 0) {
+  ImgGatherArgs a = img_gather_args(h, src_obs, src_obs2, table, rows, use_dev, with_scalars, img0, img2, n_rows, step_it, advance);
   a.chunks = 8;
   if (a.C == 3 && a.HW % 4 == 0) {   // RGB fast path: a thread per pixel quad -- exactly one trip per thread when it divides (96 x 96: 9 blocks)
     const int per = (a.HW / 4 + kThreads - 1) / kThreads;
     a.chunks = per < 1 ? 1 : (per > 16 ? 16 : per);
   }
   return launch(h, "gather_img", k_gather_img, dim3(n_rows * a.chunks + a.rp.n_blocks), dim3(kThreads), 0, a);
+}
+
+// ring rows -> staged minibatch images, from whichever ring the handle holds (fp32 or coded)
+int enqueue_gather_ring_img(dsact_handle* h, const int* table, int rows, int use_dev, long long step_it = -2, int advance = 0) {
+  if (!h->rb_code)
+    return enqueue_gather_img(h, h->rb_obs, h->rb_obs2, table, rows, use_dev, true, h->img[0], h->img[1], h->B, step_it, advance);
+  ImgCodedGatherArgs a;
+  memset(&a, 0, sizeof(a));
+  a.g = img_gather_args(h, nullptr, nullptr, table, rows, use_dev, true, h->img[0], h->img[1], h->B, step_it, advance);
+  const size_t O = (size_t)h->O;
+  a.code0 = h->rb_code; a.code1 = h->rb_code + (size_t)h->cap * O; a.book = h->code_book; a.n_codes = h->n_codes;
+  a.tiles = (a.g.HW + kCodeTile - 1) / kCodeTile;
+  a.n_gather_blocks = (h->B * a.tiles + kThreads / 64 - 1) / (kThreads / 64);
+  const dim3 grid(a.n_gather_blocks + a.g.rp.n_blocks);
+  const size_t lds = coded_gather_lds(a.g.C);
+  if (a.g.C == 3) return launch(h, "gather_img_coded", k_gather_img_coded<3>, grid, dim3(kThreads), lds, a);
+  if (a.g.C == 4) return launch(h, "gather_img_coded", k_gather_img_coded<4>, grid, dim3(kThreads), lds, a);
+  return launch(h, "gather_img_coded", k_gather_img_coded<0>, grid, dim3(kThreads), lds, a);
 }
 
 // dispatch on the number of 256-wide chunks of a hidden row (register arrays are statically indexed)
@@ -1589,8 +1622,7 @@ GatherArgs gather_args(const dsact_handle* h, const int* table, int rows, int us
 int enqueue_gather(dsact_handle* h, const int* table, int rows, int use_dev, long long it, int advance, int bookkeeping = 1) {
   if (h->cnn) {
     // bookkeeping, device noise and the padded-weight repack ride in the same launch
-    return enqueue_gather_img(h, h->rb_obs, h->rb_obs2, table, rows, use_dev, true, h->img[0], h->img[1], h->B,
-                              use_dev ? -1 : it, advance);
+    return enqueue_gather_ring_img(h, table, rows, use_dev, use_dev ? -1 : it, advance);
   }
   GatherArgs a = gather_args(h, table, rows, use_dev, it, advance);
   a.bookkeeping = bookkeeping;
@@ -3190,9 +3222,31 @@ static int ensure_wanted_graph(dsact_handle* h) {
   return dsact_graph_build(h, steps, h->want_graph_flags);
 }
 
+bool has_ring(const dsact_handle* h) { return h->rb_act != nullptr; }
+
+// a coded ring that received a value missing from its table: the encoder raised the mapped host word (read here without a
+// sync); the device record is read once, after a drain, and every later call on the handle fails with it -- the ring holds
+// wrong codes for those elements
+int check_codes(dsact_handle* h) {
+  if (!h->miss_host || !*(volatile int*)h->miss_host) return DSACT_OK;
+  if (!h->miss_seen) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(&h->miss_rec, h->code_miss, sizeof(CodeMiss), hipMemcpyDeviceToHost));
+    h->miss_seen = true;
+  }
+  uint32_t bits = h->miss_rec.bits;
+  float v;
+  memcpy(&v, &bits, 4);
+  return fail(h, DSACT_E_INVALID, "hip_obs_codebook: %llu observation value(s) written to the coded ring are not in the codebook; "
+              "first recorded: %.9g (bits 0x%08x) at ring row %lld -- the ring holds wrong codes for them",
+              h->miss_rec.count, (double)v, bits, h->miss_rec.row);
+}
+
 int check_ready(dsact_handle* h, bool need_batch) {
   if (!h) return DSACT_E_INVALID;
   TRY(check_handoff(h));
+  TRY(check_codes(h));
   if (h->state_invalid)
     return fail(h, DSACT_E_STATE, "device state is invalid after a hand-over timeout: restore parameters / optimiser state, then "
                                   "call dsact_set_state or dsact_bind_arenas");
@@ -3614,6 +3668,10 @@ int dsact_destroy(dsact_handle* h) {
   if (h->stage_img) hipFree(h->stage_img);
   for (float* p : {h->rb_obs, h->rb_obs2, h->rb_act, h->rb_rew, h->rb_done, h->rb_logp})
     if (p) hipFree(p);
+  if (h->rb_code) hipFree(h->rb_code);
+  if (h->code_book) hipFree(h->code_book);
+  if (h->code_miss) hipFree(h->code_miss);
+  if (h->miss_host) hipHostFree(h->miss_host);
   if (h->ws) hipFree(h->ws);
   if (h->aux_stream) { hipStreamSynchronize(h->aux_stream); hipStreamDestroy(h->aux_stream); }
   for (int j = 0; j <= kMaxConv; ++j) if (h->ev_conv[j]) hipEventDestroy(h->ev_conv[j]);
@@ -3759,21 +3817,14 @@ int dsact_set_hyper(dsact_handle* h, int32_t which, double value) {
   return DSACT_OK;
 }
 
-int dsact_buffer_create(dsact_handle* h, int64_t capacity) {
-  if (!h || capacity < 1) return DSACT_E_INVALID;
-  if (capacity > 2147483647LL) return fail(h, DSACT_E_INVALID, "capacity must fit int32 (device indices)");
-  HIPCHK(h, hipSetDevice(h->device));
-  if (h->rb_obs) return fail(h, DSACT_E_STATE, "buffer already created");
+namespace {
+// the columns both kinds of ring share; the caller has allocated (and zeroed) the observation columns
+int create_scalar_columns(dsact_handle* h, int64_t capacity) {
   const size_t N = (size_t)capacity;
-  HIPCHK(h, hipMalloc(&h->rb_obs, N * h->O * sizeof(float)));
-  HIPCHK(h, hipMalloc(&h->rb_obs2, N * h->O * sizeof(float)));
   HIPCHK(h, hipMalloc(&h->rb_act, N * h->A * sizeof(float)));
   HIPCHK(h, hipMalloc(&h->rb_rew, N * sizeof(float)));
   HIPCHK(h, hipMalloc(&h->rb_done, N * sizeof(float)));
   HIPCHK(h, hipMalloc(&h->rb_logp, N * sizeof(float)));
-  // replay_buffer.py:25-38: zero-initialised
-  HIPCHK(h, hipMemsetAsync(h->rb_obs, 0, N * h->O * sizeof(float), h->stream));
-  HIPCHK(h, hipMemsetAsync(h->rb_obs2, 0, N * h->O * sizeof(float), h->stream));
   HIPCHK(h, hipMemsetAsync(h->rb_act, 0, N * h->A * sizeof(float), h->stream));
   HIPCHK(h, hipMemsetAsync(h->rb_rew, 0, N * sizeof(float), h->stream));
   HIPCHK(h, hipMemsetAsync(h->rb_done, 0, N * sizeof(float), h->stream));
@@ -3781,14 +3832,96 @@ int dsact_buffer_create(dsact_handle* h, int64_t capacity) {
   h->cap = capacity; h->ptr = 0; h->size = 0;
   return DSACT_OK;
 }
+}  // namespace
+
+int dsact_buffer_create(dsact_handle* h, int64_t capacity) {
+  if (!h || capacity < 1) return DSACT_E_INVALID;
+  if (capacity > 2147483647LL) return fail(h, DSACT_E_INVALID, "capacity must fit int32 (device indices)");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (has_ring(h)) return fail(h, DSACT_E_STATE, "buffer already created");
+  const size_t N = (size_t)capacity;
+  HIPCHK(h, hipMalloc(&h->rb_obs, N * h->O * sizeof(float)));
+  HIPCHK(h, hipMalloc(&h->rb_obs2, N * h->O * sizeof(float)));
+  // replay_buffer.py:25-38: zero-initialised
+  HIPCHK(h, hipMemsetAsync(h->rb_obs, 0, N * h->O * sizeof(float), h->stream));
+  HIPCHK(h, hipMemsetAsync(h->rb_obs2, 0, N * h->O * sizeof(float), h->stream));
+  return create_scalar_columns(h, capacity);
+}
+
+int dsact_buffer_create_coded(dsact_handle* h, int64_t capacity, const float* codebook, int32_t n_codes) {
+  if (!h || capacity < 1 || !codebook) return DSACT_E_INVALID;
+  if (capacity > 2147483647LL) return fail(h, DSACT_E_INVALID, "capacity must fit int32 (device indices)");
+  if (n_codes < 1 || n_codes > 256) return fail(h, DSACT_E_INVALID, "hip_obs_codebook: %d entries (1 .. 256)", (int)n_codes);
+  for (int i = 0; i < n_codes; ++i) {
+    if (!(codebook[i] == codebook[i])) return fail(h, DSACT_E_INVALID, "hip_obs_codebook: entry %d is NaN", i);
+    if (i && !(codebook[i - 1] < codebook[i]))
+      return fail(h, DSACT_E_INVALID, "hip_obs_codebook: entries %d, %d are not strictly ascending (%.9g, %.9g)", i - 1, i,
+                  (double)codebook[i - 1], (double)codebook[i]);
+  }
+  if (!h->cnn) return fail(h, DSACT_E_INVALID, "hip_obs_codebook: codes are for image observations (C, H, W); this handle has flat ones");
+  const int C = h->cfg.img_c, HW = h->cfg.img_h * h->cfg.img_w;
+  if (HW % 16 || C > 16)
+    return fail(h, DSACT_E_INVALID, "hip_obs_codebook: a coded ring needs H * W %% 16 == 0 and C <= 16 (got C %d, H * W %d)", C, HW);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (has_ring(h)) return fail(h, DSACT_E_STATE, "buffer already created");
+  const size_t N = (size_t)capacity, O = (size_t)h->O;
+  HIPCHK(h, hipMalloc(&h->rb_code, 2 * N * O));
+  HIPCHK(h, hipMemsetAsync(h->rb_code, 0, 2 * N * O, h->stream));   // rows never written hold code 0 (never sampled)
+  float book[256] = {};
+  memcpy(book, codebook, (size_t)n_codes * sizeof(float));
+  HIPCHK(h, hipMalloc(&h->code_book, sizeof(book)));
+  HIPCHK(h, hipMemcpy(h->code_book, book, sizeof(book), hipMemcpyHostToDevice));
+  h->n_codes = n_codes;
+  HIPCHK(h, hipMalloc(&h->code_miss, sizeof(CodeMiss)));
+  HIPCHK(h, hipMemset(h->code_miss, 0, sizeof(CodeMiss)));
+  HIPCHK(h, hipHostMalloc((void**)&h->miss_host, 64, hipHostMallocMapped | hipHostMallocCoherent));
+  *(volatile int*)h->miss_host = 0;
+  HIPCHK(h, hipHostGetDevicePointer((void**)&h->miss_dev, h->miss_host, 0));
+  if (coded_gather_lds(C) > 64 * 1024)
+    HIPCHK(h, hipFuncSetAttribute((const void*)k_gather_img_coded<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)coded_gather_lds(C)));
+  return create_scalar_columns(h, capacity);
+}
+
+int dsact_buffer_check(dsact_handle* h) {
+  if (!h) return DSACT_E_INVALID;
+  if (!has_ring(h)) return fail(h, DSACT_E_STATE, "buffer not created");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return check_codes(h);
+}
+
+int64_t dsact_buffer_bytes(const dsact_handle* h) {
+  if (!h) return -1;
+  if (!has_ring(h)) return 0;
+  const int64_t O = h->O, A = h->A;
+  const int64_t obs_bytes = h->rb_code ? 2 * O : 4 * 2 * O;
+  return h->cap * (obs_bytes + 4 * (A + 3));
+}
 
 int64_t dsact_buffer_size(const dsact_handle* h) { return h ? h->size : -1; }
 int64_t dsact_buffer_ptr(const dsact_handle* h) { return h ? h->ptr : -1; }
 
+namespace {
+// fp32 image rows (row i at i * O, device memory) -> codes of ring rows (ptr + i) % cap
+int enqueue_ring_encode(dsact_handle* h, const float* s_obs, const float* s_obs2, long long ptr, long long n) {
+  CodedScatterArgs e;
+  e.s_obs = s_obs; e.s_obs2 = s_obs2;
+  e.code0 = h->rb_code; e.code1 = h->rb_code + (size_t)h->cap * h->O;
+  e.book = h->code_book; e.n_codes = h->n_codes; e.miss = h->code_miss; e.miss_flag = h->miss_dev;
+  e.ptr = ptr; e.cap = h->cap; e.n = (int)n; e.O = h->O;
+  e.wide = (h->O % 4 == 0) && ((uintptr_t)s_obs % 16 == 0) && ((uintptr_t)s_obs2 % 16 == 0);
+  const long long per_row = e.wide ? h->O / 4 : h->O;
+  const unsigned gx = (unsigned)std::min<long long>((per_row + kThreads - 1) / kThreads, 64);
+  const unsigned rows = (unsigned)(n < 65535 ? n : 65535);   // (grid y limit: the kernel strides over the rest)
+  return launch(h, "ring_write_img_coded", k_ring_write_img_coded, dim3(gx, rows, 2), dim3(kThreads), 0, e);
+}
+}  // namespace
+
 int dsact_buffer_add(dsact_handle* h, int64_t n, const float* obs, const float* act, const float* rew,
                      const float* obs2, const float* done, const float* logp) {
   if (!h || n < 0 || !obs || !act || !rew || !obs2 || !done) return DSACT_E_INVALID;
-  if (!h->rb_obs) return fail(h, DSACT_E_STATE, "buffer not created");
+  if (!has_ring(h)) return fail(h, DSACT_E_STATE, "buffer not created");
+  TRY(check_codes(h));
   if (n == 0) return DSACT_OK;
   HIPCHK(h, hipSetDevice(h->device));
   const size_t O = h->O, A = h->A;
@@ -3835,7 +3968,10 @@ int dsact_buffer_add(dsact_handle* h, int64_t n, const float* obs, const float* 
   a.s_rew = s_rew + first; a.s_done = s_done + first; a.s_logp = logp ? s_logp + first : nullptr;
   a.rb_obs = h->rb_obs; a.rb_obs2 = h->rb_obs2; a.rb_act = h->rb_act; a.rb_rew = h->rb_rew; a.rb_done = h->rb_done; a.rb_logp = h->rb_logp;
   a.ptr = (h->ptr + first) % h->cap; a.cap = h->cap; a.n = (int)cnt; a.O = h->O; a.A = h->A;
-  if (h->cnn) {
+  if (h->rb_code) {
+    TRY(enqueue_ring_encode(h, a.s_obs, a.s_obs2, a.ptr, cnt));
+    a.O = 0;
+  } else if (h->cnn) {
     // image rows are wide (C*H*W floats): a grid of blocks per row for the two images, the wave-per-row
     // kernel for the narrow columns
     ImgScatterArgs w;
@@ -3853,24 +3989,30 @@ int dsact_buffer_add(dsact_handle* h, int64_t n, const float* obs, const float* 
 int dsact_buffer_fill_device(dsact_handle* h, int64_t row0, int64_t n, const float* obs, const float* act,
                              const float* rew, const float* obs2, const float* done) {
   if (!h || row0 < 0 || n < 0) return DSACT_E_INVALID;
-  if (!h->rb_obs) return fail(h, DSACT_E_STATE, "buffer not created");
+  if (!has_ring(h)) return fail(h, DSACT_E_STATE, "buffer not created");
   if (row0 + n > h->cap) return fail(h, DSACT_E_INVALID, "fill exceeds capacity");
+  TRY(check_codes(h));
   HIPCHK(h, hipSetDevice(h->device));
   const size_t O = h->O, A = h->A;
-  HIPCHK(h, hipMemcpyAsync(h->rb_obs + row0 * O, obs, n * O * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->rb_obs2 + row0 * O, obs2, n * O * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  if (h->rb_code) {
+    if (n > 0) TRY(enqueue_ring_encode(h, obs, obs2, row0, n));   // (row0 + n <= cap: no wrap)
+  } else {
+    HIPCHK(h, hipMemcpyAsync(h->rb_obs + row0 * O, obs, n * O * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->rb_obs2 + row0 * O, obs2, n * O * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  }
   HIPCHK(h, hipMemcpyAsync(h->rb_act + row0 * A, act, n * A * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(h->rb_rew + row0, rew, n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(h->rb_done + row0, done, n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (row0 + n > h->size) h->size = row0 + n;
   h->ptr = (row0 + n) % h->cap;
-  return DSACT_OK;
+  return check_codes(h);
 }
 
 int dsact_gather(dsact_handle* h, const int64_t* idx_host, int32_t batch) {
   if (!h || !idx_host) return DSACT_E_INVALID;
-  if (!h->rb_obs) return fail(h, DSACT_E_STATE, "buffer not created");
+  if (!has_ring(h)) return fail(h, DSACT_E_STATE, "buffer not created");
+  TRY(check_codes(h));
   if (batch != h->B) return fail(h, DSACT_E_INVALID, "batch %d != configured batch %d", batch, h->B);
   if (h->size == 0) return fail(h, DSACT_E_STATE, "buffer empty");
   HIPCHK(h, hipSetDevice(h->device));
@@ -3885,7 +4027,7 @@ int dsact_gather(dsact_handle* h, const int64_t* idx_host, int32_t batch) {
   HIPCHK(h, hipEventRecord(h->h_idx_ev[slot], h->stream));
   // bookkeeping (iteration, counters) is done by the step call; this gather only stages rows
   if (h->cnn) {
-    TRY(enqueue_gather_img(h, h->rb_obs, h->rb_obs2, h->idx_eager, 1, 0, true, h->img[0], h->img[1], h->B));
+    TRY(enqueue_gather_ring_img(h, h->idx_eager, 1, 0));
     h->have_batch = true;
     return DSACT_OK;
   }
@@ -3974,7 +4116,7 @@ int dsact_load_batch(dsact_handle* h, const float* obs, const float* act, const 
 
 int dsact_upload_index_table(dsact_handle* h, const int64_t* idx_host, int32_t rows) {
   if (!h || !idx_host || rows < 1) return DSACT_E_INVALID;
-  if (!h->rb_obs) return fail(h, DSACT_E_STATE, "buffer not created");
+  if (!has_ring(h)) return fail(h, DSACT_E_STATE, "buffer not created");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   const size_t n = (size_t)rows * h->B;
@@ -4482,6 +4624,7 @@ static int set_device_iteration(dsact_handle* h, long long it) {
 int dsact_graph_run(dsact_handle* h, int64_t first_iteration, int64_t n_steps) {
   if (!h) return DSACT_E_INVALID;
   TRY(check_handoff(h));
+  TRY(check_codes(h));
   if (h->state_invalid)
     return fail(h, DSACT_E_STATE, "device state is invalid after a hand-over timeout: restore parameters / optimiser state, then "
                                   "call dsact_set_state or dsact_bind_arenas");
@@ -4509,7 +4652,7 @@ int dsact_graph_run(dsact_handle* h, int64_t first_iteration, int64_t n_steps) {
 int dsact_run_group(dsact_handle* h, int64_t first_iteration, int32_t n_steps, const int64_t* idx, const float* noise, uint32_t flags) {
   if (!h || !idx || n_steps < 1) return DSACT_E_INVALID;
   TRY(check_ready(h, false));
-  if (!h->rb_obs) return fail(h, DSACT_E_STATE, "buffer not created");
+  if (!has_ring(h)) return fail(h, DSACT_E_STATE, "buffer not created");
   if (h->size == 0) return fail(h, DSACT_E_STATE, "buffer empty");
   if (!noise && h->rng_seed == 0) return fail(h, DSACT_E_STATE, "no noise source: pass the noise rows or call dsact_set_device_rng");
   if ((flags & DSACT_F_SKIP_ACTOR_ON_OFF_ITERS) && (n_steps % h->cfg.delay_update || first_iteration % h->cfg.delay_update))

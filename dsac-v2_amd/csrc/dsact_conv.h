@@ -1322,4 +1322,195 @@ __global__ void __launch_bounds__(kThreads) k_ring_write_img(ImgScatterArgs a) {
 }
 #endif
 
+// ---------------------------------------------------------------------------------------------
+// coded image ring (dsact_buffer_create_coded): the obs / obs2 columns hold one byte per element, an index into a table of
+// at most 256 strictly ascending float32 values (CarRacing: float32(arange(256) / 255)). The writer encodes by binary search
+// plus a bit-equality check, the gather decodes through the table in LDS into the same pixel-major fp32 staging as
+// k_gather_img -- a value comes back with the bit pattern it was stored with. Ring byte offsets are size_t throughout
+// (a CarRacing code column passes 2^31 bytes at 77.7k rows).
+// ---------------------------------------------------------------------------------------------
+constexpr int kCodeTile = 1024;   // pixels of one plane per wave in the gather: 64 lanes x 16 codes (one 16-byte load)
+
+// values missing from the table: a count, the first miss recorded (its bits and ring row), and a word in mapped host memory
+// the host polls without a stream sync (a plain system-scope store, no atomics over the bus)
+struct CodeMiss {
+  unsigned long long count;
+  int claimed; unsigned int bits; long long row;
+};
+
+struct CodedScatterArgs {
+  const float* s_obs; const float* s_obs2;   // fp32 rows, row i at i * O
+  uint8_t* code0; uint8_t* code1;            // ring codes, ring row r at r * O
+  const float* book; int n_codes;
+  CodeMiss* miss; int* miss_flag;
+  long long ptr, cap; int n; long long O;
+  int wide;                                  // O % 4 == 0 and 16-byte aligned sources: 4 elements per lane
+};
+#ifndef DSACT_FAMILY_UNIT   // plain kernels: compiled in dsact_api.hip only (dsact_tu.h)
+// largest k with t[k] <= v (0 if none): 8 halving steps cover 256 entries; a hit needs the same bits (NaN, -0.0 vs 0.0)
+__device__ __forceinline__ unsigned code_of(const float* t, int n, float v, bool& ok) {
+  int k = 0;
+#pragma unroll
+  for (int s = 128; s >= 1; s >>= 1)
+    if (k + s < n && t[k + s] <= v) k += s;
+  ok = __float_as_uint(t[k]) == __float_as_uint(v);
+  return (unsigned)k;
+}
+
+__device__ __noinline__ void record_code_miss(CodeMiss* m, int* flag, float v, long long row, unsigned cnt) {
+  atomicAdd(&m->count, (unsigned long long)cnt);
+  if (atomicCAS(&m->claimed, 0, 1) == 0) { m->bits = __float_as_uint(v); m->row = row; }
+  __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// grid (x chunks, rows, image): a lane encodes 4 consecutive elements (one 16-byte load, one 4-byte store of codes; the
+// wave's stores are 256 contiguous bytes). The 8 dependent LDS reads of each search make the kernel latency-bound, not
+// bandwidth-bound: 4 elements per lane (not 16) give 4x the waves to hide them (an add of 8 CarRacing rows: 19.3 -> 5.8 us;
+// the fp32 ring's k_ring_write_img: 7.6 us)
+__global__ void __launch_bounds__(kThreads) k_ring_write_img_coded(CodedScatterArgs a) {
+  __shared__ float t[256];
+  t[threadIdx.x] = (int)threadIdx.x < a.n_codes ? a.book[threadIdx.x] : 0.f;   // kThreads == 256
+  __syncthreads();
+  const int n = a.n_codes, img = blockIdx.z;
+  const long long nq = a.wide ? a.O >> 2 : a.O;
+  for (int i = blockIdx.y; i < a.n; i += gridDim.y) {
+    const long long dst = (a.ptr + i) % a.cap;
+    {
+      const float* s = (img ? a.s_obs2 : a.s_obs) + (size_t)i * a.O;
+      uint8_t* d = (img ? a.code1 : a.code0) + (size_t)dst * a.O;
+      for (long long q = (long long)blockIdx.x * kThreads + threadIdx.x; q < nq; q += (long long)gridDim.x * kThreads) {
+        unsigned miss = 0;
+        float bad = 0.f;
+        if (a.wide) {
+          const f32x4 v = *(const f32x4*)(s + 4 * q);
+          uint32_t w = 0;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            bool ok;
+            w |= code_of(t, n, v[e], ok) << (8 * e);
+            if (!ok) { bad = miss ? bad : v[e]; ++miss; }
+          }
+          *(uint32_t*)(d + 4 * q) = w;
+        } else {
+          bool ok;
+          d[q] = (uint8_t)code_of(t, n, s[q], ok);
+          if (!ok) { bad = s[q]; miss = 1; }
+        }
+        if (miss) record_code_miss(a.miss, a.miss_flag, bad, dst, miss);
+      }
+    }
+  }
+}
+
+struct ImgCodedGatherArgs {
+  ImgGatherArgs g;              // everything but g.rb_obs / g.rb_obs2 (unused)
+  const uint8_t* code0; const uint8_t* code1; const float* book; int n_codes;
+  int tiles;                    // kCodeTile-pixel tiles per plane; one wave per (minibatch row, tile)
+  int n_gather_blocks;          // blocks [n_gather_blocks, ...) refresh the padded first-layer weights
+};
+// dynamic LDS: the table (1 KiB), then per wave [image][plane][kCodeTile] codes
+inline size_t coded_gather_lds(int C) { return 1024 + (size_t)(kThreads / 64) * 2 * C * kCodeTile; }
+
+// CT: channels known at compile time (3: type_2 RGB, 4: type_1), a lane per 4-pixel group -- one dword of codes per plane,
+// CT 16-byte stores per image, the store pattern of k_gather_img's RGB path; 0: any C, a lane per output quad (byte reads)
+template <int CT>
+__global__ void __launch_bounds__(kThreads) k_gather_img_coded(ImgCodedGatherArgs a) {
+  const ImgGatherArgs& g = a.g;
+  if ((int)blockIdx.x >= a.n_gather_blocks) {
+    repack_rows(g.rp, (int)blockIdx.x - a.n_gather_blocks, threadIdx.x);
+    return;
+  }
+  extern __shared__ __align__(16) unsigned char lds_codes[];
+  float* tab = (float*)lds_codes;
+  tab[threadIdx.x] = (int)threadIdx.x < a.n_codes ? a.book[threadIdx.x] : 0.f;   // kThreads == 256
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wg = blockIdx.x * (kThreads / 64) + wave;
+  if (wg >= g.B * a.tiles) return;
+  const int r = wg / a.tiles, tile = wg - r * a.tiles;
+  const int trow = g.use_dev ? (int)(g.st->seq_next % g.idx_rows) : g.host_row;
+  const long long src = g.idx_table[(size_t)trow * g.B + r];
+  const int C = CT ? CT : g.C;
+  const size_t O = (size_t)C * g.HW;
+  const int p0 = tile * kCodeTile;
+  const int np = min(kCodeTile, g.HW - p0);   // HW % 16 == 0 (checked at create time): whole 16-code groups
+  uint8_t* w_lds = lds_codes + 1024 + (size_t)wave * 2 * C * kCodeTile;
+  if (16 * lane < np) {
+    const uint8_t* s0 = a.code0 + (size_t)src * O + p0 + 16 * lane;
+    const uint8_t* s2 = a.code1 + (size_t)src * O + p0 + 16 * lane;
+    if constexpr (CT != 0) {
+      uint4 v[2 * CT];   // every load in flight before the first LDS write
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        v[c] = *(const uint4*)(s0 + (size_t)c * g.HW);
+        v[C + c] = *(const uint4*)(s2 + (size_t)c * g.HW);
+      }
+#pragma unroll
+      for (int k = 0; k < 2 * C; ++k) *(uint4*)(w_lds + (size_t)k * kCodeTile + 16 * lane) = v[k];
+    } else {
+      for (int c = 0; c < C; ++c) {
+        const uint4 v0 = *(const uint4*)(s0 + (size_t)c * g.HW), v2 = *(const uint4*)(s2 + (size_t)c * g.HW);
+        *(uint4*)(w_lds + (size_t)c * kCodeTile + 16 * lane) = v0;
+        *(uint4*)(w_lds + (size_t)(C + c) * kCodeTile + 16 * lane) = v2;
+      }
+    }
+  }
+  // the tile is the wave's own: a wave barrier orders the LDS writes before the other lanes' reads
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  if constexpr (CT != 0) {
+    for (int P = lane; 4 * P < np; P += 64) {
+#pragma unroll
+      for (int img = 0; img < 2; ++img) {
+        uint32_t w[CT];
+#pragma unroll
+        for (int c = 0; c < CT; ++c) w[c] = *(const uint32_t*)(w_lds + (size_t)(img * CT + c) * kCodeTile + 4 * P);
+        float* d = (img ? g.img2 : g.img0) + (size_t)r * O + (size_t)(p0 + 4 * P) * CT;
+#pragma unroll
+        for (int j = 0; j < CT; ++j) {   // output quad j holds elements 4j .. 4j+3 of (pixel e, channel c) = e*CT + c
+          f32x4 v;
+#pragma unroll
+          for (int e4 = 0; e4 < 4; ++e4) {
+            const int o = 4 * j + e4;
+            v[e4] = tab[(w[o % CT] >> (8 * (o / CT))) & 255u];
+          }
+          *(f32x4*)(d + 4 * j) = v;
+        }
+      }
+    }
+  } else {
+    const float inv_c = 1.0f / (float)C;
+    const int nq = np * C / 4;
+    for (int q = lane; q < nq; q += 64) {
+      f32x4 v, w;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int o = q * 4 + e;
+        const int pix = fast_div(o, C, inv_c), c = o - pix * C;
+        v[e] = tab[w_lds[(size_t)c * kCodeTile + pix]];
+        w[e] = tab[w_lds[(size_t)(C + c) * kCodeTile + pix]];
+      }
+      *(f32x4*)(g.img0 + (size_t)r * O + (size_t)p0 * C + 4 * q) = v;
+      *(f32x4*)(g.img2 + (size_t)r * O + (size_t)p0 * C + 4 * q) = w;
+    }
+  }
+  if (tile == 0) {   // the row's replayed action / reward / done and its step-flow duties (k_gather_img's chunk-0 block)
+    if (g.rb_act) {
+      for (int t = lane; t < g.A; t += 64) {
+        const float av = g.rb_act[(size_t)src * g.A + t];
+        g.Xa0[(size_t)r * g.ldx + g.F + t] = av;
+        g.Xa1[(size_t)r * g.ldx + g.F + t] = av;
+      }
+      if (lane == 0) { g.rew[r] = g.rb_rew[src]; g.done[r] = g.rb_done[src]; }
+    }
+    if (g.bookkeeping) {
+      const long long it = g.use_dev ? g.st->it_next : g.host_it;
+      if (g.nz.seed != 0) fill_noise_rows(g.nz, it, trow, r, r + 1, g.A, lane, 64);
+      if (wg == 0 && lane == 0) prologue_duties(g.stw, it, g.advance_counters, g.hp);
+    }
+  }
+}
+#endif
+
 }  // namespace dsact

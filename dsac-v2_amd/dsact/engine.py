@@ -234,9 +234,22 @@ class DsactEngine:
         self._graph_steps = 0
 
     # ---- replay ring -------------------------------------------------------------------------------
-    def buffer_create(self, capacity: int):
-        self._chk(self._lib.dsact_buffer_create(self._h, int(capacity)))
+    def buffer_create(self, capacity: int, codebook=None):
+        """codebook: None (fp32 ring) or the validated float32 table of a coded image ring (dsact_buffer_create_coded)"""
+        if codebook is None:
+            self._chk(self._lib.dsact_buffer_create(self._h, int(capacity)))
+        else:
+            book = np.ascontiguousarray(codebook, dtype=np.float32)
+            self._chk(self._lib.dsact_buffer_create_coded(self._h, int(capacity), _ffi.fptr(book), int(book.shape[0])))
         self.buffer_capacity = int(capacity)
+
+    def buffer_check(self):
+        """dsact_buffer_check: drains the stream; raises if a value missing from the codebook was written"""
+        self._chk(self._lib.dsact_buffer_check(self._h))
+
+    @property
+    def buffer_bytes(self):
+        return int(self._lib.dsact_buffer_bytes(self._h))
 
     def buffer_add(self, obs, act, rew, obs2, done, logp=None):
         obs, act, rew, obs2, done = _f32(obs), _f32(act), _f32(rew), _f32(obs2), _f32(done)

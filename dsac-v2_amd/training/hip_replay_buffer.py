@@ -9,12 +9,46 @@ NumPy RandomState (`np.random.randint(0, size, batch)`, bit-exact by constructio
 same call is made here on the host), `sample_batch` returns a dict with keys
 obs/obs2/act/rew/done/logp. The rows live in HBM; the gather is a HIP kernel (k_gather) that writes
 straight into the update's staging area, and the returned `HipBatch` is a token for it.
+
+`hip_obs_codebook=table` (image observations only) stores the obs / obs2 columns as one byte per element, an index into
+`table` (at most 256 float32 values, strictly ascending): a quarter of the fp32 ring's bytes, bit-identical minibatches.
+CarRacing's frames (`rgb / 255` cast to float32) take `np.float32(np.arange(256) / 255.0)`. See parse_obs_codebook.
 """
 import numpy as np
 
 from dsact.engine import DsactEngine, current_engine
 
-__all__ = ["HipReplayBuffer"]
+__all__ = ["HipReplayBuffer", "parse_obs_codebook"]
+
+MAX_CODES = 256
+
+
+def parse_obs_codebook(table, obs_shape):
+    """Validates `hip_obs_codebook` for observations of shape `obs_shape` and returns it as a float32 array (no GPU call).
+    The table is cast to float32 first and must then be strictly ascending as floats: no NaN, no duplicates, not both -0.0
+    and 0.0 (a stored value matches an entry only if the bit patterns are equal). Observations must be images (C, H, W)
+    with H * W % 16 == 0 and C <= 16 (the coded gather loads 16 codes of a plane per lane)."""
+    shape = tuple(int(d) for d in obs_shape)
+    if len(shape) != 3:
+        raise NotImplementedError("hip_obs_codebook: codes are for image observations (C, H, W); obsv_dim %r is not one" % (shape,))
+    C, H, W = shape
+    if (H * W) % 16 or C > 16:
+        raise NotImplementedError("hip_obs_codebook: a coded ring needs H * W %% 16 == 0 and C <= 16 (obsv_dim %r)" % (shape,))
+    t = np.asarray(table)
+    if t.ndim != 1 or t.size == 0:
+        raise ValueError("hip_obs_codebook: a 1-D list of 1 .. %d values, got shape %r" % (MAX_CODES, t.shape))
+    if t.size > MAX_CODES:
+        raise ValueError("hip_obs_codebook: %d entries, at most %d (one byte per code)" % (t.size, MAX_CODES))
+    with np.errstate(invalid="ignore", over="ignore"):
+        f = np.ascontiguousarray(t.astype(np.float32))
+    if np.isnan(f).any():
+        raise ValueError("hip_obs_codebook: entry %d is NaN" % int(np.flatnonzero(np.isnan(f))[0]))
+    bad = np.flatnonzero(~(f[1:] > f[:-1]))
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError("hip_obs_codebook: after the float32 cast entries %d, %d are not strictly ascending (%r, %r); "
+                         "duplicates and a -0.0 / 0.0 pair are refused" % (i, i + 1, float(f[i]), float(f[i + 1])))
+    return f
 
 
 class HipReplayBuffer:
@@ -26,6 +60,8 @@ class HipReplayBuffer:
         self.max_size = int(kwargs["buffer_max_size"])
         if kwargs.get("additional_info"):
             raise NotImplementedError("additional_info is not supported by HipReplayBuffer")
+        book = kwargs.get("hip_obs_codebook")
+        self.codebook = None if book is None else parse_obs_codebook(book, self._obs_shape)
         eng = kwargs.get("hip_engine") or current_engine()
         B = int(kwargs["replay_batch_size"])
         if eng is None or eng.obs_dim != self._obs_flat or eng.act_dim != self.act_dim or eng.batch != B:
@@ -38,7 +74,7 @@ class HipReplayBuffer:
                 hidden = list(kwargs.get("value_hidden_sizes", [32]))
                 eng = DsactEngine(self._obs_flat, self.act_dim, hidden, B, device=int(kwargs.get("hip_device", 0)))
         self.engine = eng
-        self.engine.buffer_create(self.max_size)
+        self.engine.buffer_create(self.max_size, codebook=self.codebook)
 
     @property
     def size(self):
@@ -52,8 +88,13 @@ class HipReplayBuffer:
         return self.size
 
     def __get_RAM__(self):
-        row_bytes = 4 * (2 * self._obs_flat + self.act_dim + 3)
+        obs_bytes = 2 * self._obs_flat * (1 if self.codebook is not None else 4)
+        row_bytes = obs_bytes + 4 * (self.act_dim + 3)
         return row_bytes * self.size / 1e6  # MB resident in HBM
+
+    def check(self):
+        """synchronous: raises DsactError if an observation value missing from `hip_obs_codebook` was stored"""
+        self.engine.buffer_check()
 
     def store(self, obs, info, act, rew, next_obs, done, logp, next_info):
         self.add_batch([(obs, info, act, rew, next_obs, done, logp, next_info)])

@@ -204,6 +204,19 @@ int64_t dsact_buffer_ptr(const dsact_handle* h);
  * sets size=max(size,row0+n), ptr=(row0+n)%capacity */
 int dsact_buffer_fill_device(dsact_handle* h, int64_t row0, int64_t n, const float* obs, const float* act,
                              const float* rew, const float* obs2, const float* done);
+/* Coded image ring (CNN handles only; H*W % 16 == 0, C <= 16): instead of dsact_buffer_create. The obs / obs2 columns hold
+ * one byte per element, an index into codebook[0..n_codes) -- at most 256 float32 values, strictly ascending (no NaN, no
+ * duplicates, not both -0.0 and 0.0). dsact_buffer_add and dsact_buffer_fill_device still take fp32 rows and encode them
+ * on the device; a value matches an entry only if its bits are equal, so every stored value comes back bit for bit and
+ * everything downstream equals the fp32 ring. A value missing from the table is never rounded silently: the encoder counts
+ * it and records the first one seen, and every call on the handle that starts after that write has completed on the
+ * device (add, fill, gather, step, graph, group, data-parallel enqueues) fails with DSACT_E_INVALID naming it, as does
+ * dsact_buffer_check. Rows never written hold code 0. */
+int dsact_buffer_create_coded(dsact_handle* h, int64_t capacity, const float* codebook, int32_t n_codes);
+/* SYNCHRONOUS: drains the stream, then DSACT_E_INVALID if a value missing from the codebook was written (OK for fp32 rings) */
+int dsact_buffer_check(dsact_handle* h);
+/* device bytes of the ring: capacity * (2*O + 4*(A+3)) coded, capacity * 4*(2*O + A + 3) fp32; 0 before a create */
+int64_t dsact_buffer_bytes(const dsact_handle* h);
 /* gather rows idx[0..batch) into the handle's minibatch staging area (== sample_batch + .cuda()) */
 int dsact_gather(dsact_handle* h, const int64_t* idx_host, int32_t batch);
 /* copy the staged minibatch back to host arrays (any may be NULL); synchronous. `logp` comes from
