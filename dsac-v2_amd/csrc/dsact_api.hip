@@ -4325,8 +4325,10 @@ static int enqueue_graph_step_dp(dsact_handle* h) {
   }
   TRY(enqueue_allreduce(h, h->grads, h->n_online + 2, kNcclAvg));
   TRY(enqueue_prologue(h, 1, 0, 1, 0));
-  TRY(enqueue_adam(h));
-  return policy_moved(h);
+  // no policy_moved here: this runs inside a stream capture (capture_updates), where a snapshot copy would be captured into
+  // every replay and the epoch bookkeeping would claim a copy that never ran. The callers mark the policy moved themselves
+  // (dsact_graph_run after the launch; dsact_time_steps / dsact_profile_step(s) bump pol_epoch)
+  return enqueue_adam(h);
 }
 
 static int enqueue_graph_step(dsact_handle* h, long long iteration, uint32_t flags) {
@@ -4792,7 +4794,10 @@ int dsact_dp_enqueue_apply(dsact_handle* h) {
   TRY(check_ready(h, false));
   HIPCHK(h, hipSetDevice(h->device));
   TRY(enqueue_prologue(h, 1, 0, 1, 0));
-  return enqueue_adam(h);
+  TRY(enqueue_adam(h));
+  // the device iteration decides whether this update moves the policy; the host does not know it, so the snapshot is always
+  // refreshed (a redundant copy on an iteration that leaves the policy alone)
+  return policy_moved(h);
 }
 
 int dsact_comm_unique_id(const char* rccl_path, uint8_t id[128]) {
@@ -5215,6 +5220,7 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "handoff_failures")) *value = (double)h->handoff_failures;
   else if (!strcmp(name, "graph_steps")) *value = (double)h->graph_steps;
   else if (!strcmp(name, "pipe_graph")) *value = h->pipe_graph ? 1.0 : 0.0;   // the captured graphs are the pipelined ones
+  else if (!strcmp(name, "merged_graph")) *value = h->merged_graph ? 1.0 : 0.0;   // captured with the merged gather (else one enqueue_graph_step per update)
   else if (!strcmp(name, "state_invalid")) *value = h->state_invalid ? 1.0 : 0.0;
   else if (!strcmp(name, "act_batch_calls")) *value = (double)h->ab_calls;   // dsact_act_sample_batch chunks launched on the GPU
   else if (!strcmp(name, "act_fast")) *value = act_fast_ok(h) ? 1.0 : 0.0;     // dsact_act_sample / the one-launch acting forward serve this handle

@@ -63,6 +63,9 @@ class DataParallelUpdater:
         with self._on_engine_stream():
             for t in broadcast_tensors:
                 dist.broadcast(t, src=0, group=group)
+        # a collective writes the arenas past torch's version counters: the host-side acting snapshot is stale now
+        if hasattr(engine, "policy_dirty"):
+            engine.policy_dirty()
 
     def _on_engine_stream(self):
         ts = getattr(self.engine, "torch_stream", None)   # CPU stand-ins (gloo tests) have no stream

@@ -513,9 +513,11 @@ class DsactEngine:
         self._chk(self._lib.dsact_debug_set(self._h, b"policy_dirty", 1.0))
 
     def note_torch_writes(self, params):
-        """torch bumps a tensor's version counter on every in-place write: a changed sum over the policy's parameters
-        since the last look means somebody wrote them outside the library"""
-        v = sum(p._version for p in params)
+        """torch bumps a tensor's version counter on every in-place write: a changed sum over the policy's parameters and
+        the online arena itself (slice writes through `engine.online`; the parameters are re-homed with `p.data = view`, so
+        they do not share its counter) since the last look means somebody wrote them outside the library. Writes that no
+        counter sees (`p.data.copy_`, collectives, raw pointers) need an explicit policy_dirty()"""
+        v = sum(p._version for p in params) + self.online._version
         if v != getattr(self, "_param_versions", None):
             self._param_versions = v
             self.policy_dirty()

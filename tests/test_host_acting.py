@@ -21,14 +21,20 @@ pytestmark = pytest.mark.gpu
 
 
 def both_forwards(e, obs, eps):
-    """(action, logp, logits) through the host path and through the one-launch GPU forward on the same weights"""
+    """(action, logp, logits) through the host path and through the one-launch GPU forward on the same weights. The host
+    result is taken first, with no switch before it (a switch marks the snapshot stale and would hide an update path that
+    forgot to refresh it); the switch back is consumed by one more host call, so the next update's acting calls see only
+    what that update did."""
+    assert e.debug_get("act_host") == 1.0
     out = []
     for host in (1, 0):
-        e.debug_set("host_act", host)
-        assert e.debug_get("act_host") == float(host)
+        if not host:
+            e.debug_set("host_act", 0)
+            assert e.debug_get("act_host") == 0.0
         a, lp = e.act_sample(obs, eps)
         out.append((a.copy(), float(lp[0]), e.policy_forward(obs[None])[0].copy()))
     e.debug_set("host_act", 1)
+    e.act_sample(obs, eps)
     return out
 
 
@@ -91,7 +97,6 @@ def test_snapshot_follows_every_update_entry_point():
         return h[2]
 
     l0 = check("initial")
-    e.act_sample(obs, eps)                       # (check() toggles the host path off and on, which marks the snapshot stale)
     copies = e.debug_get("act_copies")
     # an update that leaves the policy alone (iteration 1, delay_update 2): no copy is enqueued, the logits stay
     e.gather(rows[0]); e.step(1)
