@@ -19,6 +19,11 @@
 // and log-probability are therefore bitwise independent of the batch around it. The sampling epilogue is tanh_gauss_fwd of
 // dsact_math.h (the closed form k_act_mlp and the host acting path use; half range 0 selects the plain Gaussian), and the
 // log-probability is summed over the action dimensions in order, as dsact_host_act.h's head() does.
+//
+// The evaluator's deterministic acting (training/evaluator.py:50-72 over N environments, dist.mode()) is the same output
+// launch with kMode = true: the K loop, its sums and the output activation are the sampling form's instruction for
+// instruction (a row's mean is bitwise the sampling kernel's), only the epilogue differs -- act_mode of dsact_math.h writes
+// the action, no eps is read and no log-probability is reduced.
 #pragma once
 #include "dsact_kernels.h"
 
@@ -37,7 +42,7 @@ struct ActBatchHidden {
   int n, act;
 };
 
-// the output layer (2A <= 64 features) + the sample: action[r][d], logp[r]
+// the output layer (2A <= 64 features) + the sample: action[r][d], logp[r]; with kMode the mode: action[r][d] only
 struct ActBatchOut {
   const float* X; int ldx;
   const float* W; const float* b;
@@ -45,8 +50,9 @@ struct ActBatchOut {
   int out_act, out_n;                  // policy_output_activation and the outputs it applies to (2A, or A: mean half only)
   const float* eps;                    // [n][A] standard-normal draws
   const float* scale; const float* center;   // action half range / centre (0 / 0: GaussDistribution)
+  const float* lo; const float* hi;          // action limits (kMode only: GaussDistribution.mode() clamps to them)
   float lo_ls, hi_ls;
-  float* action; float* logp;          // [n][A], [n]
+  float* action; float* logp;          // [n][A], [n] (kMode: logp unused)
 };
 
 #ifdef DSACT_ACT_BATCH_DEFINE   // the kernels themselves: csrc/dsact_tu_act_batch.hip; other units see the declarations
@@ -110,7 +116,8 @@ __global__ void __launch_bounds__(256) k_act_batch_hidden(ActBatchHidden a) {
 }
 
 // 8 rows x 64 outputs (mean | raw log-std, 2A <= 64) per workgroup; thread (tr, tf) = (tid / 32, tid % 32) owns row tr and
-// outputs tf, tf + 32. grid: x = row tiles
+// outputs tf, tf + 32. grid: x = row tiles. kMode: the mode instead of the sample (eps and logp are not touched)
+template <bool kMode>
 __global__ void __launch_bounds__(256) k_act_batch_out(ActBatchOut a) {
   constexpr int KC = 64;   // (the 64-row weight tile at 128 columns runs out of scalar registers)
   __shared__ float xs[8][KC + 1];
@@ -162,8 +169,12 @@ __global__ void __launch_bounds__(256) k_act_batch_out(ActBatchOut a) {
     }
   }
   __syncthreads();
-  // the sample, one (row, action dimension) per thread: tanh_gauss_fwd term for term
   const int r = r0 + tr, d = tf;
+  if constexpr (kMode) {   // dist.mode(), one (row, action dimension) per thread
+    if (r < a.n && d < a.A) a.action[(size_t)r * a.A + d] = act_mode(raw[tr][d], a.scale[d], a.center[d], a.lo[d], a.hi[d]);
+    return;
+  }
+  // the sample, one (row, action dimension) per thread: tanh_gauss_fwd term for term
   if (r < a.n && d < a.A) {
     const TanhGaussFwd g = tanh_gauss_fwd(raw[tr][d], raw[tr][a.A + d], a.eps[(size_t)r * a.A + d], a.scale[d], a.center[d],
                                           a.lo_ls, a.hi_ls);
@@ -178,9 +189,14 @@ __global__ void __launch_bounds__(256) k_act_batch_out(ActBatchOut a) {
     a.logp[r0 + tid] = lp;
   }
 }
+template __global__ void k_act_batch_out<false>(ActBatchOut);
+template __global__ void k_act_batch_out<true>(ActBatchOut);
 #else
 __global__ void k_act_batch_hidden(ActBatchHidden a);
+template <bool kMode>
 __global__ void k_act_batch_out(ActBatchOut a);
+extern template __global__ void k_act_batch_out<false>(ActBatchOut);
+extern template __global__ void k_act_batch_out<true>(ActBatchOut);
 #endif
 
 }  // namespace dsact

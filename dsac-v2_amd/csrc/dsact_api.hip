@@ -42,6 +42,10 @@ static const int kDzSlot[N_CHAIN] = {0, -1, 1, 2, -1, -1, 3, 4};
 
 constexpr int kMaxLin = DSACT_MAX_HIDDEN_LAYERS + 1;
 constexpr int kActRows = 64;  // rows of the stand-alone policy forward (sampler feed)
+// dsact_act_mode_batch: below this many rows a handle that acts on the host runs the host forward per row, from it on the
+// batched GPU forward (profiles/vec_eval_bench.json: Humanoid 3 x 256, host ~3.2 us per row against
+// 59-66 us per GPU call from 1 to 32 rows -- equal near 20)
+constexpr int kModeHostRows = 20;
 
 // One approximator inside its arena. nblk == 2: the CNN nets' twin `mean` / `log_std` MLPs laid side
 // by side (networks/cnn.py:224-229,447-450): layer 0 is one dense (2*H0 x in) matrix, hidden layers are
@@ -141,6 +145,7 @@ struct dsact_handle {
   float *part_loss, *part_heads, *stats, *ones, *std_sums;
   long long* timeline;  // [512][8] stamps of the stage named by DSACT_TIMELINE_STAGE (instrumented builds)
   float *act_scale, *act_center;
+  float *act_lo, *act_hi;   // the action limits themselves (the mode of a GaussDistribution clamps to them; act_scale is 0 there)
   DevState* st = nullptr;
   int* idx_eager = nullptr;
   int* idx_table = nullptr;
@@ -307,6 +312,7 @@ struct dsact_handle {
   unsigned act_repins = 0;
   int act_threads = 0;                  // 0: not calibrated yet; DSACT_HOST_ACT_THREADS forces a count
   float act_scale_h[32] = {0}, act_center_h[32] = {0};   // host copies of act_scale / act_center (act_dim <= 32 on this path)
+  float act_lo_h[32] = {0}, act_hi_h[32] = {0};           // ... and of act_lo / act_hi
   double act_host_us = 0.0, act_copy_wait_us = 0.0;
   // batched acting forward (dsact_act_batch.h), allocated by the first dsact_act_sample_batch: pinned staging of a chunk's
   // (obs | eps) rows, its device copy, two activation buffers, and the mapped host block the output launch writes
@@ -314,6 +320,8 @@ struct dsact_handle {
   float* ab_stage = nullptr; float* ab_in = nullptr; float* ab_h[2] = {nullptr, nullptr};
   float* ab_out_host = nullptr; float* ab_out_dev = nullptr;
   unsigned long long ab_calls = 0;
+  unsigned long long ab_mode_calls = 0;  // dsact_act_mode_batch chunks launched on the GPU
+  int mode_host_rows = kModeHostRows;   // dsact_act_mode_batch's host / GPU crossover (debug switch "mode_host_rows": measurements)
   unsigned long long act_host_calls = 0, act_copies = 0;
   bool env_no_conv_dx_mfma = false;     // DSACT_NO_CONV_DX_MFMA: the 16-channel layer's data gradient with k_conv_dx_block (A/B)
   bool fwd_merge = false;               // launches A and B as one (batch <= 256)
@@ -622,6 +630,8 @@ void carve(dsact_handle* h, Carver& c) {
   }
   h->act_scale = c.take<float>(A);
   h->act_center = c.take<float>(A);
+  h->act_lo = c.take<float>(A);
+  h->act_hi = c.take<float>(A);
   h->idx_eager = c.take<int>(B);
   h->Xact = c.take<float>((size_t)kActRows * h->ldx);
   for (int l = 0; l < L; ++l) h->Hact[l] = c.take<float>((size_t)kActRows * h->w[l]);
@@ -3744,7 +3754,12 @@ int dsact_set_action_limits(dsact_handle* h, const float* high, const float* low
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(h->act_scale, s.data(), h->A * sizeof(float), hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->act_center, c.data(), h->A * sizeof(float), hipMemcpyHostToDevice));
-  for (int j = 0; j < h->A && j < 32; ++j) { h->act_scale_h[j] = s[j]; h->act_center_h[j] = c[j]; }
+  HIPCHK(h, hipMemcpy(h->act_lo, low, h->A * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(h->act_hi, high, h->A * sizeof(float), hipMemcpyHostToDevice));
+  for (int j = 0; j < h->A && j < 32; ++j) {
+    h->act_scale_h[j] = s[j]; h->act_center_h[j] = c[j];
+    h->act_lo_h[j] = low[j]; h->act_hi_h[j] = high[j];
+  }
   h->limits_set = true;
   return DSACT_OK;
 }
@@ -5144,6 +5159,10 @@ int dsact_debug_set(dsact_handle* h, const char* name, double value) {
     if ((int)value & 2) ((volatile int*)h->handoff_host)[1] = 1;
     return DSACT_OK;
   }
+  if (!strcmp(name, "mode_host_rows")) {   // dsact_act_mode_batch takes the host route below this many rows (measurements)
+    h->mode_host_rows = (int)value;
+    return DSACT_OK;
+  }
   if (!strcmp(name, "host_act")) {      // 1: acting forward on the host (default), 0: the one-launch GPU forward (A/B, tests)
     h->host_act = value != 0.0;
     h->pol_epoch++;
@@ -5223,6 +5242,8 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "merged_graph")) *value = h->merged_graph ? 1.0 : 0.0;   // captured with the merged gather (else one enqueue_graph_step per update)
   else if (!strcmp(name, "state_invalid")) *value = h->state_invalid ? 1.0 : 0.0;
   else if (!strcmp(name, "act_batch_calls")) *value = (double)h->ab_calls;   // dsact_act_sample_batch chunks launched on the GPU
+  else if (!strcmp(name, "act_mode_calls")) *value = (double)h->ab_mode_calls;   // dsact_act_mode_batch chunks launched on the GPU
+  else if (!strcmp(name, "mode_host_rows")) *value = (double)h->mode_host_rows;
   else if (!strcmp(name, "act_fast")) *value = act_fast_ok(h) ? 1.0 : 0.0;     // dsact_act_sample / the one-launch acting forward serve this handle
   else if (!strcmp(name, "graph_cache")) *value = (double)h->graph_cache.size();   // inactive captured graphs kept by dsact_run_group
   else if (!strcmp(name, "graph_noise_table")) *value = h->graph_noise_table ? 1.0 : 0.0;
@@ -5317,15 +5338,12 @@ static bool is_device_ptr(const void* p) {
   if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // (pageable host memory)
   return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
 }
-int dsact_act_sample_batch(dsact_handle* h, const float* obs, int32_t n, const float* eps, float* action_host, float* logp_host) {
-  if (!h || !obs || !eps || !action_host || !logp_host || n < 1) return DSACT_E_INVALID;
-  if (!h->online) return fail(h, DSACT_E_STATE, "arenas not bound");
-  if (!h->limits_set) return fail(h, DSACT_E_STATE, "action limits not set (dsact_set_action_limits)");
-  if (h->cnn) return fail(h, DSACT_E_INVALID, "dsact_act_sample_batch serves MLP policies (CNN: dsact_policy_forward)");
-  if (h->A > 32) return fail(h, DSACT_E_INVALID, "dsact_act_sample_batch serves act_dim <= 32");
+// the batched forward of both entry points below: eps != nullptr samples (action, logp), eps == nullptr writes the mode
+static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const float* eps, float* action_host, float* logp_host) {
   HIPCHK(h, hipSetDevice(h->device));
   TRY(check_handoff(h));
   const int O = h->O, A = h->A, R = kActBatchCap;
+  const bool mode = eps == nullptr;
   if (!h->ab_in) {
     HIPCHK(h, hipHostMalloc((void**)&h->ab_stage, (size_t)R * (O + A) * sizeof(float), hipHostMallocDefault));
     HIPCHK(h, hipMalloc((void**)&h->ab_in, (size_t)R * (O + A) * sizeof(float)));
@@ -5333,7 +5351,7 @@ int dsact_act_sample_batch(dsact_handle* h, const float* obs, int32_t n, const f
     HIPCHK(h, hipHostMalloc((void**)&h->ab_out_host, (size_t)R * (A + 1) * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
     HIPCHK(h, hipHostGetDevicePointer((void**)&h->ab_out_dev, h->ab_out_host, 0));
   }
-  const bool obs_dev = is_device_ptr(obs), eps_dev = is_device_ptr(eps);
+  const bool obs_dev = is_device_ptr(obs), eps_dev = !mode && is_device_ptr(eps);
   const float* base = net_params(h, N_POL);
   const NetDesc& d = h->pd;
   for (int s = 0; s < n; s += R) {
@@ -5342,13 +5360,15 @@ int dsact_act_sample_batch(dsact_handle* h, const float* obs, int32_t n, const f
     float* in_eps = h->ab_in + (size_t)m * O;
     // (obs | eps) of this chunk: host rows through the pinned stage in one copy, device rows copied on the stream
     if (!obs_dev) memcpy(h->ab_stage, obs + (size_t)s * O, (size_t)m * O * sizeof(float));
-    if (!eps_dev) memcpy(h->ab_stage + (size_t)m * O, eps + (size_t)s * A, (size_t)m * A * sizeof(float));
+    if (!mode && !eps_dev) memcpy(h->ab_stage + (size_t)m * O, eps + (size_t)s * A, (size_t)m * A * sizeof(float));
     if (!obs_dev && !eps_dev) {
-      HIPCHK(h, hipMemcpyAsync(h->ab_in, h->ab_stage, (size_t)m * (O + A) * sizeof(float), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(h->ab_in, h->ab_stage, (size_t)m * (O + (mode ? 0 : A)) * sizeof(float), hipMemcpyHostToDevice,
+                               h->stream));
     } else {
       HIPCHK(h, hipMemcpyAsync(in_obs, obs_dev ? obs + (size_t)s * O : h->ab_stage, (size_t)m * O * sizeof(float), hipMemcpyDefault, h->stream));
-      HIPCHK(h, hipMemcpyAsync(in_eps, eps_dev ? eps + (size_t)s * A : h->ab_stage + (size_t)m * O, (size_t)m * A * sizeof(float),
-                               hipMemcpyDefault, h->stream));
+      if (!mode)
+        HIPCHK(h, hipMemcpyAsync(in_eps, eps_dev ? eps + (size_t)s * A : h->ab_stage + (size_t)m * O, (size_t)m * A * sizeof(float),
+                                 hipMemcpyDefault, h->stream));
     }
     const float* X = in_obs;
     int ldx = O;
@@ -5367,25 +5387,32 @@ int dsact_act_sample_batch(dsact_handle* h, const float* obs, int32_t n, const f
     o.X = X; o.ldx = ldx; o.W = base + d.w_off[h->Lp]; o.b = base + d.b_off[h->Lp];
     o.K = d.in[h->Lp]; o.A = A; o.n = m;
     o.out_act = h->cfg.policy_out_act; o.out_n = h->cfg.policy_std_param ? A : 2 * A;
-    o.eps = in_eps; o.scale = h->act_scale; o.center = h->act_center; o.lo_ls = h->cfg.min_log_std; o.hi_ls = h->cfg.max_log_std;
-    o.action = h->ab_out_dev; o.logp = h->ab_out_dev + (size_t)m * A;
-    TRY(launch(h, "act_batch_out", k_act_batch_out, dim3((unsigned)((m + 7) / 8)), dim3(256), 0, o));
+    o.eps = mode ? nullptr : in_eps; o.scale = h->act_scale; o.center = h->act_center; o.lo_ls = h->cfg.min_log_std; o.hi_ls = h->cfg.max_log_std;
+    o.lo = h->act_lo; o.hi = h->act_hi;
+    o.action = h->ab_out_dev; o.logp = mode ? nullptr : h->ab_out_dev + (size_t)m * A;
+    const dim3 grid((unsigned)((m + 7) / 8));
+    if (mode) TRY(launch(h, "act_batch_mode", k_act_batch_out<true>, grid, dim3(256), 0, o));
+    else TRY(launch(h, "act_batch_out", k_act_batch_out<false>, grid, dim3(256), 0, o));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->ab_calls++;
+    (mode ? h->ab_mode_calls : h->ab_calls)++;
     memcpy(action_host + (size_t)s * A, h->ab_out_host, (size_t)m * A * sizeof(float));
-    memcpy(logp_host + s, h->ab_out_host + (size_t)m * A, (size_t)m * sizeof(float));
+    if (!mode) memcpy(logp_host + s, h->ab_out_host + (size_t)m * A, (size_t)m * sizeof(float));
   }
   return check_handoff(h);
 }
 
-int dsact_policy_forward(dsact_handle* h, const float* obs_host, int32_t n, float* logits_host) {
-  if (!h || !obs_host || !logits_host) return DSACT_E_INVALID;
-  if (n < 1 || n > kActRows) return fail(h, DSACT_E_INVALID, "n must be 1..%d", kActRows);
+int dsact_act_sample_batch(dsact_handle* h, const float* obs, int32_t n, const float* eps, float* action_host, float* logp_host) {
+  if (!h || !obs || !eps || !action_host || !logp_host || n < 1) return DSACT_E_INVALID;
   if (!h->online) return fail(h, DSACT_E_STATE, "arenas not bound");
-  HIPCHK(h, hipSetDevice(h->device));
+  if (!h->limits_set) return fail(h, DSACT_E_STATE, "action limits not set (dsact_set_action_limits)");
+  if (h->cnn) return fail(h, DSACT_E_INVALID, "dsact_act_sample_batch serves MLP policies (CNN: dsact_policy_forward)");
+  if (h->A > 32) return fail(h, DSACT_E_INVALID, "dsact_act_sample_batch serves act_dim <= 32");
+  return act_batch_gpu(h, obs, n, eps, action_host, logp_host);
+}
+
+// the stand-alone policy forward of n <= kActRows rows on the GPU, enqueued on the handle's stream: (mean | std) in h->act_out
+static int enqueue_policy_logits(dsact_handle* h, const float* obs_host, int32_t n) {
   const size_t O = h->O, ld = h->ldx;
-  if (n == 1 && act_host_ok(h)) return act_forward_host(h, obs_host, nullptr, logits_host, nullptr);   // on the calling thread (dsact_host_act.h)
-  if (n == 1 && act_fast_ok(h)) return act_forward_fast(h, obs_host, nullptr, logits_host);   // one launch (dsact_act.h)
   if (h->cnn) {
     // conv stack of the online policy on n images: (C,H,W) rows -> pixel-major -> conv layers -> feature rows
     if (!h->stage_img) HIPCHK(h, hipMalloc(&h->stage_img, 2 * (size_t)h->Brows * O * sizeof(float)));
@@ -5423,6 +5450,54 @@ int dsact_policy_forward(dsact_handle* h, const float* obs_host, int32_t n, floa
   a.out_act = h->cfg.policy_out_act; a.out_n = h->cfg.policy_std_param ? h->A : 2 * h->A;
 #define CALL_POUT(N) TRY(launch(h, "policy_out", k_policy_out<N>, dim3((n + 3) / 4), dim3(kThreads), 0, a))
   NCH_DISPATCH(a.W, CALL_POUT);
+  return DSACT_OK;
+}
+
+// Evaluator.run_an_episode's acting (training/evaluator.py:50-72) for n environments: dist.mode() of policy(obs) per row
+static void mode_rows(const dsact_handle* h, const float* logits, int n, float* action) {
+  const int A = h->A;
+  for (int r = 0; r < n; ++r)
+    for (int d = 0; d < A; ++d)
+      action[(size_t)r * A + d] = act_mode(logits[(size_t)r * 2 * A + d], h->act_scale_h[d], h->act_center_h[d], h->act_lo_h[d], h->act_hi_h[d]);
+}
+int dsact_act_mode_batch(dsact_handle* h, const float* obs, int32_t n, float* action_host) {
+  if (!h || !obs || !action_host || n < 1) return DSACT_E_INVALID;
+  if (!h->online) return fail(h, DSACT_E_STATE, "arenas not bound");
+  if (!h->limits_set) return fail(h, DSACT_E_STATE, "action limits not set (dsact_set_action_limits)");
+  if (h->A > 32) return fail(h, DSACT_E_INVALID, "dsact_act_mode_batch serves act_dim <= 32");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int O = h->O, A = h->A;
+  if (h->cnn) {
+    // the stand-alone forward's stages in chunks of kActRows frames, the mode of the (mean | std) rows on the host
+    float lg[kActRows * 64];
+    for (int s = 0; s < n; s += kActRows) {
+      const int m = n - s < kActRows ? n - s : kActRows;
+      TRY(enqueue_policy_logits(h, obs + (size_t)s * O, m));
+      HIPCHK(h, hipMemcpyAsync(lg, h->act_out, (size_t)m * 2 * A * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      mode_rows(h, lg, m, action_host + (size_t)s * A);
+    }
+    return check_handoff(h);
+  }
+  if (act_host_ok(h) && n < h->mode_host_rows && !is_device_ptr(obs)) {
+    float lg[64];   // the host forward per row (dsact_host_act.h) on the snapshot of the last completed update
+    for (int r = 0; r < n; ++r) {
+      TRY(act_forward_host(h, obs + (size_t)r * O, nullptr, lg, nullptr));
+      mode_rows(h, lg, 1, action_host + (size_t)r * A);
+    }
+    return DSACT_OK;
+  }
+  return act_batch_gpu(h, obs, n, nullptr, action_host, nullptr);
+}
+
+int dsact_policy_forward(dsact_handle* h, const float* obs_host, int32_t n, float* logits_host) {
+  if (!h || !obs_host || !logits_host) return DSACT_E_INVALID;
+  if (n < 1 || n > kActRows) return fail(h, DSACT_E_INVALID, "n must be 1..%d", kActRows);
+  if (!h->online) return fail(h, DSACT_E_STATE, "arenas not bound");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (n == 1 && act_host_ok(h)) return act_forward_host(h, obs_host, nullptr, logits_host, nullptr);   // on the calling thread (dsact_host_act.h)
+  if (n == 1 && act_fast_ok(h)) return act_forward_fast(h, obs_host, nullptr, logits_host);   // one launch (dsact_act.h)
+  TRY(enqueue_policy_logits(h, obs_host, n));
   HIPCHK(h, hipMemcpyAsync(logits_host, h->act_out, (size_t)n * 2 * h->A * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return DSACT_OK;

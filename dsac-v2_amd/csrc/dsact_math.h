@@ -165,7 +165,18 @@ DSACT_HD TanhGaussFwd tanh_gauss_fwd(float mu, float raw, float eps, float s, fl
   return o;
 }
 
-// backward of the above: given dL/da (gA) and dL/dlogp (gLp) returns dL/dmu, dL/draw.
+// ---- the deterministic action, one action dimension: the evaluator's dist.mode() ------------------
+// s == 0 selects the plain Gaussian as above. TanhGaussDistribution.mode() (utils/act_distribution_cls.py:71-74):
+// half_range * tanh(mean) + center, the product rounded on its own -- with eps = 0, tanh_gauss_fwd's x is mu exactly and its
+// action is this value bit for bit. GaussDistribution.mode() (:110-111): torch.clamp(mean, low, high) = min(max(mean, low),
+// high); lo / hi are the real action limits (a Gaussian handle's s and c are 0).
+DSACT_HD float act_mode(float mu, float s, float c, float lo, float hi) {
+#pragma clang fp contract(off)
+  if (s == 0.0f) return fminf(fmaxf(mu, lo), hi);
+  return s * tanhf(mu) + c;
+}
+
+// backward of tanh_gauss_fwd: given dL/da (gA) and dL/dlogp (gLp) returns dL/dmu, dL/draw.
 DSACT_HD void tanh_gauss_bwd(float mu, float raw, float eps, float s, float lo_ls, float hi_ls, float gA,
                              float gLp, float& dmu, float& draw) {
 #pragma clang fp contract(off)

@@ -117,6 +117,7 @@ SYMBOLS = [
     ("dsact_policy_forward", C.c_int, [_P, _FP, C.c_int32, _FP]),
     ("dsact_act_sample", C.c_int, [_P, _FP, _FP, _FP, _FP]),
     ("dsact_act_sample_batch", C.c_int, [_P, _FP, C.c_int32, _FP, _FP, _FP]),
+    ("dsact_act_mode_batch", C.c_int, [_P, _FP, C.c_int32, _FP]),
 ]
 
 _lib = None

@@ -573,6 +573,33 @@ class DsactEngine:
         if rc != 0:
             self._chk(rc)
 
+    def act_mode_batch(self, obs) -> np.ndarray:
+        """dsact_act_mode_batch: action float32[N, A], the action distribution's mode() of policy(obs) for N observation rows
+        (the evaluator's deterministic acting). obs: numpy / CPU tensors, or (MLP policies) CUDA tensors on this engine's GPU.
+        Callers that may have written the policy with torch ops call note_torch_writes(policy.parameters()) first."""
+        torch = self.torch
+        n = int(np.prod(np.shape(obs))) // self.obs_dim
+        if self.conv_type and isinstance(obs, torch.Tensor):
+            obs = obs.detach().cpu()   # (the CNN route reads host frames)
+        src = self._src(obs, n * self.obs_dim)
+        if isinstance(src[1], torch.Tensor):
+            torch.cuda.current_stream(self.device).synchronize()   # the producer of the CUDA source has finished
+        act = np.empty((n, self.act_dim), np.float32)
+        self._chk(self._lib.dsact_act_mode_batch(self._h, src[0], n, _ffi.fptr(act)))
+        return act
+
+    def act_mode_batch_addr(self, obs_addr: int, n: int, act_addr: int):
+        """dsact_act_mode_batch on plain integer addresses (the vectorised evaluator's per-step call; the actions land in the
+        caller's rows). A second binding of the same symbol whose pointer arguments are void*."""
+        f = getattr(self, "_act_mode_addr_fn", None)
+        if f is None:
+            f = self._lib["dsact_act_mode_batch"]      # a fresh function object: its argtypes are its own
+            f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+            self._act_mode_addr_fn = f
+        rc = f(self._h, obs_addr, n, act_addr)
+        if rc != 0:
+            self._chk(rc)
+
     def policy_forward(self, obs) -> np.ndarray:
         obs = _f32(obs).reshape(-1, self.obs_dim)
         n = obs.shape[0]

@@ -7,6 +7,9 @@ training/trainer.py:155-158): the drop-in surface of this repository.
     create_sampler(**kw)                                 -> training.hip_sampler.HipOffSampler, or with
                                                             sampler_name="hip_vec_off_sampler"
                                                             training.hip_vec_sampler.HipVecOffSampler
+    create_evaluator(**kw)                               -> training.hip_trainer.HipEvaluator, or with
+                                                            hip_eval_env_num=N >= 2
+                                                            training.hip_vec_evaluator.HipVecEvaluator
     create_trainer(alg, sampler, buffer, evaluator, **kw) -> training.hip_trainer.HipOffSerialTrainer
 """
 import importlib
@@ -81,6 +84,16 @@ def create_sampler(**kwargs):
 
 
 def create_evaluator(**kwargs):
+    """hip_eval_env_num=N >= 2: the vectorised evaluator (training/hip_vec_evaluator.py; the evaluation episodes over N
+    environments in lockstep, `eval_envs` = the N environments if given). Absent or 1: HipEvaluator as it is."""
+    n = kwargs.get("hip_eval_env_num")
+    if n is not None and int(n) >= 2:
+        from training.hip_vec_evaluator import HipVecEvaluator
+
+        return HipVecEvaluator(**kwargs)
+    envs = kwargs.get("eval_envs")
+    if n is not None and envs is not None and len(envs) != int(n):
+        raise ValueError("hip_eval_env_num=%s but %d evaluation environments were passed" % (n, len(envs)))
     from training.hip_trainer import HipEvaluator
 
     return HipEvaluator(**kwargs)

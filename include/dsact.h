@@ -399,6 +399,17 @@ int dsact_act_sample(dsact_handle* h, const float* obs_host, const float* eps_ho
  * act_dim <= 32 (DSACT_E_INVALID for CNN policies). Synchronous. */
 int dsact_act_sample_batch(dsact_handle* h, const float* obs, int32_t n, const float* eps, float* action_host,
                            float* logp_host);
+/* The evaluator's acting for N environments stepped in lockstep (training/hip_vec_evaluator.py): the reference's
+ * Evaluator.run_an_episode (training/evaluator.py:50-72) acts with dist.mode() of policy(obs) -- here for n observation rows
+ * at once: action[n*A] on the host, TanhGaussDistribution.mode() = half_range * tanh(mean) + center or
+ * GaussDistribution.mode() = clamp(mean, low, high) (utils/act_distribution_cls.py:71-74, :110-111), with the weights of the
+ * last enqueued update. The library picks the route from n: an MLP policy that acts on the host (dsact_act_sample) runs
+ * the host forward per row below a measured crossover, else the batched GPU forward of dsact_act_sample_batch with the mode
+ * in its output epilogue (a row's action is then bitwise independent of n and of its position; with eps = 0 it equals
+ * dsact_act_sample_batch's action bit for bit). CNN policies run dsact_policy_forward's stages in chunks of 64 frames and
+ * the mode on the host. obs[n*O] may be a host or (MLP) device pointer. Any n >= 1; act_dim <= 32 (DSACT_E_INVALID
+ * otherwise); DSACT_E_STATE without bound arenas or action limits. Synchronous. */
+int dsact_act_mode_batch(dsact_handle* h, const float* obs, int32_t n, float* action_host);
 
 #ifdef __cplusplus
 }
