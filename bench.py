@@ -21,11 +21,16 @@ Timing: W untimed warm-up steps, then R timed regions of EXACTLY K steps each, e
 barrier + device synchronisation on both sides, MAX over ranks per region; `value` is the MEDIAN region
 (R = 61 for K <= 100, 5 for K <= 10000, else 3; all regions are listed in `regions_ms`).
 
-Prints ONE JSON line (rank 0). Extra objects: `roofline` (the dominant kernel: algorithmic FLOP per launch / its
-average in-chain duration, measured live with the dispatch's own start/stop events), `roofline_step` (whole
-update vs the FP32 peak, the binding roofline per SURVEY.md section 8d), `roofline_hbm` (the HBM view north_star
-asks for), `kernels`, `cpu_baseline` (the oracle port of the reference arithmetic; 4 threads and all cores), `alt` (the other
-hidden-layer setting of SURVEY.md D1).
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times the regions, writes --dump-outputs and prints the line,
+nothing else: besides the headline fields it carries `roofline_step` (whole update vs the FP32 peak, the binding roofline per
+SURVEY.md section 8d) and `roofline_hbm` (the HBM view north_star asks for), both computed from the timed regions, and
+`roofline` = `roofline_step`.
+
+`--full` adds every informational leg after that line's measurement (informational_legs): `kernels` and `roofline` (the
+dominant kernel: algorithmic FLOP per launch / its average in-chain duration, measured with the dispatch's own start/stop
+events over eager runs of the timed launch sequence), `fast`, `boundary`, `e2e` / `e2e_si8`, `alt` (the other hidden-layer
+setting of SURVEY.md D1), `dsac_v1`, `shapes`, `cpu_baseline` (the oracle port of the reference arithmetic; 4 threads and all
+cores) and `cnn` (configs[3]). None of them changes the timed regions or what --dump-outputs writes: they run afterwards.
 
 `--dump-outputs DIR` writes, after the headline configuration's timed regions and before anything else runs on its
 engine, what a caller of the timed path holds after the last timed update: DIR/stats.npy (the 14 tb_info statistics,
@@ -867,6 +872,21 @@ def dump_outputs(e, stats, out_dir):
     return sorted(arrays)
 
 
+def informational_legs(args, rank=0, use_dp=False):
+    """the legs that run after the headline measurement: none in a plain run; with --full what each leg's own conditions allow
+    (the data-parallel path, --batch other than 256, --fast, --no-alt and --no-cpu-baseline rule some out)"""
+    if not args.full or args.headline_only or rank != 0:
+        return set()
+    legs = {"kernels"}
+    if not use_dp and not args.fast:
+        legs.add("fast")
+    if not use_dp and not args.no_alt and args.batch == B:
+        legs |= {"boundary", "e2e", "alt", "dsac_v1", "shapes", "cnn"}
+    if not args.no_cpu_baseline and args.batch == B:
+        legs.add("cpu_baseline")
+    return legs
+
+
 def self_spawn(args):
     """`python bench.py --gpus N` without a torch.distributed environment: re-execute under torch.distributed.run with N
     ranks on this node. Never measures fewer GPUs than were asked for."""
@@ -885,18 +905,22 @@ def self_spawn(args):
     sys.exit(subprocess.call(cmd))
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20000)
     ap.add_argument("--warmup", type=int, default=2000)
     ap.add_argument("--hidden", type=str, default="256,256,256",
                     help="reference default (example_train/*.py); BASELINE.json words it as 256,256 -> reported in `alt`")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also run every informational leg: eager per-kernel profile + dominant-kernel "
+                         "roofline, fast mode, drop-in boundary, end-to-end loops, the other hidden setting, DSAC_V1, other shapes, CPU "
+                         "baselines, the CNN workload (off: a plain run measures the headline configuration alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full or --cnn-only: no CPU baseline leg")
+    ap.add_argument("--no-alt", action="store_true", help="with --full: no boundary / e2e / alt / V1 / shapes / CNN legs")
     ap.add_argument("--headline-only", action="store_true",
-                    help="the timed regions of the headline configuration and nothing else (no fast / alt / V1 / e2e / CNN legs, no eager "
-                         "per-kernel profile): what a rocprofv3 pass should see so that its kernel statistics are this configuration's alone")
+                    help="the timed regions of the headline configuration and nothing else, even with --full (what a plain run does): "
+                         "what a rocprofv3 pass should see so that its kernel statistics are this configuration's alone")
     ap.add_argument("--fast", action="store_true", help="primary number with DSACT_F_SKIP_ACTOR_ON_OFF_ITERS (default: strict; fast is reported in `fast`)")
     ap.add_argument("--replay-rows", "--rows", dest="replay_rows", type=int, default=N_REPLAY,
                     help="rows of the replay ring in HBM per GPU (configs[1]: 1M; configs[4]: 10M = 30.9 GB)")
@@ -910,11 +934,14 @@ def main():
     ap.add_argument("--dp-eager", action="store_true", help="data-parallel leg through torch.distributed eagerly instead of the graph-captured native RCCL path")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed regions, write the last update's tb_info statistics and parameter arenas as DIR/<name>.npy (rank 0)")
+    return ap
+
+
+def main():
+    ap = arg_parser()
     args = ap.parse_args()
     if args.dump_outputs and args.cnn_only:
         ap.error("--dump-outputs covers the headline workload; it cannot be combined with --cnn-only")
-    if args.headline_only:
-        args.no_alt = args.no_cpu_baseline = True
     steps, warmup = int(args.steps), int(args.warmup)
     if args.fast:   # whole delay_update periods per graph
         steps += steps & 1
@@ -974,7 +1001,7 @@ def main():
         if args.cnn_type == "type_1":
             global CNN_OBS, CNN_A, CNN_TYPE
             CNN_OBS, CNN_A, CNN_TYPE = (4, 84, 84), 3, "type_1"
-        print(json.dumps({"cnn": bench_cnn(local, args.cnn_steps, 40, cpu=not args.no_cpu_baseline)}))
+        print(json.dumps({"cnn": bench_cnn(local, args.cnn_steps, 40, cpu=not (args.no_cpu_baseline or args.headline_only))}))
         return
     hidden = [int(x) for x in args.hidden.split(",")]
     alg = make_alg(hidden, local, seed=0, batch=args.batch)
@@ -1004,6 +1031,7 @@ def main():
         dp_mode = "EAGER launches + ncclAllReduce on the library-owned RCCL communicator (the hipGraph capture of the data-parallel update FAILED on this runtime: see stderr)"
     stats = e.read_stats()
     dumped = dump_outputs(e, stats, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    legs = informational_legs(args, rank, use_dp)
     finite = all(v == v and abs(v) < 1e30 for v in stats.values())
     updates_per_s = steps / wall
     value = updates_per_s * world  # batch-B gradient-step equivalents per second over the whole job
@@ -1050,86 +1078,89 @@ def main():
         }
         if ev_ms is not None:
             out["hip_event_ms_per_step"] = ev_ms / steps
-        try:
-            if args.headline_only:
-                raise RuntimeError("--headline-only: no eager per-kernel profile")
-            pipe = (not use_dp) and e.debug_get("pipe_graph") == 1.0
-            if pipe:
-                # the timed graph is the pipelined one: profile ITS launch sequence (same first-iteration parity, same length)
-                prof, per_update = profile_kernels_pipe(e, warmup + steps * len(regions), gs)
-                out["kernels"] = [{"name": n, "us": round(ms * 1000, 2), "blocks": b, "launches_per_update": round(per_update[n], 4)}
-                                  for n, ms, b in prof]
-                out["kernels_per_update_us"] = round(sum(ms * 1000.0 * per_update[n] for n, ms, _ in prof if n not in ("gather", "pack")), 2)
-                lpu = sum(per_update[n] for n, _, _ in prof if n not in ("gather", "pack"))
-                out["config"]["kernels"] = ("row-slice fused chains + transposed-operand weight-gradient tiles with fused Adam / Polyak: "
-                                            "%.3g launches/update in the timed (pipelined) graph -- one forward launch + one merged backward launch" % lpu)
-                out["config"]["launch"] = ("hipGraph (%d steps/graph), delayed-update-aware pipelining: the forward launch of an update that "
-                                           "leaves the policy alone also runs pi / pi_target of the next minibatch (chain_fwd+next), the next "
-                                           "update's forward holds only the fresh-critic chains (chain_fwd_q); gather rides two updates ahead" % gs)
-            else:
-                prof = profile_kernels(e, warmup + steps * len(regions))
-                out["kernels"] = [{"name": n, "us": round(ms * 1000, 2), "blocks": b} for n, ms, b in prof]
-            out["kernels_note"] = ("average in-chain duration per launch: start/stop events attached to each dispatch (hipExtLaunchKernelGGL) "
-                                   "-- the kernel's own begin / end timestamps, what rocprofv3 --kernel-trace reports -- over eager runs of the "
-                                   "launch sequence the timed graph captures; rocprofv3 summary of this configuration ALONE: "
-                                   "profiles/r06_bench_kernel_stats.csv, two consecutive updates launch by launch: profiles/r06_step_trace.txt")
-            # the two streaming parts of the update, reported separately
-            kus = {n: ms * 1000.0 for n, ms, _ in prof}
-            if "gather" in kus:
-                gb = 4.0 * Bb * (2 * lay.obs_dim + lay.act_dim + 2)
-                out["roofline_gather"] = {
-                    "bound": "hbm", "bytes": gb, "avg_launch_us": kus["gather"], "achieved": gb / kus["gather"] / 1e3, "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s", "frac": gb / kus["gather"] / 1e3 / HBM_PEAK_GBS,
-                    "note": "k_gather as its own launch (eager updates): %d random replay rows of %d B -- two dependent HBM round trips, "
-                            "latency- not bandwidth-bound at this size; in the timed graph replays the gather of update s+1 rides in the "
-                            "critics' backward launch of update s and costs no launch of its own" % (Bb, 4 * lay.obs_dim)}
-            opt_names = [n for n in ("chain_bwd_pi", "dW", "adam_polyak") if n in kus]
-            if chain and opt_names:
-                n_on = 2 * lay.n_q + lay.n_pi
-                ob = 24.0 * 2 * lay.n_q + (24.0 * lay.n_pi + 8.0 * n_on) / 2.0
-                ous = sum(kus[n] for n in opt_names)
-                out["roofline_adam"] = {
-                    "bound": "hbm", "bytes": ob, "us": ous, "achieved": ob / ous / 1e3, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": ob / ous / 1e3 / HBM_PEAK_GBS, "launches": opt_names,
-                    "note": "Adam (24 B/param: read and write p, m, v) + Polyak (8 B/param on every 2nd update) of SURVEY.md 8(d). The "
-                            "optimiser has no launch of its own: it is the epilogue of the weight-gradient tiles, so `us` is the duration of "
-                            "the launches that carry those tiles (which also hold the policy backward chain and the tiles' MFMA work)"}
-            timed = [r for r in prof if r[0] not in ("gather", "pack")]
-            dom = max(timed, key=lambda r: r[1])
-            out["dominant_kernel"] = {"name": dom[0], "us": round(dom[1] * 1000, 2)}
-            if chain and Bb % 256 == 0 or chain and Bb <= 256:
-                fl = chain_flops(lay, Bb)
-                if any(r[0] == "chain_dw_q" for r in prof):   # the policy backward of the previous update rides in these launches
-                    fl["chain_fwd_q"] += fl["deferred_bwd_pi"]
-                    fl["chain_fwd_q+next"] += fl["deferred_bwd_pi"]
-                kname = {"chain_fwd+next": "dsact::k_chain_fwdp (own minibatch: all 8 chains; + policy / policy_target of the next minibatch)",
-                         "chain_fwd_q": "dsact::k_chain_fwdp (fresh-critic chains only)", "chain_fwd_q+next": "dsact::k_chain_fwdp",
-                         "chain_bwd": "dsact::k_chain_bwd2 (critics' + policy backward + all dW/Adam tiles in one launch)",
-                         "chain_fwd": "dsact::k_chain_fwd2 (groups A + B in one launch)", "chain_fwd_a": "dsact::k_chain_fwd (group A)", "chain_fwd_b": "dsact::k_chain_fwd (group B)",
-                         "chain_bwd_q": "dsact::k_chain_bwd_q", "chain_bwd_qt": "dsact::k_chain_bwd_qt (critics' backward + their dW/Adam tiles + close)",
-                         "chain_bwd_qpt": "dsact::k_chain_bwd_qpt (critics' backward -> policy backward -> all dW/Adam/Polyak tiles -> close)", "chain_bwd_pi": "dsact::k_chain_bwd_pi (+ riding k_dw2 tiles)",
-                         "dW": "dsact::k_dw2"}.get(dom[0], dom[0])
-                if dom[0] in fl:
-                    dur_us = dom[1] * 1000.0
-                    ach = fl[dom[0]] / (dur_us * 1e-6) / 1e12
-                    out["roofline"] = {
-                        "bound": "mfma", "achieved": ach, "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ach / FP32_PEAK_TFLOPS,
-                        "traffic": pmc_traffic({"chain_bwd": "k_chain_bwd2", "chain_fwd": "k_chain_fwdp" if pipe else "k_chain_fwd2", "chain_fwd+next": "k_chain_fwdp", "chain_fwd_q": "k_chain_fwdpb" if any(r[0] == "chain_dw_q" for r in prof) else "k_chain_fwdp", "chain_fwd_q+next": "k_chain_fwdp", "chain_fwd_a": "k_chain_fwd", "chain_fwd_b": "k_chain_fwd", "chain_bwd_q": "k_chain_bwd_q", "chain_bwd_qt": "k_chain_bwd_qt", "chain_bwd_qpt": "k_chain_bwd_qpt",
-                                                "chain_bwd_pi": "k_chain_bwd_pi", "dW": "k_dw2"}.get(dom[0], dom[0]),
-                                               "min" if dom[0] == "chain_fwd_b" else "max"),
-                        "traffic_source": "%s (a committed rocprofv3 --pmc pass of this bench; NOT measured in this run)" % getattr(pmc_traffic, "source", None),
-                        "kernel": kname, "avg_launch_us": dur_us, "flop_per_launch": fl[dom[0]],
-                        "note": "dominant launch of the update by in-chain duration; achieved = algorithmic FLOP of the launch (2 x MAC of "
-                                "the layers its workgroups run, elementwise ignored) / its average duration (dispatch start/stop events, "
-                                "10 eager updates); fp32 MFMA peak == fp32 vector peak. The launch runs %d workgroups on 256 CUs: the "
-                                "chip-level fraction is bounded by that occupancy (per-workgroup phase timeline: profiles/r02_chain_*_timeline.txt); "
-                                "traffic = bytes/launch (2*FETCH_SIZE + WRITE_SIZE) from the committed PMC passes, or null" % dom[2],
-                    }
-        except Exception as ex:  # profiling is informational
-            out["kernels_error"] = str(ex)
+        pipe = (not use_dp) and e.debug_get("pipe_graph") == 1.0
+        if pipe:
+            out["config"]["kernels"] = ("row-slice fused chains + transposed-operand weight-gradient tiles with fused Adam / Polyak: "
+                                        "one forward launch + one merged backward launch per update in the timed (pipelined) graph")
+            out["config"]["launch"] = ("hipGraph (%d steps/graph), delayed-update-aware pipelining: the forward launch of an update that "
+                                       "leaves the policy alone also runs pi / pi_target of the next minibatch (chain_fwd+next), the next "
+                                       "update's forward holds only the fresh-critic chains (chain_fwd_q); gather rides two updates ahead" % gs)
+        if "kernels" in legs:
+            try:
+                if pipe:
+                    # the timed graph is the pipelined one: profile ITS launch sequence (same first-iteration parity, same length)
+                    prof, per_update = profile_kernels_pipe(e, warmup + steps * len(regions), gs)
+                    out["kernels"] = [{"name": n, "us": round(ms * 1000, 2), "blocks": b, "launches_per_update": round(per_update[n], 4)}
+                                      for n, ms, b in prof]
+                    out["kernels_per_update_us"] = round(sum(ms * 1000.0 * per_update[n] for n, ms, _ in prof if n not in ("gather", "pack")), 2)
+                    lpu = sum(per_update[n] for n, _, _ in prof if n not in ("gather", "pack"))
+                    out["config"]["kernels"] = ("row-slice fused chains + transposed-operand weight-gradient tiles with fused Adam / Polyak: "
+                                                "%.3g launches/update in the timed (pipelined) graph -- one forward launch + one merged backward launch" % lpu)
+                else:
+                    prof = profile_kernels(e, warmup + steps * len(regions))
+                    out["kernels"] = [{"name": n, "us": round(ms * 1000, 2), "blocks": b} for n, ms, b in prof]
+                out["kernels_note"] = ("average in-chain duration per launch: start/stop events attached to each dispatch (hipExtLaunchKernelGGL) "
+                                       "-- the kernel's own begin / end timestamps, what rocprofv3 --kernel-trace reports -- over eager runs of the "
+                                       "launch sequence the timed graph captures; rocprofv3 summary of this configuration ALONE: "
+                                       "profiles/r06_bench_kernel_stats.csv, two consecutive updates launch by launch: profiles/r06_step_trace.txt")
+                # the two streaming parts of the update, reported separately
+                kus = {n: ms * 1000.0 for n, ms, _ in prof}
+                if "gather" in kus:
+                    gb = 4.0 * Bb * (2 * lay.obs_dim + lay.act_dim + 2)
+                    out["roofline_gather"] = {
+                        "bound": "hbm", "bytes": gb, "avg_launch_us": kus["gather"], "achieved": gb / kus["gather"] / 1e3, "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": gb / kus["gather"] / 1e3 / HBM_PEAK_GBS,
+                        "note": "k_gather as its own launch (eager updates): %d random replay rows of %d B -- two dependent HBM round trips, "
+                                "latency- not bandwidth-bound at this size; in the timed graph replays the gather of update s+1 rides in the "
+                                "critics' backward launch of update s and costs no launch of its own" % (Bb, 4 * lay.obs_dim)}
+                opt_names = [n for n in ("chain_bwd_pi", "dW", "adam_polyak") if n in kus]
+                if chain and opt_names:
+                    n_on = 2 * lay.n_q + lay.n_pi
+                    ob = 24.0 * 2 * lay.n_q + (24.0 * lay.n_pi + 8.0 * n_on) / 2.0
+                    ous = sum(kus[n] for n in opt_names)
+                    out["roofline_adam"] = {
+                        "bound": "hbm", "bytes": ob, "us": ous, "achieved": ob / ous / 1e3, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": ob / ous / 1e3 / HBM_PEAK_GBS, "launches": opt_names,
+                        "note": "Adam (24 B/param: read and write p, m, v) + Polyak (8 B/param on every 2nd update) of SURVEY.md 8(d). The "
+                                "optimiser has no launch of its own: it is the epilogue of the weight-gradient tiles, so `us` is the duration of "
+                                "the launches that carry those tiles (which also hold the policy backward chain and the tiles' MFMA work)"}
+                timed = [r for r in prof if r[0] not in ("gather", "pack")]
+                dom = max(timed, key=lambda r: r[1])
+                out["dominant_kernel"] = {"name": dom[0], "us": round(dom[1] * 1000, 2)}
+                if chain and Bb % 256 == 0 or chain and Bb <= 256:
+                    fl = chain_flops(lay, Bb)
+                    if any(r[0] == "chain_dw_q" for r in prof):   # the policy backward of the previous update rides in these launches
+                        fl["chain_fwd_q"] += fl["deferred_bwd_pi"]
+                        fl["chain_fwd_q+next"] += fl["deferred_bwd_pi"]
+                    kname = {"chain_fwd+next": "dsact::k_chain_fwdp (own minibatch: all 8 chains; + policy / policy_target of the next minibatch)",
+                             "chain_fwd_q": "dsact::k_chain_fwdp (fresh-critic chains only)", "chain_fwd_q+next": "dsact::k_chain_fwdp",
+                             "chain_bwd": "dsact::k_chain_bwd2 (critics' + policy backward + all dW/Adam tiles in one launch)",
+                             "chain_fwd": "dsact::k_chain_fwd2 (groups A + B in one launch)", "chain_fwd_a": "dsact::k_chain_fwd (group A)", "chain_fwd_b": "dsact::k_chain_fwd (group B)",
+                             "chain_bwd_q": "dsact::k_chain_bwd_q", "chain_bwd_qt": "dsact::k_chain_bwd_qt (critics' backward + their dW/Adam tiles + close)",
+                             "chain_bwd_qpt": "dsact::k_chain_bwd_qpt (critics' backward -> policy backward -> all dW/Adam/Polyak tiles -> close)", "chain_bwd_pi": "dsact::k_chain_bwd_pi (+ riding k_dw2 tiles)",
+                             "dW": "dsact::k_dw2"}.get(dom[0], dom[0])
+                    if dom[0] in fl:
+                        dur_us = dom[1] * 1000.0
+                        ach = fl[dom[0]] / (dur_us * 1e-6) / 1e12
+                        out["roofline"] = {
+                            "bound": "mfma", "achieved": ach, "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ach / FP32_PEAK_TFLOPS,
+                            "traffic": pmc_traffic({"chain_bwd": "k_chain_bwd2", "chain_fwd": "k_chain_fwdp" if pipe else "k_chain_fwd2", "chain_fwd+next": "k_chain_fwdp", "chain_fwd_q": "k_chain_fwdpb" if any(r[0] == "chain_dw_q" for r in prof) else "k_chain_fwdp", "chain_fwd_q+next": "k_chain_fwdp", "chain_fwd_a": "k_chain_fwd", "chain_fwd_b": "k_chain_fwd", "chain_bwd_q": "k_chain_bwd_q", "chain_bwd_qt": "k_chain_bwd_qt", "chain_bwd_qpt": "k_chain_bwd_qpt",
+                                                    "chain_bwd_pi": "k_chain_bwd_pi", "dW": "k_dw2"}.get(dom[0], dom[0]),
+                                                   "min" if dom[0] == "chain_fwd_b" else "max"),
+                            "traffic_source": "%s (a committed rocprofv3 --pmc pass of this bench; NOT measured in this run)" % getattr(pmc_traffic, "source", None),
+                            "kernel": kname, "avg_launch_us": dur_us, "flop_per_launch": fl[dom[0]],
+                            "note": "dominant launch of the update by in-chain duration; achieved = algorithmic FLOP of the launch (2 x MAC of "
+                                    "the layers its workgroups run, elementwise ignored) / its average duration (dispatch start/stop events, "
+                                    "10 eager updates); fp32 MFMA peak == fp32 vector peak. The launch runs %d workgroups on 256 CUs: the "
+                                    "chip-level fraction is bounded by that occupancy (per-workgroup phase timeline: profiles/r02_chain_*_timeline.txt); "
+                                    "traffic = bytes/launch (2*FETCH_SIZE + WRITE_SIZE) from the committed PMC passes, or null" % dom[2],
+                        }
+            except Exception as ex:  # profiling is informational
+                out["kernels_error"] = str(ex)
         if "roofline" not in out:
-            out["roofline"] = dict(out["roofline_step"], note="whole update (no per-kernel profile available on this path)")
-    if rank == 0 and not use_dp and not args.fast and not args.headline_only:
+            out["roofline"] = dict(out["roofline_step"], note="whole update (no per-kernel profile available on this path)" if "kernels" in legs
+                                   else "whole update (the per-kernel profile runs with --full)")
+    if "fast" in legs:
         # same workload with the actor/alpha backward skipped on the off iterations of the delayed update: the
         # reference computes and discards those gradients (dsac_v2.py:174-186 vs :324); bitwise-identical parameter
         # trajectory (tests/test_hip_parity.py::test_skip_discarded_actor_backward_keeps_trajectory)
@@ -1137,12 +1168,12 @@ def main():
         wf, _, _ = measure(alg, fs, fw, flags=1)
         out["fast"] = {"value": fs / wf, "unit": "steps/s", "ms_per_step": 1000.0 * wf / fs,
                        "note": "DSACT_F_SKIP_ACTOR_ON_OFF_ITERS; not the headline value"}
-    if rank == 0 and not use_dp and not args.no_alt and args.batch == B:
+    if "boundary" in legs:
         try:
             out["boundary"] = boundary_rates(alg, min(max(steps, 100), 600))
         except Exception as ex:  # informational leg
             out["boundary_error"] = repr(ex)
-    if rank == 0 and not use_dp and not args.no_alt and args.batch == B:
+    if "e2e" in legs:
         try:
             out["e2e"] = e2e_gpu(hidden, local)
         except Exception as ex:  # informational leg
@@ -1151,7 +1182,7 @@ def main():
             out["e2e_si8"] = e2e_gpu_grouped(hidden, local)
         except Exception as ex:  # informational leg
             out["e2e_si8_error"] = repr(ex)
-    if not use_dp and not args.no_alt and args.batch == B:
+    if "alt" in legs:
         alt_hidden = [256, 256] if hidden != [256, 256] else [256, 256, 256]
         del alg
         alg2 = make_alg(alt_hidden, local, seed=0)
@@ -1162,7 +1193,7 @@ def main():
         out["alt"] = {"hidden": alt_hidden, "value": steps / w2, "unit": "steps/s",
                       "frac_fp32": l2.flop_per_step(B) * steps / w2 / 1e12 / FP32_PEAK_TFLOPS,
                       "frac_hbm": l2.bytes_per_step(B, 2) * steps / w2 / 1e9 / HBM_PEAK_GBS}
-    if rank == 0 and not use_dp and not args.no_alt and args.batch == B:
+    if "dsac_v1" in legs:
         # the reference's DSAC_V1 (one critic) on the chain kernels + pipelined graph, same shapes
         try:
             alg1 = make_alg(hidden, local, seed=0, v1=True)
@@ -1175,19 +1206,19 @@ def main():
             del alg1
         except Exception as ex:
             out["dsac_v1_error"] = repr(ex)
-    if rank == 0 and not use_dp and not args.no_alt and args.batch == B:
+    if "shapes" in legs:
         try:
             out["shapes"] = bench_shapes(local)
         except Exception as ex:  # informational leg
             out["shapes_error"] = repr(ex)
-    if rank == 0 and not args.no_cpu_baseline and args.batch == B:
+    if "cpu_baseline" in legs:
         try:
             out["cpu_baseline"] = cpu_baseline(hidden)
             if "e2e" in out and isinstance(out["cpu_baseline"].get("e2e"), dict):
                 out["e2e"]["cpu"] = out["cpu_baseline"].pop("e2e")   # the same loop on the host cores, beside the GPU figure
         except Exception as ex:
             out["cpu_baseline_error"] = repr(ex)
-    if rank == 0 and not use_dp and not args.no_alt and args.batch == B:
+    if "cnn" in legs:
         try:
             out["cnn"] = bench_cnn(local, args.cnn_steps, 40, cpu=not args.no_cpu_baseline)
         except Exception as ex:  # secondary workload: never costs the headline line

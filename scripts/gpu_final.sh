@@ -14,7 +14,7 @@ if [ "${1:-}" != "notests" ]; then
   timeout 300 python __graft_entry__.py --smoke > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $OUT/smoke.log
 fi
 t0=$(date +%s); timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.log 2>&1; echo "driver bench rc=$? wall=$(( $(date +%s) - t0 ))s"; tail -1 $OUT/bench_driver.log | cut -c1-260
-timeout 600 python bench.py --steps 4000 --warmup 400 > $OUT/bench.log 2>&1; echo "long bench rc=$?"; tail -1 $OUT/bench.log | cut -c1-260
+timeout 600 python bench.py --full --steps 4000 --warmup 400 > $OUT/bench.log 2>&1; echo "long bench rc=$?"; tail -1 $OUT/bench.log | cut -c1-260
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python bench.py --steps 2000 --warmup 200 --no-cpu-baseline --no-alt > $OUT/rocprof.log 2>&1; echo "rocprof rc=$?"
 f=$(find $OUT/prof -name "*kernel_trace.csv" | head -1)
 [ -n "$f" ] && python scripts/step_trace.py "$f" 1000 > $OUT/step_trace.txt && head -16 $OUT/step_trace.txt

@@ -16,8 +16,8 @@ print("  %.0f steps/s  %.2f us/step  ev %.2f  kernels %s" % (d["value"], d["ms_p
 PY
 }
 run() { # tag, env
-  env $2 timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-alt > $OUT/bench_driver_$1.log 2>&1; echo "[$1] driver-style rc=$?"; line $OUT/bench_driver_$1.log
-  env $2 timeout 300 python bench.py --steps 4000 --warmup 200 --no-cpu-baseline --no-alt > $OUT/bench_long_$1.log 2>&1; echo "[$1] long rc=$?"; line $OUT/bench_long_$1.log
+  env $2 timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-alt > $OUT/bench_driver_$1.log 2>&1; echo "[$1] driver-style rc=$?"; line $OUT/bench_driver_$1.log
+  env $2 timeout 300 python bench.py --full --steps 4000 --warmup 200 --no-cpu-baseline --no-alt > $OUT/bench_long_$1.log 2>&1; echo "[$1] long rc=$?"; line $OUT/bench_long_$1.log
 }
 run base "X_=1"
 i=0

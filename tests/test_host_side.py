@@ -216,6 +216,25 @@ def test_bench_helpers():
     assert bench.pmc_traffic("no-such-kernel") is None
 
 
+def test_bench_plain_run_measures_the_headline_alone_and_full_runs_every_leg():
+    """a plain `bench.py --gpus 1 --steps K --warmup W` runs no leg after the headline measurement; --full runs each one its own
+    conditions allow, and --headline-only still wins over --full"""
+    import bench
+    ap = bench.arg_parser()
+    plain = ["--gpus", "1", "--steps", "20", "--warmup", "5"]
+    every = {"kernels", "fast", "boundary", "e2e", "alt", "dsac_v1", "shapes", "cpu_baseline", "cnn"}
+    assert bench.informational_legs(ap.parse_args(plain)) == set()
+    assert bench.informational_legs(ap.parse_args(plain), use_dp=True) == set()
+    full = ap.parse_args(plain + ["--full"])
+    assert bench.informational_legs(full) == every
+    assert bench.informational_legs(full, use_dp=True) == {"kernels", "cpu_baseline"}
+    assert bench.informational_legs(full, rank=1) == set()
+    assert bench.informational_legs(ap.parse_args(plain + ["--full", "--fast"])) == every - {"fast"}
+    assert bench.informational_legs(ap.parse_args(plain + ["--full", "--no-alt", "--no-cpu-baseline"])) == {"kernels", "fast"}
+    assert bench.informational_legs(ap.parse_args(plain + ["--full", "--batch", "1024"])) == {"kernels", "fast"}
+    assert bench.informational_legs(ap.parse_args(plain + ["--full", "--headline-only"])) == set()
+
+
 def test_bench_gpus_flag_spawns_ranks_and_never_underreports(tmp_path):
     """`python bench.py --gpus 2` without a torch.distributed environment re-executes itself with 2 ranks (gloo dry run
     here: no GPU); without --dry-run-cpu and with fewer than N devices it refuses instead of printing n_gpus: 1."""
