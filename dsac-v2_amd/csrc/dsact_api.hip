@@ -323,6 +323,19 @@ struct dsact_handle {
   unsigned long long ab_mode_calls = 0;  // dsact_act_mode_batch chunks launched on the GPU
   int mode_host_rows = kModeHostRows;   // dsact_act_mode_batch's host / GPU crossover (debug switch "mode_host_rows": measurements)
   unsigned long long act_host_calls = 0, act_copies = 0;
+  // behaviour policy (dsact_behaviour_hold): a device copy of the policy net taken on the handle's stream
+  // behind everything enqueued so far. While it is held, dsact_act_sample / dsact_act_sample_batch act with it on act_stream,
+  // which waits for beh_ev only -- never for the updates enqueued after the hold
+  bool beh_held = false;
+  float* beh_dev = nullptr;             // device: the policy net's n_pi floats in arena order
+  hipEvent_t beh_ev = nullptr;          // recorded on `stream` right behind the copy into beh_dev
+  hipStream_t act_stream = nullptr;     // non-blocking: held acting launches and the copy into beh_host
+  float* beh_host = nullptr;            // pinned: beh_dev on the host (the host acting route)
+  hipEvent_t beh_host_ev = nullptr;     // recorded on act_stream right behind the copy into beh_host
+  bool beh_host_pending = false;
+  bool beh_host_ok = false;             // beh_host belongs to the current hold (a hold on a handle acting on the GPU leaves it stale)
+  bool beh_live_copy = false;           // debug switch "beh_live_copy": keep the eager live-snapshot copy behind every update while held
+  unsigned long long beh_holds = 0, beh_acts = 0;
   bool env_no_conv_dx_mfma = false;     // DSACT_NO_CONV_DX_MFMA: the 16-channel layer's data gradient with k_conv_dx_block (A/B)
   bool fwd_merge = false;               // launches A and B as one (batch <= 256)
   bool pi_merge = false;                // the policy's weight-gradient tiles + the closing block inside the policy-backward launch (batch <= 512; measured equal-to-slower at 1024)
@@ -3649,6 +3662,11 @@ int dsact_destroy(dsact_handle* h) {
   for (int i = 0; i < 2; ++i) if (h->ab_h[i]) hipFree(h->ab_h[i]);
   if (h->pol_host) hipHostFree(h->pol_host);
   if (h->pol_ev) hipEventDestroy(h->pol_ev);
+  if (h->act_stream) { hipStreamSynchronize(h->act_stream); hipStreamDestroy(h->act_stream); }
+  if (h->beh_dev) hipFree(h->beh_dev);
+  if (h->beh_host) hipHostFree(h->beh_host);
+  if (h->beh_ev) hipEventDestroy(h->beh_ev);
+  if (h->beh_host_ev) hipEventDestroy(h->beh_host_ev);
   free(h->act_buf);
   delete h->act_pool;
   if (h->d_tiles) hipFree(h->d_tiles);
@@ -4189,40 +4207,58 @@ static int enqueue_policy_copy(dsact_handle* h) {
 // called by every entry point that enqueued work which may change the policy's parameters (an update with
 // iteration % delay_update == 0, graph replays, the data-parallel apply): the snapshot of a handle that acts on the host is
 // refreshed right behind it, so the copy is already in flight when the sampler asks
+// While a behaviour policy is held the sampler does not read the live snapshot: only the epoch moves, and the next live acting
+// call (an evaluation) copies lazily -- the update stream then carries no copy between two groups
 static int policy_moved(dsact_handle* h) {
   h->pol_epoch++;
-  if (h->pol_host && h->host_act) return enqueue_policy_copy(h);
+  if (h->pol_host && h->host_act && (!h->beh_held || h->beh_live_copy)) return enqueue_policy_copy(h);
   return DSACT_OK;
 }
 static bool act_fast_ok(const dsact_handle* h);
 static bool act_host_ok(const dsact_handle* h) { return h->host_act && act_fast_ok(h); }
+// waits for the copy event `ev` of a host snapshot: poll first -- a blocking wait sleeps the thread and its wake-up (tens of us)
+// would sit in front of every burst of environment steps; after ~5 ms fall back to the blocking wait
+static int wait_snapshot(dsact_handle* h, hipEvent_t ev, std::chrono::steady_clock::time_point t0) {
+  hipError_t q = hipErrorNotReady;
+  while ((q = hipEventQuery(ev)) == hipErrorNotReady) {
+    if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) break;
+  }
+  if (q != hipSuccess) HIPCHK(h, hipEventSynchronize(ev));
+  TRY(check_handoff(h));     // (an update kernel that gave up while the stream drained: this snapshot is not to be acted on)
+  h->act_copy_wait_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+  return DSACT_OK;
+}
 // policy(obs) [+ TanhGaussDistribution.sample()] on the calling thread with the weights of the last completed update
-// (training/off_sampler.py:46-56). eps == nullptr: out = the 2A logits; else out = A actions and *logp
-static int act_forward_host(dsact_handle* h, const float* obs_host, const float* eps, float* out, float* logp) {
+// (training/off_sampler.py:46-56). eps == nullptr: out = the 2A logits; else out = A actions and *logp.
+// behaviour: act with the held behaviour policy's host copy (dsact_behaviour_hold) instead of the live snapshot
+static int act_forward_host(dsact_handle* h, const float* obs_host, const float* eps, float* out, float* logp, bool behaviour = false) {
   TRY(check_handoff(h));
   const auto t0 = std::chrono::steady_clock::now();
-  if (!h->pol_host) {
-    HIPCHK(h, hipHostMalloc((void**)&h->pol_host, ((size_t)h->n_pi + 64) * sizeof(float), hipHostMallocDefault));
-    HIPCHK(h, hipEventCreateWithFlags(&h->pol_ev, hipEventDisableTiming));
+  if (!h->act_buf) {
     h->act_buf = (float*)malloc((size_t)(2 * (kMaxWidth + 64) + 128) * sizeof(float));
     if (!h->act_buf) return fail(h, DSACT_E_HIP, "out of host memory");
   }
-  if (h->pol_copied != h->pol_epoch) TRY(enqueue_policy_copy(h));
-  if (h->pol_pending) {
-    // poll first: a blocking wait sleeps the thread and its wake-up (tens of us) would sit in front of every burst of
-    // environment steps; after ~5 ms fall back to the blocking wait
-    hipError_t q = hipErrorNotReady;
-    while ((q = hipEventQuery(h->pol_ev)) == hipErrorNotReady) {
-      if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) break;
+  const float* P = h->beh_host;
+  if (behaviour) {
+    if (h->beh_host_pending) {
+      TRY(wait_snapshot(h, h->beh_host_ev, t0));
+      h->beh_host_pending = false;
     }
-    if (q != hipSuccess) HIPCHK(h, hipEventSynchronize(h->pol_ev));
-    h->pol_pending = false;
-    TRY(check_handoff(h));     // (an update kernel that gave up while the stream drained: this snapshot is not to be acted on)
-    h->act_copy_wait_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+  } else {
+    if (!h->pol_host) {
+      HIPCHK(h, hipHostMalloc((void**)&h->pol_host, ((size_t)h->n_pi + 64) * sizeof(float), hipHostMallocDefault));
+      HIPCHK(h, hipEventCreateWithFlags(&h->pol_ev, hipEventDisableTiming));
+    }
+    if (h->pol_copied != h->pol_epoch) TRY(enqueue_policy_copy(h));
+    if (h->pol_pending) {
+      TRY(wait_snapshot(h, h->pol_ev, t0));
+      h->pol_pending = false;
+    }
+    P = h->pol_host;
   }
   hostact::Layer ly[kActMaxLayers];
   for (int l = 0; l <= h->Lp; ++l) {
-    ly[l].W = h->pol_host + h->pd.w_off[l]; ly[l].b = h->pol_host + h->pd.b_off[l];
+    ly[l].W = P + h->pd.w_off[l]; ly[l].b = P + h->pd.b_off[l];
     ly[l].K = h->pd.in[l]; ly[l].N = h->pd.out[l]; ly[l].half = 0;
     if (h->pd.nblk == 2 && l > 0 && l < h->Lp) { ly[l].K = h->pd.in[l] / 2; ly[l].half = h->pd.out[l] / 2; }   // two (H x Hprev) blocks
   }
@@ -5168,6 +5204,10 @@ int dsact_debug_set(dsact_handle* h, const char* name, double value) {
     h->pol_epoch++;
     return DSACT_OK;
   }
+  if (!strcmp(name, "beh_live_copy")) {   // 1: keep the eager live-snapshot copy behind every update while a behaviour policy is held (A/B)
+    h->beh_live_copy = value != 0.0;
+    return DSACT_OK;
+  }
   if (!strcmp(name, "policy_dirty")) {  // the caller wrote policy parameters itself (torch ops on the arena: load_state_dict, ...)
     h->pol_epoch++;
     return DSACT_OK;
@@ -5234,6 +5274,10 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "act_copy_wait_us")) *value = h->act_copy_wait_us;
   else if (!strcmp(name, "act_host_calls")) *value = (double)h->act_host_calls;
   else if (!strcmp(name, "act_copies")) *value = (double)h->act_copies;
+  else if (!strcmp(name, "beh_held")) *value = h->beh_held ? 1.0 : 0.0;            // a behaviour policy is held (dsact_behaviour_hold)
+  else if (!strcmp(name, "beh_holds")) *value = (double)h->beh_holds;
+  else if (!strcmp(name, "beh_acts")) *value = (double)h->beh_acts;                // acting calls served by a held behaviour policy
+  else if (!strcmp(name, "beh_live_copy")) *value = h->beh_live_copy ? 1.0 : 0.0;
   else if (!strcmp(name, "act_wait_us")) *value = h->act_wait_us;
   else if (!strcmp(name, "fat")) *value = (h->fat ? 1.0 : 0.0) + (h->fat_bwd ? 2.0 : 0.0);
   else if (!strcmp(name, "handoff_failures")) *value = (double)h->handoff_failures;
@@ -5314,12 +5358,20 @@ static bool act_fast_ok(const dsact_handle* h) {
 // (torch.randn(1, A) consumes the torch generator exactly as Normal.sample() does and mean + std * eps IS its result):
 // action[A] (inside the action limits by construction of the tanh squashing; the caller clips like the reference) and
 // its log-probability. MLP policies only (DSACT_E_INVALID otherwise: the caller takes dsact_policy_forward).
+static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const float* eps, float* action_host, float* logp_host,
+                        const float* base, hipStream_t stream);
 int dsact_act_sample(dsact_handle* h, const float* obs_host, const float* eps_host, float* action_host, float* logp_host) {
   if (!h || !obs_host || !eps_host || !action_host || !logp_host) return DSACT_E_INVALID;
   if (!h->online) return fail(h, DSACT_E_STATE, "arenas not bound");
   if (!h->limits_set) return fail(h, DSACT_E_STATE, "action limits not set (dsact_set_action_limits)");
   if (!act_fast_ok(h)) return fail(h, DSACT_E_INVALID, "dsact_act_sample serves MLP policies with obs <= %d floats", kActMaxObs);
   HIPCHK(h, hipSetDevice(h->device));
+  if (h->beh_held) {
+    // the held behaviour policy (dsact_behaviour_hold): its host copy, or the batched forward at n = 1 on the acting stream
+    h->beh_acts++;
+    if (act_host_ok(h) && h->beh_host_ok) return act_forward_host(h, obs_host, eps_host, action_host, logp_host, true);
+    return act_batch_gpu(h, obs_host, 1, eps_host, action_host, logp_host, h->beh_dev, h->act_stream);
+  }
   if (act_host_ok(h)) return act_forward_host(h, obs_host, eps_host, action_host, logp_host);   // dsact_host_act.h
   float out[64];
   TRY(act_forward_fast(h, obs_host, eps_host, out));
@@ -5338,21 +5390,30 @@ static bool is_device_ptr(const void* p) {
   if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // (pageable host memory)
   return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
 }
-// the batched forward of both entry points below: eps != nullptr samples (action, logp), eps == nullptr writes the mode
-static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const float* eps, float* action_host, float* logp_host) {
+// the batched forward's buffers, allocated by its first call (or by the first dsact_behaviour_hold: no allocation then stands
+// between a held acting call and its launches)
+static int alloc_act_batch(dsact_handle* h) {
+  if (h->ab_in) return DSACT_OK;
+  const int O = h->O, A = h->A, R = kActBatchCap;
+  HIPCHK(h, hipHostMalloc((void**)&h->ab_stage, (size_t)R * (O + A) * sizeof(float), hipHostMallocDefault));
+  HIPCHK(h, hipMalloc((void**)&h->ab_in, (size_t)R * (O + A) * sizeof(float)));
+  for (int i = 0; i < 2; ++i) HIPCHK(h, hipMalloc((void**)&h->ab_h[i], (size_t)R * kMaxWidth * sizeof(float)));
+  HIPCHK(h, hipHostMalloc((void**)&h->ab_out_host, (size_t)R * (A + 1) * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
+  HIPCHK(h, hipHostGetDevicePointer((void**)&h->ab_out_dev, h->ab_out_host, 0));
+  return DSACT_OK;
+}
+// the batched forward of both entry points below: eps != nullptr samples (action, logp), eps == nullptr writes the mode.
+// base: the policy net's parameters (the live arena, or a held behaviour copy); stream: where the copies and launches go and
+// the one stream the call waits for (the handle's stream: behind every enqueued update; the acting stream: behind the hold)
+static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const float* eps, float* action_host, float* logp_host,
+                        const float* base, hipStream_t stream) {
   HIPCHK(h, hipSetDevice(h->device));
   TRY(check_handoff(h));
+  if (stream != h->stream) HIPCHK(h, hipStreamWaitEvent(stream, h->beh_ev, 0));
   const int O = h->O, A = h->A, R = kActBatchCap;
   const bool mode = eps == nullptr;
-  if (!h->ab_in) {
-    HIPCHK(h, hipHostMalloc((void**)&h->ab_stage, (size_t)R * (O + A) * sizeof(float), hipHostMallocDefault));
-    HIPCHK(h, hipMalloc((void**)&h->ab_in, (size_t)R * (O + A) * sizeof(float)));
-    for (int i = 0; i < 2; ++i) HIPCHK(h, hipMalloc((void**)&h->ab_h[i], (size_t)R * kMaxWidth * sizeof(float)));
-    HIPCHK(h, hipHostMalloc((void**)&h->ab_out_host, (size_t)R * (A + 1) * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(h, hipHostGetDevicePointer((void**)&h->ab_out_dev, h->ab_out_host, 0));
-  }
+  TRY(alloc_act_batch(h));
   const bool obs_dev = is_device_ptr(obs), eps_dev = !mode && is_device_ptr(eps);
-  const float* base = net_params(h, N_POL);
   const NetDesc& d = h->pd;
   for (int s = 0; s < n; s += R) {
     const int m = n - s < R ? n - s : R;
@@ -5363,12 +5424,12 @@ static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const flo
     if (!mode && !eps_dev) memcpy(h->ab_stage + (size_t)m * O, eps + (size_t)s * A, (size_t)m * A * sizeof(float));
     if (!obs_dev && !eps_dev) {
       HIPCHK(h, hipMemcpyAsync(h->ab_in, h->ab_stage, (size_t)m * (O + (mode ? 0 : A)) * sizeof(float), hipMemcpyHostToDevice,
-                               h->stream));
+                               stream));
     } else {
-      HIPCHK(h, hipMemcpyAsync(in_obs, obs_dev ? obs + (size_t)s * O : h->ab_stage, (size_t)m * O * sizeof(float), hipMemcpyDefault, h->stream));
+      HIPCHK(h, hipMemcpyAsync(in_obs, obs_dev ? obs + (size_t)s * O : h->ab_stage, (size_t)m * O * sizeof(float), hipMemcpyDefault, stream));
       if (!mode)
         HIPCHK(h, hipMemcpyAsync(in_eps, eps_dev ? eps + (size_t)s * A : h->ab_stage + (size_t)m * O, (size_t)m * A * sizeof(float),
-                                 hipMemcpyDefault, h->stream));
+                                 hipMemcpyDefault, stream));
     }
     const float* X = in_obs;
     int ldx = O;
@@ -5380,7 +5441,8 @@ static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const flo
       a.Y = h->ab_h[l & 1]; a.ldy = d.out[l]; a.n = m; a.act = h->cfg.policy_act;
       const int seg_n = a.half > 0 ? a.half : a.N;
       const dim3 grid((unsigned)((a.half > 0 ? 2 : 1) * ((seg_n + 31) / 32)), (unsigned)((m + 31) / 32));
-      TRY(launch(h, "act_batch_hidden", k_act_batch_hidden, grid, dim3(256), 0, a));
+      TRY(stream == h->stream ? launch(h, "act_batch_hidden", k_act_batch_hidden, grid, dim3(256), 0, a)
+                              : launch_on(h, stream, "act_batch_hidden", k_act_batch_hidden, grid, dim3(256), 0, a));
       X = a.Y; ldx = a.ldy;
     }
     ActBatchOut o;
@@ -5392,8 +5454,9 @@ static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const flo
     o.action = h->ab_out_dev; o.logp = mode ? nullptr : h->ab_out_dev + (size_t)m * A;
     const dim3 grid((unsigned)((m + 7) / 8));
     if (mode) TRY(launch(h, "act_batch_mode", k_act_batch_out<true>, grid, dim3(256), 0, o));
-    else TRY(launch(h, "act_batch_out", k_act_batch_out<false>, grid, dim3(256), 0, o));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    else if (stream == h->stream) TRY(launch(h, "act_batch_out", k_act_batch_out<false>, grid, dim3(256), 0, o));
+    else TRY(launch_on(h, stream, "act_batch_out", k_act_batch_out<false>, grid, dim3(256), 0, o));
+    HIPCHK(h, hipStreamSynchronize(stream));
     (mode ? h->ab_mode_calls : h->ab_calls)++;
     memcpy(action_host + (size_t)s * A, h->ab_out_host, (size_t)m * A * sizeof(float));
     if (!mode) memcpy(logp_host + s, h->ab_out_host + (size_t)m * A, (size_t)m * sizeof(float));
@@ -5407,7 +5470,11 @@ int dsact_act_sample_batch(dsact_handle* h, const float* obs, int32_t n, const f
   if (!h->limits_set) return fail(h, DSACT_E_STATE, "action limits not set (dsact_set_action_limits)");
   if (h->cnn) return fail(h, DSACT_E_INVALID, "dsact_act_sample_batch serves MLP policies (CNN: dsact_policy_forward)");
   if (h->A > 32) return fail(h, DSACT_E_INVALID, "dsact_act_sample_batch serves act_dim <= 32");
-  return act_batch_gpu(h, obs, n, eps, action_host, logp_host);
+  if (h->beh_held) {   // the held behaviour policy (dsact_behaviour_hold) on the acting stream
+    h->beh_acts++;
+    return act_batch_gpu(h, obs, n, eps, action_host, logp_host, h->beh_dev, h->act_stream);
+  }
+  return act_batch_gpu(h, obs, n, eps, action_host, logp_host, net_params(h, N_POL), h->stream);
 }
 
 // the stand-alone policy forward of n <= kActRows rows on the GPU, enqueued on the handle's stream: (mean | std) in h->act_out
@@ -5487,7 +5554,64 @@ int dsact_act_mode_batch(dsact_handle* h, const float* obs, int32_t n, float* ac
     }
     return DSACT_OK;
   }
-  return act_batch_gpu(h, obs, n, nullptr, action_host, nullptr);
+  return act_batch_gpu(h, obs, n, nullptr, action_host, nullptr, net_params(h, N_POL), h->stream);
+}
+
+// ---- behaviour policy ----------------------------------------------------------------------------
+int dsact_behaviour_hold(dsact_handle* h) {
+  if (!h) return DSACT_E_INVALID;
+  if (!h->online) return fail(h, DSACT_E_STATE, "arenas not bound");
+  if (h->cnn) return fail(h, DSACT_E_INVALID, "dsact_behaviour_hold serves MLP policies (the CNN acting forward reads the live weights)");
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  HIPCHK(h, hipStreamIsCapturing(h->stream, &cap));
+  if (cap != hipStreamCaptureStatusNone) return fail(h, DSACT_E_STATE, "dsact_behaviour_hold under stream capture");
+  HIPCHK(h, hipSetDevice(h->device));
+  TRY(check_handoff(h));
+  const size_t bytes = (size_t)h->n_pi * sizeof(float);
+  if (!h->beh_dev) {
+    HIPCHK(h, hipMalloc((void**)&h->beh_dev, bytes + 256 * sizeof(float)));   // (a zeroed tail, as the arena has data behind the policy)
+    HIPCHK(h, hipMemsetAsync(h->beh_dev, 0, bytes + 256 * sizeof(float), h->stream));
+    HIPCHK(h, hipEventCreateWithFlags(&h->beh_ev, hipEventDisableTiming));
+    HIPCHK(h, hipEventCreateWithFlags(&h->beh_host_ev, hipEventDisableTiming));
+    // the acting stream at the device's greatest priority: the runtime keeps a pool of hardware queues per priority, so the
+    // held acting launches never share a queue with the update stream (a shared queue would put them behind the group --
+    // the pool of normal-priority queues is shared round-robin once a process has more streams than queues)
+    int least = 0, greatest = 0;
+    HIPCHK(h, hipDeviceGetStreamPriorityRange(&least, &greatest));
+    HIPCHK(h, hipStreamCreateWithPriority(&h->act_stream, hipStreamNonBlocking, greatest));
+    TRY(alloc_act_batch(h));
+  } else {
+    // the copy of the previous hold into beh_host may still be queued on the acting stream: the new snapshot is written behind it
+    HIPCHK(h, hipStreamWaitEvent(h->stream, h->beh_host_ev, 0));
+  }
+  HIPCHK(h, hipMemcpyAsync(h->beh_dev, net_params(h, N_POL), bytes, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipEventRecord(h->beh_ev, h->stream));
+  if (act_host_ok(h)) {
+    if (!h->beh_host) HIPCHK(h, hipHostMalloc((void**)&h->beh_host, bytes + 64 * sizeof(float), hipHostMallocDefault));
+    HIPCHK(h, hipStreamWaitEvent(h->act_stream, h->beh_ev, 0));
+    HIPCHK(h, hipMemcpyAsync(h->beh_host, h->beh_dev, bytes, hipMemcpyDeviceToHost, h->act_stream));
+    h->beh_host_pending = true;
+  }
+  h->beh_host_ok = act_host_ok(h);
+  HIPCHK(h, hipEventRecord(h->beh_host_ev, h->act_stream));
+  h->beh_held = true;
+  h->beh_holds++;
+  return DSACT_OK;
+}
+
+int dsact_behaviour_release(dsact_handle* h) {
+  if (!h) return DSACT_E_INVALID;
+  h->beh_held = false;
+  return DSACT_OK;
+}
+
+int dsact_stream_idle(dsact_handle* h) {
+  if (!h) return DSACT_E_INVALID;
+  if (hipSetDevice(h->device) != hipSuccess) return 0;
+  const hipError_t e = hipStreamQuery(h->stream);
+  if (e == hipSuccess) return 1;
+  if (e != hipErrorNotReady) (void)hipGetLastError();
+  return 0;
 }
 
 int dsact_policy_forward(dsact_handle* h, const float* obs_host, int32_t n, float* logits_host) {

@@ -769,6 +769,14 @@ class DSAC_V2_HIP:
         self.engine.step(int(iteration), self.flags)
         return self._new_tb(t0)
 
+    def hold_behaviour(self):
+        """the sampler's acting (dsact_act_sample / dsact_act_sample_batch) uses the policy as it stands behind every update
+        issued so far, whatever is issued after this call, until release_behaviour() -- training/hip_async_trainer.py"""
+        self.engine.behaviour_hold()
+
+    def release_behaviour(self):
+        self.engine.behaviour_release()
+
     def local_update_group(self, group: "HipBatchGroup", iteration: int) -> dict:
         """len(group) consecutive { sample_batch -> local_update } of the reference's loop (training/trainer.py:68-82), for
         iterations `iteration` .. `iteration + len(group) - 1`, as ONE graph replay (dsact_run_group: the pipelined graph

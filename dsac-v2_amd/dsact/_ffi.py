@@ -118,6 +118,9 @@ SYMBOLS = [
     ("dsact_act_sample", C.c_int, [_P, _FP, _FP, _FP, _FP]),
     ("dsact_act_sample_batch", C.c_int, [_P, _FP, C.c_int32, _FP, _FP, _FP]),
     ("dsact_act_mode_batch", C.c_int, [_P, _FP, C.c_int32, _FP]),
+    ("dsact_behaviour_hold", C.c_int, [_P]),
+    ("dsact_behaviour_release", C.c_int, [_P]),
+    ("dsact_stream_idle", C.c_int, [_P]),
 ]
 
 _lib = None

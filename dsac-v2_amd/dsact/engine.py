@@ -600,6 +600,23 @@ class DsactEngine:
         if rc != 0:
             self._chk(rc)
 
+    def behaviour_hold(self):
+        """dsact_behaviour_hold: from now on act_sample / act_sample_batch act with a copy of the policy taken on the engine's
+        stream behind everything enqueued so far -- without waiting for anything enqueued later (act_mode_batch and
+        policy_forward stay live). MLP policies only; refused under stream capture."""
+        self._chk(self._lib.dsact_behaviour_hold(self._h))
+
+    def behaviour_release(self):
+        """dsact_behaviour_release: act_sample / act_sample_batch act with the live weights again"""
+        self._chk(self._lib.dsact_behaviour_release(self._h))
+
+    def stream_idle(self) -> bool:
+        """dsact_stream_idle: True when everything enqueued on the engine's stream has completed (never blocks)"""
+        rc = self._lib.dsact_stream_idle(self._h)
+        if rc < 0:
+            self._chk(rc)
+        return rc == 1
+
     def policy_forward(self, obs) -> np.ndarray:
         obs = _f32(obs).reshape(-1, self.obs_dim)
         n = obs.shape[0]

@@ -10,7 +10,9 @@ training/trainer.py:155-158): the drop-in surface of this repository.
     create_evaluator(**kw)                               -> training.hip_trainer.HipEvaluator, or with
                                                             hip_eval_env_num=N >= 2
                                                             training.hip_vec_evaluator.HipVecEvaluator
-    create_trainer(alg, sampler, buffer, evaluator, **kw) -> training.hip_trainer.HipOffSerialTrainer
+    create_trainer(alg, sampler, buffer, evaluator, **kw) -> training.hip_trainer.HipOffSerialTrainer, or with
+                                                            trainer="hip_off_async_trainer"
+                                                            training.hip_async_trainer.HipOffAsyncTrainer
 """
 import importlib
 import os
@@ -107,6 +109,13 @@ def save_tb_to_csv(path):
 
 
 def create_trainer(alg, sampler, buffer, evaluator, **kwargs):
+    """trainer="hip_off_async_trainer": the overlapped trainer (training/hip_async_trainer.py; the sampler acts with the policy
+    one group old while the group's updates run). Every other name -- the reference's off_serial_trainer and its
+    off_async_trainer, which the reference itself runs serially -- or none is HipOffSerialTrainer."""
+    if kwargs.get("trainer") == "hip_off_async_trainer":
+        from training.hip_async_trainer import HipOffAsyncTrainer
+
+        return HipOffAsyncTrainer(alg, sampler, buffer, evaluator, **kwargs)
     from training.hip_trainer import HipOffSerialTrainer
 
     return HipOffSerialTrainer(alg, sampler, buffer, evaluator, **kwargs)

@@ -224,6 +224,10 @@ class HipOffSerialTrainer:
             samples, sampler_tb = self.sampler.sample()
             self.buffer.add_batch(samples)
         alg_tb = self._update(self.iteration)
+        self._events(alg_tb, sampler_tb)
+
+    def _events(self, alg_tb, sampler_tb):
+        """the host-side end of iteration `self.iteration` (trainer.py:84-135): log, evaluation, checkpoint"""
         if self.iteration % self.log_save_interval == 0:
             self.writer.add_dict(dict(alg_tb.items()), self.iteration)  # the only host sync of the update
             self.writer.add_dict(sampler_tb, self.iteration)
@@ -254,6 +258,9 @@ class HipOffSerialTrainer:
                 self.iteration += 1
         finally:
             self._grouping = False
+        self._finish()
+
+    def _finish(self):
         if self.save_folder:
             self.save_apprfunc()
         self.writer.flush()

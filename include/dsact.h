@@ -410,6 +410,19 @@ int dsact_act_sample_batch(dsact_handle* h, const float* obs, int32_t n, const f
  * the mode on the host. obs[n*O] may be a host or (MLP) device pointer. Any n >= 1; act_dim <= 32 (DSACT_E_INVALID
  * otherwise); DSACT_E_STATE without bound arenas or action limits. Synchronous. */
 int dsact_act_mode_batch(dsact_handle* h, const float* obs, int32_t n, float* action_host);
+/* Behaviour policy of an overlapped trainer (training/hip_async_trainer.py): the sampler acts with the
+ * policy of the previous group while the current group's updates run.
+ * dsact_behaviour_hold: on the handle's stream, behind everything already enqueued, copies the policy net's n_pi floats into a
+ * device buffer of the same arena layout and records an event. From then on dsact_act_sample and dsact_act_sample_batch --
+ * and ONLY they -- act with that copy: they wait for that event and never for work enqueued after it (held acting runs on a
+ * third, non-blocking acting stream; a handle that acts on the host copies the snapshot into a second pinned buffer there).
+ * dsact_act_mode_batch and dsact_policy_forward keep acting with the live weights. A second hold replaces the snapshot;
+ * dsact_bind_arenas leaves it valid (it is a copy). DSACT_E_INVALID on CNN handles, DSACT_E_STATE under stream capture.
+ * dsact_behaviour_release: back to live acting (the default).
+ * dsact_stream_idle: 1 when all work enqueued on the handle's stream has completed, else 0. Never blocks. */
+int dsact_behaviour_hold(dsact_handle* h);
+int dsact_behaviour_release(dsact_handle* h);
+int dsact_stream_idle(dsact_handle* h);
 
 #ifdef __cplusplus
 }
