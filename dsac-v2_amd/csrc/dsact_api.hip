@@ -46,6 +46,12 @@ constexpr int kActRows = 64;  // rows of the stand-alone policy forward (sampler
 // batched GPU forward (profiles/vec_eval_bench.json: Humanoid 3 x 256, host ~3.2 us per row against
 // 59-66 us per GPU call from 1 to 32 rows -- equal near 20)
 constexpr int kModeHostRows = 20;
+// conv launch shapes: fewest 64 x 64 tiles a conv forward launch must have to use them; fewest rows of a dCol product for
+// the 64 x 64 stage tiles (layer 5 at batch 256: 11.4 -> 8.9 us); workgroups (4 waves each) a register-tile weight-gradient
+// launch (k_conv_dw_reg) aims for
+constexpr int kConvFwd64MinTiles = 256;
+constexpr int kDcol64MinRows = 256;
+constexpr int kConvDwRegWgs = 512;
 
 // One approximator inside its arena. nblk == 2: the CNN nets' twin `mean` / `log_std` MLPs laid side
 // by side (networks/cnn.py:224-229,447-450): layer 0 is one dense (2*H0 x in) matrix, hidden layers are
@@ -92,14 +98,6 @@ struct dsact_handle {
   char err[512] = {0};
   hipStream_t stream = nullptr;
   bool own_stream = false;
-  hipStream_t aux_stream = nullptr;   // forked branch: critics' dW + Adam run beside the actor backward chain
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool use_fork = false;
-  // conv backward on two queues: the data-gradient chain (dCol -> col2im / direct dX, layer by layer) on the handle's
-  // stream, the weight-gradient launches of the same layers on aux_stream -- they only need dY[j], which is ready when the
-  // data-gradient launch of layer j starts. ev_conv[j]: dY[j] complete.
-  bool conv_fork = false;
-  hipEvent_t ev_conv[kMaxConv + 1] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   // nets
   int nq = 2;            // critics: 2 (DSAC_V2) or 1 (DSAC_V1)
   NetDesc qd, pd;
@@ -181,19 +179,8 @@ struct dsact_handle {
   // environment switches, read once at dsact_create (getenv walks the whole environment: ~20 calls per eager update
   // were host time on the launch path)
   std::string env_timeline_stage;   // DSACT_TIMELINE_STAGE
-  bool env_no_merged_gather = false, env_no_adam_pack = false;
   int n_cu = 256;                       // compute units of the device (hipDeviceAttributeMultiprocessorCount)
-  int env_conv_dw_nkt = 0;
-  int conv_dw_nkt_l[kMaxConv] = {1, 1, 1, 1, 1, 1};   // k-tiles per k_conv_dw workgroup, per layer (DSACT_CONV_DW_NKT_L=a,b,..; DSACT_CONV_DW_NKT: all)
-  int env_conv_fwd64_min = 256;         // DSACT_CONV_FWD64_MIN: fewest 64 x 64 tiles a conv forward launch must have to use them
   bool env_no_dcol_ident = false;       // DSACT_NO_DCOL_IDENT: keep dCol + col2im on the layer whose col2im is the identity (round 6 fuses the mask into the product)
-  int env_dcol64_min_m = 256;           // DSACT_DCOL64_MIN_M: fewest rows of a dCol product for the 64 x 64 stage tiles (layer 5 at batch 256: 11.4 -> 8.9 us)
-  bool env_no_conv_fwd32x64 = false;    // DSACT_NO_CONV_FWD32X64
-  int env_conv_dw_reg = 0;              // DSACT_CONV_DW_REG: bit mask of the (narrow) layers whose weight gradient runs on register tiles (k_conv_dw_reg)
-  int env_conv_dw_reg_wgs = 512;        // DSACT_CONV_DW_REG_WGS: workgroups (4 waves each) such a launch aims for
-  bool env_conv_dw_sb3 = false;         // DSACT_CONV_DW_SB3: layers with three k-tiles per workgroup run the single-buffered form
-  bool env_no_conv_fwd64 = false;       // DSACT_NO_CONV_FWD64: wide conv layers' forward on the 32 x 32 tile kernel
-  bool env_no_conv_narrow9 = false;     // DSACT_NO_CONV_NARROW9: type_2's third conv layer stays on the LDS-tile forward kernel
   bool mirror_w0 = false;      // set while the merged-gather graph is being captured (see FusedOpt::mir_*)
   bool merged_graph = false;   // the captured graph uses the merged-gather flow
   bool have_local_tail = false;   // the gradient arena's tail holds mean_std of a gradient computed HERE and not yet committed
@@ -267,7 +254,6 @@ struct dsact_handle {
   int c_obs = 0, c_act = 0, c_out = 0;  // fat mode: 16-k chunks of the observation / action segment of a first layer, of the policy outputs (2A)
   int env_fat_rt = 0;                   // DSACT_FAT_RT=1|2: force the rows per fat workgroup (16 / 32)
   int cRG = 2;                          // row groups of 4 per chain workgroup (8 rows) when 4-row workgroups would oversubscribe the CUs
-  int env_chain_rg = 0;                 // DSACT_CHAIN_RG=1|2|4: force
   bool env_no_fat_stage = false;        // DSACT_NO_FAT_STAGE: the throughput-regime forward reads its first layer's rows from global memory
   bool rg4_ok = false;                  // 16-row chain workgroups fit (LDS) and divide the batch
   int n_slices = 0;
@@ -336,7 +322,6 @@ struct dsact_handle {
   bool beh_host_ok = false;             // beh_host belongs to the current hold (a hold on a handle acting on the GPU leaves it stale)
   bool beh_live_copy = false;           // debug switch "beh_live_copy": keep the eager live-snapshot copy behind every update while held
   unsigned long long beh_holds = 0, beh_acts = 0;
-  bool env_no_conv_dx_mfma = false;     // DSACT_NO_CONV_DX_MFMA: the 16-channel layer's data gradient with k_conv_dx_block (A/B)
   bool fwd_merge = false;               // launches A and B as one (batch <= 256)
   bool pi_merge = false;                // the policy's weight-gradient tiles + the closing block inside the policy-backward launch (batch <= 512; measured equal-to-slower at 1024)
   float* zobs[4];                       // first-layer accumulators after the observation part: q1, q2 (obs), q1_t, q2_t (obs2)
@@ -373,8 +358,7 @@ struct dsact_handle {
   static constexpr int kPipePhases = 4;
   PipeSet pset[kPipeSets];
   char* pipe_ws = nullptr;
-  unsigned long long* pipe_hand[3] = {nullptr, nullptr, nullptr};   // tagged hand-over buffers [B][32] (value, tag): new_act, act2, act2 of the next minibatch
-  bool env_no_pipe_tagged = false;      // DSACT_NO_PIPE_TAGGED: ready flags + separate data instead of (value, tag) pairs (A/B)
+  unsigned long long* pipe_hand[2] = {nullptr, nullptr};   // tagged hand-over buffers [B][32] (value, tag): new_act, act2
   bool pipe_defer_now = false;          // set while the update being enqueued defers its (discarded) policy backward
   // merged critic backward + critic tiles + close (k_chain_bwd_qt) on the updates that defer their policy backward
   int* bqt_cnt = nullptr;               // arrival counters [2 critics][8 x kArriveStride], zeroed by the forward launch's bookkeeping block
@@ -389,9 +373,6 @@ struct dsact_handle {
   hipGraph_t pgraph[kPipePhases] = {nullptr, nullptr, nullptr, nullptr};
   hipGraphExec_t pexec[kPipePhases] = {nullptr, nullptr, nullptr, nullptr};
   PipeFwd* pargs[kPipePhases] = {nullptr, nullptr, nullptr, nullptr};   // device: one PipeFwd per captured forward launch
-  bool env_no_pipe = false;             // DSACT_NO_PIPE: graph replays without the pipelining (A/B)
-  int env_pk_pad = 0;                   // DSACT_PK_PAD: see build_chain
-  bool env_no_pipe_warm = true;         // DSACT_PIPE_WARM=1: L2 warm-up touches in the pipelined forward launches (measured: slower, 60.4 vs 59.6 us)
   bool env_no_pipe_defer = false;       // DSACT_NO_PIPE_DEFER: the discarded policy backward stays in its own update's last launch (A/B)
   std::string env_pipe_map;             // DSACT_PIPE_MAP: XCD lists per unit (experiments), see pipe_xcds
   // native collective (RCCL): communicator of this rank, see dsact_comm_init
@@ -755,10 +736,9 @@ int build_chain(dsact_handle* h) {
   // fat mode (dsact_fat.h): EVERY pack is style 16 (16-row tiles x chunks of 16 k; a tile-chunk block is 256 floats like
   // a style-44 step, so the sizes below count blocks either way)
   const bool fat = h->fat, fatb = h->fat_bwd;
-  const int tiles_f = fat ? W / 16 : tiles, S_hid = fat ? CH : SH + (h->fat ? 0 : h->env_pk_pad);
+  const int tiles_f = fat ? W / 16 : tiles, S_hid = fat ? CH : SH;
   const int tiles_b = fatb ? W / 16 : tiles, S_hidb = fatb ? CH : SH, S_out = fatb ? h->c_out : h->SoT;
-  const int tpad = fat ? 0 : h->env_pk_pad;   // style-44 forward packs: padding steps behind every tile (DSACT_PK_PAD)
-  const int C0q = fat ? h->c_obs + h->c_act : h->s_obs + h->s_act + tpad, C0p = fat ? h->c_obs : h->s_obs + tpad;
+  const int C0q = fat ? h->c_obs + h->c_act : h->s_obs + h->s_act, C0p = fat ? h->c_obs : h->s_obs;
   const int nth_q = 1, nth_p = (2 * A + 15) / 16, nta = (A + 15) / 16;
   // twin trunks (nb = 2): a net's first layer is the dense [2W x in] matrix = 2 x tiles row tiles (trunk t: the second half);
   // hidden layers are two [W x W] blocks with a pack each (trunk t: t * tiles * steps * 256 floats further); the output layer
@@ -879,12 +859,12 @@ int build_pack_jobs(dsact_handle* h) {
   return DSACT_OK;
 }
 
-// after_update: the pack follows this update's optimiser pass (data-parallel graph) -- the target nets' copies are
-// rebuilt only on delayed-update steps; otherwise (start of an eager step: anything may have written the arenas) all
-int enqueue_pack(dsact_handle* h, bool after_update = false) {
+// every packed copy (start of an eager step: anything may have written the arenas); after a graph's optimiser pass
+// k_adam_pack refreshes them itself
+int enqueue_pack(dsact_handle* h) {
   PackArgs a;
   a.jobs = h->d_pack; a.n_jobs = h->n_pack_jobs;
-  a.targets_if = after_update ? &h->st->do_delayed : nullptr;
+  a.targets_if = nullptr;
   return launch(h, "pack", k_pack, dim3(h->pack_blocks), dim3(kThreads), 0, a);
 }
 
@@ -1151,7 +1131,7 @@ int run_stage(dsact_handle* h, const Stage& s0, int x0 = 0, int x1 = 0, bool fus
         const int K4 = (K + 3) & ~3;
         if (s.kind == 0 && g.ldp >= K4 && g.ldq >= K4) K = K4; else ok = false;
       }
-      ok = ok && g.M >= (s.kind >= 2 ? h->env_dcol64_min_m : 512) && g.M % 64 == 0 && g.N % 64 == 0;
+      ok = ok && g.M >= (s.kind >= 2 ? kDcol64MinRows : 512) && g.M % 64 == 0 && g.N % 64 == 0;
       g.K = K;
       g.tiles_n = g.N / 64;
       blocks += (g.M / 64) * g.tiles_n;
@@ -1185,15 +1165,13 @@ int run_stage(dsact_handle* h, const Stage& s0, int x0 = 0, int x1 = 0, bool fus
 
 // weight-gradient tiles [x0, x1) as their own launch; `fused`: Adam/Polyak in the tile epilogue;
 // `finalize`: one extra block closes the update (alpha step, EMA commit, counters)
-int run_dw(dsact_handle* h, int x0, int x1, bool fused, bool finalize, hipStream_t on = nullptr) {
+int run_dw(dsact_handle* h, int x0, int x1, bool fused, bool finalize) {
   if (x1 <= x0 && !finalize) return DSACT_OK;
   TableArgs a;
   a.tiles = h->d_tiles + x0; a.n_tiles = x1 > x0 ? x1 - x0 : 0;
   a.fo = fused_opt(h, fused);
   a.finalize = finalize ? 1 : 0;
   a.timeline = tl_for(h, "dW");
-  if (on)
-    return launch_on(h, on, "dW", k_stage_table, dim3(a.n_tiles + (finalize ? 1 : 0)), dim3(kThreads), tile_lds_bytes(dw_k(h)), a);
   return launch(h, "dW", k_stage_table, dim3(a.n_tiles + (finalize ? 1 : 0)), dim3(kThreads), tile_lds_bytes(dw_k(h)), a);
 }
 
@@ -1276,7 +1254,7 @@ int enqueue_conv_forward(dsact_handle* h) {
     const std::string name = "conv_fwd_l" + std::to_string(j);
     // (K <= 144 with 32 channels -- type_2's third layer: 9 k-groups, 256 VGPRs, ONE wave per SIMD that prefetches the next
     //  tile's 18 patch quads under its 144 MFMAs; round 4: 40.0 us on the LDS-tile kernel)
-    const bool narrow9 = g.K > 80 && g.K <= 144 && per_group * g.Cout <= 32 && !h->env_no_conv_narrow9;
+    const bool narrow9 = g.K > 80 && g.K <= 144 && per_group * g.Cout <= 32;
     if ((g.K <= 80 || narrow9) && per_group * g.Cout <= 32) {
       // narrow layer: wave-autonomous register tiles (k_conv_fwd_narrow); every wave works on one group
       const int waves_total = narrow9 ? 4 * h->n_cu : 5120;   // ~20 waves per CU; the 9-group form: every SIMD one wave, one round
@@ -1293,8 +1271,7 @@ int enqueue_conv_forward(dsact_handle* h) {
       continue;
     }
     // wide layers: 64 x 64 tiles when they divide the problem and still give every CU a workgroup (type_2 layers 3, 4)
-    if (per_group == 1 && M % 64 == 0 && g.Cout % 64 == 0 && g.K % 4 == 0 && !h->env_no_conv_fwd64 &&
-        (long long)a.n_prob * (M / 64) * (g.Cout / 64) >= h->env_conv_fwd64_min) {
+    if (per_group == 1 && M % 64 == 0 && g.Cout % 64 == 0 && g.K % 4 == 0 && (long long)a.n_prob * (M / 64) * (g.Cout / 64) >= kConvFwd64MinTiles) {
       int it64 = 0;
       for (int q = 0; q < a.n_prob; ++q) { it64 += (M / 64) * (g.Cout / 64); a.p[q].item_end = it64; a.p[q].tiles_n = g.Cout / 64; }
       a.n_items = it64;
@@ -1303,7 +1280,7 @@ int enqueue_conv_forward(dsact_handle* h) {
       continue;
     }
     // ... 32 x 64 tiles where those would leave CUs idle but the contraction is long (type_2 layer 5: K = 1152, M = batch)
-    if (per_group == 1 && M % 32 == 0 && g.Cout % 64 == 0 && g.K % 4 == 0 && g.K >= 512 && !h->env_no_conv_fwd64 && !h->env_no_conv_fwd32x64) {
+    if (per_group == 1 && M % 32 == 0 && g.Cout % 64 == 0 && g.K % 4 == 0 && g.K >= 512) {
       int it = 0;
       for (int q = 0; q < a.n_prob; ++q) { it += (M / 32) * (g.Cout / 64); a.p[q].item_end = it; a.p[q].tiles_n = g.Cout / 64; }
       a.n_items = it;
@@ -1335,11 +1312,17 @@ int enqueue_conv_forward(dsact_handle* h) {
 // arithmetic nor fewer L1 requests had moved it). Longer chunks mean fewer, longer workgroups: pick the multiple of 64
 // that minimises rounds x (start-up + steps) under the measured ~3 us + ~1.1 us per 64-pixel step.
 // narrow layers (all channels of a problem in <= 32 rows, K + 4 <= 160 columns): the register-tile weight gradient (k_conv_dw_reg)
+// -- taken by the 16-channel layers whose K + 4 columns make three LDS k-tiles (type_2 layer 1: 37.0 -> 30.3 us)
 bool conv_dw_reg_ok(const dsact_handle* h, int j, int n_st) {
   const ConvGeom& g = h->cg[j];
   const int per_prob = j == 0 ? n_st : 1;
-  return ((h->env_conv_dw_reg >> j) & 1) && per_prob * g.Cout <= 32 && g.K + 4 <= 160 && g.OW >= 4 && !h->conv_fork;
+  return j >= 1 && g.Cout == 16 && tiles_of(g.K + 4, TN) == 3 && per_prob * g.Cout <= 32 && g.K + 4 <= 160 && g.OW >= 4;
 }
+
+// k-tiles per k_conv_dw workgroup: two (the dY tile of a step is staged once for both) unless the layer has three -- a 2 + 1
+// split leaves the odd workgroups half as long (measured at type_2, batch 256, profiles/r04_convdw_nkt.txt: layers
+// 0 / 2 / 3 / 4 / 5 35.5 / 24.0 / 16.6 / 19.6 / 12.7 -> 33.3 / 20.4 / 15.5 / 19.0 / 12.3 us, layer 1 36.6 -> 44.2)
+int conv_dw_nkt(const dsact_handle* h, int j) { return tiles_of(h->cg[j].K + 4, TN) == 3 ? 1 : 2; }
 
 int conv_dw_pick_chunk(const dsact_handle* h, int j, int n_st) {
   const ConvGeom& g = h->cg[j];
@@ -1348,15 +1331,15 @@ int conv_dw_pick_chunk(const dsact_handle* h, int j, int n_st) {
   if (conv_dw_reg_ok(h, j, n_st)) {
     // one workgroup (4 waves) per chunk and problem: about two workgroups per CU, never more chunks than the partial buffers hold
     const int n_prob = j == 0 ? 1 : n_st;
-    const long long want = ((long long)h->env_conv_dw_reg_wgs + n_prob - 1) / n_prob;
+    const long long want = ((long long)kConvDwRegWgs + n_prob - 1) / n_prob;
     long long c = (M + want - 1) / want;
     c = (c + 63) / 64 * 64;
     return (int)(c < c0 ? c0 : c);
   }
-  const int nkt = h->conv_dw_nkt_l[j];
+  const int nkt = conv_dw_nkt(h, j);
   const int per_prob = j == 0 ? n_st : 1, n_prob = n_st / per_prob;
   const long long per_chunk = (long long)tiles_of(per_prob * g.Cout, TM) * tiles_of(tiles_of(g.K + 4, TN), nkt) * n_prob;
-  const long long slots = ((nkt == 1 || (nkt == 3 && h->env_conv_dw_sb3)) ? 4LL : 2LL) * h->n_cu;   // (1 or 2) x (1 + nkt) LDS tiles of 9 KB per workgroup
+  const long long slots = (nkt == 1 ? 4LL : 2LL) * h->n_cu;   // 2 x (1 + nkt) LDS tiles of 9 KB per workgroup
   int best = c0;
   double best_cost = 1e30;
   for (int c = c0; c <= 16 * c0 && c <= 8192; c += 64) {
@@ -1380,8 +1363,6 @@ int enqueue_conv_backward(dsact_handle* h, int n_st, bool fused, int st_lo = 0) 
     const long long n = (long long)B * h->F;
     TRY(launch(h, "feat_bwd", k_feat_bwd, dim3((unsigned)((n + kThreads - 1) / kThreads), n_st), dim3(kThreads), 0, f));
   }
-  const bool fork = h->conv_fork && !h->profiling;   // (the per-kernel profile runs everything on one stream)
-  if (fork) HIPCHK(h, hipEventRecord(h->ev_conv[last], h->stream));
   for (int j = last; j >= 0; --j) {
     const ConvGeom& g = h->cg[j];
     const int M = B * g.OH * g.OW;
@@ -1393,9 +1374,7 @@ int enqueue_conv_backward(dsact_handle* h, int n_st, bool fused, int st_lo = 0) 
       a.g = g; a.ix = conv_index(g);
       a.chunk = chunk; a.n_chunks = n_chunks; a.K1p = K1p;
       const int kt_all = tiles_of(a.K1p, TN);
-      // k-tiles per workgroup (the dY tile would be staged once for all of them): measured slower than one
-      // k-tile per workgroup on every layer (fewer, longer dependent chains) -> 1
-      const int nkt = h->conv_dw_nkt_l[j];
+      const int nkt = conv_dw_nkt(h, j);
       a.tiles_k = tiles_of(kt_all, nkt);             // k-groups
       int blocks = 0;
       // layer 0: every differentiated stack reads the staged `obs` image -> one problem, dY rows concatenated
@@ -1410,8 +1389,7 @@ int enqueue_conv_backward(dsact_handle* h, int n_st, bool fused, int st_lo = 0) 
         blocks += a.n_chunks * p.tiles_co * a.tiles_k;
         p.block_end = blocks;
       }
-      const bool sb3 = nkt == 3 && h->env_conv_dw_sb3;   // single-buffered three-k-tile form
-      const size_t lds = (size_t)(sb3 ? 1 : 2) * (1 + nkt) * TILE_LDS * sizeof(float);
+      const size_t lds = (size_t)2 * (1 + nkt) * TILE_LDS * sizeof(float);
       if (conv_dw_reg_ok(h, j, n_st)) {
         // register tiles: one workgroup per (problem, chunk)
         int rb = 0;
@@ -1425,17 +1403,9 @@ int enqueue_conv_backward(dsact_handle* h, int n_st, bool fused, int st_lo = 0) 
         else if (ncb == 1) TRY(launch(h, nm.c_str(), (k_conv_dw_reg<1, 10>), dim3(rb), dim3(kThreads), 0, a));
         else TRY(launch(h, nm.c_str(), (k_conv_dw_reg<2, 10>), dim3(rb), dim3(kThreads), 0, a));
       } else
-      if (fork) {
-        HIPCHK(h, hipStreamWaitEvent(h->aux_stream, h->ev_conv[j], 0));
-        if (nkt != 1) return fail(h, DSACT_E_INVALID, "DSACT_CONV_FORK needs DSACT_CONV_DW_NKT=1");
-        TRY(launch_on(h, h->aux_stream, ("conv_dw" + sfx).c_str(), k_conv_dw<1>, dim3(blocks), dim3(kThreads), lds, a));
-      } else
       // (three / four steps of loads in flight, k_conv_dw<1, 3|4>: 46.4-48.3 us vs 45 us on layers 0 / 1 -- not latency-bound)
       if (nkt == 1) TRY(launch(h, ("conv_dw" + sfx).c_str(), k_conv_dw<1>, dim3(blocks), dim3(kThreads), lds, a));
-      else if (nkt == 2) TRY(launch(h, ("conv_dw" + sfx).c_str(), k_conv_dw<2>, dim3(blocks), dim3(kThreads), lds, a));
-      else if (sb3) TRY(launch(h, ("conv_dw" + sfx).c_str(), (k_conv_dw<3, 2, false>), dim3(blocks), dim3(kThreads), lds, a));
-      else if (nkt == 3) TRY(launch(h, ("conv_dw" + sfx).c_str(), k_conv_dw<3>, dim3(blocks), dim3(kThreads), lds, a));
-      else return fail(h, DSACT_E_INVALID, "DSACT_CONV_DW_NKT must be 1..3");
+      else TRY(launch(h, ("conv_dw" + sfx).c_str(), k_conv_dw<2>, dim3(blocks), dim3(kThreads), lds, a));
     }
     // (the 16-channel layer through dCol + col2im instead: 49.5 + 23.8 us vs 42 us direct, measured round 3)
     const bool direct_dx = j > 0 && (g.Cin == 8 || g.Cin == 16) && g.Cout <= 32;
@@ -1450,19 +1420,18 @@ int enqueue_conv_backward(dsact_handle* h, int n_st, bool fused, int st_lo = 0) 
         c.x[st] = h->cact[S(st)][j - 1]; c.dx[st] = h->cdy[S(st)][j - 1];
       }
       const int Yq = (g.H + g.stride - 1) / g.stride, Xq = (g.W + g.stride - 1) / g.stride;   // largest parity class
-      if (g.KS == 3 && g.stride == 2 && g.Cin == 16 && g.Cout == 32 && !h->env_no_conv_dx_mfma) {
+      if (g.KS == 3 && g.stride == 2 && g.Cin == 16 && g.Cout == 32) {
         // matrix-core variant (dsact_conv.h: k_conv_dx_mfma): two 16-pixel-pair tiles per wave. 16-channel layer: 43.9 ->
         // 24.3 us; the 8-channel layer (half of every tile's columns idle) 30.9 -> 38.6 us, so it keeps the block kernel
         const int Xq_ = (g.W + 1) / 2, Yc0 = (g.H + 1) / 2;
         const int tiles0 = (B * Yc0 * Xq_ + 15) / 16;
         const dim3 gm((unsigned)((tiles0 + 7) / 8), n_st, 2);
         TRY(launch(h, ("conv_dx" + sfx).c_str(), (k_conv_dx_mfma<16, 32>), gm, dim3(kThreads), 0, c));
-      } else if (g.KS == 3 && g.stride == 2) {
+      } else if (g.KS == 3 && g.stride == 2 && g.Cin == 8) {
         // one thread per 2x2 pixel block (all four parity classes); (one thread per pixel on the 16-channel layer, 4x the
         // workgroups: 72.5 us vs 42.6 us, round 3)
         const dim3 gb((unsigned)((B * Yq * Xq + kThreads - 1) / kThreads), n_st);
-        if (g.Cin == 8) TRY(launch(h, ("conv_dx" + sfx).c_str(), (k_conv_dx_block<2, 3, 2>), gb, dim3(kThreads), 0, c));
-        else TRY(launch(h, ("conv_dx" + sfx).c_str(), (k_conv_dx_block<4, 3, 2>), gb, dim3(kThreads), 0, c));
+        TRY(launch(h, ("conv_dx" + sfx).c_str(), (k_conv_dx_block<2, 3, 2>), gb, dim3(kThreads), 0, c));
       } else {
         const dim3 grid((unsigned)((B * Yq * Xq + kThreads - 1) / kThreads), n_st, g.stride * g.stride);
         if (g.Cin == 8) TRY(launch(h, ("conv_dx" + sfx).c_str(), k_conv_dx_direct<2>, grid, dim3(kThreads), 0, c));
@@ -1491,7 +1460,7 @@ int enqueue_conv_backward(dsact_handle* h, int n_st, bool fused, int st_lo = 0) 
         stage_add(s, t);
       }
       TRY(run_stage(h, s));
-      if (ident) { if (fork && j > 0) HIPCHK(h, hipEventRecord(h->ev_conv[j - 1], h->stream)); continue; }
+      if (ident) continue;
       Col2imArgs c;
       memset(&c, 0, sizeof(c));
       c.g = g; c.n_prob = n_st; c.B = B;
@@ -1499,11 +1468,6 @@ int enqueue_conv_backward(dsact_handle* h, int n_st, bool fused, int st_lo = 0) 
       const long long n = (long long)B * g.H * g.W * (g.Cin / 4);
       TRY(launch(h, ("col2im" + sfx).c_str(), k_col2im, dim3((unsigned)((n + kThreads - 1) / kThreads), n_st), dim3(kThreads), 0, c));
     }
-    if (fork && j > 0) HIPCHK(h, hipEventRecord(h->ev_conv[j - 1], h->stream));   // dY[j-1] is complete
-  }
-  if (fork) {
-    HIPCHK(h, hipEventRecord(h->ev_join, h->aux_stream));
-    HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
   }
   {
     // ordered reduce of the partials of ALL layers (+ Adam / Polyak when fused) in one launch, after the whole conv
@@ -1828,7 +1792,6 @@ int run_dw2(dsact_handle* h, int x0, int x1, bool fused, bool finalize) {
 // hides less latency than two 8-row ones), the policy backward is even -- so only the critics' backward asks for it
 // (`allow4`), and only when even 16-row slices give every CU a workgroup.
 int chain_rg(const dsact_handle* h, int n_units, bool allow4 = false) {
-  if (h->env_chain_rg) return h->env_chain_rg;
   if (n_units * (h->B / 4) <= 256) return 1;
   if (allow4 && h->rg4_ok && n_units * (h->B / 16) >= 256) return 4;
   return h->cRG;
@@ -1867,7 +1830,9 @@ void fill_fwd_common(dsact_handle* h, FwdArgs& a, int rg, const char* name, cons
   a.timeline = tl_for(h, name);
   a.spin_timeout = h->handoff_dev;
   a.debug_withhold = h->debug_withhold == 1;
-  a.tpad = h->fat ? 0 : h->env_pk_pad;
+  // the forward packs have no padding steps; FwdArgs::tpad stays (always 0, here and in the zeroed PipeFwd of the pipelined
+  // forward) so that the chain kernels' code is unchanged
+  a.tpad = 0;
 }
 
 // group A: policy(obs), policy_target(obs2), q1/q2(obs,act) + observation part of q1_t/q2_t(obs2, .)
@@ -2214,7 +2179,7 @@ int alloc_pipe_sets(dsact_handle* h) {
       p.part_heads = c.take<float>((size_t)h->n_heads_wg * 2);
       p.X0t = c.take<float>(B * (size_t)((h->F + A + 31) / 32 * 32));
     }
-    for (int i = 0; i < 3; ++i) h->pipe_hand[i] = c.take<unsigned long long>(B * 32);
+    for (int i = 0; i < 2; ++i) h->pipe_hand[i] = c.take<unsigned long long>(B * 32);
     if (!pass) {
       HIPCHK(h, hipMalloc((void**)&h->pipe_ws, c.off + 256));
       HIPCHK(h, hipMemset(h->pipe_ws, 0, c.off + 256));
@@ -2252,8 +2217,8 @@ const char* pipe_fwd_name(bool pre, bool do_pre) {
 
 // roles of a pipelined forward launch, in dispatch-priority order: units that never wait, own minibatch then next; then
 // their consumers. A unit waits only for units EARLIER in this order, and every XCD's queue is filled in this order.
-enum PipeRole { PR_PI = 0, PR_PIT, PR_Q1C, PR_Q2C, PR_PIN, PR_PITN, PR_Q1P, PR_Q2P, PR_Q1T, PR_Q2T, PR_Q1TN, PR_Q2TN, PR_N };
-static const char* kPipeRoleName[PR_N] = {"pi", "pit", "q1c", "q2c", "pin", "pitn", "q1p", "q2p", "q1t", "q2t", "q1tn", "q2tn"};
+enum PipeRole { PR_PI = 0, PR_PIT, PR_Q1C, PR_Q2C, PR_PIN, PR_PITN, PR_Q1P, PR_Q2P, PR_Q1T, PR_Q2T, PR_N };
+static const char* kPipeRoleName[PR_N] = {"pi", "pit", "q1c", "q2c", "pin", "pitn", "q1p", "q2p", "q1t", "q2t"};
 static_assert(PR_N <= kPipeUnits, "unit table too small");
 
 // XCDs of a role in a launch shape (pre = the policy units of this minibatch were computed by the previous launch, do_pre =
@@ -2265,15 +2230,15 @@ static const char* pipe_xcds_default(bool pre, bool do_pre, int role) {
     // cost 7 - 16 us, single-unit moves around this one +-1 us (scripts/pipe_map_search.py, profiles/r04_pipe_map_search.txt)
     // pi and pi_target (their consumers q_p / q_t are the two critical paths) 4-row workgroups on two XCDs each, one per CU;
     // q_t's 4-row workgroups half beside pi_target (they resume when it exits), half beside the next minibatch's policy units
-    static const char* t[PR_N] = {"01", "27", "3", "4", "5", "6", "30", "41", "52", "67", "52", "67"};
+    static const char* t[PR_N] = {"01", "27", "3", "4", "5", "6", "30", "41", "52", "67"};
     return t[role];
   }
   if (!do_pre) {   // TF: only the fresh-critic chains, all independent: 8-row workgroups (half the L2 traffic of 4-row ones:
     // 22.2 vs 26.6 us, profiles/r04_pipe_map_search.txt), every unit on two or more XCDs (placement among those: equal)
-    static const char* t[PR_N] = {"", "", "04", "15", "", "", "26", "37", "0246", "1357", "", ""};
+    static const char* t[PR_N] = {"", "", "04", "15", "", "", "26", "37", "0246", "1357"};
     return t[role];
   }
-  static const char* t[PR_N] = {"", "", "04", "15", "26", "37", "26", "37", "0246", "1357", "0246", "1357"};   // TT (delay_update >= 3)
+  static const char* t[PR_N] = {"", "", "04", "15", "26", "37", "26", "37", "0246", "1357"};   // TT (delay_update >= 3)
   return t[role];
 }
 
@@ -2308,7 +2273,6 @@ static PipePlace pipe_place(const dsact_handle* h, bool pre, bool do_pre, int ro
 // bp: nullptr, or the deferred policy backward of the previous update this launch carries (its chain slices and tiles)
 int pipe_fwd_build(dsact_handle* h, int set_own, int set_next, bool pre, bool do_pre, PipeFwd& P, const BwdPiArgs* bp = nullptr, bool book = false) {
   memset(&P, 0, sizeof(P));
-  const bool qt_pre = false;   // (precomputing the NEXT minibatch's target units too -- DSACT_PIPE_QT, rounds 4-5 -- measured slower and removed)
   int* f = h->chain_flags;
   const int B = h->B;
   int idx[PR_N];
@@ -2318,52 +2282,39 @@ int pipe_fwd_build(dsact_handle* h, int set_own, int set_next, bool pre, bool do
   // rows per workgroup: the critical units (pi -> q_p) run 4-row workgroups; the others 8-row ones (39 % less CU time per
   // row) unless the launch leaves CUs idle anyway; a consumer never has more rows than its producer (it waits for ONE flag)
   const int side = (B % 8 == 0) ? 2 : 1, nxt = side;   // 8-row workgroups off the critical path (4-row ones: measured slower, rounds 4-5)
-  const int dflt[PR_N] = {1, pre ? side : 1, side, side, nxt, nxt, pre ? side : 1, pre ? side : 1, pre ? side : 1, pre ? side : 1, side, side};
+  const int dflt[PR_N] = {1, pre ? side : 1, side, side, nxt, nxt, pre ? side : 1, pre ? side : 1, pre ? side : 1, pre ? side : 1};
   for (int r = 0; r < PR_N; ++r) {
     const PipePlace pl = pipe_place(h, pre, do_pre, r, dflt[r]);
     rgs[r] = (B % 8 == 0) ? pl.rg : 1; xc[r] = pl.xcds;
   }
+  // (q_p waits for q_c's saved accumulators by flag, hence the cap; the sampled actions arrive as tagged pairs, polled per
+  //  element: any rows)
   auto cap = [&](int consumer, int producer) { if (rgs[consumer] > rgs[producer]) rgs[consumer] = rgs[producer]; };
   if (!pre) { cap(PR_Q1P, PR_Q1C); cap(PR_Q2P, PR_Q2C); }
-  if (!pre && h->env_no_pipe_tagged) { cap(PR_Q1P, PR_PI); cap(PR_Q2P, PR_PI); cap(PR_Q1T, PR_PIT); cap(PR_Q2T, PR_PIT); }
-  if (h->env_no_pipe_tagged) { cap(PR_Q1TN, PR_PITN); cap(PR_Q2TN, PR_PITN); }   // (tagged pairs are polled per element: any rows)
   auto put = [&](int role, const FwdUnit& u) {
     idx[role] = role;
     P.u[role] = u;
     P.u[role].rg = (short)rgs[role];
     P.u[role].n_slices = (short)(B / (4 * rgs[role]));
   };
-  // in-launch hand-over of the sampled actions: (value, tag) pairs (the data is the flag) or, DSACT_NO_PIPE_TAGGED, ready flags
-  const bool tagged = !h->env_no_pipe_tagged;
-  auto policy_units = [&](int r_pi, int r_pit, bool flag_pi, bool flag_pit) {
+  // in-launch hand-over of the sampled actions: (value, tag) pairs, the data is the flag (pipe_hand[0]: new_act, [1]: act2)
+  auto policy_units = [&](int r_pi, int r_pit, bool hand_over) {
     FwdUnit pi = fwd_unit(h, C_PI, SEG_FULL, HEAD_POLICY);
     pi.logits = h->logits_pi; pi.logp = h->logp_new; pi.eps = h->eps_new; pi.xact = h->Xc[C_Q1P]; pi.part_heads = h->part_heads;
-    if (flag_pi && tagged) { pi.xact2 = (float*)h->pipe_hand[0]; pi.late_wait |= HW_PAIRS_OUT; }
-    else if (flag_pi) pi.done = f + 0 * kChainFlagSlices;
+    if (hand_over) { pi.xact2 = (float*)h->pipe_hand[0]; pi.late_wait |= HW_PAIRS_OUT; }
     put(r_pi, pi);
     FwdUnit pt = fwd_unit(h, C_PIT, SEG_FULL, HEAD_POLICY);
     pt.logits = h->logits_pit; pt.logp = h->logp2; pt.eps = h->eps_2; pt.xact = h->Xc[C_Q1T];
     for (int l = 0; l < h->L; ++l) pt.G[l] = nullptr;   // never differentiated
-    if (flag_pit && tagged) { pt.xact2 = (float*)h->pipe_hand[r_pit == PR_PIT ? 1 : 2]; pt.late_wait |= HW_PAIRS_OUT; }
-    else if (flag_pit) pt.done = f + (r_pit == PR_PIT ? 1 : 4) * kChainFlagSlices;
+    if (hand_over) { pt.xact2 = (float*)h->pipe_hand[1]; pt.late_wait |= HW_PAIRS_OUT; }
     put(r_pit, pt);
   };
-  auto target_units = [&](int r_q1t, int r_pit, bool wait) {
-    for (int i = 0; i < h->nq; ++i) {   // (one critic: DSAC_V1)
-      FwdUnit qt = fwd_unit(h, C_Q1T + i, SEG_FULL_SPLIT, HEAD_Q);
-      qt.qout = h->qout_t[i];
-      for (int l = 0; l < h->L; ++l) qt.G[l] = nullptr;   // never differentiated
-      if (wait && tagged) { qt.wait0 = (const int*)h->pipe_hand[r_pit == PR_PIT ? 1 : 2]; qt.wait_rows0 = 4; qt.late_wait = HW_LATE | HW_PAIRS_IN; }
-      else if (wait) { qt.wait0 = P.u[r_pit].done; qt.wait_rows0 = 4 * rgs[r_pit]; qt.late_wait = HW_LATE; }
-      put(r_q1t + i, qt);
-    }
-  };
   apply_pipe_set(h, set_own);
-  if (!pre) policy_units(PR_PI, PR_PIT, true, true);
+  if (!pre) policy_units(PR_PI, PR_PIT, true);
   // q(obs, new_act): eager updates run it as "saved observation part of q(obs, act)'s first layer + action part". A unit
   // that computes the observation part itself and merges the accumulators where the hand-over would have (SEG_FULL_SPLIT)
   // produces the same bits with no producer: that is how the launches whose policy units ran earlier hold it (no in-launch
-  // dependency at all), and -- DSACT_PIPE_QP_SPLIT=1 -- optionally the others (observation part under the wait for pi)
+  // dependency at all)
   const bool qp_split = pre;
   for (int i = 0; i < h->nq; ++i) {   // (one critic: DSAC_V1)
     FwdUnit qc = fwd_unit(h, C_Q1C + i, qp_split ? SEG_FULL : SEG_FULL_SAVE, HEAD_Q);
@@ -2373,16 +2324,20 @@ int pipe_fwd_build(dsact_handle* h, int set_own, int set_next, bool pre, bool do
     put(PR_Q1C + i, qc);
     FwdUnit qp = fwd_unit(h, C_Q1P + i, qp_split ? SEG_FULL_SPLIT : SEG_ACT_FROM_SAVED, HEAD_Q);
     qp.qout = h->qout_p[i];
-    if (!pre && tagged) { qp.wait0 = (const int*)h->pipe_hand[0]; qp.wait_rows0 = 4; qp.late_wait = HW_LATE | HW_PAIRS_IN; }
-    else if (!pre) { qp.wait0 = P.u[PR_PI].done; qp.wait_rows0 = 4 * rgs[PR_PI]; qp.late_wait = HW_LATE; }
+    if (!pre) { qp.wait0 = (const int*)h->pipe_hand[0]; qp.wait_rows0 = 4; qp.late_wait = HW_LATE | HW_PAIRS_IN; }
     if (!qp_split) { qp.zinit = h->zobs[i]; qp.wait1 = qc.zdone; qp.wait_rows1 = 4 * rgs[PR_Q1C + i]; }
     put(PR_Q1P + i, qp);
   }
-  if (!pre || !qt_pre) target_units(PR_Q1T, PR_PIT, !pre);
+  for (int i = 0; i < h->nq; ++i) {   // (one critic: DSAC_V1)
+    FwdUnit qt = fwd_unit(h, C_Q1T + i, SEG_FULL_SPLIT, HEAD_Q);
+    qt.qout = h->qout_t[i];
+    for (int l = 0; l < h->L; ++l) qt.G[l] = nullptr;   // never differentiated
+    if (!pre) { qt.wait0 = (const int*)h->pipe_hand[1]; qt.wait_rows0 = 4; qt.late_wait = HW_LATE | HW_PAIRS_IN; }
+    put(PR_Q1T + i, qt);
+  }
   if (do_pre) {
     apply_pipe_set(h, set_next);
-    policy_units(PR_PIN, PR_PITN, false, qt_pre);
-    if (qt_pre) target_units(PR_Q1TN, PR_PITN, true);
+    policy_units(PR_PIN, PR_PITN, false);
     apply_pipe_set(h, set_own);
   }
   // common fields
@@ -2395,7 +2350,6 @@ int pipe_fwd_build(dsact_handle* h, int set_own, int set_next, bool pre, bool do
   a.spin_timeout = h->handoff_dev;
   a.debug_withhold = h->debug_withhold == 1;
   a.tagp = &h->st->tag_seq;
-  a.tpad = h->env_pk_pad;
   // block table: every XCD's queue is filled role by role (the enum is the priority order), a role's slices are dealt
   // round-robin over its XCDs; block 8 r + x = entry r of XCD x's queue (the dispatcher places block b on XCD b % 8)
   std::vector<int> q[8];
@@ -2422,17 +2376,7 @@ int pipe_fwd_build(dsact_handle* h, int set_own, int set_next, bool pre, bool do
   P.n_blocks = (int)(8 * rounds);
   for (size_t r = 0; r < rounds; ++r)
     for (int x = 0; x < 8; ++x) P.blk[8 * r + x] = r < q[x].size() ? q[x][r] : -1;
-  if (!h->env_no_pipe_warm) {   // L2 warm-up shares: (index, count) among the workgroups of the same unit on the same XCD
-    for (int x = 0; x < 8; ++x) {
-      int cnt[PR_N], seen[PR_N];
-      for (int r = 0; r < PR_N; ++r) cnt[r] = seen[r] = 0;
-      for (int code : q[x]) if ((code >> 16) < PR_N) cnt[code >> 16]++;
-      for (size_t r = 0; r < q[x].size(); ++r) {
-        const int role = q[x][r] >> 16;
-        if (role < PR_N) P.warm[8 * r + x] = (seen[role]++ << 16) | cnt[role];
-      }
-    }
-  }
+  // (P.warm stays zero: no L2 warm-up touches -- measured slower, 60.4 vs 59.6 us)
   h->n_heads_parts = h->B / 4;
   return DSACT_OK;
 }
@@ -2564,9 +2508,9 @@ void bwd_pi_args(dsact_handle* h, int x0, int x1, bool fused, BwdPiArgs& a, int&
   for (int l = 0; l < L; ++l) { a.G[l] = h->Gb[C_PI][l]; a.dZ[l] = h->dZ[kDzSlot[C_PI]][l]; }
   a.dout_pi = h->dout_pi; a.d_new_act = h->d_new_act; a.dout_piT = h->doutT[2];
   // the policy chain shares its launch with ~2 rounds of weight-gradient tiles, which bound it: 8-row workgroups leave
-  // them 32 more CUs (measured: 15.7 us vs 16.3 us with 4-row workgroups at batch 256)
-  const int rg_pi = 0;   // (4-row slices with the merged tiles waiting for the chain measured 20.99 vs 20.04 us, round 3: the chain's own choice)
-  const int rg = rg_force ? rg_force : h->fat_bwd ? 4 * fat_rt(h, 1) : rg_pi ? rg_pi : h->env_chain_rg ? h->env_chain_rg : (h->B >= 8 ? h->cRG : 1);
+  // them 32 more CUs (measured: 15.7 us vs 16.3 us with 4-row workgroups at batch 256; 4-row slices with the merged tiles
+  // waiting for the chain: 20.99 vs 20.04 us, round 3)
+  const int rg = rg_force ? rg_force : h->fat_bwd ? 4 * fat_rt(h, 1) : (h->B >= 8 ? h->cRG : 1);
   a.n_slices = h->B / (4 * rg); a.B = h->B; a.A = h->A; a.L = L; a.Cb = h->B / 16;
   a.inv_B = 1.0f / (float)h->B; a.auto_alpha = h->cfg.auto_alpha; a.alpha_fixed = h->cfg.alpha_fixed;
   a.act_scale = h->act_scale; a.lo_ls = h->cfg.min_log_std; a.hi_ls = h->cfg.max_log_std;
@@ -2992,15 +2936,9 @@ actor_part:
   // tiles that may ride: the critics' + (behind heads_bwd only) the policy's output layer
   const int ride_end = h->bwdpi.empty() ? h->dw_off[2] : h->dw_pol_rest;
   int ride_hb = 0;
-  if (phase == 0 && !(h->use_fork && !h->profiling)) {
+  if (phase == 0) {
     ride_hb = (ride_end - h->dw_off[0]) / n_carriers;
     if (ride_hb > crit_tiles) ride_hb = crit_tiles;
-  }
-  if (h->use_fork && !h->profiling) {
-    HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
-    HIPCHK(h, hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
-    TRY(run_dw(h, h->dw_off[0], h->dw_off[2], fused, false, h->aux_stream));
-    HIPCHK(h, hipEventRecord(h->ev_join, h->aux_stream));
   }
   {
     HeadsBwdArgs a;
@@ -3027,16 +2965,6 @@ actor_part:
     NCH_DISPATCH(a.WL, CALL_HBWD);
   }
   const size_t np = h->bwdpi.size();
-  if (h->use_fork && !h->profiling) {
-    // The critics' weight gradients (+ their Adam/Polyak) depend only on the critic backward above,
-    // not on the actor chain (heads_bwd -> policy backward): they run on a forked branch -- a second
-    // HIP stream, captured as a parallel branch of the graph -- and join before the final launch.
-    // (heads_bwd was already enqueued on the main stream; the fork event is recorded before it.)
-    for (size_t i = 0; i < np; ++i) TRY(run_stage(h, h->bwdpi[i], 0, 0, fused));
-    HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
-    TRY(run_dw(h, h->dw_off[2], h->dw_off[3], fused, fused));
-    return DSACT_OK;
-  }
   if (phase == 4) {
     for (size_t i = 0; i < np; ++i) TRY(run_stage(h, h->bwdpi[i]));
     if (h->cnn) TRY(run_stage(h, h->dfeat_pi));
@@ -3045,7 +2973,7 @@ actor_part:
     TRY(sum_parts(h, (size_t)h->nq * h->n_q, h->n_online - 1));
     return DSACT_OK;
   }
-  // unforked: the rest of the critics' tiles ride along in the policy-backward launches, evenly
+  // the rest of the critics' tiles ride along in the policy-backward launches, evenly
   {
     int x = h->dw_off[0] + ride_hb;
     for (size_t i = 0; i < np; ++i) {
@@ -3400,50 +3328,14 @@ int dsact_create(const dsact_config* cfg, int device, dsact_handle** out) {
   h->loss_rows = 4;
   h->auto_std_sums = h->B > 1024;   // large batches: the std column is summed once, not by every wave
   if (const char* v = getenv("DSACT_TIMELINE_STAGE")) h->env_timeline_stage = v;
-  h->env_no_merged_gather = getenv("DSACT_NO_MERGED_GATHER") != nullptr;
-  h->env_no_adam_pack = getenv("DSACT_NO_ADAM_PACK") != nullptr;
   { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && v > 0) h->n_cu = v; (void)hipGetLastError(); }
-  if (const char* v = getenv("DSACT_CONV_DW_NKT")) h->env_conv_dw_nkt = atoi(v);
-  for (int j = 0; j < kMaxConv; ++j) h->conv_dw_nkt_l[j] = h->env_conv_dw_nkt;   // (0: the per-layer default, set below once the geometry is known)
-  if (const char* v = getenv("DSACT_CONV_DW_NKT_L")) {
-    int j = 0;
-    for (const char* p = v; *p && j < kMaxConv; ++j) {
-      const int n = atoi(p);
-      if (n >= 1 && n <= 3) h->conv_dw_nkt_l[j] = n;
-      while (*p && *p != ',') ++p;
-      if (*p == ',') ++p;
-    }
-  }
-  // default: two k-tiles per workgroup (the dY tile of a step is staged once for both) unless the layer has three -- a 2 + 1
-  // split leaves the odd workgroups half as long (measured at type_2, batch 256, profiles/r04_convdw_nkt.txt: layers
-  // 0 / 2 / 3 / 4 / 5 35.5 / 24.0 / 16.6 / 19.6 / 12.7 -> 33.3 / 20.4 / 15.5 / 19.0 / 12.3 us, layer 1 36.6 -> 44.2)
-  for (int j = 0; j < h->n_conv; ++j)
-    if (h->conv_dw_nkt_l[j] < 1 || h->conv_dw_nkt_l[j] > 3) h->conv_dw_nkt_l[j] = tiles_of(h->cg[j].K + 4, TN) == 3 ? 1 : 2;
-  for (int j = h->n_conv; j < kMaxConv; ++j) h->conv_dw_nkt_l[j] = 1;
-  h->env_no_pipe = getenv("DSACT_NO_PIPE") != nullptr;
   h->env_no_pipe_defer = getenv("DSACT_NO_PIPE_DEFER") != nullptr;
   h->env_no_bqt = getenv("DSACT_NO_BQT_MERGE") != nullptr;
   h->env_no_bqp = getenv("DSACT_NO_BQP_MERGE") != nullptr;
-  h->env_no_pipe_warm = getenv("DSACT_PIPE_WARM") == nullptr;
-  h->env_no_pipe_tagged = getenv("DSACT_NO_PIPE_TAGGED") != nullptr;
-  if (const char* v = getenv("DSACT_PK_PAD")) h->env_pk_pad = atoi(v) > 0 && atoi(v) <= 64 ? atoi(v) : 0;
   if (const char* v = getenv("DSACT_PIPE_MAP")) h->env_pipe_map = v;
-  h->env_no_conv_dx_mfma = getenv("DSACT_NO_CONV_DX_MFMA") != nullptr;
-  h->env_no_conv_narrow9 = getenv("DSACT_NO_CONV_NARROW9") != nullptr;
-  h->env_no_conv_fwd64 = getenv("DSACT_NO_CONV_FWD64") != nullptr;
-  h->env_no_conv_fwd32x64 = getenv("DSACT_NO_CONV_FWD32X64") != nullptr;
-  h->env_conv_dw_sb3 = getenv("DSACT_CONV_DW_SB3") != nullptr;
-  // default: the 16-channel layers whose K + 4 columns make three LDS k-tiles (type_2 layer 1: 37.0 -> 30.3 us)
-  for (int j = 1; j < h->n_conv; ++j)
-    if (h->cg[j].Cout == 16 && tiles_of(h->cg[j].K + 4, TN) == 3) h->env_conv_dw_reg |= 1 << j;
-  if (const char* v = getenv("DSACT_CONV_DW_REG")) h->env_conv_dw_reg = atoi(v);
-  if (const char* v = getenv("DSACT_CONV_DW_REG_WGS")) h->env_conv_dw_reg_wgs = atoi(v) > 0 ? atoi(v) : 512;
-  if (const char* v = getenv("DSACT_CONV_FWD64_MIN")) h->env_conv_fwd64_min = atoi(v);
-  if (const char* v = getenv("DSACT_DCOL64_MIN_M")) h->env_dcol64_min_m = atoi(v);
   h->env_no_dcol_ident = getenv("DSACT_NO_DCOL_IDENT") != nullptr;
   h->env_no_fat_stage = getenv("DSACT_NO_FAT_STAGE") != nullptr;
-  if (const char* v = getenv("DSACT_CHAIN_RG")) h->env_chain_rg = atoi(v) == 1 ? 1 : atoi(v) == 4 ? 4 : 2;
-  h->dw_chunks = (h->B > 448 && h->B % 256 == 0 && getenv("DSACT_NO_SPLITK") == nullptr) ? h->B / 256 : 1;   // (chain path: below)
+  h->dw_chunks = (h->B > 448 && h->B % 256 == 0) ? h->B / 256 : 1;   // (chain path: below)
   h->dw_part_stride = (h->n_online + 2 + 63) & ~(size_t)63;
   {
     // row-slice fused chains: MLP nets of DSAC_V2 with equal hidden widths of 64 / 128 / 256, batch a multiple of 16
@@ -3469,29 +3361,26 @@ int dsact_create(const dsact_config* cfg, int device, dsact_handle** out) {
     ok = ok && (size_t)chain_lds(4 * (h->s_obs + h->s_act), W0, R).total * sizeof(float) <= 150 * 1024;
     h->chain_ok = ok;
     h->twin = ok && h->cnn;
-    if (h->cnn) h->env_pk_pad = 0;
     h->env_twin_seq = getenv("DSACT_TWIN_SEQ") != nullptr;
     if (ok) {
       // chain path: a weight-gradient tile contracts up to 1024 batch rows itself (rounds of 256, dw2_tile), so up to
       // batch 1024 there is ONE gradient arena and the optimiser stays fused into the tiles (no split-K partials, no
       // streaming Adam pass, and the graph keeps the riding gather); beyond that one partial arena per 1024 rows
-      const int per = (h->B > 1024 && h->B % 1024 == 0 && getenv("DSACT_DW_RANGE_256") == nullptr) ? 1024 : 256;
-      h->dw_chunks = h->B > 1024 || (h->B > 256 && getenv("DSACT_DW_RANGE_256") != nullptr) ? h->B / per : 1;
+      const int per = (h->B > 1024 && h->B % 1024 == 0) ? 1024 : 256;
+      h->dw_chunks = h->B > 1024 ? h->B / per : 1;
     }
     h->cW = W0; h->cNT = W0 / 64; h->n_slices = h->B / R;
-    h->rg4_ok = ok && h->B % 16 == 0 && getenv("DSACT_NO_RG4") == nullptr &&
+    h->rg4_ok = ok && h->B % 16 == 0 &&
                 (size_t)chain_lds(4 * (h->s_obs + h->s_act), W0, 16).total * sizeof(float) <= 150 * 1024;
     // merged forward launch: both groups resident at once (4-row group-B workgroups: batch <= 256), one flag per slice
     h->c_obs = (h->F + 15) / 16; h->c_act = (h->A + 15) / 16; h->c_out = (2 * h->A + 15) / 16;
     {
       const char* fm = getenv("DSACT_FAT_MIN");
       const int fat_min = fm ? atoi(fm) : 1024;
-      const char* fb = getenv("DSACT_FAT_BWD_MIN");
-      const int fat_bwd_min = fb ? atoi(fb) : 4096;
       // (the throughput-regime kernels hold DSAC_V2's two-critic row phase: one critic keeps the 8-row chains at every batch)
-      h->fat = ok && !h->cnn && h->nq == 2 && h->B >= fat_min && h->B % 32 == 0 && (W0 == 128 || W0 == 256) && getenv("DSACT_NO_FAT") == nullptr &&
+      h->fat = ok && !h->cnn && h->nq == 2 && h->B >= fat_min && h->B % 32 == 0 && (W0 == 128 || W0 == 256) &&
                cfg->value_out_act == 0 && cfg->policy_out_act == 0;   // (their heads are linear-only)
-      h->fat_bwd = h->fat && h->B >= fat_bwd_min;
+      h->fat_bwd = h->fat && h->B >= 4096;
       if (const char* v = getenv("DSACT_FAT_RT")) h->env_fat_rt = atoi(v) == 2 ? 2 : 1;
     }
     h->fwd_merge = ok && !h->cnn && h->B <= 256 && h->B / 4 <= kChainFlagSlices && chain_rg(h, 4) == 1 && getenv("DSACT_NO_FWD_MERGE") == nullptr;
@@ -3528,13 +3417,6 @@ int dsact_create(const dsact_config* cfg, int device, dsact_handle** out) {
   }
   HIPCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   h->own_stream = true;
-  HIPCHK(h, hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
-  HIPCHK(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-  HIPCHK(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-  for (int j = 0; j <= kMaxConv; ++j) HIPCHK(h, hipEventCreateWithFlags(&h->ev_conv[j], hipEventDisableTiming));
-  h->conv_fork = h->cnn && getenv("DSACT_CONV_FORK") != nullptr;
-  if (h->conv_fork) for (int j = 0; j < kMaxConv; ++j) h->conv_dw_nkt_l[j] = 1;   // (the second-queue launches are the one-k-tile form)
-  h->use_fork = getenv("DSACT_FORK") != nullptr && !h->cnn && h->dw_chunks == 1;  // measured: a forked graph branch costs +20 us/update (cross-queue signals) -> opt-in only
   {
     const int max_lds = (int)tile_lds_bytes(BK * kMaxPrefetchTiles);  // 129 KB of the CU's 160 KB
     HIPCHK(h, hipFuncSetAttribute((const void*)k_stage<false, false, EPI_GELU>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
@@ -3549,7 +3431,6 @@ int dsact_create(const dsact_config* cfg, int device, dsact_handle** out) {
     HIPCHK(h, hipFuncSetAttribute((const void*)k_heads_bwd<3>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
     HIPCHK(h, hipFuncSetAttribute((const void*)k_heads_bwd<4>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
     HIPCHK(h, hipFuncSetAttribute((const void*)k_stage<false, true, EPI_STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_conv_dw<3>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
     HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
     HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<1, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
     HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
@@ -3701,10 +3582,6 @@ int dsact_destroy(dsact_handle* h) {
   if (h->code_miss) hipFree(h->code_miss);
   if (h->miss_host) hipHostFree(h->miss_host);
   if (h->ws) hipFree(h->ws);
-  if (h->aux_stream) { hipStreamSynchronize(h->aux_stream); hipStreamDestroy(h->aux_stream); }
-  for (int j = 0; j <= kMaxConv; ++j) if (h->ev_conv[j]) hipEventDestroy(h->ev_conv[j]);
-  if (h->ev_fork) hipEventDestroy(h->ev_fork);
-  if (h->ev_join) hipEventDestroy(h->ev_join);
   if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
   delete h;
   return DSACT_OK;
@@ -4415,8 +4292,7 @@ static int capture_updates(dsact_handle* h, int n, uint32_t flags, bool merged, 
         // path) -> all-reduce -> streaming Adam/Polyak -> packed weight copies rebuilt for the next forward
         rc = enqueue_grads(h, true, false, 0, &ride);
         if (rc == DSACT_OK) rc = enqueue_allreduce(h, h->grads, h->n_online + 2, kNcclAvg);
-        if (rc == DSACT_OK) rc = h->env_no_adam_pack ? enqueue_adam(h) : enqueue_adam_pack(h);
-        if (rc == DSACT_OK && h->env_no_adam_pack) rc = enqueue_pack(h, true);
+        if (rc == DSACT_OK) rc = enqueue_adam_pack(h);
       } else {
         rc = enqueue_grads(h, actor, true, 0, &ride);
       }
@@ -4456,7 +4332,7 @@ static int plan_updates_pipe(dsact_handle* h, int n, int phase, PipePlan& plan, 
   plan.host.resize((size_t)n); plan.pre.resize((size_t)n); plan.dop.resize((size_t)n);
   plan.defer.assign((size_t)n, 0); plan.bp.resize((size_t)n); plan.bp_rg.assign((size_t)n, 2);
   // the discarded policy backward can move when it is the merged launch's (chain + its own tiles behind the arrival counter)
-  const int rg_pi = h->env_chain_rg ? h->env_chain_rg : (h->B >= 8 ? h->cRG : 1);
+  const int rg_pi = h->B >= 8 ? h->cRG : 1;
   // (data parallel: the same -- on those updates k_adam_pack leaves the policy alone, so the policy segment of the all-reduced
   //  arena is read by nobody; the deferred tiles store nothing and that segment simply keeps its previous content)
   const bool can_defer = h->pi_merge && h->dw_chunks == 1 && !h->fat_bwd && rg_pi <= 2 && !h->env_no_pipe_defer;
@@ -4552,8 +4428,7 @@ static int enqueue_updates_pipe(dsact_handle* h, int n, const PipePlan& plan, Pi
       h->bqt_now = false;
       h->bqp_now = false;
       if (rc == DSACT_OK) rc = enqueue_allreduce(h, h->grads, h->n_online + 2, kNcclAvg);
-      if (rc == DSACT_OK) rc = h->env_no_adam_pack ? enqueue_adam(h) : enqueue_adam_pack(h);
-      if (rc == DSACT_OK && h->env_no_adam_pack) rc = enqueue_pack(h, true);
+      if (rc == DSACT_OK) rc = enqueue_adam_pack(h);
       continue;
     }
     h->pipe_defer_now = plan.defer[(size_t)s] != 0;
@@ -4586,13 +4461,12 @@ static int capture_updates_pipe(dsact_handle* h, int n, int phase, hipGraph_t* g
 // would dsact_graph_build(steps_per_graph, flags) capture the pipelined graph?
 static bool pipe_eligible(const dsact_handle* h, int steps_per_graph, uint32_t flags) {
   const int D = h->cfg.delay_update;
-  const bool merged = !h->cnn && h->use_w1p && h->dw_chunks == 1 && !h->use_fork && !h->use_std_sums && h->alt_ws != nullptr &&
-                      !h->env_no_merged_gather;
+  const bool merged = !h->cnn && h->use_w1p && h->dw_chunks == 1 && !h->use_std_sums && h->alt_ws != nullptr;
   // (data parallel too: replicas hold identical policies, which change on the same iterations)
   // (noise comes from the device either way: Philox keyed by iteration, or the uploaded noise table of dsact_run_group)
   return merged && h->chain_ok && !h->fat && h->fwd_merge && h->B % 4 == 0 && (h->rng_seed != 0 || h->noise_table_on) &&
          (!(flags & DSACT_F_DATA_PARALLEL) || h->comm != nullptr) && D >= 2 &&
-         D <= dsact_handle::kPipePhases && steps_per_graph >= 2 && !h->env_no_pipe;
+         D <= dsact_handle::kPipePhases && steps_per_graph >= 2;
 }
 
 int dsact_graph_build(dsact_handle* h, int32_t steps_per_graph, uint32_t flags) {
@@ -4616,8 +4490,8 @@ int dsact_graph_build(dsact_handle* h, int32_t steps_per_graph, uint32_t flags) 
   // of the padded first-layer copies is done by the weight-gradient tiles themselves (FusedOpt::mir_*).
   // Update s of n uses set (n-1-s)&1, so the last staged minibatch sits in set 0 like after eager updates.
   // (data parallel: only on the chain path, whose packed copies k_pack can rebuild after the streaming optimiser)
-  const bool merged = !h->cnn && h->use_w1p && h->dw_chunks == 1 && !h->use_fork && !h->use_std_sums && h->alt_ws != nullptr &&
-                      !h->env_no_merged_gather && (!(flags & DSACT_F_DATA_PARALLEL) || h->chain_ok);
+  const bool merged = !h->cnn && h->use_w1p && h->dw_chunks == 1 && !h->use_std_sums && h->alt_ws != nullptr &&
+                      (!(flags & DSACT_F_DATA_PARALLEL) || h->chain_ok);
   h->merged_graph = merged;
   // Pipelined graph (fused single-GPU update on the row-slice chains with both in-launch hand-overs available, device RNG,
   // 2 <= delay_update <= 4, at least 2 updates per graph): one graph per phase first_iteration % delay_update

@@ -658,7 +658,7 @@ struct FwdArgs {
                                     // HOST memory: every entry point of the library checks it and fails the call
   int debug_withhold;               // tests only (dsact_debug_set "withhold_flag"): unit 0 / slice 0 never raises its flag
   const long long* tagp;            // tagged hand-over: DevState::tag_seq (advances with every closed update, never reset): tag = low word + 1
-  int tpad;                         // steps of padding behind every 64-row tile of the forward packs (experiments: DSACT_PK_PAD)
+  int tpad;                         // steps of padding behind every 64-row tile of the forward packs: always 0 (see fill_fwd_common)
   int x0_lds;                       // throughput-regime forward (dsact_fat.h): the slice's input rows are staged in LDS (round 6)
 };
 
@@ -1134,7 +1134,7 @@ __global__ void __launch_bounds__(64 * NW, 2) k_chain_fwd2(Fwd2Args a) {
 // position in the dispatch order. A unit waits only for units that come EARLIER in every XCD's queue (the table is
 // built group by group), so the bounded spins cannot deadlock. Same body, same arithmetic per row as k_chain_fwd2.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int kPipeUnits = 16;     // (12 roles of the pipelined graph; 16 trunk units of a merged twin-trunk forward)
+constexpr int kPipeUnits = 16;     // (10 roles of the pipelined graph; 16 trunk units of a merged twin-trunk forward)
 constexpr int kPipeMaxBlocks = 1536;
 struct PipeFwd {
   FwdArgs c;                        // common fields (c.u / c.map unused)
@@ -1145,7 +1145,7 @@ struct PipeFwd {
   // state before they wait
   DevState* book_st; StepHyper book_hp; int* book_cnt; int book_ncnt;
   int blk[kPipeMaxBlocks];          // (unit << 16) | slice, or -1: padding block
-  int warm[kPipeMaxBlocks];         // (index << 16) | count among the workgroups of the same unit on the same XCD; 0: no warm-up
+  int warm[kPipeMaxBlocks];         // (index << 16) | count among the workgroups of the same unit on the same XCD; 0: no warm-up (pipe_fwd_build leaves every entry 0)
 };
 constexpr int kPipeRoleBook = 13;
 // the bookkeeping block of a forward launch (see PipeFwd::book_*): one thread

@@ -448,12 +448,10 @@ struct ConvDwArgs {
 // NKT = k-tiles (32 patch columns each) per workgroup: the dY tile of a step is staged once and multiplied
 // with NKT patch tiles, so dY is not re-read per k-tile (PMC: the weight gradient was the largest consumer
 // of memory-side traffic, 2-3x its algorithmic bytes, when every k-tile had its own workgroup).
-// NS = steps of global loads in flight (register sets).
-// DB = LDS double buffering (one barrier per step, 2 x (1 + NKT) tiles); false: ONE set of 1 + NKT tiles and a second barrier per
-// step -- NKT = 3 then costs the LDS of the double-buffered NKT = 1 form (four workgroups per CU) while dY is read once.
-template <int NKT, int NS = 2, bool DB = true>
+// NS = steps of global loads in flight (register sets). LDS is double buffered: one barrier per step, 2 x (1 + NKT) tiles.
+template <int NKT, int NS = 2>
 __global__ void __launch_bounds__(kThreads) k_conv_dw(ConvDwArgs s) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];   // (DB ? 2 : 1) x (1 + NKT) tiles
+  extern __shared__ __attribute__((aligned(16))) float lds[];   // 2 x (1 + NKT) tiles
   const int b = blockIdx.x;
   int pi = 0;
   if (s.n_prob > 1 && b >= s.p[0].block_end) pi = 1;
@@ -555,7 +553,7 @@ __global__ void __launch_bounds__(kThreads) k_conv_dw(ConvDwArgs s) {
 #pragma unroll
   for (int st = 0; st < NS; ++st) load_next(ps0[st], ps1[st], qs0[st], qs1[st]);   // steps 0 .. NS-1 (past T: masked, clamped)
   auto step = [&](int it, f32x4& P0, f32x4& P1, f32x4 (&Q0)[NKT], f32x4 (&Q1)[NKT]) {
-    float* Ps = lds + (DB ? (it & 1) : 0) * (1 + NKT) * TILE_LDS;
+    float* Ps = lds + (it & 1) * (1 + NKT) * TILE_LDS;
     mask(it, P0, P1, Q0, Q1);
     tile_store_lds<true>(Ps, tid, P0, P1);
 #pragma unroll
@@ -565,7 +563,6 @@ __global__ void __launch_bounds__(kThreads) k_conv_dw(ConvDwArgs s) {
 #pragma unroll
     for (int u = 0; u < NKT; ++u)
       tile_mma<true, true>(Ps, Ps + (1 + u) * TILE_LDS, wr * 16 + i, wc * 16 + i, gq, acc0[u], acc1[u]);
-    if (!DB) lds_barrier();                    // the next step's stores overwrite these tiles
   };
   int it = 0;
   for (; it + NS <= T; it += NS) {
@@ -598,7 +595,7 @@ __global__ void __launch_bounds__(kThreads) k_conv_dw(ConvDwArgs s) {
 // multiplied; the four partial tiles meet in LDS once, at the end (fixed order). Same partial layout as k_conv_dw.
 // Measured at type_2, batch 256 (two groups in flight, ~512 workgroups): layer 1 37.0 -> 30.3 us, layer 0 33.4 -> 41.0, layer 2
 // (228 VGPRs, one wave per SIMD) 20.2 -> 37.0; more, shorter workgroups are slower (layer 1: 39 us at 1024-2048): chosen per
-// layer (DSACT_CONV_DW_REG = bit mask of layers; default: the layers with 16 channels and three k-tiles, i.e. layer 1).
+// layer (the layers with 16 channels and three k-tiles, i.e. layer 1: conv_dw_reg_ok).
 // ---------------------------------------------------------------------------------------------
 template <int NCB, int NKB>
 __global__ void __launch_bounds__(kThreads) k_conv_dw_reg(ConvDwArgs s) {
@@ -914,7 +911,7 @@ __global__ void __launch_bounds__(kThreads) k_conv_dx_block(ConvDxArgs a) {
 // ---------------------------------------------------------------------------------------------
 // The same data gradient on the matrix cores, wave-autonomous like k_conv_fwd_narrow (no LDS, no column buffer), for the
 // 3x3 / stride-2 layer with 16 input channels (round 3: 43.9 -> 24.3 us; with 8 input channels half of every tile's
-// columns are idle and the block kernel above wins, 30.9 vs 38.6 us; DSACT_NO_CONV_DX_MFMA=1 = A/B):
+// columns are idle and the block kernel above wins, 30.9 vs 38.6 us):
 //   an input pixel (y, x) = (2 yq + py, 2 xq + px) receives from the taps ky = py + 2 ay, kx = px + 2 ax (< 3), i.e. from
 //   the output pixels (yq - ay, xq - ax): per row parity py (grid.z) a tile is 16 consecutive (b, yq, xq) PAIRS of pixels
 //   (px = 0 and 1 of the same xq -- written as one contiguous 2 * Cin floats per lane group, whole lines per wave);

@@ -238,7 +238,7 @@ __device__ __forceinline__ void fat_fwd_body(const FwdArgs& a, int unit, int sli
   const int c_obs = a.s_obs, c_act = u.s_act, C0 = c_obs + c_act;
   const bool do_obs = u.seg != SEG_ACT_FROM_SAVED;
   const bool do_act = u.seg != SEG_OBS_ONLY && c_act > 0;
-  CTL(a.timeline, 0);   // (instrumented builds: scripts/gpu_r5_timeline_fat.sh)
+  CTL(a.timeline, 0);   // (instrumented builds: scripts/gpu_r5_timeline_fat.sh, commit 50e414e)
   CTLR(a.timeline, 14);
   CTLV(a.timeline, 11, 1 + unit);
   CTLV(a.timeline, 10, ((long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4));   // (XCC_ID, HW_ID)

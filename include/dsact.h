@@ -260,8 +260,8 @@ int dsact_step(dsact_handle* h, int64_t iteration, uint32_t flags); /* compute_g
  * update it + 1 of such a window sees the policy update `it` saw -- the forward launch of update `it` also evaluates
  * policy(obs) + rsample and policy_target(obs2) for the NEXT minibatch (gathered two updates ahead) and update it + 1's
  * forward launch holds only the chains that need the fresh critics. One graph per phase first_iteration % delay_update is
- * captured; dsact_graph_run picks per replay. Same bits as eager updates. DSACT_NO_PIPE=1 captures the plain graph;
- * dsact_debug_get(h, "pipe_graph") tells which one was captured. */
+ * captured; dsact_graph_run picks per replay. Same bits as eager updates. Configurations that do not meet these
+ * conditions capture the plain graph; dsact_debug_get(h, "pipe_graph") tells which one was captured. */
 int dsact_graph_build(dsact_handle* h, int32_t steps_per_graph, uint32_t flags);
 int dsact_graph_run(dsact_handle* h, int64_t first_iteration, int64_t n_steps);
 /* OffSerialTrainer.step between two sampler calls (training/trainer.py:63-82 with sample_interval = n_steps; the reference's

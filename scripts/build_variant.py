@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A differently COMPILED library for A/B runs on one box: python scripts/build_variant.py <name> <hipcc flag> [...]
 -> build/libdsact_<name>.so (objects in build/obj_<name>/), e.g.  python scripts/build_variant.py nt1 -DDSACT_NT_OPT=1
-Use it with DSACT_LIB_PATH=$PWD/build/libdsact_<name>.so (scripts/gpu_r5_libs.sh: LIBS="nt1 nt2")."""
+Use it with DSACT_LIB_PATH=$PWD/build/libdsact_<name>.so."""
 import glob
 import os
 import subprocess

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""gpurun_out/r6_prof (scratch, written by scripts/gpu_r6_prof.sh on the GPU box) -> profiles/r06_* (tracked)."""
+"""SRC (untracked output of the round-6 profiling script scripts/gpu_r6_prof.sh, commit 50e414e) -> profiles/r06_* (tracked)."""
 import json
 import os
 import shutil

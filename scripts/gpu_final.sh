@@ -54,7 +54,7 @@ DSACT_BENCH_FORCE_DP=1 timeout 300 python bench.py --steps 4000 --warmup 200 --n
 DSACT_BENCH_FORCE_DP=1 timeout 300 python bench.py --steps 2000 --warmup 200 --no-cpu-baseline --no-alt --dp-eager > $OUT/bench_dp_eager.log 2>&1; echo "dp eager rc=$?"; tail -1 $OUT/bench_dp_eager.log | cut -c1-200
 # ---- CNN workload (configs[3]): bench object, kernel stats, PMC traffic per kernel (own passes, kernel-trace only)
 timeout 400 python bench.py --cnn-only --cnn-steps 400 > $OUT/bench_cnn.log 2>&1; echo "cnn bench rc=$?"; grep '^{"cnn"' $OUT/bench_cnn.log | cut -c1-300
-DSACT_NO_CHAIN_CNN=1 DSACT_NO_CONV_NARROW9=1 timeout 300 python bench.py --cnn-only --cnn-steps 400 --no-cpu-baseline > $OUT/bench_cnn_r3_paths.log 2>&1; echo "cnn (tile-path trunks, LDS-tile layer 2) rc=$?"; grep '^{"cnn"' $OUT/bench_cnn_r3_paths.log | cut -c1-200
+DSACT_NO_CHAIN_CNN=1 timeout 300 python bench.py --cnn-only --cnn-steps 400 --no-cpu-baseline > $OUT/bench_cnn_r3_paths.log 2>&1; echo "cnn (tile-path trunks) rc=$?"; grep '^{"cnn"' $OUT/bench_cnn_r3_paths.log | cut -c1-200
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_cnn -o cnn -- python bench.py --cnn-only --cnn-steps 200 --no-cpu-baseline > $OUT/rocprof_cnn.log 2>&1; echo "rocprof cnn rc=$?"
 cp $(find $OUT/prof_cnn -name "*kernel_stats.csv" | head -1) $OUT/cnn_kernel_stats.csv 2>/dev/null
 rm -rf $OUT/prof_cnn

@@ -786,17 +786,17 @@ PIPE_BUFFERS = ("logits_pi", "logp_new", "logp2", "qout_t0", "qout_t1", "qout_p0
     (16, 4, (64, 64), 64, 2, 4, 1, 8, {}),             # starts on an odd iteration: every update is half of a pair
     (16, 4, (64, 64), 64, 2, 4, 0, 8, {}),             # starts on an even one: single, pairs, single
     (16, 4, (64, 64), 64, 2, 3, 1, 9, {}),             # odd graph length: replays alternate between the two phase graphs
-    (16, 4, (64, 64), 64, 2, 5, 2, 10, {"DSACT_PIPE_QT": "1"}),           # q_target of the next minibatch precomputed too
+    (16, 4, (64, 64), 64, 2, 5, 2, 10, {}),            # odd graph length from an even first iteration: replays start on both parities
     (24, 6, (128, 128, 128), 32, 3, 6, 1, 12, {}),     # delay_update 3: a (has, makes) launch in the middle of every window
-    (24, 6, (128, 128, 128), 32, 3, 4, 0, 12, {"DSACT_PIPE_QT": "1", "DSACT_PIPE_RG_SIDE": "1"}),
+    (24, 6, (128, 128, 128), 32, 3, 4, 0, 12, {}),     # three 128-wide layers, batch 32, delay_update 3: graphs of 4 cut across the windows
     (16, 4, (64, 64), 64, 1, 4, 0, 8, {}),             # delay_update 1: nothing to share, the plain graph
-    (16, 4, (64, 64), 16, 2, 2, 1, 6, {"DSACT_PIPE_RG_NEXT": "1"}),       # 4 slices per unit
+    (16, 4, (64, 64), 16, 2, 2, 1, 6, {}),             # batch 16, the shortest graph (2 updates) from an odd first iteration
     (16, 4, (64, 64), 64, 2, 4, 1, 8, {"DSACT_NO_PIPE_DEFER": "1"}),      # the discarded policy backward stays in its own update
     (16, 4, (64, 64), 64, 2, 4, 1, 8, {"DSACT_NO_BQT_MERGE": "1"}),       # critics' backward and their tiles as two launches (round 4's form)
     (376, 17, (256, 256, 256), 256, 2, 8, 1, 16, {"DSACT_NO_BQT_MERGE": "1"}),
     (16, 4, (64, 64), 64, 2, 4, 0, 8, {"DSACT_NO_BQP_MERGE": "1"}),       # policy-moving updates: critics' and policy backward as two launches
     (24, 6, (128, 128, 128), 32, 3, 6, 2, 12, {"DSACT_NO_BQP_MERGE": "1"}),
-    (32, 8, (256, 256), 48, 2, 5, 1, 10, {"DSACT_PIPE_QT": "1", "DSACT_PIPE_QP_SPLIT": "1"}),
+    (32, 8, (256, 256), 48, 2, 5, 1, 10, {}),          # two 256-wide layers, 8 actions, batch 48; odd graph length from an odd first iteration
     (376, 17, (256, 256, 256), 256, 2, 8, 1, 16, {}),  # the BASELINE.json shape
     (376, 17, (256, 256, 256), 256, 2, 6, 4, 12, {"DSACT_PIPE_MAP": "FT.pit=23:1;FT.q1t=01;TF.q1c=0123:2"}),
 ])
