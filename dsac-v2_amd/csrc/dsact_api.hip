@@ -212,6 +212,7 @@ struct dsact_handle {
   int h_idx_slot = 0;
   // rng
   uint64_t rng_seed = 0;
+  uint64_t idx_seed = 0;   // dsact_set_index_rng: 0 = the caller draws the replay indices (np.random.randint)
   bool have_batch = false;
   bool limits_set = false;
   // graph
@@ -3208,6 +3209,32 @@ int check_ready(dsact_handle* h, bool need_batch) {
   return DSACT_OK;
 }
 
+// the index table (and with it the noise table) of dsact_run_group / dsact_draw_indices: at least n_rows rows. Their addresses
+// and row counts are baked into every captured graph, so growing them drops the graphs.
+int ensure_group_tables(dsact_handle* h, int n_rows) {
+  if (h->idx_table && h->idx_rows >= n_rows) return DSACT_OK;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  drop_graphs(h);
+  if (h->idx_table) hipFree(h->idx_table);
+  if (h->noise_table) { hipFree(h->noise_table); h->noise_table = nullptr; }
+  h->idx_table = nullptr;
+  const int rows = n_rows > 16 ? n_rows : 16;
+  HIPCHK(h, hipMalloc(&h->idx_table, (size_t)rows * h->B * sizeof(int)));
+  // on the handle's stream: a null-stream memset is not ordered against work enqueued on `stream` right behind it (the draw)
+  HIPCHK(h, hipMemsetAsync(h->idx_table, 0, (size_t)rows * h->B * sizeof(int), h->stream));
+  h->idx_rows = rows;
+  return DSACT_OK;
+}
+
+// replay_buffer.py:86 on the device: rows [0, n) of the index table <- the draws of iterations first_iteration .. + n - 1 over the
+// ring size of THIS call (the caller has checked seed != 0, size > 0 and the table's rows)
+int enqueue_draw_indices(dsact_handle* h, int64_t first_iteration, int n) {
+  DrawIdxArgs a;
+  a.idx_table = h->idx_table; a.first_it = (long long)first_iteration; a.seed = h->idx_seed; a.size = (unsigned long long)h->size;
+  a.B = h->B; a.n_steps = n;
+  return launch(h, "draw_indices", k_draw_indices, dim3(n), dim3(kThreads), 0, a);
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -3920,21 +3947,27 @@ int dsact_buffer_fill_device(dsact_handle* h, int64_t row0, int64_t n, const flo
 }
 
 int dsact_gather(dsact_handle* h, const int64_t* idx_host, int32_t batch) {
-  if (!h || !idx_host) return DSACT_E_INVALID;
+  if (!h) return DSACT_E_INVALID;
   if (!has_ring(h)) return fail(h, DSACT_E_STATE, "buffer not created");
   TRY(check_codes(h));
   if (batch != h->B) return fail(h, DSACT_E_INVALID, "batch %d != configured batch %d", batch, h->B);
   if (h->size == 0) return fail(h, DSACT_E_STATE, "buffer empty");
   HIPCHK(h, hipSetDevice(h->device));
-  const int slot = h->h_idx_slot;
-  h->h_idx_slot = (slot + 1) & 7;
-  HIPCHK(h, hipEventSynchronize(h->h_idx_ev[slot]));
-  for (int i = 0; i < batch; ++i) {
-    if (idx_host[i] < 0 || idx_host[i] >= h->size) return fail(h, DSACT_E_INVALID, "index %lld out of range [0,%lld)", (long long)idx_host[i], h->size);
-    h->h_idx[slot][i] = (int)idx_host[i];
+  if (!idx_host) {
+    // row 0 of the index table as dsact_draw_indices left it (device to device, stream-ordered behind the draw)
+    if (h->idx_seed == 0 || !h->idx_table) return fail(h, DSACT_E_STATE, "idx_host == NULL gathers the row dsact_draw_indices drew: call dsact_set_index_rng and dsact_draw_indices first");
+    HIPCHK(h, hipMemcpyAsync(h->idx_eager, h->idx_table, batch * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+  } else {
+    const int slot = h->h_idx_slot;
+    h->h_idx_slot = (slot + 1) & 7;
+    HIPCHK(h, hipEventSynchronize(h->h_idx_ev[slot]));
+    for (int i = 0; i < batch; ++i) {
+      if (idx_host[i] < 0 || idx_host[i] >= h->size) return fail(h, DSACT_E_INVALID, "index %lld out of range [0,%lld)", (long long)idx_host[i], h->size);
+      h->h_idx[slot][i] = (int)idx_host[i];
+    }
+    HIPCHK(h, hipMemcpyAsync(h->idx_eager, h->h_idx[slot], batch * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->h_idx_ev[slot], h->stream));
   }
-  HIPCHK(h, hipMemcpyAsync(h->idx_eager, h->h_idx[slot], batch * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipEventRecord(h->h_idx_ev[slot], h->stream));
   // bookkeeping (iteration, counters) is done by the step call; this gather only stages rows
   if (h->cnn) {
     TRY(enqueue_gather_ring_img(h, h->idx_eager, 1, 0));
@@ -4065,6 +4098,37 @@ int dsact_set_device_rng(dsact_handle* h, uint64_t seed) {
   if (!h) return DSACT_E_INVALID;
   if (any_graph(h)) return fail(h, DSACT_E_STATE, "rng mode is baked into the captured graph");
   h->rng_seed = seed;
+  return DSACT_OK;
+}
+
+// replay_buffer.py:86 (np.random.randint(0, size, batch)) made by the device instead: Philox keyed by (seed, iteration, position),
+// csrc/dsact_kernels.h k_draw_indices. Not captured into any graph, so it may be switched at any time.
+int dsact_set_index_rng(dsact_handle* h, uint64_t seed) {
+  if (!h) return DSACT_E_INVALID;
+  h->idx_seed = seed;
+  return DSACT_OK;
+}
+
+int dsact_draw_indices(dsact_handle* h, int64_t first_iteration, int32_t n) {
+  if (!h || n < 1) return DSACT_E_INVALID;
+  if (!has_ring(h)) return fail(h, DSACT_E_STATE, "buffer not created");
+  if (h->idx_seed == 0) return fail(h, DSACT_E_STATE, "no index seed (dsact_set_index_rng)");
+  if (h->size == 0) return fail(h, DSACT_E_STATE, "buffer empty");   // np.random.randint(0, 0) raises too
+  TRY(check_codes(h));
+  HIPCHK(h, hipSetDevice(h->device));
+  TRY(ensure_group_tables(h, n));
+  return enqueue_draw_indices(h, first_iteration, n);
+}
+
+int dsact_read_indices(dsact_handle* h, int64_t* out, int32_t rows) {
+  if (!h || !out || rows < 1) return DSACT_E_INVALID;
+  if (!h->idx_table || rows > h->idx_rows) return fail(h, DSACT_E_STATE, "the index table holds %d rows, %d asked for", h->idx_table ? h->idx_rows : 0, rows);
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t n = (size_t)rows * h->B;
+  std::vector<int> tmp(n);
+  HIPCHK(h, hipMemcpyAsync(tmp.data(), h->idx_table, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (size_t i = 0; i < n; ++i) out[i] = tmp[i];
   return DSACT_OK;
 }
 
@@ -4577,30 +4641,22 @@ int dsact_graph_run(dsact_handle* h, int64_t first_iteration, int64_t n_steps) {
 // the device: the rows travel through pinned staging slots, the replay counters are reset by a stream-ordered kernel, and
 // captured graphs are kept per (n_steps, flags, noise mode) -- the first group of a new shape pays its capture.
 int dsact_run_group(dsact_handle* h, int64_t first_iteration, int32_t n_steps, const int64_t* idx, const float* noise, uint32_t flags) {
-  if (!h || !idx || n_steps < 1) return DSACT_E_INVALID;
+  if (!h || n_steps < 1) return DSACT_E_INVALID;
   TRY(check_ready(h, false));
   if (!has_ring(h)) return fail(h, DSACT_E_STATE, "buffer not created");
   if (h->size == 0) return fail(h, DSACT_E_STATE, "buffer empty");
+  if (!idx && h->idx_seed == 0)
+    return fail(h, DSACT_E_STATE, "no index rows: pass idx, or call dsact_set_index_rng to have the device draw them");
   if (!noise && h->rng_seed == 0) return fail(h, DSACT_E_STATE, "no noise source: pass the noise rows or call dsact_set_device_rng");
   if ((flags & DSACT_F_SKIP_ACTOR_ON_OFF_ITERS) && (n_steps % h->cfg.delay_update || first_iteration % h->cfg.delay_update))
     return fail(h, DSACT_E_INVALID, "with DSACT_F_SKIP_ACTOR_ON_OFF_ITERS a group must cover whole delay_update periods");
   HIPCHK(h, hipSetDevice(h->device));
   const size_t B = (size_t)h->B, A = (size_t)h->A;
   const size_t n_idx = (size_t)n_steps * B, nz_row = 2 * B * A + 2 * B;
-  for (size_t i = 0; i < n_idx; ++i)
+  for (size_t i = 0; idx && i < n_idx; ++i)
     if (idx[i] < 0 || idx[i] >= h->size) return fail(h, DSACT_E_INVALID, "index %lld out of range [0,%lld)", (long long)idx[i], h->size);
   // ---- tables (their addresses and row counts are baked into every captured graph)
-  if (!h->idx_table || h->idx_rows < n_steps) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    drop_graphs(h);
-    if (h->idx_table) hipFree(h->idx_table);
-    if (h->noise_table) { hipFree(h->noise_table); h->noise_table = nullptr; }
-    h->idx_table = nullptr;
-    const int rows = n_steps > 16 ? n_steps : 16;
-    HIPCHK(h, hipMalloc(&h->idx_table, (size_t)rows * B * sizeof(int)));
-    HIPCHK(h, hipMemset(h->idx_table, 0, (size_t)rows * B * sizeof(int)));
-    h->idx_rows = rows;
-  }
+  TRY(ensure_group_tables(h, n_steps));
   if (noise && !h->noise_table) {
     HIPCHK(h, hipMalloc(&h->noise_table, (size_t)h->idx_rows * nz_row * sizeof(float)));
     HIPCHK(h, hipMemset(h->noise_table, 0, (size_t)h->idx_rows * nz_row * sizeof(float)));
@@ -4620,28 +4676,36 @@ int dsact_run_group(dsact_handle* h, int64_t first_iteration, int32_t n_steps, c
     }
   }
   // ---- rows -> pinned slot -> tables (stream-ordered; the slot is reused four groups later)
-  const size_t need = n_idx * sizeof(int) + (noise ? (size_t)n_steps * nz_row * sizeof(float) : 0);
-  if (need > h->grp_pin_bytes) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    size_t cap = need < (1u << 16) ? (1u << 16) : need;
-    for (int i = 0; i < 4; ++i) {
-      if (h->grp_pin[i]) { hipHostFree(h->grp_pin[i]); h->grp_pin[i] = nullptr; }
-      HIPCHK(h, hipHostMalloc((void**)&h->grp_pin[i], cap, hipHostMallocDefault));
-      if (!h->grp_ev[i]) HIPCHK(h, hipEventCreateWithFlags(&h->grp_ev[i], hipEventDisableTiming));
+  // idx == nullptr (dsact_set_index_rng): no staging, conversion or H2D of index rows -- k_draw_indices fills the table rows on the
+  // stream, directly in front of the replay and outside the captured graph (the ring size of THIS call is its argument)
+  const size_t idx_bytes = idx ? n_idx * sizeof(int) : 0;
+  const size_t need = idx_bytes + (noise ? (size_t)n_steps * nz_row * sizeof(float) : 0);
+  if (!idx) TRY(enqueue_draw_indices(h, first_iteration, n_steps));
+  if (need) {
+    if (need > h->grp_pin_bytes) {
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      size_t cap = need < (1u << 16) ? (1u << 16) : need;
+      for (int i = 0; i < 4; ++i) {
+        if (h->grp_pin[i]) { hipHostFree(h->grp_pin[i]); h->grp_pin[i] = nullptr; }
+        HIPCHK(h, hipHostMalloc((void**)&h->grp_pin[i], cap, hipHostMallocDefault));
+        if (!h->grp_ev[i]) HIPCHK(h, hipEventCreateWithFlags(&h->grp_ev[i], hipEventDisableTiming));
+      }
+      h->grp_pin_bytes = cap;
     }
-    h->grp_pin_bytes = cap;
+    const int slot = (int)(h->grp_k++ & 3);
+    HIPCHK(h, hipEventSynchronize(h->grp_ev[slot]));
+    if (idx) {
+      int* pin_idx = (int*)h->grp_pin[slot];
+      for (size_t i = 0; i < n_idx; ++i) pin_idx[i] = (int)idx[i];
+      HIPCHK(h, hipMemcpyAsync(h->idx_table, pin_idx, n_idx * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    }
+    if (noise) {
+      float* pin_nz = (float*)(h->grp_pin[slot] + idx_bytes);
+      memcpy(pin_nz, noise, (size_t)n_steps * nz_row * sizeof(float));
+      HIPCHK(h, hipMemcpyAsync(h->noise_table, pin_nz, (size_t)n_steps * nz_row * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(h, hipEventRecord(h->grp_ev[slot], h->stream));
   }
-  const int slot = (int)(h->grp_k++ & 3);
-  HIPCHK(h, hipEventSynchronize(h->grp_ev[slot]));
-  int* pin_idx = (int*)h->grp_pin[slot];
-  for (size_t i = 0; i < n_idx; ++i) pin_idx[i] = (int)idx[i];
-  HIPCHK(h, hipMemcpyAsync(h->idx_table, pin_idx, n_idx * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  if (noise) {
-    float* pin_nz = (float*)(h->grp_pin[slot] + n_idx * sizeof(int));
-    memcpy(pin_nz, noise, (size_t)n_steps * nz_row * sizeof(float));
-    HIPCHK(h, hipMemcpyAsync(h->noise_table, pin_nz, (size_t)n_steps * nz_row * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  }
-  HIPCHK(h, hipEventRecord(h->grp_ev[slot], h->stream));
   // ---- iteration of the first update, table row 0; then the replay
   hipLaunchKernelGGL(k_set_counters, dim3(1), dim3(64), 0, h->stream, h->st, (long long)first_iteration, 0LL);
   if (hipGetLastError() != hipSuccess) return fail(h, DSACT_E_HIP, "launch k_set_counters failed");

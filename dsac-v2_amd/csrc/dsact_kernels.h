@@ -578,6 +578,47 @@ __global__ void k_set_counters(DevState* st, long long it_next, long long seq_ne
 }
 #endif
 
+// k_draw_indices: the uniform index draw of ReplayBuffer.sample_batch (training/replay_buffer.py:86, np.random.randint(0, size,
+// batch)) made on the device for n_steps consecutive updates: row r of the index table [rows][B] gets the B indices of iteration
+// first_it + r. Opt-in (dsact_set_index_rng); the draw is uniform with replacement like the reference's, not the reference's stream.
+//   generator: philox4x32, counter (position / 2, iteration low, iteration high, kIndexStream), key = the index seed (low, high).
+//              kIndexStream = 4: normal4's callers (fill_noise above) use stream ids 1 (eps_new), 2 (eps_2) and 3 (z5 | z6), so even
+//              an index seed EQUAL to the noise seed never shares a counter block with the noise.
+//   map:       one call = four words w[0..3] = two 64-bit draws u_k = (w[2k+1] << 32) | w[2k] = the indices of positions 2p + k;
+//              index = mulhi64(u, size) = floor(u * size / 2^64). Integer arithmetic only, no loop, no rejection: a pure function of
+//              (seed, iteration, position, size). NOT exactly uniform: each index is hit by floor(2^64 / size) or one more of the
+//              2^64 draws, i.e. a bias of at most size / 2^64 per index (< 2^-40 for a 10M-row ring).
+//   grouping:  the values depend on the iteration only -- row r of a draw that starts at i is the single-row draw at i + r.
+// One workgroup per row; a thread makes one Philox call per pass and stores its two indices (one dwordx2 when B is even).
+struct DrawIdxArgs {
+  int* idx_table;        // [>= n_steps][B]
+  long long first_it;
+  unsigned long long seed, size;   // size in [1, 2^31)
+  int B, n_steps;
+};
+constexpr uint32_t kIndexStream = 4u;
+#ifndef DSACT_FAMILY_UNIT   // plain kernel: compiled in dsact_api.hip only (dsact_tu.h)
+__global__ void __launch_bounds__(kThreads) k_draw_indices(DrawIdxArgs a) {
+  const int row = blockIdx.x;
+  if (row >= a.n_steps) return;
+  const long long it = a.first_it + row;
+  int* out = a.idx_table + (size_t)row * a.B;
+  const int pairs = (a.B + 1) >> 1;
+  for (int p = threadIdx.x; p < pairs; p += blockDim.x) {
+    uint32_t w[4];
+    philox4x32((uint32_t)p, (uint32_t)it, (uint32_t)((uint64_t)it >> 32), kIndexStream, (uint32_t)a.seed, (uint32_t)(a.seed >> 32), w);
+    const int i0 = (int)__umul64hi(((uint64_t)w[1] << 32) | w[0], a.size);
+    const int i1 = (int)__umul64hi(((uint64_t)w[3] << 32) | w[2], a.size);
+    if (!(a.B & 1)) {
+      *reinterpret_cast<int2*>(out + 2 * p) = make_int2(i0, i1);   // row * B + 2p is even: 8-byte aligned
+    } else {
+      out[2 * p] = i0;
+      if (2 * p + 1 < a.B) out[2 * p + 1] = i1;
+    }
+  }
+}
+#endif
+
 // replay ring scatter (training/replay_buffer.py:58-83): n staged rows -> ring rows (ptr+i) % cap
 struct ScatterArgs {
   const float* s_obs; const float* s_obs2; const float* s_act; const float* s_rew; const float* s_done; const float* s_logp;

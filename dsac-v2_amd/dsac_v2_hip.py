@@ -510,16 +510,36 @@ class HipBatch(dict):
     engine, so local_update skips the host round trip. Behaves like the reference's dict of tensors when somebody
     else indexes it (materialised on demand). The engine stages ONE minibatch at a time: a token that is no longer the
     staged one (the caller sampled ahead, or fed another batch in between) re-gathers its own rows by the indices it
-    was drawn with before it is trained on or read."""
+    was drawn with before it is trained on or read.
 
-    def __init__(self, engine, idxs):
+    Device-drawn indices (HipReplayBuffer(hip_device_indices=True)): `idxs` is None and `drawn` = (iteration, ring size, index
+    seed) names the draw instead. The indices are a pure function of those three (include/dsact.h, dsact_set_index_rng), so
+    a token that has to re-gather draws them again; it fetches them to the host (`idxs`: a draw + a synchronous
+    dsact_read_indices) only when rows were written to the ring since it was sampled and it has to know which."""
+
+    def __init__(self, engine, idxs, drawn=None):
         super().__init__()
-        self.engine, self.idxs = engine, np.array(idxs, dtype=np.int64, copy=True)
+        self.engine, self._drawn = engine, drawn
+        self._idxs = None if idxs is None else np.array(idxs, dtype=np.int64, copy=True)
+        assert (self._idxs is None) != (drawn is None)
         self.serial = engine.stage_serial
         # ring write position when the rows were sampled: the reference's batch is a COPY taken at sample time
         # (replay_buffer.py:85-90), so a late re-gather must not silently train on rows add_batch has replaced
         self._ptr0, self._added0 = engine.buffer_ptr, engine.rows_added
         self._fill_epoch0 = engine.fill_epoch
+
+    @property
+    def idxs(self):
+        if self._idxs is None:
+            self._idxs = _fetch_drawn(self.engine, self._drawn, 1)[0]
+        return self._idxs
+
+    @idxs.setter
+    def idxs(self, v):
+        self._idxs = v
+
+    def _ring_untouched(self):
+        return self.engine.rows_added == self._added0 and self.engine.fill_epoch == self._fill_epoch0
 
     def _overwritten(self):
         cap, written = self.engine.buffer_capacity, self.engine.rows_added - self._added0
@@ -535,6 +555,12 @@ class HipBatch(dict):
 
     def restage(self):
         if self.serial != self.engine.stage_serial:
+            if self._idxs is None and self._ring_untouched() and _same_draw(self.engine, self._drawn):
+                # nothing was written since the draw: the same draw again, on the device, with no host index
+                self.engine.draw_indices(self._drawn[0], 1)
+                self.engine.gather(None)
+                self.serial = self.engine.stage_serial
+                return
             n = self._overwritten()
             if n:
                 raise RuntimeError(
@@ -568,28 +594,75 @@ class HipBatch(dict):
         return dict.__iter__(self)
 
 
+def _same_draw(engine, drawn):
+    """would dsact_draw_indices reproduce the draw `drawn` = (iteration, ring size, index seed) now?"""
+    return engine.buffer_size == drawn[1] and engine.index_seed == drawn[2]
+
+
+def _fetch_drawn(engine, drawn, n):
+    """the int64 [n][batch] indices of a device draw, on the host: draws them again (they are a pure function of iteration,
+    ring size and seed) and reads them back -- synchronous, the tokens' slow path only"""
+    if not _same_draw(engine, drawn):
+        raise RuntimeError(
+            "a device-drawn minibatch token of iteration %d was drawn over a ring of %d rows with index seed %#x; the ring now "
+            "holds %d rows (index seed %#x), so the draw cannot be repeated and the token's rows are unknown. Use a token "
+            "before adding to a ring that is still filling, or sample again."
+            % (drawn[0], drawn[1], drawn[2], engine.buffer_size, engine.index_seed))
+    engine.draw_indices(drawn[0], n)
+    return engine.read_indices(n)
+
+
 class HipBatchGroup:
     """Token returned by HipReplayBuffer.sample_batches(batch_size, n): the index rows of the next n minibatches, drawn with
     the reference's own n `np.random.randint` calls (replay_buffer.py:86) while the ring cannot change between them. The
     rows are gathered on the device by the graph replay DSAC_V2_HIP.local_update_group issues; like a HipBatch it refuses
-    to be trained on once add_batch has replaced sampled rows."""
+    to be trained on once add_batch has replaced sampled rows.
 
-    def __init__(self, engine, idxs):
-        self.engine, self.idxs = engine, np.array(idxs, dtype=np.int64, copy=True)
-        assert self.idxs.ndim == 2
+    Device-drawn indices (HipReplayBuffer(hip_device_indices=True)): `idxs` is None, `drawn` = (first iteration, n, ring size,
+    index seed); the rows are "drawn by the device at issue" (dsact_run_group with idx == NULL) and no index exists on the
+    host unless rows were written to the ring since sample_batches (see HipBatch)."""
+
+    def __init__(self, engine, idxs, drawn=None):
+        self.engine, self._drawn = engine, drawn
+        self._idxs = None if idxs is None else np.array(idxs, dtype=np.int64, copy=True)
+        assert (self._idxs is None) != (drawn is None)
+        assert self._idxs is None or self._idxs.ndim == 2
         self._ptr0, self._added0, self._fill_epoch0 = engine.buffer_ptr, engine.rows_added, engine.fill_epoch
 
+    @property
+    def idxs(self):
+        if self._idxs is None:
+            it, n, size, seed = self._drawn
+            self._idxs = _fetch_drawn(self.engine, (it, size, seed), n)
+        return self._idxs
+
     def __len__(self):
-        return int(self.idxs.shape[0])
+        return int(self._drawn[1] if self._idxs is None else self._idxs.shape[0])
+
+    def device_rows(self, iteration, j=0):
+        """True when updates `iteration`.. may take rows j.. of this group straight from the device's draw: the indices are
+        device-drawn and not on the host, row j was drawn for that iteration, nothing was written to the ring since
+        sample_batches (so nothing is overwritten and the ring size is the one drawn over) and the seed is the same"""
+        if self._idxs is not None or self._drawn is None:
+            return False
+        it, _, size, seed = self._drawn
+        return (it + j == int(iteration) and self.engine.rows_added == self._added0
+                and self.engine.fill_epoch == self._fill_epoch0 and _same_draw(self.engine, (it, size, seed)))
 
     def batch(self, j):
         """minibatch j as an ordinary HipBatch token (re-gathers its rows when used)"""
-        b = HipBatch(self.engine, self.idxs[j])
+        if self._idxs is None:
+            it, _, size, seed = self._drawn
+            b = HipBatch(self.engine, None, drawn=(it + j, size, seed))
+        else:
+            b = HipBatch(self.engine, self._idxs[j])
         b.serial = -1
         b._ptr0, b._added0, b._fill_epoch0 = self._ptr0, self._added0, self._fill_epoch0
         return b
 
     def check_fresh(self):
+        if self._idxs is None and self.engine.rows_added == self._added0 and self.engine.fill_epoch == self._fill_epoch0:
+            return   # device-drawn and the ring was not written since: nothing to look at, no index fetched
         probe = self.batch(0)
         probe.idxs = self.idxs.reshape(-1)
         n = probe._overwritten()
@@ -800,21 +873,23 @@ class DSAC_V2_HIP:
             tb, j = None, 0
             while j < n:
                 if j == head and body >= 2:
-                    tb = self._run_group_rows(group.idxs[j:j + body], int(iteration) + j, time.time())
+                    # (device-drawn indices are keyed by the iteration, so the pieces draw the rows the whole group would)
+                    rows = None if group.device_rows(int(iteration) + j, j) else group.idxs[j:j + body]
+                    tb = self._run_group_rows(rows, int(iteration) + j, time.time(), body)
                     j += body
                 else:
                     tb = self.local_update(group.batch(j), int(iteration) + j)
                     j += 1
             return tb
-        return self._run_group_rows(group.idxs, int(iteration), t0)
+        return self._run_group_rows(None if group.device_rows(iteration) else group.idxs, int(iteration), t0, n)
 
-    def _run_group_rows(self, idxs, iteration, t0):
+    def _run_group_rows(self, idxs, iteration, t0, n):
+        """idxs None: the device draws the n index rows of iterations `iteration`.. itself (dsact_run_group, idx == NULL)"""
         self._keep_previous_stats()
-        n = int(idxs.shape[0])
         noise = None
         if self.strict_rng:
             noise = np.stack([np.concatenate([a.reshape(-1) for a in self._draw_noise()]) for _ in range(n)]).astype(np.float32)
-        self.engine.run_group(iteration, idxs, noise, self.flags)
+        self.engine.run_group(iteration, idxs, noise, self.flags, n=n)
         return self._new_tb(t0, n)
 
     def _grad_views(self):

@@ -80,6 +80,9 @@ SYMBOLS = [
     ("dsact_read_batch", C.c_int, [_P, _FP, _FP, _FP, _FP, _FP, _FP]),
     ("dsact_load_batch", C.c_int, [_P, _FP, _FP, _FP, _FP, _FP]),
     ("dsact_upload_index_table", C.c_int, [_P, _I64P, C.c_int32]),
+    ("dsact_set_index_rng", C.c_int, [_P, C.c_uint64]),
+    ("dsact_draw_indices", C.c_int, [_P, C.c_int64, C.c_int32]),
+    ("dsact_read_indices", C.c_int, [_P, _I64P, C.c_int32]),
     ("dsact_set_noise", C.c_int, [_P, _FP, _FP, _FP, _FP]),
     ("dsact_set_device_rng", C.c_int, [_P, C.c_uint64]),
     ("dsact_compute_grads", C.c_int, [_P, C.c_int64, C.c_uint32]),

@@ -36,6 +36,15 @@ import torch.distributed as dist
 F_DATA_PARALLEL = 2   # dsact.h DSACT_F_DATA_PARALLEL
 
 
+def rank_index_seed(seed: int, rank: int) -> int:
+    """Philox key of rank `rank`'s device-side index draw (dsact_set_index_rng) in a data-parallel run with the global
+    `seed`: ranks must sample DIFFERENT minibatches of their replay shards, so the key is the single-process default
+    (training.hip_replay_buffer.index_seed_from) of seed, plus rank times an odd 64-bit constant, folded into [1, 2^63).
+    Distinct ranks below 2^63 give distinct keys: the multiplier is odd, hence invertible modulo 2^63."""
+    base = (int(seed or 0) * 0xD1342543DE82EF95 + 0x2545F4914F6CDD1D) % (1 << 63)
+    return (base + int(rank) * 0x9E3779B97F4A7C15) % (1 << 63) or 1
+
+
 class DataParallelUpdater:
     def __init__(self, engine, group=None, broadcast_tensors=(), strict=False, overlap=False, native=False):
         if not dist.is_initialized():
@@ -127,6 +136,19 @@ class DataParallelUpdater:
 
     def run_graph(self, first_iteration: int, n_steps: int):
         self.engine.graph_run(first_iteration, n_steps)
+
+    def seed_indices(self, seed: int) -> int:
+        """opt-in device-side index draw for this rank: sets the rank-distinct key rank_index_seed(seed, rank) and returns
+        it. run_graph itself is unchanged -- it replays over the index table as it stands; call draw_indices in front of it."""
+        key = rank_index_seed(seed, self.rank)
+        self.engine.set_index_rng(key)
+        return key
+
+    def draw_indices(self, first_iteration: int, n_steps: int):
+        """fills the first n_steps rows of this rank's index table (uploaded once with n_steps rows: its shape is baked into
+        the captured graph) with the device's draw for iterations first_iteration .. + n_steps - 1, stream-ordered in front
+        of the run_graph(first_iteration, n_steps) that follows -- instead of cycling a pre-uploaded table"""
+        self.engine.draw_indices(first_iteration, n_steps)
 
     def allreduce_grads(self):
         g = self.engine.grads

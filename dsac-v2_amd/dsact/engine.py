@@ -165,6 +165,7 @@ class DsactEngine:
         self.buffer_capacity = 0
         self.rows_added = 0      # rows ever written to the ring (HipBatch tokens detect overwritten rows with it)
         self.fill_epoch = 0      # bumped by buffer_fill_device (writes at an arbitrary row: outstanding tokens become invalid)
+        self.index_seed = 0      # set_index_rng: 0 = the replay indices are the caller's host draws
 
     # ---- plumbing -----------------------------------------------------------------------------
     def _chk(self, rc):
@@ -279,8 +280,12 @@ class DsactEngine:
         return int(self._lib.dsact_buffer_ptr(self._h))
 
     def gather(self, idx):
-        idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int64))
-        self._chk(self._lib.dsact_gather(self._h, idx.ctypes.data_as(C.POINTER(C.c_int64)), int(idx.shape[0])))
+        """idx None: row 0 of the index table as draw_indices left it (dsact_gather with idx_host == NULL)"""
+        if idx is None:
+            self._chk(self._lib.dsact_gather(self._h, None, self.batch))
+        else:
+            idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int64))
+            self._chk(self._lib.dsact_gather(self._h, idx.ctypes.data_as(C.POINTER(C.c_int64)), int(idx.shape[0])))
         self.stage_serial += 1   # which minibatch sits in the staging set (HipBatch tokens compare against it)
 
     def read_batch(self, with_logp=True) -> Dict[str, np.ndarray]:
@@ -327,6 +332,23 @@ class DsactEngine:
         self._chk(self._lib.dsact_upload_index_table(self._h, idx.ctypes.data_as(C.POINTER(C.c_int64)),
                                                      int(idx.shape[0])))
 
+    # ---- device-side index draw (opt-in; replaces the np.random.randint of reference replay_buffer.py:86) --------------
+    def set_index_rng(self, seed: int):
+        """dsact_set_index_rng: Philox key of the device-side index draw; 0 switches it off (the default)"""
+        self._chk(self._lib.dsact_set_index_rng(self._h, int(seed)))
+        self.index_seed = int(seed)
+
+    def draw_indices(self, first_iteration: int, n: int = 1):
+        """dsact_draw_indices: rows [0, n) of the index table <- the draws of iterations first_iteration .. + n - 1 over the
+        current ring size. Asynchronous."""
+        self._chk(self._lib.dsact_draw_indices(self._h, int(first_iteration), int(n)))
+
+    def read_indices(self, rows: int = 1) -> np.ndarray:
+        """dsact_read_indices: the first `rows` rows of the index table, int64 [rows][batch]. Synchronous."""
+        out = np.empty((int(rows), self.batch), np.int64)
+        self._chk(self._lib.dsact_read_indices(self._h, out.ctypes.data_as(C.POINTER(C.c_int64)), int(rows)))
+        return out
+
     # ---- noise ---------------------------------------------------------------------------------------
     def set_noise(self, eps_new, eps_2, z5, z6):
         a, b, c, d = _f32(eps_new), _f32(eps_2), _f32(z5), _f32(z6)
@@ -354,21 +376,27 @@ class DsactEngine:
         self.stage_serial += 1   # the index table's device-side gather replaces the staged minibatch
         self._chk(self._lib.dsact_graph_run(self._h, int(first_iteration), int(n_steps)))
 
-    def run_group(self, first_iteration: int, idx_rows, noise_rows=None, flags: int = 0):
+    def run_group(self, first_iteration: int, idx_rows, noise_rows=None, flags: int = 0, n: int = None):
         """dsact_run_group: len(idx_rows) x { sample_batch -> local_update } of the reference's loop between two sampler calls
-        as one graph replay. idx_rows int64 [n][batch] (drawn by the caller with the reference's np.random.randint calls);
+        as one graph replay. idx_rows int64 [n][batch] (drawn by the caller with the reference's np.random.randint calls), or
+        None with `n` given: the device draws the rows of those n iterations itself (set_index_rng; NULL crosses the C-ABI);
         noise_rows float32 [n][2*B*A + 2*B] (eps_new | eps_2 | z5 | z6 per update) or None for device Philox noise.
         Asynchronous."""
-        idx = np.ascontiguousarray(np.asarray(idx_rows, dtype=np.int64))
-        assert idx.ndim == 2 and idx.shape[1] == self.batch, idx.shape
-        n = int(idx.shape[0])
+        if idx_rows is None:
+            if n is None or int(n) < 1:
+                raise ValueError("run_group(idx_rows=None) needs n, the number of updates the device draws indices for")
+            n, idx_ptr = int(n), None
+        else:
+            idx = np.ascontiguousarray(np.asarray(idx_rows, dtype=np.int64))
+            assert idx.ndim == 2 and idx.shape[1] == self.batch, idx.shape
+            assert n is None or int(n) == idx.shape[0], (n, idx.shape)
+            n, idx_ptr = int(idx.shape[0]), idx.ctypes.data_as(C.POINTER(C.c_int64))
         nz = None
         if noise_rows is not None:
             nz = _f32(noise_rows)
             assert nz.shape == (n, 2 * self.batch * self.act_dim + 2 * self.batch), nz.shape
         self.stage_serial += 1   # the group's last minibatch replaces the staged one
-        self._chk(self._lib.dsact_run_group(self._h, int(first_iteration), n, idx.ctypes.data_as(C.POINTER(C.c_int64)),
-                                            _ffi.fptr(nz), int(flags)))
+        self._chk(self._lib.dsact_run_group(self._h, int(first_iteration), n, idx_ptr, _ffi.fptr(nz), int(flags)))
         self._graph_steps = n
 
     # data-parallel halves (iteration and index-table row come from device state)

@@ -13,6 +13,15 @@ straight into the update's staging area, and the returned `HipBatch` is a token 
 `hip_obs_codebook=table` (image observations only) stores the obs / obs2 columns as one byte per element, an index into
 `table` (at most 256 float32 values, strictly ascending): a quarter of the fp32 ring's bytes, bit-identical minibatches.
 CarRacing's frames (`rgb / 255` cast to float32) take `np.float32(np.arange(256) / 255.0)`. See parse_obs_codebook.
+
+`hip_device_indices=True` (opt-in) moves the index draw to the device: uniform with replacement in [0, size) like the
+reference's, from Philox4x32-10 keyed by (index seed, minibatch counter, position) -- include/dsact.h, dsact_set_index_rng.
+No np.random call is made, so the run is reproducible from its seeds but is NOT index for index the reference's run, exactly
+as `strict_rng=False` is for the noise. The minibatch counter `index_iteration` starts at 0 and advances by one per minibatch
+drawn: in the reference's loop (one minibatch per update, iterations from 0) it IS the trainer's iteration, which is what
+makes a group's rows equal the per-update draws; a caller that starts elsewhere assigns it. `hip_index_seed` (default:
+index_seed_from(seed)) is the Philox key; the noise of `strict_rng=False` uses other stream ids of the same generator, so the
+two never share a counter block whatever the seeds.
 """
 import numpy as np
 
@@ -21,6 +30,12 @@ from dsact.engine import DsactEngine, current_engine
 __all__ = ["HipReplayBuffer", "parse_obs_codebook"]
 
 MAX_CODES = 256
+
+
+def index_seed_from(seed):
+    """default `hip_index_seed` of a run with the global `seed`: an odd-multiplier affine map into [1, 2^63) (0 would switch
+    the draw off). Any value works -- independence from the noise comes from the Philox stream id, not from this map."""
+    return (int(seed or 0) * 0xD1342543DE82EF95 + 0x2545F4914F6CDD1D) % (1 << 63) or 1
 
 
 def parse_obs_codebook(table, obs_shape):
@@ -62,8 +77,15 @@ class HipReplayBuffer:
             raise NotImplementedError("additional_info is not supported by HipReplayBuffer")
         book = kwargs.get("hip_obs_codebook")
         self.codebook = None if book is None else parse_obs_codebook(book, self._obs_shape)
+        self.device_indices = bool(kwargs.get("hip_device_indices", False))
+        if self.device_indices and kwargs.get("strict_rng", False):
+            raise ValueError("hip_device_indices=True with strict_rng=True: a parity run wants the reference's np.random.randint "
+                             "indices as well as its torch.randn noise; drop one of the two kwargs")
         eng = kwargs.get("hip_engine") or current_engine()
         B = int(kwargs["replay_batch_size"])
+        if self.device_indices and (eng is None or eng.obs_dim != self._obs_flat or eng.act_dim != self.act_dim or eng.batch != B):
+            raise ValueError("hip_device_indices=True needs the buffer attached to the algorithm's engine (create the algorithm "
+                             "first, or pass hip_engine=): the device draws the indices where the update reads them")
         if eng is None or eng.obs_dim != self._obs_flat or eng.act_dim != self.act_dim or eng.batch != B:
             if len(self._obs_shape) == 3:
                 from dsact.layout import CONV_TYPES
@@ -75,6 +97,13 @@ class HipReplayBuffer:
                 eng = DsactEngine(self._obs_flat, self.act_dim, hidden, B, device=int(kwargs.get("hip_device", 0)))
         self.engine = eng
         self.engine.buffer_create(self.max_size, codebook=self.codebook)
+        self.index_seed, self.index_iteration = 0, 0
+        if self.device_indices:
+            seed = kwargs.get("hip_index_seed")
+            self.index_seed = int(seed) if seed is not None else index_seed_from(kwargs.get("seed"))
+            if not 0 < self.index_seed < (1 << 64):
+                raise ValueError("hip_index_seed must be in [1, 2^64) (0 switches the device draw off), got %r" % (seed,))
+            self.engine.set_index_rng(self.index_seed)
 
     @property
     def size(self):
@@ -148,15 +177,32 @@ class HipReplayBuffer:
 
         if batch_size != self.engine.batch:
             raise ValueError("batch_size %d != the engine's minibatch rows %d" % (batch_size, self.engine.batch))
+        if self.device_indices:
+            # no draw here, no index on the host: "the rows the device draws at issue" for minibatches index_iteration .. + n - 1
+            size, it = self._drawable_size(), self.index_iteration
+            self.index_iteration += int(n)
+            return HipBatchGroup(self.engine, None, drawn=(it, int(n), size, self.index_seed))
         # ONE call of shape (n, batch): the legacy RandomState fills int64 draws element by element with no buffering between
         # calls, so this is the stream of n calls of `batch` draws (values AND final generator state; tests/test_host_side.py
         # pins it, the trainer-trajectory fixtures compare every index with the reference loop's) at a quarter of the host time
         idxs = np.random.randint(0, self.size, size=(int(n), batch_size))
         return HipBatchGroup(self.engine, idxs)
 
+    def _drawable_size(self):
+        size = self.size
+        if size <= 0:
+            raise ValueError("cannot sample from an empty buffer (np.random.randint(0, 0) raises in the reference too)")
+        return size
+
     def sample_batch(self, batch_size: int):
         from dsac_v2_hip import HipBatch
 
+        if self.device_indices:
+            size, it = self._drawable_size(), self.index_iteration
+            self.index_iteration += 1
+            self.engine.draw_indices(it, 1)   # replay_buffer.py:86 on the device ...
+            self.engine.gather(None)          # ... and :87-90 from the row it drew
+            return HipBatch(self.engine, None, drawn=(it, size, self.index_seed))
         idxs = np.random.randint(0, self.size, size=batch_size)  # reference replay_buffer.py:86
         self.engine.gather(idxs)
         return HipBatch(self.engine, idxs)

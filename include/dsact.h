@@ -13,7 +13,8 @@
  *   training/replay_buffer.py:20-50   ReplayBuffer.__init__   -> dsact_buffer_create
  *   training/replay_buffer.py:58-83   store / add_batch       -> dsact_buffer_add
  *   training/replay_buffer.py:85-90   sample_batch            -> dsact_gather (index draw stays on the
- *                                                                host: np.random.randint, bit-exact)
+ *                                                                host: np.random.randint, bit-exact;
+ *                                                                opt-in device draw: dsact_set_index_rng)
  *   training/trainer.py:72-74         per-key .cuda() of a CPU minibatch -> dsact_load_batch
  *   dsac_v2.py:188-204                the 14 numeric tb_info entries     -> dsact_read_stats
  *
@@ -217,7 +218,9 @@ int dsact_buffer_create_coded(dsact_handle* h, int64_t capacity, const float* co
 int dsact_buffer_check(dsact_handle* h);
 /* device bytes of the ring: capacity * (2*O + 4*(A+3)) coded, capacity * 4*(2*O + A + 3) fp32; 0 before a create */
 int64_t dsact_buffer_bytes(const dsact_handle* h);
-/* gather rows idx[0..batch) into the handle's minibatch staging area (== sample_batch + .cuda()) */
+/* gather rows idx[0..batch) into the handle's minibatch staging area (== sample_batch + .cuda()). idx_host == NULL (an
+ * index seed is set, DSACT_E_STATE otherwise): the rows of index-table row 0 as dsact_draw_indices left it, copied device to
+ * device behind the draw -- replay_buffer.py:86-90 with no host index at all. */
 int dsact_gather(dsact_handle* h, const int64_t* idx_host, int32_t batch);
 /* copy the staged minibatch back to host arrays (any may be NULL); synchronous. `logp` comes from
  * the ring (it is not part of the staging area the update reads). */
@@ -231,6 +234,28 @@ int dsact_load_batch(dsact_handle* h, const float* obs, const float* act, const 
                      const float* obs2, const float* done);
 /* index table for graph replay: rows x batch indices, row r is consumed by the r-th replayed step */
 int dsact_upload_index_table(dsact_handle* h, const int64_t* idx_host, int32_t rows);
+
+/* Device-side index draw (opt-in; replaces the np.random.randint(0, size, batch) of replay_buffer.py:86 the caller otherwise
+ * makes on the host). Every update's `batch` indices are drawn uniformly with replacement in [0, size) from Philox4x32-10
+ * with counter (position / 2, iteration low, iteration high, stream id 4) and key = seed (low, high word); the noise of
+ * dsact_set_device_rng uses stream ids 1 .. 3 of the same generator, so the two never share a counter block whatever their
+ * seeds. One Philox call gives words w[0..3] = two 64-bit draws u_k = (w[2k+1] << 32) | w[2k] for positions 2p + k, and
+ * index = floor(u * size / 2^64) (the high 64 bits of the 128-bit product). That map is a pure function of (seed, iteration,
+ * position, size); its bias is at most size / 2^64 per index (below 2^-40 for a 10M-row ring), it is not exactly uniform.
+ * The values depend on the iteration, never on the grouping: row r of a draw starting at iteration i is the one-row draw
+ * at i + r. A run is reproducible from its seeds; it is NOT index for index the reference's run (the NumPy stream is not
+ * consumed), exactly as dsact_set_device_rng's noise is not torch.randn's.
+ *   dsact_set_index_rng(h, seed)   0 disables (the default). Independent of dsact_set_device_rng; not baked into any graph.
+ *   dsact_draw_indices(h, first_iteration, n)   replay_buffer.py:86 for n consecutive updates without an update: enqueues
+ *                                  the draw over the ring size at the time of the call; afterwards rows [0, n) of the
+ *                                  index table hold it (for dsact_gather(h, NULL, batch), data-parallel replays that
+ *                                  read the table, and tests). DSACT_E_STATE without a seed or on an empty ring
+ *                                  (np.random.randint(0, 0) raises too). Asynchronous.
+ *   dsact_read_indices(h, out, rows)   the first `rows` index-table rows as int64 out[rows * batch] -- what
+ *                                  replay_buffer.py:86 returned for them. SYNCHRONOUS (tokens that must re-gather, tests). */
+int dsact_set_index_rng(dsact_handle* h, uint64_t seed);
+int dsact_draw_indices(dsact_handle* h, int64_t first_iteration, int32_t n);
+int dsact_read_indices(dsact_handle* h, int64_t* out, int32_t rows);
 
 /* ---- noise (the torch.randn draws of one __compute_gradient) ------------- */
 /* parity mode: inject eps_new[B*A], eps_2[B*A], z5[B], z6[B] (host pointers) for the next step */
@@ -274,7 +299,12 @@ int dsact_graph_run(dsact_handle* h, int64_t first_iteration, int64_t n_steps);
  * iteration (dsact_set_device_rng). Asynchronous: pinned staging, a stream-ordered reset of the replay counters, no host
  * wait. Captured graphs are kept per (n_steps, flags, noise mode); the first group of a new shape pays its capture.
  * Same bits as n_steps x { dsact_gather; dsact_step }. The ring must not be written while the group runs (dsact_sync or
- * any synchronising call first) -- dsact_buffer_add is stream-ordered behind it and therefore safe. */
+ * any synchronising call first) -- dsact_buffer_add is stream-ordered behind it and therefore safe.
+ * idx == NULL: allowed only with an index seed (dsact_set_index_rng; DSACT_E_STATE otherwise). The n_steps draws of
+ * replay_buffer.py:86 are then made by the device for iterations first_iteration .. + n_steps - 1 over the ring size at the
+ * time of the call: no pinned staging, conversion or upload of index rows; one small launch on the handle's stream in front
+ * of the replay, outside the captured graph (graphs and their cache keys are the same with and without it). Same bits as
+ * passing dsact_read_indices' rows of the same draw as idx. With idx != NULL the call is unchanged, seed set or not. */
 int dsact_run_group(dsact_handle* h, int64_t first_iteration, int32_t n_steps, const int64_t* idx, const float* noise, uint32_t flags);
 
 /* data-parallel replay (one process per GPU): the same two halves with iteration / index-table row
