@@ -24,6 +24,17 @@
 // launch with kMode = true: the K loop, its sums and the output activation are the sampling form's instruction for
 // instruction (a row's mean is bitwise the sampling kernel's), only the epilogue differs -- act_mode of dsact_math.h writes
 // the action, no eps is read and no log-probability is reduced.
+//
+// The device-resident sampler's acting (training/hip_tensor_sampler.py, dsact_act_sample_device; training/off_sampler.py:46-65
+// over N environments of a batched simulator) is the sampling form with kDev = true: the same K loop, sums, output activation
+// and tanh_gauss_fwd (a row's action and log-probability are bitwise the sampling kernel's for the same eps), but
+//   * eps comes from a device array, or -- eps == nullptr -- is drawn here: normal4 / philox4x32 (dsact_kernels.h) with stream id
+//     kActStream = 5 (1 .. 3: the update noise, 4: the index draw), counter (row * ceil(A/4) + d/4, step low, step high, 5), key =
+//     the acting seed, element d % 4 of the four normals. `row` is the environment's row in the whole call (row0 + the row in
+//     this launch), `step` the caller's 64-bit acting-step counter: the noise of environment i at step t is a pure function of
+//     (seed, t, i, d) -- independent of N and of the chunking at kActBatchCap;
+//   * action[n][A], logp[n] and clipped[n][A] = min(max(action, lo), hi) (the value the environment receives,
+//     off_sampler.py:62-65) are written to DEVICE memory the caller owns; nothing is mapped to the host.
 #pragma once
 #include "dsact_kernels.h"
 
@@ -53,7 +64,13 @@ struct ActBatchOut {
   const float* lo; const float* hi;          // action limits (kMode only: GaussDistribution.mode() clamps to them)
   float lo_ls, hi_ls;
   float* action; float* logp;          // [n][A], [n] (kMode: logp unused)
+  // kDev only (appended: the other forms' argument offsets are what they were)
+  float* clipped;                      // [n][A] the action clamped to [lo, hi]
+  unsigned long long seed;             // the acting seed (eps == nullptr: the draw is made here)
+  long long step;                      // the acting-step counter
+  int row0;                            // the first row of this launch in the whole call (the chunk offset)
 };
+constexpr uint32_t kActStream = 5u;
 
 #ifdef DSACT_ACT_BATCH_DEFINE   // the kernels themselves: csrc/dsact_tu_act_batch.hip; other units see the declarations
 // 32 rows x 32 features per workgroup; thread (tr, tf) = (tid / 16, tid % 16) owns rows tr, tr + 16 and features tf, tf + 16.
@@ -116,8 +133,9 @@ __global__ void __launch_bounds__(256) k_act_batch_hidden(ActBatchHidden a) {
 }
 
 // 8 rows x 64 outputs (mean | raw log-std, 2A <= 64) per workgroup; thread (tr, tf) = (tid / 32, tid % 32) owns row tr and
-// outputs tf, tf + 32. grid: x = row tiles. kMode: the mode instead of the sample (eps and logp are not touched)
-template <bool kMode>
+// outputs tf, tf + 32. grid: x = row tiles. kMode: the mode instead of the sample (eps and logp are not touched). kDev: the
+// device-resident sampling form (see the header comment)
+template <bool kMode, bool kDev>
 __global__ void __launch_bounds__(256) k_act_batch_out(ActBatchOut a) {
   constexpr int KC = 64;   // (the 64-row weight tile at 128 columns runs out of scalar registers)
   __shared__ float xs[8][KC + 1];
@@ -175,11 +193,30 @@ __global__ void __launch_bounds__(256) k_act_batch_out(ActBatchOut a) {
     return;
   }
   // the sample, one (row, action dimension) per thread: tanh_gauss_fwd term for term
+  if constexpr (kDev) {
+    // eps from the caller's device array or drawn here; then tanh_gauss_fwd as below, plus the clipped copy
+    if (r < a.n && d < a.A) {
+      float e;
+      if (a.eps) {
+        e = a.eps[(size_t)r * a.A + d];
+      } else {
+        float z[4];
+        normal4(a.seed, a.step, kActStream, (uint32_t)(a.row0 + r) * (uint32_t)((a.A + 3) >> 2) + (uint32_t)(d >> 2), z);
+        const int q = d & 3;
+        e = q == 0 ? z[0] : q == 1 ? z[1] : q == 2 ? z[2] : z[3];
+      }
+      const TanhGaussFwd g = tanh_gauss_fwd(raw[tr][d], raw[tr][a.A + d], e, a.scale[d], a.center[d], a.lo_ls, a.hi_ls);
+      a.action[(size_t)r * a.A + d] = g.a;
+      a.clipped[(size_t)r * a.A + d] = fminf(fmaxf(g.a, a.lo[d]), a.hi[d]);
+      lps[tr][d] = g.lp;
+    }
+  } else {
   if (r < a.n && d < a.A) {
     const TanhGaussFwd g = tanh_gauss_fwd(raw[tr][d], raw[tr][a.A + d], a.eps[(size_t)r * a.A + d], a.scale[d], a.center[d],
                                           a.lo_ls, a.hi_ls);
     a.action[(size_t)r * a.A + d] = g.a;
     lps[tr][d] = g.lp;
+  }
   }
   __syncthreads();
   // Independent(..., 1): the log-probability summed over the action dimensions, in order
@@ -189,14 +226,16 @@ __global__ void __launch_bounds__(256) k_act_batch_out(ActBatchOut a) {
     a.logp[r0 + tid] = lp;
   }
 }
-template __global__ void k_act_batch_out<false>(ActBatchOut);
-template __global__ void k_act_batch_out<true>(ActBatchOut);
+template __global__ void k_act_batch_out<false, false>(ActBatchOut);
+template __global__ void k_act_batch_out<true, false>(ActBatchOut);
+template __global__ void k_act_batch_out<false, true>(ActBatchOut);
 #else
 __global__ void k_act_batch_hidden(ActBatchHidden a);
-template <bool kMode>
+template <bool kMode, bool kDev>
 __global__ void k_act_batch_out(ActBatchOut a);
-extern template __global__ void k_act_batch_out<false>(ActBatchOut);
-extern template __global__ void k_act_batch_out<true>(ActBatchOut);
+extern template __global__ void k_act_batch_out<false, false>(ActBatchOut);
+extern template __global__ void k_act_batch_out<true, false>(ActBatchOut);
+extern template __global__ void k_act_batch_out<false, true>(ActBatchOut);
 #endif
 
 }  // namespace dsact

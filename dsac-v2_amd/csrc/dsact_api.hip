@@ -308,6 +308,11 @@ struct dsact_handle {
   float* ab_out_host = nullptr; float* ab_out_dev = nullptr;
   unsigned long long ab_calls = 0;
   unsigned long long ab_mode_calls = 0;  // dsact_act_mode_batch chunks launched on the GPU
+  // device-resident sampling (dsact_act_sample_device / dsact_buffer_add_device)
+  uint64_t act_seed = 0;                 // dsact_set_act_rng: 0 = no in-kernel draw (eps must be passed)
+  unsigned long long act_dev_calls = 0;  // dsact_act_sample_device chunks launched
+  unsigned long long ring_commit_rows = 0;   // transitions written by dsact_buffer_add_device
+  unsigned long long act_dev_syncs = 0;  // stream synchronisations made inside those two entry points (stays 0)
   int mode_host_rows = kModeHostRows;   // dsact_act_mode_batch's host / GPU crossover (debug switch "mode_host_rows": measurements)
   unsigned long long act_host_calls = 0, act_copies = 0;
   // behaviour policy (dsact_behaviour_hold): a device copy of the policy net taken on the handle's stream
@@ -3946,6 +3951,49 @@ int dsact_buffer_fill_device(dsact_handle* h, int64_t row0, int64_t n, const flo
   return check_codes(h);
 }
 
+// a pointer into device memory of the handle's GPU (hipMalloc / a torch CUDA tensor): pinned, mapped, managed and pageable
+// host memory are all refused
+static bool on_handle_gpu(const dsact_handle* h, const void* p) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return at.type == hipMemoryTypeDevice && at.device == h->device;
+}
+// check_handoff of the two asynchronous entry points: its failure path drains the stream, which act_dev_syncs reports
+static int check_handoff_counted(dsact_handle* h) {
+  const unsigned long long before = h->handoff_failures;
+  const int rc = check_handoff(h);
+  if (h->handoff_failures != before) h->act_dev_syncs++;
+  return rc;
+}
+
+int dsact_buffer_add_device(dsact_handle* h, int64_t n, const float* obs, const float* act, const float* rew, const float* obs2,
+                            const uint8_t* terminated, const uint8_t* truncated, const float* logp, double reward_scale) {
+  if (!h || n < 0 || !obs || !act || !rew || !obs2 || !terminated || !truncated || !logp) return DSACT_E_INVALID;
+  if (!has_ring(h)) return fail(h, DSACT_E_STATE, "buffer not created");
+  if (h->rb_code) return fail(h, DSACT_E_INVALID, "dsact_buffer_add_device serves the fp32 MLP ring (coded rings: dsact_buffer_add)");
+  if (h->cnn) return fail(h, DSACT_E_INVALID, "dsact_buffer_add_device serves the fp32 MLP ring (image rings: dsact_buffer_add)");
+  if (n > h->cap) return fail(h, DSACT_E_INVALID, "dsact_buffer_add_device: n = %lld exceeds the capacity %lld", (long long)n, (long long)h->cap);
+  if (n == 0) return DSACT_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const void* ptrs[7] = {obs, act, rew, obs2, terminated, truncated, logp};
+  for (const void* p : ptrs)
+    if (!on_handle_gpu(h, p))
+      return fail(h, DSACT_E_INVALID, "dsact_buffer_add_device takes device pointers on the handle's GPU (host rows: dsact_buffer_add)");
+  TRY(check_handoff_counted(h));
+  RingCommitArgs a;
+  a.s_obs = obs; a.s_act = act; a.s_rew = rew; a.s_obs2 = obs2; a.s_term = terminated; a.s_trunc = truncated; a.s_logp = logp;
+  a.rb_obs = h->rb_obs; a.rb_obs2 = h->rb_obs2; a.rb_act = h->rb_act; a.rb_rew = h->rb_rew; a.rb_done = h->rb_done; a.rb_logp = h->rb_logp;
+  a.ptr = h->ptr; a.cap = h->cap; a.n = (int)n; a.O = h->O; a.A = h->A;
+  a.wide = (h->O % 4 == 0) && ((uintptr_t)obs % 16 == 0) && ((uintptr_t)obs2 % 16 == 0) && ((uintptr_t)h->rb_obs % 16 == 0) &&
+           ((uintptr_t)h->rb_obs2 % 16 == 0);
+  a.reward_scale = (float)reward_scale;
+  TRY(launch(h, "ring_commit", k_ring_commit, dim3((unsigned)((n + 3) / 4)), dim3(kThreads), 0, a));
+  h->ptr = (h->ptr + n) % h->cap;                           // replay_buffer.py:78-79, n times
+  h->size = h->size + n > h->cap ? h->cap : h->size + n;
+  h->ring_commit_rows += (unsigned long long)n;
+  return DSACT_OK;
+}
+
 int dsact_gather(dsact_handle* h, const int64_t* idx_host, int32_t batch) {
   if (!h) return DSACT_E_INVALID;
   if (!has_ring(h)) return fail(h, DSACT_E_STATE, "buffer not created");
@@ -5226,6 +5274,9 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "act_batch_calls")) *value = (double)h->ab_calls;   // dsact_act_sample_batch chunks launched on the GPU
   else if (!strcmp(name, "act_mode_calls")) *value = (double)h->ab_mode_calls;   // dsact_act_mode_batch chunks launched on the GPU
   else if (!strcmp(name, "mode_host_rows")) *value = (double)h->mode_host_rows;
+  else if (!strcmp(name, "act_dev_calls")) *value = (double)h->act_dev_calls;       // dsact_act_sample_device chunks launched
+  else if (!strcmp(name, "ring_commit_rows")) *value = (double)h->ring_commit_rows; // transitions written by dsact_buffer_add_device
+  else if (!strcmp(name, "act_dev_syncs")) *value = (double)h->act_dev_syncs;       // stream drains inside those two (0)
   else if (!strcmp(name, "act_fast")) *value = act_fast_ok(h) ? 1.0 : 0.0;     // dsact_act_sample / the one-launch acting forward serve this handle
   else if (!strcmp(name, "graph_cache")) *value = (double)h->graph_cache.size();   // inactive captured graphs kept by dsact_run_group
   else if (!strcmp(name, "graph_noise_table")) *value = h->graph_noise_table ? 1.0 : 0.0;
@@ -5391,9 +5442,9 @@ static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const flo
     o.lo = h->act_lo; o.hi = h->act_hi;
     o.action = h->ab_out_dev; o.logp = mode ? nullptr : h->ab_out_dev + (size_t)m * A;
     const dim3 grid((unsigned)((m + 7) / 8));
-    if (mode) TRY(launch(h, "act_batch_mode", k_act_batch_out<true>, grid, dim3(256), 0, o));
-    else if (stream == h->stream) TRY(launch(h, "act_batch_out", k_act_batch_out<false>, grid, dim3(256), 0, o));
-    else TRY(launch_on(h, stream, "act_batch_out", k_act_batch_out<false>, grid, dim3(256), 0, o));
+    if (mode) TRY(launch(h, "act_batch_mode", k_act_batch_out<true, false>, grid, dim3(256), 0, o));
+    else if (stream == h->stream) TRY(launch(h, "act_batch_out", k_act_batch_out<false, false>, grid, dim3(256), 0, o));
+    else TRY(launch_on(h, stream, "act_batch_out", k_act_batch_out<false, false>, grid, dim3(256), 0, o));
     HIPCHK(h, hipStreamSynchronize(stream));
     (mode ? h->ab_mode_calls : h->ab_calls)++;
     memcpy(action_host + (size_t)s * A, h->ab_out_host, (size_t)m * A * sizeof(float));
@@ -5493,6 +5544,62 @@ int dsact_act_mode_batch(dsact_handle* h, const float* obs, int32_t n, float* ac
     return DSACT_OK;
   }
   return act_batch_gpu(h, obs, n, nullptr, action_host, nullptr, net_params(h, N_POL), h->stream);
+}
+
+// ---- device-resident sampling ----------------------------------------------------------------------
+int dsact_set_act_rng(dsact_handle* h, uint64_t seed) {
+  if (!h) return DSACT_E_INVALID;
+  h->act_seed = seed;
+  return DSACT_OK;
+}
+
+int dsact_act_sample_device(dsact_handle* h, const float* obs_dev, int32_t n, const float* eps_dev, int64_t step,
+                            float* action_dev, float* clipped_dev, float* logp_dev) {
+  if (!h || !obs_dev || !action_dev || !clipped_dev || !logp_dev || n < 1) return DSACT_E_INVALID;
+  if (!h->online) return fail(h, DSACT_E_STATE, "arenas not bound");
+  if (!h->limits_set) return fail(h, DSACT_E_STATE, "action limits not set (dsact_set_action_limits)");
+  if (h->cnn) return fail(h, DSACT_E_INVALID, "dsact_act_sample_batch serves MLP policies (CNN: dsact_policy_forward)");
+  if (h->A > 32) return fail(h, DSACT_E_INVALID, "dsact_act_sample_batch serves act_dim <= 32");
+  if (!eps_dev && h->act_seed == 0)
+    return fail(h, DSACT_E_STATE, "eps == NULL draws the noise in the kernel: call dsact_set_act_rng with a non-zero seed first");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!on_handle_gpu(h, obs_dev) || (eps_dev && !on_handle_gpu(h, eps_dev)) || !on_handle_gpu(h, action_dev) ||
+      !on_handle_gpu(h, clipped_dev) || !on_handle_gpu(h, logp_dev))
+    return fail(h, DSACT_E_INVALID, "dsact_act_sample_device takes device pointers on the handle's GPU (host rows: dsact_act_sample_batch)");
+  TRY(check_handoff_counted(h));
+  TRY(alloc_act_batch(h));   // (the hidden layers' two activation buffers; the first call allocates)
+  const int O = h->O, A = h->A, R = kActBatchCap;
+  const float* base = net_params(h, N_POL);   // the live weights: the launches sit behind every enqueued update
+  const NetDesc& d = h->pd;
+  for (int s = 0; s < n; s += R) {
+    const int m = n - s < R ? n - s : R;
+    const float* X = obs_dev + (size_t)s * O;   // read in place: no staging copy
+    int ldx = O;
+    for (int l = 0; l < h->Lp; ++l) {
+      ActBatchHidden a;
+      a.X = X; a.ldx = ldx; a.W = base + d.w_off[l]; a.b = base + d.b_off[l];
+      a.K = d.in[l]; a.N = d.out[l]; a.half = 0;
+      if (d.nblk == 2 && l > 0) { a.K = d.in[l] / 2; a.half = d.out[l] / 2; }   // two (H x Hprev) blocks
+      a.Y = h->ab_h[l & 1]; a.ldy = d.out[l]; a.n = m; a.act = h->cfg.policy_act;
+      const int seg_n = a.half > 0 ? a.half : a.N;
+      const dim3 grid((unsigned)((a.half > 0 ? 2 : 1) * ((seg_n + 31) / 32)), (unsigned)((m + 31) / 32));
+      TRY(launch(h, "act_batch_hidden", k_act_batch_hidden, grid, dim3(256), 0, a));
+      X = a.Y; ldx = a.ldy;
+    }
+    ActBatchOut o;
+    memset(&o, 0, sizeof(o));
+    o.X = X; o.ldx = ldx; o.W = base + d.w_off[h->Lp]; o.b = base + d.b_off[h->Lp];
+    o.K = d.in[h->Lp]; o.A = A; o.n = m;
+    o.out_act = h->cfg.policy_out_act; o.out_n = h->cfg.policy_std_param ? A : 2 * A;
+    o.eps = eps_dev ? eps_dev + (size_t)s * A : nullptr;
+    o.scale = h->act_scale; o.center = h->act_center; o.lo_ls = h->cfg.min_log_std; o.hi_ls = h->cfg.max_log_std;
+    o.lo = h->act_lo; o.hi = h->act_hi;
+    o.action = action_dev + (size_t)s * A; o.logp = logp_dev + s; o.clipped = clipped_dev + (size_t)s * A;
+    o.seed = h->act_seed; o.step = step; o.row0 = s;
+    TRY(launch(h, "act_batch_out_dev", k_act_batch_out<false, true>, dim3((unsigned)((m + 7) / 8)), dim3(256), 0, o));
+    h->act_dev_calls++;
+  }
+  return check_handoff_counted(h);
 }
 
 // ---- behaviour policy ----------------------------------------------------------------------------

@@ -644,6 +644,52 @@ __global__ void __launch_bounds__(kThreads) k_ring_write(ScatterArgs a) {
 }
 #endif
 
+// k_ring_commit: the ring write of the device-resident sampler (training/hip_tensor_sampler.py, dsact_buffer_add_device) -- n
+// transitions that a batched simulator left in DEVICE arrays go to ring rows (ptr + i) % cap in one launch: what n reference
+// store() calls do (training/replay_buffer.py:58-79) with the sampler's own bookkeeping of a step folded in
+// (training/off_sampler.py:66-73): rew is stored as rew * reward_scale, done as terminated && !truncated (a time-out is
+// stored as non-terminal). term / trunc are one byte per transition (a torch.bool tensor), non-zero = set.
+//   reward_scale: the reference multiplies Python doubles and the ring's float32 column rounds the product once; here it is ONE
+//   fp32 product with the scale rounded to fp32 first. The two are equal whenever the scale is exactly representable in fp32
+//   (1, 0.25, 0.1f is not): the double product of two fp32 values is exact, so both round the same real number once.
+// The fp32 MLP ring's layout (k_ring_write above): one wave per transition, rows of 4 * O bytes contiguous per column. `wide`
+// (O % 4 == 0 and 16-byte aligned sources; the ring's columns are allocation-aligned): a lane moves 16 bytes per access --
+// a 376-float Humanoid row is 94 dwordx4 per column, two passes of the wave -- else 4 bytes. Vector loads and stores only; n <= cap,
+// so no two transitions of a launch share a ring row.
+struct RingCommitArgs {
+  const float* s_obs; const float* s_act; const float* s_rew; const float* s_obs2;
+  const unsigned char* s_term; const unsigned char* s_trunc; const float* s_logp;
+  float* rb_obs; float* rb_obs2; float* rb_act; float* rb_rew; float* rb_done; float* rb_logp;
+  long long ptr, cap; int n, O, A, wide;
+  float reward_scale;
+};
+#ifndef DSACT_FAMILY_UNIT   // plain kernel: compiled in dsact_api.hip only (dsact_tu.h)
+__global__ void __launch_bounds__(kThreads) k_ring_commit(RingCommitArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long i = (long long)blockIdx.x * 4 + wave;
+  if (i >= a.n) return;
+  const long long dst = (a.ptr + i) % a.cap;
+  if (a.wide) {
+    const float4* so = reinterpret_cast<const float4*>(a.s_obs + (size_t)i * a.O);
+    const float4* so2 = reinterpret_cast<const float4*>(a.s_obs2 + (size_t)i * a.O);
+    float4* ro = reinterpret_cast<float4*>(a.rb_obs + (size_t)dst * a.O);
+    float4* ro2 = reinterpret_cast<float4*>(a.rb_obs2 + (size_t)dst * a.O);
+    for (int k = lane; k < a.O / 4; k += 64) { ro[k] = so[k]; ro2[k] = so2[k]; }
+  } else {
+    for (int k = lane; k < a.O; k += 64) {
+      a.rb_obs[(size_t)dst * a.O + k] = a.s_obs[(size_t)i * a.O + k];
+      a.rb_obs2[(size_t)dst * a.O + k] = a.s_obs2[(size_t)i * a.O + k];
+    }
+  }
+  for (int k = lane; k < a.A; k += 64) a.rb_act[(size_t)dst * a.A + k] = a.s_act[(size_t)i * a.A + k];
+  if (lane == 0) {
+    a.rb_rew[dst] = a.s_rew[i] * a.reward_scale;
+    a.rb_done[dst] = (a.s_term[i] != 0 && a.s_trunc[i] == 0) ? 1.0f : 0.0f;
+    a.rb_logp[dst] = a.s_logp[i];
+  }
+}
+#endif
+
 // ---------------------------------------------------------------------------------------------
 // k_tiles: C[m][n] (+epilogue) = sum_k P(m,k) * Q(n,k) on 32x32 tiles, BK = 64
 //   operand storage: KC  element (row,k) at base[row*ld + k]   (k contiguous)

@@ -214,6 +214,7 @@ class DsactEngine:
     def set_action_limits(self, high, low):
         hi, lo = _f32(high), _f32(low)
         self._chk(self._lib.dsact_set_action_limits(self._h, _ffi.fptr(hi), _ffi.fptr(lo)))
+        self.act_high, self.act_low = hi.reshape(-1).copy(), lo.reshape(-1).copy()   # (what act_sample_device clips to)
 
     # ---- state ------------------------------------------------------------------------------------
     def get_state(self):
@@ -627,6 +628,56 @@ class DsactEngine:
         rc = f(self._h, obs_addr, n, act_addr)
         if rc != 0:
             self._chk(rc)
+
+    # ---- device-resident sampling: everything stays on the GPU, nothing waits -------------------------
+    def _dev(self, t, shape, dtypes, name):
+        """address of a torch tensor the asynchronous entry points may read or write: on this engine's GPU, contiguous, of
+        the given shape and one of `dtypes`"""
+        torch = self.torch
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device_index:
+            raise ValueError("%s must be a torch tensor on %s (got %s)" % (name, self.device, getattr(t, "device", type(t).__name__)))
+        if t.dtype not in dtypes:
+            raise ValueError("%s must have dtype %s (got %s)" % (name, " or ".join(str(d) for d in dtypes), t.dtype))
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("%s must have shape %r (got %r)" % (name, tuple(shape), tuple(t.shape)))
+        return t.data_ptr()
+
+    def set_act_rng(self, seed: int):
+        """dsact_set_act_rng: Philox key of act_sample_device's in-kernel N(0,1) draw; 0 switches it off (the default)"""
+        self._chk(self._lib.dsact_set_act_rng(self._h, int(seed)))
+        self.act_seed = int(seed)
+
+    def act_sample_device(self, obs, eps, step, action, clipped, logp):
+        """dsact_act_sample_device: policy(obs[n, O]) on the live weights + the action distribution's sample, written into the
+        caller's device tensors action[n, A] (what the ring stores), clipped[n, A] (inside the action limits: what the
+        environment receives) and logp[n]. eps[n, A]: the caller's N(0,1) draws, or None: drawn in the kernel for acting step
+        `step` (set_act_rng). float32 contiguous tensors on this engine's GPU. Asynchronous on the engine's stream: issue the
+        torch work that produces obs / consumes the results under `torch.cuda.stream(engine.torch_stream)`."""
+        f32 = (self.torch.float32,)
+        n = int(obs.shape[0]) if hasattr(obs, "shape") and len(obs.shape) else 0
+        O, A = self.obs_dim, self.act_dim
+        po = self._dev(obs, (n, O), f32, "obs")
+        pe = self._dev(eps, (n, A), f32, "eps") if eps is not None else None
+        pa, pc, pl = self._dev(action, (n, A), f32, "action"), self._dev(clipped, (n, A), f32, "clipped"), self._dev(logp, (n,), f32, "logp")
+        rc = self._lib.dsact_act_sample_device(self._h, po, n, pe, int(step), pa, pc, pl)
+        if rc != 0:
+            self._chk(rc)
+
+    def buffer_add_device(self, obs, act, rew, obs2, terminated, truncated, logp, reward_scale=1.0):
+        """dsact_buffer_add_device: n transitions from device tensors into ring rows (ptr + i) % capacity; rew is stored as
+        rew * reward_scale, done as terminated & ~truncated. obs / obs2 [n, O], act [n, A], rew / logp [n] float32,
+        terminated / truncated [n] bool (or uint8). Asynchronous on the engine's stream."""
+        torch = self.torch
+        f32, flag = (torch.float32,), (torch.bool, torch.uint8)
+        n = int(rew.shape[0]) if hasattr(rew, "shape") and len(rew.shape) else 0
+        O, A = self.obs_dim, self.act_dim
+        ptrs = [self._dev(obs, (n, O), f32, "obs"), self._dev(act, (n, A), f32, "act"), self._dev(rew, (n,), f32, "rew"),
+                self._dev(obs2, (n, O), f32, "obs2"), self._dev(terminated, (n,), flag, "terminated"),
+                self._dev(truncated, (n,), flag, "truncated"), self._dev(logp, (n,), f32, "logp")]
+        self._chk(self._lib.dsact_buffer_add_device(self._h, n, *ptrs, float(reward_scale)))
+        self.rows_added += n
 
     def behaviour_hold(self):
         """dsact_behaviour_hold: from now on act_sample / act_sample_batch act with a copy of the policy taken on the engine's

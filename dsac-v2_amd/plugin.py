@@ -6,7 +6,9 @@ training/trainer.py:155-158): the drop-in surface of this repository.
                                                             class HipReplayBuffer
     create_sampler(**kw)                                 -> training.hip_sampler.HipOffSampler, or with
                                                             sampler_name="hip_vec_off_sampler"
-                                                            training.hip_vec_sampler.HipVecOffSampler
+                                                            training.hip_vec_sampler.HipVecOffSampler, with
+                                                            sampler_name="hip_tensor_env_sampler"
+                                                            training.hip_tensor_sampler.HipTensorEnvSampler
     create_evaluator(**kw)                               -> training.hip_trainer.HipEvaluator, or with
                                                             hip_eval_env_num=N >= 2
                                                             training.hip_vec_evaluator.HipVecEvaluator
@@ -74,12 +76,17 @@ def create_env(**kwargs):
 
 def create_sampler(**kwargs):
     """sampler_name="hip_vec_off_sampler": the vectorised sampler (training/hip_vec_sampler.py; N = vector_env_num
-    environments in lockstep). Every other name -- or none -- is the one-environment HipOffSampler, whatever
+    environments in lockstep); sampler_name="hip_tensor_env_sampler": the device-resident sampler for batched tensor
+    environments (training/hip_tensor_sampler.py; observations, actions and transitions never leave the GPU). Every other name -- or none -- is the one-environment HipOffSampler, whatever
     vector_env_num says (the reference's CNN examples pass it and step one environment)."""
     if kwargs.get("sampler_name") == "hip_vec_off_sampler":
         from training.hip_vec_sampler import HipVecOffSampler
 
         return HipVecOffSampler(**kwargs)
+    if kwargs.get("sampler_name") == "hip_tensor_env_sampler":
+        from training.hip_tensor_sampler import HipTensorEnvSampler
+
+        return HipTensorEnvSampler(**kwargs)
     from training.hip_sampler import HipOffSampler
 
     return HipOffSampler(**kwargs)

@@ -22,12 +22,16 @@ drawn: in the reference's loop (one minibatch per update, iterations from 0) it 
 makes a group's rows equal the per-update draws; a caller that starts elsewhere assigns it. `hip_index_seed` (default:
 index_seed_from(seed)) is the Philox key; the noise of `strict_rng=False` uses other stream ids of the same generator, so the
 two never share a counter block whatever the seeds.
+
+`add_batch` also takes a `DeviceSampleBatch` (training/hip_tensor_sampler.py: the transitions of a batched tensor environment,
+already on the GPU) and hands its seven device tensors to the ring in one asynchronous call (dsact_buffer_add_device); every
+other input takes the paths it always took.
 """
 import numpy as np
 
 from dsact.engine import DsactEngine, current_engine
 
-__all__ = ["HipReplayBuffer", "parse_obs_codebook"]
+__all__ = ["HipReplayBuffer", "parse_obs_codebook", "index_seed_from", "act_seed_from"]
 
 MAX_CODES = 256
 
@@ -36,6 +40,13 @@ def index_seed_from(seed):
     """default `hip_index_seed` of a run with the global `seed`: an odd-multiplier affine map into [1, 2^63) (0 would switch
     the draw off). Any value works -- independence from the noise comes from the Philox stream id, not from this map."""
     return (int(seed or 0) * 0xD1342543DE82EF95 + 0x2545F4914F6CDD1D) % (1 << 63) or 1
+
+
+def act_seed_from(seed):
+    """default `hip_act_seed` of a run with the global `seed` (training/hip_tensor_sampler.py: the Philox key of the in-kernel
+    acting noise): another fixed odd-multiplier affine map into [1, 2^63), so that a run's index draw and acting noise do not
+    share a key by default either (their Philox stream ids, 4 and 5, already keep them apart for ANY pair of seeds)."""
+    return (int(seed or 0) * 0x9FB21C651E98DF25 + 0x6A09E667F3BCC909) % (1 << 63) or 1
 
 
 def parse_obs_codebook(table, obs_shape):
@@ -131,6 +142,13 @@ class HipReplayBuffer:
     def add_batch(self, samples: list):
         n = len(samples)
         if n == 0:
+            return
+        cols = getattr(samples, "device_columns", None)
+        if cols is not None:
+            # a DeviceSampleBatch (training/hip_tensor_sampler.py): the transitions are device tensors -- ONE ring commit, no copy
+            if n > self.max_size:
+                raise ValueError("a device batch of %d transitions does not fit a ring of %d rows" % (n, self.max_size))
+            self.engine.buffer_add_device(*cols, reward_scale=samples.reward_scale)
             return
         packed = getattr(samples, "packed", None)
         if packed is not None and packed[0].shape == (n, self._obs_flat) and self._packed_matches(samples, packed):

@@ -1,0 +1,256 @@
+"""HipTensorEnvSampler -- the sampler for BATCHED TENSOR ENVIRONMENTS: simulators that take an [N, A] action tensor on the GPU and
+return [N, O] observations, rewards and done flags on the GPU (`plugin.create_sampler(sampler_name="hip_tensor_env_sampler",
+env=..., ...)`).
+
+HipVecOffSampler (training/hip_vec_sampler.py) steps N Python environments and moves every observation, action and transition
+across the bus; for an environment that already lives on the device that is pure overhead. Here nothing leaves the GPU and
+nothing waits: a lockstep step is ONE dsact_act_sample_device call (policy(obs) on the live weights + the distribution's sample
+with noise drawn in the kernel + the clip to the action limits, csrc/dsact_act_batch.h), the environment's own step / reset,
+and a few row copies -- all enqueued on the engine's stream. The returned DeviceSampleBatch goes to the replay ring with one
+launch (HipReplayBuffer.add_batch -> dsact_buffer_add_device). A whole sample() costs launches only.
+
+Environment protocol (all values float32 / bool torch tensors on the engine's device):
+    env.num_envs                          N
+    env.action_low / env.action_high      [A] or [N, A]
+    env.reset() -> obs[N, O]              start every environment
+    env.step(clipped[N, A]) -> (obs2[N, O], reward[N], terminated[N], truncated[N])
+                                          obs2 is the TRUE next observation, before any reset
+    env.reset(mask[N]) -> obs[N, O]       rows where the bool mask is set are restarted, the others returned as they are
+The environment's torch ops are issued under `torch.cuda.stream(engine.torch_stream)`, so they are ordered with the acting
+launches without any synchronisation. An environment that launches kernels of its own must launch them on torch's current
+stream.
+
+Per environment the semantics are the reference OffSampler's (training/off_sampler.py:46-84): the action is clipped to the
+environment's limits, the reward is multiplied by reward_scale, a truncated step is stored as non-terminal, an environment
+that ends (terminated or truncated) restarts alone. Transitions are STEP-MAJOR like HipVecOffSampler's: sample() runs S / N
+lockstep steps (S = batch_size_per_sampler or sample_batch_size, a multiple of N) and transition t * N + i is environment i's
+step t.
+
+Noise: the N(0,1) draws behind Normal.sample() are made in the acting kernel -- Philox4x32-10, stream id 5, keyed by
+`hip_act_seed` (default act_seed_from(seed), training/hip_replay_buffer.py) and counted by `act_step`, which starts at 0,
+advances by one per lockstep step and is assignable like the buffer's `index_iteration`. Environment i's noise at step t is a
+pure function of (seed, t, i, action dimension): a run is reproducible from its seeds, and independent of N. It is NOT
+torch.randn's stream, so `strict_rng=True` is refused.
+
+The clip: the kernel clips to the policy's action limits (dsact_set_action_limits). When the environment's limits are those
+-- the usual case -- its `clipped` output is what the environment receives; otherwise the clip is made with two torch ops on
+the device.
+
+Refused (NotImplementedError / ValueError, before an environment step or an engine call is made): an unattached or CNN policy,
+strict_rng=True, noise_params, S not a multiple of N, an environment on another device than the engine. The overlapped
+trainer (hip_off_async_trainer) refuses this sampler as an unknown sampler class: held-behaviour acting is not built for it.
+
+sample() returns (DeviceSampleBatch, {sampler time}). The time is the HOST time of issuing the work. The batch's tensors are the
+sampler's own preallocated [S, .] buffers: they are valid until the next sample() call (add_batch consumes them in stream
+order before that).
+"""
+import contextlib
+import time
+
+import numpy as np
+import torch
+
+from training.hip_replay_buffer import act_seed_from
+from training.hip_sampler import SAMPLER_TIME_KEY, _container
+
+__all__ = ["HipTensorEnvSampler", "DeviceSampleBatch", "act_noise_words", "act_noise_reference"]
+
+ACT_STREAM = 5    # the acting noise's Philox stream id (include/dsact.h: 1 .. 3 the update noise, 4 the index draw)
+_M32 = 0xFFFFFFFF
+
+
+def act_noise_words(seed, step, row, d, act_dim):
+    """(the four Philox4x32-10 words, which of the four normals) behind the in-kernel N(0,1) draw of environment `row`, action
+    dimension `d` at acting step `step` -- include/dsact.h's description in Python integers (no GPU, no library call): counter
+    (row * ceil(A/4) + d // 4, step low, step high, 5), key = the seed's (low, high) words; element d % 4."""
+    step &= 0xFFFFFFFFFFFFFFFF
+    c0, c1, c2, c3 = (row * ((act_dim + 3) // 4) + d // 4) & _M32, step & _M32, step >> 32, ACT_STREAM
+    k0, k1 = seed & _M32, (seed >> 32) & _M32
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & _M32, (p0 >> 32) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return (c0, c1, c2, c3), d % 4
+
+
+def act_noise_reference(seed, step, n_rows, act_dim):
+    """float64 [n_rows, act_dim]: the normals the kernel draws for rows 0 .. n_rows - 1 at `step`, by the Box-Muller map of
+    include/dsact.h evaluated in float64 on the same words (u = ((w >> 8) + 0.5) / 2^24; z0, z1 = r(u0) (cos, sin)(2 pi u1);
+    z2, z3 = r(u2) (cos, sin)(2 pi u3); r(u) = sqrt(-2 ln u)). act_noise_words over whole arrays (uint64 lanes holding 32-bit
+    words). The kernel evaluates the map in fp32: DESIGN.md section 15 has the measured distance."""
+    per_row = (act_dim + 3) // 4
+    step &= 0xFFFFFFFFFFFFFFFF
+    m32 = np.uint64(_M32)
+    c0 = np.arange(n_rows * per_row, dtype=np.uint64) & m32
+    c1, c2, c3 = (np.full_like(c0, v) for v in (step & _M32, step >> 32, ACT_STREAM))
+    k0, k1 = seed & _M32, (seed >> 32) & _M32
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ np.uint64(k0), p1 & m32, (p0 >> s32) ^ c3 ^ np.uint64(k1), p0 & m32
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    u = [((w >> np.uint64(8)).astype(np.float64) + 0.5) / 16777216.0 for w in (c0, c1, c2, c3)]
+    ra, rb = np.sqrt(-2.0 * np.log(u[0])), np.sqrt(-2.0 * np.log(u[2]))
+    z = np.stack([ra * np.cos(2 * np.pi * u[1]), ra * np.sin(2 * np.pi * u[1]), rb * np.cos(2 * np.pi * u[3]), rb * np.sin(2 * np.pi * u[3])], axis=1)
+    return np.ascontiguousarray(z.reshape(n_rows, per_row * 4)[:, :act_dim])
+
+
+class DeviceSampleBatch:
+    """S transitions as seven device tensors -- obs[S, O], act[S, A], rew[S] (the environment's reward, NOT yet scaled),
+    obs2[S, O], terminated[S], truncated[S] (bool), logp[S] -- plus `reward_scale`. HipReplayBuffer.add_batch hands
+    `device_columns` to the ring in one call. Any other consumer may walk it like the reference's list of
+    (obs, info, act, rew, next_obs, done, logp, next_info) tuples (training/off_sampler.py:74-84): the first such use makes ONE
+    device-to-host copy of the whole batch (which waits for the stream that produced it)."""
+
+    def __init__(self, obs, act, rew, obs2, terminated, truncated, logp, reward_scale=1, stream=None):
+        self.obs, self.act, self.rew, self.obs2 = obs, act, rew, obs2
+        self.terminated, self.truncated, self.logp = terminated, truncated, logp
+        self.reward_scale = reward_scale
+        self.stream = stream          # the torch stream the tensors were produced on (None: the current one)
+        self._tuples = None
+
+    @property
+    def device_columns(self):
+        return (self.obs, self.act, self.rew, self.obs2, self.terminated, self.truncated, self.logp)
+
+    def __len__(self):
+        return int(self.rew.shape[0])
+
+    def _host(self):
+        if self._tuples is None:
+            S, O, A = len(self), self.obs.shape[1], self.act.shape[1]
+            ctx = torch.cuda.stream(self.stream) if self.stream is not None else contextlib.nullcontext()
+            with ctx:
+                flat = torch.cat([self.obs, self.obs2, self.act, self.rew[:, None], self.logp[:, None],
+                                  self.terminated[:, None].to(torch.float32), self.truncated[:, None].to(torch.float32)], dim=1)
+                h = flat.cpu().numpy()     # the one copy
+            obs, obs2, act = h[:, :O], h[:, O:2 * O], h[:, 2 * O:2 * O + A]
+            rew, logp, term, trunc = (h[:, 2 * O + A + k] for k in range(4))
+            self._tuples = [(obs[i], {}, act[i], self.reward_scale * float(rew[i]), obs2[i], bool(term[i]) and not bool(trunc[i]),
+                             logp[i], {"TimeLimit.truncated": bool(trunc[i])}) for i in range(S)]
+        return self._tuples
+
+    def __iter__(self):
+        return iter(self._host())
+
+    def __getitem__(self, i):
+        return self._host()[i]
+
+
+class HipTensorEnvSampler:
+    def __init__(self, index=0, **kwargs):
+        if kwargs.get("noise_params") is not None:
+            raise NotImplementedError("exploration noise is not part of the DSAC-T path (default None)")
+        if kwargs.get("strict_rng", False):
+            raise ValueError("hip_tensor_env_sampler with strict_rng=True: the acting noise is drawn in the kernel (Philox), not "
+                             "from torch.randn's stream; a parity run wants hip_vec_off_sampler")
+        env = kwargs.get("env")
+        if env is None:
+            from plugin import create_env
+            env = create_env(**kwargs)
+        self.env = env
+        self.n_envs = int(env.num_envs)
+        self.sample_batch_size = kwargs["batch_size_per_sampler"] if "batch_size_per_sampler" in kwargs \
+            else kwargs["sample_batch_size"]
+        if self.n_envs < 1 or self.sample_batch_size % self.n_envs:
+            raise ValueError("the sample batch size %d is not a multiple of the environment's num_envs %d"
+                             % (self.sample_batch_size, self.n_envs))
+        self.action_type = kwargs.get("action_type", "continu")
+        self.reward_scale = kwargs.get("reward_scale", 1)
+        seed = kwargs.get("hip_act_seed")
+        self.act_seed = int(seed) if seed is not None else act_seed_from(kwargs.get("seed"))
+        if not 0 < self.act_seed < (1 << 64):
+            raise ValueError("hip_act_seed must be in [1, 2^64) (0 switches the in-kernel draw off), got %r" % (seed,))
+        self.act_step = 0                 # the acting-step counter: one per lockstep step (assignable)
+        self.total_sample_number = 0
+        self._ready = None                # id of the engine the buffers / seed / clip route were set up for
+        self._started = False             # env.reset() has been called
+        # the reference's own throw-away container (off_sampler.py:19-23), built for its use of the torch generator
+        given = kwargs.get("networks")
+        self.networks = given
+        if given is None and "algorithm" in kwargs:
+            self.networks = _container(**kwargs)
+        if given is not None:
+            self._engine()                # an explicit policy is checked right away
+
+    def load_state_dict(self, state_dict):
+        self.networks.load_state_dict(state_dict)
+
+    def get_total_sample_number(self):
+        return self.total_sample_number
+
+    def _engine(self):
+        """the engine behind the ATTACHED MLP policy; every other setup is refused"""
+        pol = getattr(self.networks, "policy", None)
+        eng = getattr(pol, "_engine", None)
+        if eng is None:
+            raise NotImplementedError("hip_tensor_env_sampler needs a policy attached to a DsactEngine (the learner's networks); an "
+                                      "unattached container acts through the module forward: use hip_vec_off_sampler")
+        if getattr(eng, "conv_type", None):
+            raise NotImplementedError("hip_tensor_env_sampler serves MLP policies (dsact_act_sample_device); CNN policies: "
+                                      "hip_vec_off_sampler")
+        if self.action_type != "continu":
+            raise NotImplementedError("hip_tensor_env_sampler serves continuous actions")
+        low = torch.as_tensor(self.env.action_low)
+        if low.device != torch.device(eng.device):
+            raise ValueError("the environment lives on %s, the engine on %s: hip_tensor_env_sampler moves nothing between devices"
+                             % (low.device, eng.device))
+        return eng
+
+    def _setup(self, eng):
+        """once per engine: the [S, .] buffers, the acting seed, and whether the kernel's clip is the environment's"""
+        N, S, O, A = self.n_envs, self.sample_batch_size, eng.obs_dim, eng.act_dim
+        dev = torch.device(eng.device)
+        f = dict(dtype=torch.float32, device=dev)
+        self._obs_b, self._obs2_b = torch.zeros(S, O, **f), torch.zeros(S, O, **f)
+        self._act_b, self._clip_b = torch.zeros(S, A, **f), torch.zeros(S, A, **f)
+        self._rew_b, self._logp_b = torch.zeros(S, **f), torch.zeros(S, **f)
+        self._term_b = torch.zeros(S, dtype=torch.bool, device=dev)
+        self._trunc_b = torch.zeros(S, dtype=torch.bool, device=dev)
+        self._obs = torch.zeros(N, O, **f)
+        low = torch.as_tensor(self.env.action_low, **f)
+        high = torch.as_tensor(self.env.action_high, **f)
+        self._low, self._high = low.expand(N, A).contiguous(), high.expand(N, A).contiguous()
+        e_lo, e_hi = getattr(eng, "act_low", None), getattr(eng, "act_high", None)
+        lo_h, hi_h = self._low.cpu().numpy(), self._high.cpu().numpy()
+        self._kernel_clip = bool(e_lo is not None and e_hi is not None and (lo_h == np.asarray(e_lo)[None, :]).all()
+                                 and (hi_h == np.asarray(e_hi)[None, :]).all())
+        eng.set_act_rng(self.act_seed)
+        if not self._started:
+            self._obs.copy_(self.env.reset().reshape(N, O))
+            self._started = True
+        if dev.type == "cuda":
+            # the buffers, the environment's state and its first observation were produced on torch's current stream; from here on
+            # everything runs on the engine's. The only wait this sampler ever makes, once.
+            torch.cuda.current_stream(dev).synchronize()
+        self._ready = id(eng)
+
+    def sample(self):
+        eng = self._engine()
+        t0 = time.perf_counter()
+        if self._ready != id(eng):
+            self._setup(eng)
+        N, S = self.n_envs, self.sample_batch_size
+        env = self.env
+        obs_b, obs2_b, act_b, clip_b = self._obs_b, self._obs2_b, self._act_b, self._clip_b
+        rew_b, logp_b, term_b, trunc_b = self._rew_b, self._logp_b, self._term_b, self._trunc_b
+        stream = getattr(eng, "torch_stream", None) if torch.device(eng.device).type == "cuda" else None
+        with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()), torch.no_grad():
+            obs_b[0:N].copy_(self._obs)
+            for t in range(S // N):
+                r0, r1 = t * N, (t + 1) * N
+                eng.act_sample_device(obs_b[r0:r1], None, self.act_step, act_b[r0:r1], clip_b[r0:r1], logp_b[r0:r1])
+                self.act_step += 1
+                if not self._kernel_clip:
+                    torch.minimum(torch.maximum(act_b[r0:r1], self._low), self._high, out=clip_b[r0:r1])
+                obs2, rew, term, trunc = env.step(clip_b[r0:r1])
+                obs2_b[r0:r1].copy_(obs2.reshape(N, -1))
+                rew_b[r0:r1].copy_(rew)
+                term_b[r0:r1].copy_(term)
+                trunc_b[r0:r1].copy_(trunc)
+                # the next step's observations: this step's, with every environment that ended restarted on its own
+                nxt = env.reset(term_b[r0:r1] | trunc_b[r0:r1])
+                (obs_b[r1:r1 + N] if r1 < S else self._obs).copy_(nxt.reshape(N, -1))
+        self.total_sample_number += S
+        batch = DeviceSampleBatch(obs_b, act_b, rew_b, obs2_b, term_b, trunc_b, logp_b, self.reward_scale, stream=stream)
+        return batch, {SAMPLER_TIME_KEY: (time.perf_counter() - t0) * 1000}

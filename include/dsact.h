@@ -454,6 +454,50 @@ int dsact_behaviour_hold(dsact_handle* h);
 int dsact_behaviour_release(dsact_handle* h);
 int dsact_stream_idle(dsact_handle* h);
 
+/* ---- Device-resident sampling (training/hip_tensor_sampler.py) ----------------------------------------
+ * For batched simulators whose observations, rewards and done flags already live on the GPU: one environment step of N
+ * environments costs launches only -- nothing is copied to or from the host and nothing waits for the stream.
+ *   dsact_set_act_rng(h, seed)     the acting seed: Philox key of the in-kernel N(0,1) draw of dsact_act_sample_device; 0
+ *                                  switches the draw off (the default). Replaces the torch.randn behind Normal.sample() of
+ *                                  training/off_sampler.py:52-54 (utils/act_distribution_cls.py:32-42) -- standard normals
+ *                                  like the reference's, not the reference's stream.
+ *     generator: philox4x32-10, counter (row * ceil(A/4) + d/4, step low, step high, 5), key = the seed's (low, high) words;
+ *                the four words become four normals by the Box-Muller map of the update noise (u = ((w >> 8) + 0.5) / 2^24,
+ *                z0 = r(u0) cos(2 pi u1), z1 = r(u0) sin(2 pi u1), z2 = r(u2) cos(2 pi u3), z3 = r(u2) sin(2 pi u3), r(u) =
+ *                sqrt(-2 ln u)); action dimension d takes element d % 4. Stream id 5: the update noise uses 1 .. 3 and the index
+ *                draw 4, so no seed ever shares a counter block with them. Environment row i's noise at step t is a pure
+ *                function of (seed, t, i, d): independent of n and of the chunking inside the call.
+ *   dsact_act_sample_device        training/off_sampler.py:46-65 for n environments: policy(obs) on the live weights +
+ *                                  TanhGaussDistribution.sample() / GaussDistribution.sample() (utils/act_distribution_cls.py)
+ *                                  + the clip to the action limits (off_sampler.py:62-65), with every operand on the device:
+ *                                  obs[n*O] in, action[n*A] (the distribution's sample: what the replay ring stores), logp[n]
+ *                                  and clipped[n*A] = min(max(action, low), high) with the limits of dsact_set_action_limits
+ *                                  (what the environment receives) out. eps[n*A]: the caller's standard-normal draws, or NULL:
+ *                                  drawn in the kernel for acting step `step` (DSACT_E_STATE without a seed). With the same
+ *                                  eps a row's action and logp are bit for bit dsact_act_sample_batch's. Enqueued on the handle's
+ *                                  stream behind every enqueued update (the live weights, like dsact_act_sample_batch's GPU
+ *                                  route) -- the inputs must be ready in that stream's order. ASYNCHRONOUS: no stream
+ *                                  synchronisation, no host copy. All pointers must be device memory of the handle's GPU
+ *                                  (DSACT_E_INVALID otherwise). Any n >= 1 (chunked inside the call); MLP policies with
+ *                                  act_dim <= 32 (DSACT_E_INVALID for CNN policies).
+ *   dsact_buffer_add_device        n x ReplayBuffer.store (training/replay_buffer.py:58-79) fed from device arrays, with the
+ *                                  sampler's per-step bookkeeping (training/off_sampler.py:66-73) folded in: transition i goes to
+ *                                  ring row (ptr + i) % capacity; rew is stored as rew * reward_scale (ONE fp32 product with
+ *                                  the scale rounded to fp32: equal to the reference's double product whenever the scale is
+ *                                  exactly representable in fp32); done as terminated && !truncated (a time-out is stored
+ *                                  as non-terminal); terminated / truncated: one byte per transition, non-zero = set. ptr =
+ *                                  (ptr + n) % capacity, size = min(size + n, capacity) (replay_buffer.py:78-79), visible to
+ *                                  dsact_buffer_size / dsact_buffer_ptr at once like dsact_buffer_add's. n <= capacity.
+ *                                  ASYNCHRONOUS on the handle's stream. fp32 MLP rings only (DSACT_E_INVALID on coded rings and
+ *                                  CNN handles); device pointers of the handle's GPU only.
+ * dsact_debug_get: "act_dev_calls" (chunks launched by dsact_act_sample_device), "ring_commit_rows" (transitions written by
+ * dsact_buffer_add_device), "act_dev_syncs" (stream synchronisations made inside the two: 0). */
+int dsact_set_act_rng(dsact_handle* h, uint64_t seed);
+int dsact_act_sample_device(dsact_handle* h, const float* obs_dev, int32_t n, const float* eps_dev, int64_t step,
+                            float* action_dev, float* clipped_dev, float* logp_dev);
+int dsact_buffer_add_device(dsact_handle* h, int64_t n, const float* obs, const float* act, const float* rew, const float* obs2,
+                            const uint8_t* terminated, const uint8_t* truncated, const float* logp, double reward_scale);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,152 @@
+#!/usr/bin/env python3
+"""The device-resident sampler (sampler_name="hip_tensor_env_sampler") against HipVecOffSampler's GPU route
+on the SAME dynamics: tests/envs/synth_tensor_humanoid.py (obs 376, act 17) as one batched environment on the GPU for the new
+route, and as N per-environment objects (environment i alone on the CPU device, behind the gym-0.23 face HipVecOffSampler
+steps) for the baseline. Policy and update are the bench's Humanoid configuration (3 x 256 nets, batch 256). Needs the GPU.
+
+  python scripts/tensor_sampler_bench.py [--out profiles] [--pairs 3] [--window 0.6]
+      per N in 64, 256, 1024, 4096 (each in a fresh child process) and per metric
+        sampler: environment steps / s of sample() alone (one lockstep step per call, the stream drained at the window's end)
+        trainer: iterations / s of HipOffSerialTrainer at sample_interval K = 8, hip_device_indices=True
+      one warm-up window per leg (which also sizes the windows to about --window seconds), then `pairs` alternating pairs of
+      windows. Medians, per-pair ratios (tensor / vec) and each leg's spread over its own windows are recorded.
+Writes DIR/tensor_sampler_bench.json and prints it. The library must have been built (__graft_entry__.build())."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "dsac-v2_amd"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "envs")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from helpers import hip_kwargs  # noqa: E402
+from synth_humanoid_data import _Box  # noqa: E402
+from synth_tensor_humanoid import ACT_LIMIT, A, O, SynthTensorHumanoid  # noqa: E402
+
+NS = [64, 256, 1024, 4096]
+HID, B, K, SEED = (256, 256, 256), 256, 8, 3
+
+
+class OneEnv:
+    """environment i of the batched fixture on its own, with the interface HipVecOffSampler steps"""
+
+    pool = None
+
+    def __init__(self, i):
+        self.env = SynthTensorHumanoid(1, seed=SEED, env_offset=i, pool=OneEnv.pool)
+        OneEnv.pool = self.env.pool     # one pool for the N objects
+        self.action_space = _Box(np.full(A, -ACT_LIMIT), np.full(A, ACT_LIMIT))
+        self.started = False
+        self.all = torch.ones(1, dtype=torch.bool)
+
+    def reset(self):
+        obs = self.env.reset(self.all) if self.started else self.env.reset()
+        self.started = True
+        return obs[0].numpy(), {}
+
+    def step(self, a):
+        o2, r, te, tr = self.env.step(torch.from_numpy(np.asarray(a, np.float32).reshape(1, A)))
+        return o2[0].numpy(), float(r), bool(te), {"TimeLimit.truncated": bool(tr)}
+
+
+def _leg(leg, N, trainer):
+    import plugin
+
+    kw = hip_kwargs(O, A, HID, B, seed=SEED, sample_batch_size=N, buffer_max_size=max(100_000, 4 * N), buffer_warm_size=max(B, N),
+                    sample_interval=K, max_iteration=0, log_save_interval=10 ** 9, apprfunc_save_interval=10 ** 9, eval_interval=10 ** 9,
+                    save_folder=None, ini_network_dir=None, strict_rng=False, hip_device_indices=True, hip_pad_widths=True)
+    torch.manual_seed(SEED)
+    np.random.seed(SEED)
+    alg = plugin.create_alg(**kw)
+    if leg == "tensor":
+        smp = plugin.create_sampler(sampler_name="hip_tensor_env_sampler", env=SynthTensorHumanoid(N, device="cuda", seed=SEED), **kw)
+    else:
+        smp = plugin.create_sampler(sampler_name="hip_vec_off_sampler", envs=[OneEnv(i) for i in range(N)], hip_vec_act="gpu", **kw)
+    smp.networks = alg.networks
+    tr = None
+    if trainer:
+        buf = plugin.create_buffer(**kw)
+        tr = plugin.create_trainer(alg, smp, buf, None, **kw)
+    if leg == "vec":
+        assert smp.route() == "gpu", smp.route()
+    return alg, smp, tr
+
+
+def _window(alg, smp, tr, count):
+    """`count` sample() calls, or `count` trainer iterations; seconds, the stream drained at both ends"""
+    alg.engine.sync()
+    t0 = time.perf_counter()
+    if tr is None:
+        for _ in range(count):
+            smp.sample()
+    else:
+        tr.max_iteration = tr.iteration + count
+        tr.train()
+    alg.engine.sync()
+    return time.perf_counter() - t0
+
+
+def run(N, metric, pairs, window):
+    trainer = metric == "trainer"
+    unit = K if trainer else 1
+    legs = {leg: _leg(leg, N, trainer) for leg in ("tensor", "vec")}
+    counts = {}
+    for leg, h in legs.items():                      # warm-up; its rate sizes the windows
+        c = 2 * unit
+        dt = _window(*h, c)
+        dt = _window(*h, c)
+        counts[leg] = max(2 * unit, int(round(window / (dt / c) / unit)) * unit)
+    rows = {leg: [] for leg in legs}
+    for _ in range(pairs):
+        for leg, h in legs.items():
+            dt = _window(*h, counts[leg])
+            rows[leg].append(counts[leg] * (1 if trainer else N) / dt)
+    ratios = [t / v for t, v in zip(rows["tensor"], rows["vec"])]
+    out = {"N": N, "metric": "iterations_per_s" if trainer else "env_steps_per_s", "window_counts": counts, "rows": rows,
+           "median": {k: float(np.median(v)) for k, v in rows.items()},
+           "tensor_over_vec": ratios, "tensor_over_vec_median": float(np.median(ratios)),
+           "spread": {k: (max(v) - min(v)) / float(np.median(v)) for k, v in rows.items()},
+           "act_dev_syncs": legs["tensor"][0].engine.debug_get("act_dev_syncs"),
+           "handoff_failures": {k: h[0].engine.debug_get("handoff_failures") for k, h in legs.items()}}
+    for h in legs.values():
+        h[0].engine.close()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
+    ap.add_argument("--pairs", type=int, default=3)
+    ap.add_argument("--window", type=float, default=0.6)
+    ap.add_argument("--only", default="", help="N:metric -- one configuration, in this process")
+    a = ap.parse_args()
+    if a.only:
+        n, metric = a.only.split(":")
+        print("RESULT " + json.dumps(run(int(n), metric, a.pairs, a.window)), flush=True)
+        return
+    res = {"pairs": a.pairs, "window_s": a.window, "policy": "376-256-256-256-34", "batch": B, "K": K, "configs": []}
+    for n in NS:
+        for metric in ("sampler", "trainer"):
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--only", "%d:%s" % (n, metric), "--pairs", str(a.pairs),
+                                "--window", str(a.window)], capture_output=True, text=True, timeout=420)
+            line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+            if p.returncode != 0 or not line:
+                sys.stderr.write(p.stdout + p.stderr)
+                raise SystemExit("configuration %d:%s failed (exit status %d)" % (n, metric, p.returncode))
+            r = json.loads(line[-1][len("RESULT "):])
+            res["configs"].append(r)
+            print(json.dumps(r), flush=True)
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "tensor_sampler_bench.json"), "w") as f:
+        json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
