@@ -35,6 +35,12 @@
 //     (seed, t, i, d) -- independent of N and of the chunking at kActBatchCap;
 //   * action[n][A], logp[n] and clipped[n][A] = min(max(action, lo), hi) (the value the environment receives,
 //     off_sampler.py:62-65) are written to DEVICE memory the caller owns; nothing is mapped to the host.
+//
+// The device-resident evaluator's acting (training/hip_tensor_evaluator.py, dsact_act_mode_device; training/evaluator.py:50-72
+// over N environments of a batched simulator) is the mode form with kDev = true -- k_act_batch_out<true, true>: the K loop, sums,
+// output activation and act_mode of <true, false> (a row's action is bitwise dsact_act_mode_batch's GPU route), launched on obs
+// the hidden layers read IN PLACE from the caller's device array (no staging copy) with action[n][A] in the caller's DEVICE
+// memory. No eps is read, no logp, clipped, seed, step or row0: act_mode already clamps the plain Gaussian to the limits.
 #pragma once
 #include "dsact_kernels.h"
 
@@ -134,7 +140,7 @@ __global__ void __launch_bounds__(256) k_act_batch_hidden(ActBatchHidden a) {
 
 // 8 rows x 64 outputs (mean | raw log-std, 2A <= 64) per workgroup; thread (tr, tf) = (tid / 32, tid % 32) owns row tr and
 // outputs tf, tf + 32. grid: x = row tiles. kMode: the mode instead of the sample (eps and logp are not touched). kDev: the
-// device-resident sampling form (see the header comment)
+// device-resident form (see the header comment; with kMode it is the mode epilogue on the caller's device arrays)
 template <bool kMode, bool kDev>
 __global__ void __launch_bounds__(256) k_act_batch_out(ActBatchOut a) {
   constexpr int KC = 64;   // (the 64-row weight tile at 128 columns runs out of scalar registers)
@@ -229,6 +235,7 @@ __global__ void __launch_bounds__(256) k_act_batch_out(ActBatchOut a) {
 template __global__ void k_act_batch_out<false, false>(ActBatchOut);
 template __global__ void k_act_batch_out<true, false>(ActBatchOut);
 template __global__ void k_act_batch_out<false, true>(ActBatchOut);
+template __global__ void k_act_batch_out<true, true>(ActBatchOut);
 #else
 __global__ void k_act_batch_hidden(ActBatchHidden a);
 template <bool kMode, bool kDev>
@@ -236,6 +243,7 @@ __global__ void k_act_batch_out(ActBatchOut a);
 extern template __global__ void k_act_batch_out<false, false>(ActBatchOut);
 extern template __global__ void k_act_batch_out<true, false>(ActBatchOut);
 extern template __global__ void k_act_batch_out<false, true>(ActBatchOut);
+extern template __global__ void k_act_batch_out<true, true>(ActBatchOut);
 #endif
 
 }  // namespace dsact

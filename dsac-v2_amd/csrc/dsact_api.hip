@@ -313,6 +313,15 @@ struct dsact_handle {
   unsigned long long act_dev_calls = 0;  // dsact_act_sample_device chunks launched
   unsigned long long ring_commit_rows = 0;   // transitions written by dsact_buffer_add_device
   unsigned long long act_dev_syncs = 0;  // stream synchronisations made inside those two entry points (stays 0)
+  // device-resident evaluation (dsact_act_mode_device / dsact_eval_*): the episode bookkeeping's state
+  int* ev_ep = nullptr; double* ev_acc = nullptr; int* ev_len = nullptr;   // [ev_cap_n]
+  double* ev_returns = nullptr; int* ev_lengths = nullptr;                 // [ev_cap_e]
+  int* ev_remaining = nullptr;            // one int32 on the device
+  int* ev_remaining_host = nullptr;       // its pinned landing place (dsact_eval_poll)
+  int ev_cap_n = 0, ev_cap_e = 0;
+  int ev_n = 0, ev_e = 0;                 // the running evaluation's N and E (0: no dsact_eval_begin yet)
+  unsigned long long act_mode_dev_calls = 0;   // dsact_act_mode_device chunks launched
+  unsigned long long eval_commit_calls = 0, eval_polls = 0;
   int mode_host_rows = kModeHostRows;   // dsact_act_mode_batch's host / GPU crossover (debug switch "mode_host_rows": measurements)
   unsigned long long act_host_calls = 0, act_copies = 0;
   // behaviour policy (dsact_behaviour_hold): a device copy of the policy net taken on the handle's stream
@@ -3572,6 +3581,9 @@ int dsact_destroy(dsact_handle* h) {
   if (h->ab_stage) hipHostFree(h->ab_stage);
   if (h->ab_out_host) hipHostFree(h->ab_out_host);
   if (h->ab_in) hipFree(h->ab_in);
+  for (void* p : {(void*)h->ev_ep, (void*)h->ev_acc, (void*)h->ev_len, (void*)h->ev_returns, (void*)h->ev_lengths, (void*)h->ev_remaining})
+    if (p) hipFree(p);
+  if (h->ev_remaining_host) hipHostFree(h->ev_remaining_host);
   for (int i = 0; i < 2; ++i) if (h->ab_h[i]) hipFree(h->ab_h[i]);
   if (h->pol_host) hipHostFree(h->pol_host);
   if (h->pol_ev) hipEventDestroy(h->pol_ev);
@@ -5277,6 +5289,9 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "act_dev_calls")) *value = (double)h->act_dev_calls;       // dsact_act_sample_device chunks launched
   else if (!strcmp(name, "ring_commit_rows")) *value = (double)h->ring_commit_rows; // transitions written by dsact_buffer_add_device
   else if (!strcmp(name, "act_dev_syncs")) *value = (double)h->act_dev_syncs;       // stream drains inside those two (0)
+  else if (!strcmp(name, "act_mode_dev_calls")) *value = (double)h->act_mode_dev_calls;   // dsact_act_mode_device chunks launched
+  else if (!strcmp(name, "eval_commit_calls")) *value = (double)h->eval_commit_calls;     // dsact_eval_commit launches
+  else if (!strcmp(name, "eval_polls")) *value = (double)h->eval_polls;                   // dsact_eval_poll waits
   else if (!strcmp(name, "act_fast")) *value = act_fast_ok(h) ? 1.0 : 0.0;     // dsact_act_sample / the one-launch acting forward serve this handle
   else if (!strcmp(name, "graph_cache")) *value = (double)h->graph_cache.size();   // inactive captured graphs kept by dsact_run_group
   else if (!strcmp(name, "graph_noise_table")) *value = h->graph_noise_table ? 1.0 : 0.0;
@@ -5600,6 +5615,136 @@ int dsact_act_sample_device(dsact_handle* h, const float* obs_dev, int32_t n, co
     h->act_dev_calls++;
   }
   return check_handoff_counted(h);
+}
+
+// ---- device-resident evaluation --------------------------------------------------------------------
+// training/evaluator.py:50-72 for n environments whose observations live on the device: dist.mode() of policy(obs) per row,
+// the launches of dsact_act_sample_device with the mode epilogue
+int dsact_act_mode_device(dsact_handle* h, const float* obs_dev, int32_t n, float* action_dev) {
+  if (!h || !obs_dev || !action_dev || n < 1) return DSACT_E_INVALID;
+  if (!h->online) return fail(h, DSACT_E_STATE, "arenas not bound");
+  if (!h->limits_set) return fail(h, DSACT_E_STATE, "action limits not set (dsact_set_action_limits)");
+  if (h->cnn) return fail(h, DSACT_E_INVALID, "dsact_act_mode_device serves MLP policies (CNN: dsact_act_mode_batch)");
+  if (h->A > 32) return fail(h, DSACT_E_INVALID, "dsact_act_mode_device serves act_dim <= 32");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!on_handle_gpu(h, obs_dev) || !on_handle_gpu(h, action_dev))
+    return fail(h, DSACT_E_INVALID, "dsact_act_mode_device takes device pointers on the handle's GPU (host rows: dsact_act_mode_batch)");
+  TRY(check_handoff_counted(h));
+  TRY(alloc_act_batch(h));   // (the hidden layers' two activation buffers; the first call allocates)
+  const int O = h->O, A = h->A, R = kActBatchCap;
+  const float* base = net_params(h, N_POL);   // the live weights, also under a behaviour hold (like dsact_act_mode_batch)
+  const NetDesc& d = h->pd;
+  for (int s = 0; s < n; s += R) {
+    const int m = n - s < R ? n - s : R;
+    const float* X = obs_dev + (size_t)s * O;   // read in place: no staging copy
+    int ldx = O;
+    for (int l = 0; l < h->Lp; ++l) {
+      ActBatchHidden a;
+      a.X = X; a.ldx = ldx; a.W = base + d.w_off[l]; a.b = base + d.b_off[l];
+      a.K = d.in[l]; a.N = d.out[l]; a.half = 0;
+      if (d.nblk == 2 && l > 0) { a.K = d.in[l] / 2; a.half = d.out[l] / 2; }   // two (H x Hprev) blocks
+      a.Y = h->ab_h[l & 1]; a.ldy = d.out[l]; a.n = m; a.act = h->cfg.policy_act;
+      const int seg_n = a.half > 0 ? a.half : a.N;
+      const dim3 grid((unsigned)((a.half > 0 ? 2 : 1) * ((seg_n + 31) / 32)), (unsigned)((m + 31) / 32));
+      TRY(launch(h, "act_batch_hidden", k_act_batch_hidden, grid, dim3(256), 0, a));
+      X = a.Y; ldx = a.ldy;
+    }
+    ActBatchOut o;
+    memset(&o, 0, sizeof(o));
+    o.X = X; o.ldx = ldx; o.W = base + d.w_off[h->Lp]; o.b = base + d.b_off[h->Lp];
+    o.K = d.in[h->Lp]; o.A = A; o.n = m;
+    o.out_act = h->cfg.policy_out_act; o.out_n = h->cfg.policy_std_param ? A : 2 * A;
+    o.scale = h->act_scale; o.center = h->act_center; o.lo_ls = h->cfg.min_log_std; o.hi_ls = h->cfg.max_log_std;
+    o.lo = h->act_lo; o.hi = h->act_hi;
+    o.action = action_dev + (size_t)s * A;
+    TRY(launch(h, "act_batch_mode_dev", k_act_batch_out<true, true>, dim3((unsigned)((m + 7) / 8)), dim3(256), 0, o));
+    h->act_mode_dev_calls++;
+  }
+  return check_handoff_counted(h);
+}
+
+static EvalCommitArgs eval_args(const dsact_handle* h) {
+  EvalCommitArgs a;
+  memset(&a, 0, sizeof(a));
+  a.ep = h->ev_ep; a.acc = h->ev_acc; a.len = h->ev_len; a.returns = h->ev_returns; a.lengths = h->ev_lengths;
+  a.remaining = h->ev_remaining; a.N = h->ev_n; a.E = h->ev_e;
+  return a;
+}
+
+// the state of training/evaluator.py:34-84's loops (the episode counter, reward_list, episode_return) for n_envs rows
+int dsact_eval_begin(dsact_handle* h, int32_t n_envs, int32_t n_episodes) {
+  if (!h) return DSACT_E_INVALID;
+  if (n_envs < 1 || n_episodes < 1) return fail(h, DSACT_E_INVALID, "dsact_eval_begin: n_envs = %d and n_episodes = %d must be >= 1", (int)n_envs, (int)n_episodes);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!h->ev_remaining) {
+    HIPCHK(h, hipMalloc(&h->ev_remaining, 64));
+    HIPCHK(h, hipHostMalloc((void**)&h->ev_remaining_host, 64, hipHostMallocDefault));
+  }
+  if (n_envs > h->ev_cap_n || n_episodes > h->ev_cap_e) {
+    // the running evaluation's launches (if any) read the old arrays: they finish before the arrays go
+    h->ev_n = h->ev_e = 0;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  if (n_envs > h->ev_cap_n) {
+    for (void* p : {(void*)h->ev_ep, (void*)h->ev_acc, (void*)h->ev_len}) if (p) HIPCHK(h, hipFree(p));
+    h->ev_ep = nullptr; h->ev_acc = nullptr; h->ev_len = nullptr; h->ev_cap_n = 0;
+    HIPCHK(h, hipMalloc(&h->ev_ep, (size_t)n_envs * sizeof(int)));
+    HIPCHK(h, hipMalloc(&h->ev_acc, (size_t)n_envs * sizeof(double)));
+    HIPCHK(h, hipMalloc(&h->ev_len, (size_t)n_envs * sizeof(int)));
+    h->ev_cap_n = n_envs;
+  }
+  if (n_episodes > h->ev_cap_e) {
+    for (void* p : {(void*)h->ev_returns, (void*)h->ev_lengths}) if (p) HIPCHK(h, hipFree(p));
+    h->ev_returns = nullptr; h->ev_lengths = nullptr; h->ev_cap_e = 0;
+    HIPCHK(h, hipMalloc(&h->ev_returns, (size_t)n_episodes * sizeof(double)));
+    HIPCHK(h, hipMalloc(&h->ev_lengths, (size_t)n_episodes * sizeof(int)));
+    h->ev_cap_e = n_episodes;
+  }
+  h->ev_n = n_envs; h->ev_e = n_episodes;
+  *h->ev_remaining_host = n_episodes;
+  const int m = n_envs > n_episodes ? n_envs : n_episodes;
+  return launch(h, "eval_init", k_eval_init, dim3((unsigned)((m + kThreads - 1) / kThreads)), dim3(kThreads), 0, eval_args(h));
+}
+
+int dsact_eval_commit(dsact_handle* h, const float* reward_dev, const uint8_t* terminated_dev, const uint8_t* truncated_dev,
+                      uint8_t* ended_dev) {
+  if (!h || !reward_dev || !terminated_dev || !truncated_dev || !ended_dev) return DSACT_E_INVALID;
+  if (h->ev_n < 1) return fail(h, DSACT_E_STATE, "dsact_eval_commit before dsact_eval_begin");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!on_handle_gpu(h, reward_dev) || !on_handle_gpu(h, terminated_dev) || !on_handle_gpu(h, truncated_dev) || !on_handle_gpu(h, ended_dev))
+    return fail(h, DSACT_E_INVALID, "dsact_eval_commit takes device pointers on the handle's GPU");
+  TRY(check_handoff_counted(h));
+  EvalCommitArgs a = eval_args(h);
+  a.reward = reward_dev; a.term = terminated_dev; a.trunc = truncated_dev; a.ended = ended_dev;
+  TRY(launch(h, "eval_commit", k_eval_commit, dim3((unsigned)((h->ev_n + kThreads - 1) / kThreads)), dim3(kThreads), 0, a));
+  h->eval_commit_calls++;
+  return DSACT_OK;
+}
+
+// the one wait of the evaluation loop: the counter behind everything enqueued so far
+int dsact_eval_poll(dsact_handle* h, int32_t* remaining) {
+  if (!h || !remaining) return DSACT_E_INVALID;
+  if (h->ev_n < 1) return fail(h, DSACT_E_STATE, "dsact_eval_poll before dsact_eval_begin");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpyAsync(h->ev_remaining_host, h->ev_remaining, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->eval_polls++;
+  *remaining = *h->ev_remaining_host;
+  return check_handoff(h);
+}
+
+int dsact_eval_read(dsact_handle* h, double* returns, int32_t* lengths, int32_t n_episodes) {
+  if (!h || !returns || !lengths) return DSACT_E_INVALID;
+  if (h->ev_n < 1) return fail(h, DSACT_E_STATE, "dsact_eval_read before dsact_eval_begin");
+  if (n_episodes != h->ev_e) return fail(h, DSACT_E_INVALID, "dsact_eval_read: n_episodes = %d, the evaluation has %d", (int)n_episodes, h->ev_e);
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpyAsync(h->ev_remaining_host, h->ev_remaining, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (*h->ev_remaining_host != 0)
+    return fail(h, DSACT_E_STATE, "dsact_eval_read: %d of %d episodes have not ended", *h->ev_remaining_host, h->ev_e);
+  HIPCHK(h, hipMemcpy(returns, h->ev_returns, (size_t)n_episodes * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(lengths, h->ev_lengths, (size_t)n_episodes * sizeof(int), hipMemcpyDeviceToHost));
+  return check_handoff(h);
 }
 
 // ---- behaviour policy ----------------------------------------------------------------------------

@@ -690,6 +690,51 @@ __global__ void __launch_bounds__(kThreads) k_ring_commit(RingCommitArgs a) {
 }
 #endif
 
+// k_eval_commit: the episode bookkeeping of the device-resident evaluator (training/hip_tensor_evaluator.py, dsact_eval_commit)
+// -- what Evaluator.run_an_episode / run_n_episodes keep in Python lists (training/evaluator.py:34-84: reward_list.append,
+// sum(reward_list), the episode counter) for N environments that step in lockstep, one launch per lockstep step, one thread per
+// environment row. State (owned by the handle, initialised by dsact_eval_begin): ep[i] the episode row i is playing (-1: none
+// left), acc[i] / len[i] its running return and length, returns[E] / lengths[E] the finished episodes, `remaining` the number
+// of episodes not finished yet. Episode e runs on row e % N and a row plays its episodes in index order (HipVecEvaluator's
+// rule): the next episode of a row is e + N.
+//   * the return is the fp64 sum of the fp32 rewards in step order (one thread owns a row: no reduction order to choose);
+//   * ended[i] = terminated | truncated for EVERY row -- the mask of env.reset(mask): a row without an episode is restarted as
+//     well, so the simulator is never stepped past a terminal state;
+//   * each row writes its own slots (episodes of different rows are different indices); only `remaining` is shared, by atomicAdd.
+// Plain C++, vector loads / stores and one vector atomic; no LDS.
+struct EvalCommitArgs {
+  const float* reward; const unsigned char* term; const unsigned char* trunc; unsigned char* ended;
+  int* ep; double* acc; int* len; double* returns; int* lengths; int* remaining;
+  int N, E;
+};
+#ifndef DSACT_FAMILY_UNIT   // plain kernel: compiled in dsact_api.hip only (dsact_tu.h)
+__global__ void __launch_bounds__(kThreads) k_eval_commit(EvalCommitArgs a) {
+  const int i = (int)blockIdx.x * kThreads + (int)threadIdx.x;
+  if (i >= a.N) return;
+  const bool end = (a.term[i] | a.trunc[i]) != 0;
+  a.ended[i] = end ? 1 : 0;
+  const int e = a.ep[i];
+  if (e < 0) return;
+  const double acc = a.acc[i] + (double)a.reward[i];
+  const int len = a.len[i] + 1;
+  if (end) {
+    a.returns[e] = acc; a.lengths[e] = len;
+    a.acc[i] = 0.0; a.len[i] = 0;
+    a.ep[i] = (long long)e + a.N < a.E ? e + a.N : -1;
+    atomicAdd(a.remaining, -1);
+  } else {
+    a.acc[i] = acc; a.len[i] = len;
+  }
+}
+// dsact_eval_begin's initialisation in stream order: ep[i] = i < E ? i : -1, zeros elsewhere, remaining = E
+__global__ void __launch_bounds__(kThreads) k_eval_init(EvalCommitArgs a) {
+  const int i = (int)blockIdx.x * kThreads + (int)threadIdx.x;
+  if (i < a.N) { a.ep[i] = i < a.E ? i : -1; a.acc[i] = 0.0; a.len[i] = 0; }
+  if (i < a.E) { a.returns[i] = 0.0; a.lengths[i] = 0; }
+  if (i == 0) *a.remaining = a.E;
+}
+#endif
+
 // ---------------------------------------------------------------------------------------------
 // k_tiles: C[m][n] (+epilogue) = sum_k P(m,k) * Q(n,k) on 32x32 tiles, BK = 64
 //   operand storage: KC  element (row,k) at base[row*ld + k]   (k contiguous)

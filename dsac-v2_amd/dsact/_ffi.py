@@ -127,6 +127,11 @@ SYMBOLS = [
     ("dsact_set_act_rng", C.c_int, [_P, C.c_uint64]),
     ("dsact_act_sample_device", C.c_int, [_P, _P, C.c_int32, _P, C.c_int64, _P, _P, _P]),
     ("dsact_buffer_add_device", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_double]),
+    ("dsact_act_mode_device", C.c_int, [_P, _P, C.c_int32, _P]),
+    ("dsact_eval_begin", C.c_int, [_P, C.c_int32, C.c_int32]),
+    ("dsact_eval_commit", C.c_int, [_P, _P, _P, _P, _P]),
+    ("dsact_eval_poll", C.c_int, [_P, _P]),
+    ("dsact_eval_read", C.c_int, [_P, _P, _P, C.c_int32]),
 ]
 
 _lib = None

@@ -679,6 +679,54 @@ class DsactEngine:
         self._chk(self._lib.dsact_buffer_add_device(self._h, n, *ptrs, float(reward_scale)))
         self.rows_added += n
 
+    # ---- device-resident evaluation: launches only, one wait in eval_poll ------------------------------
+    def act_mode_device(self, obs, action):
+        """dsact_act_mode_device: the action distribution's mode() of policy(obs[n, O]) on the live weights, written into the
+        caller's device tensor action[n, A] (bit for bit act_mode_batch's GPU route). float32 contiguous tensors on this engine's
+        GPU. Asynchronous on the engine's stream: issue the torch work that produces obs / consumes action under
+        `torch.cuda.stream(engine.torch_stream)`."""
+        f32 = (self.torch.float32,)
+        n = int(obs.shape[0]) if hasattr(obs, "shape") and len(obs.shape) else 0
+        po, pa = self._dev(obs, (n, self.obs_dim), f32, "obs"), self._dev(action, (n, self.act_dim), f32, "action")
+        rc = self._lib.dsact_act_mode_device(self._h, po, n, pa)
+        if rc != 0:
+            self._chk(rc)
+
+    def eval_begin(self, n_envs: int, n_episodes: int):
+        """dsact_eval_begin: the episode bookkeeping for n_envs lockstep rows and n_episodes episodes, initialised in stream
+        order (row i plays episode i, then i + n_envs, ...)"""
+        self._chk(self._lib.dsact_eval_begin(self._h, int(n_envs), int(n_episodes)))
+        self._eval_n = int(n_envs)
+
+    def eval_commit(self, reward, terminated, truncated, ended):
+        """dsact_eval_commit: one lockstep step of the bookkeeping. reward[N] float32, terminated / truncated [N] bool (or uint8)
+        in; ended[N] bool (or uint8) out = terminated | truncated, the mask for env.reset. Asynchronous on the engine's stream."""
+        torch = self.torch
+        f32, flag = (torch.float32,), (torch.bool, torch.uint8)
+        n = getattr(self, "_eval_n", None)
+        if n is None:
+            n = int(reward.shape[0]) if hasattr(reward, "shape") and len(reward.shape) else 0   # (the library refuses: E_STATE)
+        ptrs = [self._dev(reward, (n,), f32, "reward"), self._dev(terminated, (n,), flag, "terminated"),
+                self._dev(truncated, (n,), flag, "truncated"), self._dev(ended, (n,), flag, "ended")]
+        rc = self._lib.dsact_eval_commit(self._h, *ptrs)
+        if rc != 0:
+            self._chk(rc)
+
+    def eval_poll(self) -> int:
+        """dsact_eval_poll: the number of episodes that have not ended, behind everything enqueued so far. WAITS for the
+        engine's stream: the one wait of an evaluation loop."""
+        v = C.c_int32()
+        self._chk(self._lib.dsact_eval_poll(self._h, C.byref(v)))
+        return int(v.value)
+
+    def eval_read(self, n_episodes: int):
+        """dsact_eval_read: (returns float64[E], lengths int32[E]) in episode-index order, once every episode has ended
+        (DsactError E_STATE before that)"""
+        E = int(n_episodes)
+        returns, lengths = np.empty(max(E, 0), np.float64), np.empty(max(E, 0), np.int32)
+        self._chk(self._lib.dsact_eval_read(self._h, returns.ctypes.data_as(C.c_void_p), lengths.ctypes.data_as(C.c_void_p), E))
+        return returns, lengths
+
     def behaviour_hold(self):
         """dsact_behaviour_hold: from now on act_sample / act_sample_batch act with a copy of the policy taken on the engine's
         stream behind everything enqueued so far -- without waiting for anything enqueued later (act_mode_batch and

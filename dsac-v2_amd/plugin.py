@@ -11,7 +11,9 @@ training/trainer.py:155-158): the drop-in surface of this repository.
                                                             training.hip_tensor_sampler.HipTensorEnvSampler
     create_evaluator(**kw)                               -> training.hip_trainer.HipEvaluator, or with
                                                             hip_eval_env_num=N >= 2
-                                                            training.hip_vec_evaluator.HipVecEvaluator
+                                                            training.hip_vec_evaluator.HipVecEvaluator, with
+                                                            evaluator_name="hip_tensor_env_evaluator"
+                                                            training.hip_tensor_evaluator.HipTensorEnvEvaluator
     create_trainer(alg, sampler, buffer, evaluator, **kw) -> training.hip_trainer.HipOffSerialTrainer, or with
                                                             trainer="hip_off_async_trainer"
                                                             training.hip_async_trainer.HipOffAsyncTrainer
@@ -94,7 +96,15 @@ def create_sampler(**kwargs):
 
 def create_evaluator(**kwargs):
     """hip_eval_env_num=N >= 2: the vectorised evaluator (training/hip_vec_evaluator.py; the evaluation episodes over N
-    environments in lockstep, `eval_envs` = the N environments if given). Absent or 1: HipEvaluator as it is."""
+    environments in lockstep, `eval_envs` = the N environments if given). Absent or 1: HipEvaluator as it is.
+    evaluator_name="hip_tensor_env_evaluator": the device-resident evaluator for batched tensor environments
+    (training/hip_tensor_evaluator.py; `eval_env` = the batched environment -- its own instance, not the sampler's; the
+    episodes run on the GPU with one wait every `hip_eval_poll_steps` lockstep steps). Every other evaluator_name -- the
+    reference's default "evaluator" included -- or none is routed as above."""
+    if kwargs.get("evaluator_name") == "hip_tensor_env_evaluator":
+        from training.hip_tensor_evaluator import HipTensorEnvEvaluator
+
+        return HipTensorEnvEvaluator(**kwargs)
     n = kwargs.get("hip_eval_env_num")
     if n is not None and int(n) >= 2:
         from training.hip_vec_evaluator import HipVecEvaluator

@@ -1,0 +1,172 @@
+"""HipTensorEnvEvaluator -- the evaluator for BATCHED TENSOR ENVIRONMENTS: the evaluation episodes of training/evaluator.py:34-84
+on a simulator that keeps N environments as tensors on the GPU (`plugin.create_evaluator(evaluator_name=
+"hip_tensor_env_evaluator", eval_env=..., ...)`). It is HipTensorEnvSampler's counterpart
+(training/hip_tensor_sampler.py): with both, a tensor-environment run trains and evaluates without a per-row adapter.
+
+HipEvaluator and HipVecEvaluator step Python objects, copy every observation to the device and wait for every action. Here a
+lockstep step is launches only, all enqueued on the engine's stream:
+    dsact_act_mode_device   policy(obs) on the live weights + the action distribution's mode() (csrc/dsact_act_batch.h)
+    env.step(action)        the environment's own torch ops
+    dsact_eval_commit       the episode bookkeeping of all N rows in one launch (k_eval_commit, csrc/dsact_kernels.h)
+    env.reset(ended)        rows whose episode ended restart alone
+and the host waits once every `hip_eval_poll_steps` lockstep steps (dsact_eval_poll: the number of episodes not finished yet).
+
+Environment protocol: exactly the sampler's (float32 / bool torch tensors on the engine's device) --
+    env.num_envs                          N
+    env.action_low / env.action_high      [A] or [N, A]
+    env.reset() -> obs[N, O]              start every environment
+    env.step(action[N, A]) -> (obs2[N, O], reward[N], terminated[N], truncated[N])
+    env.reset(mask[N]) -> obs[N, O]       rows where the bool mask is set are restarted, the others returned as they are
+The environment is `eval_env`, else `env`, else `create_env(**kwargs)`. It must be a DIFFERENT INSTANCE from the sampler's:
+an evaluation calls reset() and steps every row, which would throw away the episodes the sampler is in the middle of. Its
+torch ops are issued under `torch.cuda.stream(engine.torch_stream)`; an environment that launches kernels of its own must
+launch them on torch's current stream.
+
+Episode order: episode e (0 .. num_eval_episode - 1) runs on environment e % N, and an environment plays its episodes in index
+order -- HipVecEvaluator's rule. An episode ends on `terminated | truncated`.
+
+Rows that have finished: a row with no episode left keeps stepping (and is restarted when it ends, so the simulator is never
+stepped past a terminal state) and counts nothing. The result is therefore a pure function of the weights and the environment,
+never of the poll period; up to hip_eval_poll_steps - 1 lockstep steps are wasted at the end.
+
+Returns: an episode's return is the float64 sum of its float32 rewards in step order, accumulated on the device. It is NOT Python's
+built-in `sum` (the reference's `sum(reward_list)`, evaluator.py:74): from Python 3.12 on `sum` compensates a float sum
+(Neumaier), so a restatement adds the rewards one by one in float64. The result
+of run_evaluation is np.mean(returns) in episode-index order (evaluator.py:77-81).
+
+The clip: act_mode is inside the policy's action limits already. When the environment's limits are not the policy's, the
+action is clipped to the environment's with two torch ops on the device, as in the sampler.
+
+hip_eval_poll_steps (default 16): lockstep steps between two waits. hip_eval_max_steps (default 100 000): an evaluation that
+has not finished after that many lockstep steps raises RuntimeError (the handle stays usable) -- an environment that never ends
+an episode must not spin on the GPU forever.
+
+Refused (NotImplementedError / ValueError, before an environment or engine call is made): an unattached or CNN policy,
+non-continuous actions, an environment on another device than the engine, num_eval_episode < 1, hip_eval_poll_steps < 1.
+
+Evaluation draws nothing from the torch or NumPy generators and enqueues no update: the training state is not touched.
+After run_evaluation, `returns` (float64[E]), `lengths` (int32[E]) and `steps` (lockstep steps made) describe the last run.
+"""
+import contextlib
+
+import numpy as np
+import torch
+
+__all__ = ["HipTensorEnvEvaluator"]
+
+
+class HipTensorEnvEvaluator:
+    def __init__(self, index=0, **kwargs):
+        self.num_eval_episode = int(kwargs.get("num_eval_episode", 5))
+        if self.num_eval_episode < 1:
+            raise ValueError("num_eval_episode must be >= 1 (got %d)" % self.num_eval_episode)
+        self.poll_steps = int(kwargs.get("hip_eval_poll_steps", 16))
+        if self.poll_steps < 1:
+            raise ValueError("hip_eval_poll_steps must be >= 1 (got %d)" % self.poll_steps)
+        self.max_steps = int(kwargs.get("hip_eval_max_steps", 100000))
+        env = kwargs.get("eval_env")
+        if env is None:
+            env = kwargs.get("env")
+        if env is None:
+            from plugin import create_env
+            env = create_env(**kwargs)
+        self.env = env
+        self.n_envs = int(env.num_envs)
+        if self.n_envs < 1:
+            raise ValueError("the environment's num_envs must be >= 1 (got %d)" % self.n_envs)
+        self.action_type = kwargs.get("action_type", "continu")
+        self.steps = 0            # lockstep steps of the last run_evaluation
+        self.returns = None       # its episode returns, float64[E] in episode-index order
+        self.lengths = None       # its episode lengths, int32[E]
+        self._ready = None        # id of the engine the buffers / clip route were set up for
+        given = kwargs.get("networks")
+        self.networks = given
+        if given is None and "algorithm" in kwargs:   # evaluator.py:16-20: the generator is consumed as HipEvaluator's
+            from training.hip_sampler import _container
+            self.networks = _container(**kwargs)
+        if given is not None:
+            self._engine()        # an explicit policy is checked right away
+
+    def load_state_dict(self, state_dict):
+        self.networks.load_state_dict(state_dict)
+
+    def _engine(self):
+        """the engine behind the ATTACHED MLP policy; every other setup is refused"""
+        pol = getattr(self.networks, "policy", None)
+        eng = getattr(pol, "_engine", None)
+        if eng is None:
+            raise NotImplementedError("hip_tensor_env_evaluator needs a policy attached to a DsactEngine (the learner's networks); an "
+                                      "unattached container acts through the module forward: use hip_eval_env_num")
+        if getattr(eng, "conv_type", None):
+            raise NotImplementedError("hip_tensor_env_evaluator serves MLP policies (dsact_act_mode_device); CNN policies: "
+                                      "hip_eval_env_num")
+        if self.action_type != "continu":
+            raise NotImplementedError("hip_tensor_env_evaluator serves continuous actions")
+        low = torch.as_tensor(self.env.action_low)
+        if low.device != torch.device(eng.device):
+            raise ValueError("the environment lives on %s, the engine on %s: hip_tensor_env_evaluator moves nothing between devices"
+                             % (low.device, eng.device))
+        return eng
+
+    def _setup(self, eng):
+        """once per engine: the [N, .] buffers and whether the policy's limits are the environment's"""
+        N, O, A = self.n_envs, eng.obs_dim, eng.act_dim
+        dev = torch.device(eng.device)
+        f = dict(dtype=torch.float32, device=dev)
+        self._obs, self._act, self._clip = torch.zeros(N, O, **f), torch.zeros(N, A, **f), torch.zeros(N, A, **f)
+        self._rew = torch.zeros(N, **f)
+        self._term, self._trunc, self._ended = (torch.zeros(N, dtype=torch.bool, device=dev) for _ in range(3))
+        low = torch.as_tensor(self.env.action_low, **f)
+        high = torch.as_tensor(self.env.action_high, **f)
+        self._low, self._high = low.expand(N, A).contiguous(), high.expand(N, A).contiguous()
+        e_lo, e_hi = getattr(eng, "act_low", None), getattr(eng, "act_high", None)
+        lo_h, hi_h = self._low.cpu().numpy(), self._high.cpu().numpy()
+        self._policy_clip = bool(e_lo is not None and e_hi is not None and (lo_h == np.asarray(e_lo)[None, :]).all()
+                                 and (hi_h == np.asarray(e_hi)[None, :]).all())
+        if dev.type == "cuda":
+            # the buffers and the environment's own state were produced on torch's current stream; from here on everything runs on
+            # the engine's. Once per engine.
+            torch.cuda.current_stream(dev).synchronize()
+        self._ready = id(eng)
+
+    def run_evaluation(self, iteration):
+        eng = self._engine()
+        if self._ready != id(eng):
+            self._setup(eng)
+        pol = self.networks.policy
+        if hasattr(pol, "parameters"):
+            eng.note_torch_writes(pol.parameters())   # (weights written with torch ops since the last call)
+        N, E, P, env = self.n_envs, self.num_eval_episode, self.poll_steps, self.env
+        obs, act, clip, rew, term, trunc, ended = self._obs, self._act, self._clip, self._rew, self._term, self._trunc, self._ended
+        stream = getattr(eng, "torch_stream", None) if torch.device(eng.device).type == "cuda" else None
+        self.steps, remaining = 0, E
+        with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()), torch.no_grad():
+            eng.eval_begin(N, E)
+            obs.copy_(env.reset().reshape(N, -1))
+            while self.steps < self.max_steps:
+                eng.act_mode_device(obs, act)
+                if self._policy_clip:
+                    a = act
+                else:
+                    a = torch.minimum(torch.maximum(act, self._low), self._high, out=clip)
+                obs2, r, te, tr = env.step(a)
+                rew.copy_(r)
+                term.copy_(te)
+                trunc.copy_(tr)
+                eng.eval_commit(rew, term, trunc, ended)
+                # the next step's observations: this step's, with every environment that ended restarted on its own (rows
+                # without an episode too)
+                obs.copy_(env.reset(ended).reshape(N, -1))
+                self.steps += 1
+                if self.steps % P == 0:
+                    remaining = eng.eval_poll()
+                    if remaining == 0:
+                        break
+            else:
+                if self.steps % P:
+                    remaining = eng.eval_poll()   # (drains the stream: the handle is idle when the error is raised)
+            if remaining != 0:
+                raise RuntimeError("hip_tensor_env_evaluator: %d of %d episodes have not ended after hip_eval_max_steps = %d lockstep "
+                                   "steps" % (remaining, E, self.max_steps))
+            self.returns, self.lengths = eng.eval_read(E)
+        return np.mean(self.returns)   # episode-index order (evaluator.py:77-81)

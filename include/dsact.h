@@ -498,6 +498,45 @@ int dsact_act_sample_device(dsact_handle* h, const float* obs_dev, int32_t n, co
 int dsact_buffer_add_device(dsact_handle* h, int64_t n, const float* obs, const float* act, const float* rew, const float* obs2,
                             const uint8_t* terminated, const uint8_t* truncated, const float* logp, double reward_scale);
 
+/* ---- Device-resident evaluation (training/hip_tensor_evaluator.py) -------------------------------------
+ * The evaluation episodes of training/evaluator.py:34-84 for batched simulators whose observations, rewards and done flags live
+ * on the GPU: N environments step in lockstep; a lockstep step costs launches only, and the loop waits in dsact_eval_poll alone.
+ *   dsact_act_mode_device          training/evaluator.py:34-84's acting (logits = policy(obs), action = dist.mode(), lines
+ *                                  47-51) for n environments with every operand on the device: obs[n*O] in, read in place;
+ *                                  action[n*A] out. Bit for bit dsact_act_mode_batch's GPU route; the mode of a plain Gaussian
+ *                                  is clamped to the action limits. Enqueued on the handle's stream behind every enqueued
+ *                                  update: the LIVE weights, also under a behaviour hold (like dsact_act_mode_batch).
+ *                                  ASYNCHRONOUS: no stream synchronisation, no host copy. All pointers must be device memory
+ *                                  of the handle's GPU (DSACT_E_INVALID otherwise). Any n >= 1 (chunked inside the call); MLP
+ *                                  policies with act_dim <= 32 (DSACT_E_INVALID for CNN policies).
+ *   dsact_eval_begin               training/evaluator.py:34-84's bookkeeping (lines 40-46 and 77-81: the reward list and the
+ *                                  episode loop) moved to the device: allocates (or grows) the state for n_envs rows and n_episodes
+ *                                  episodes and initialises it in stream order -- row i plays episode i (none when
+ *                                  i >= n_episodes), zeros elsewhere, remaining = n_episodes. Episode e runs on row e % n_envs,
+ *                                  a row plays its episodes in index order. n_envs < 1 or n_episodes < 1: DSACT_E_INVALID.
+ *   dsact_eval_commit              one lockstep step of training/evaluator.py:34-84 (lines 46-62 and 74: the reward is appended, the
+ *                                  episode ends on done or a time-out, its return is the sum of its rewards) for every row
+ *                                  in ONE launch: reward[n_envs] fp32, terminated / truncated [n_envs] one byte each (non-zero
+ *                                  = set). ended[i] = terminated[i] | truncated[i] is written for every row (the mask of the
+ *                                  environment's reset); a row with an episode adds the reward to its fp64 sum in step order
+ *                                  and counts the step; at an end the episode's return and length are stored, the row goes
+ *                                  on to episode e + n_envs (or to none) and `remaining` drops by one. ASYNCHRONOUS.
+ *                                  DSACT_E_STATE before dsact_eval_begin; device pointers of the handle's GPU only.
+ *   dsact_eval_poll                the number of episodes that have not ended, read behind everything enqueued so far: the
+ *                                  counter is copied to pinned memory on the handle's stream and the call WAITS for it -- the
+ *                                  only wait of the evaluation loop (training/evaluator.py:34-84 waits for every action).
+ *   dsact_eval_read                waits, then copies returns[n_episodes] (fp64) and lengths[n_episodes] to the host: the
+ *                                  episode returns training/evaluator.py:34-84 averages (lines 77-84). DSACT_E_STATE while an
+ *                                  episode has not ended; n_episodes must be dsact_eval_begin's.
+ * dsact_debug_get: "act_mode_dev_calls" (chunks launched by dsact_act_mode_device), "eval_commit_calls", "eval_polls";
+ * "act_dev_syncs" stays 0 across dsact_act_mode_device and dsact_eval_commit too. */
+int dsact_act_mode_device(dsact_handle* h, const float* obs_dev, int32_t n, float* action_dev);
+int dsact_eval_begin(dsact_handle* h, int32_t n_envs, int32_t n_episodes);
+int dsact_eval_commit(dsact_handle* h, const float* reward_dev, const uint8_t* terminated_dev, const uint8_t* truncated_dev,
+                      uint8_t* ended_dev);
+int dsact_eval_poll(dsact_handle* h, int32_t* remaining);
+int dsact_eval_read(dsact_handle* h, double* returns, int32_t* lengths, int32_t n_episodes);
+
 #ifdef __cplusplus
 }
 #endif
