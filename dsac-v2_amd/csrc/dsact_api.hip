@@ -5406,7 +5406,55 @@ static int alloc_act_batch(dsact_handle* h) {
   HIPCHK(h, hipHostGetDevicePointer((void**)&h->ab_out_dev, h->ab_out_host, 0));
   return DSACT_OK;
 }
-// the batched forward of both entry points below: eps != nullptr samples (action, logp), eps == nullptr writes the mode.
+// ---- the batched acting forward's host side (dsact_act_batch.h): ONE launch sequence behind dsact_act_sample_batch,
+// dsact_act_mode_batch, dsact_act_sample_device and dsact_act_mode_device ------------------------------------------------------
+// what the four entry points require of the handle, refused in `who`'s name. cnn_route: where a CNN policy is served instead
+// (nullptr: `who` serves CNN policies itself)
+static int act_batch_ready(dsact_handle* h, const char* who, const char* cnn_route) {
+  if (!h->online) return fail(h, DSACT_E_STATE, "arenas not bound");
+  if (!h->limits_set) return fail(h, DSACT_E_STATE, "action limits not set (dsact_set_action_limits)");
+  if (h->cnn && cnn_route) return fail(h, DSACT_E_INVALID, "%s serves MLP policies (CNN: %s)", who, cnn_route);
+  if (h->A > 32) return fail(h, DSACT_E_INVALID, "%s serves act_dim <= 32", who);
+  return DSACT_OK;
+}
+// the four forms of the output launch, k_act_batch_out<kMode, kDev> at index kMode + 2 * kDev, under their profile names
+enum { kActOutSample = 0, kActOutMode = 1, kActOutSampleDev = 2, kActOutModeDev = 3 };
+static const struct { const char* name; void (*kernel)(ActBatchOut); } kActOutForms[4] = {
+    {"act_batch_out", k_act_batch_out<false, false>}, {"act_batch_mode", k_act_batch_out<true, false>},
+    {"act_batch_out_dev", k_act_batch_out<false, true>}, {"act_batch_mode_dev", k_act_batch_out<true, true>}};
+// policy(X[m][ldx]) for one chunk of m <= kActBatchCap device rows, enqueued on `stream`: one launch per hidden layer (ping-pong
+// through h->ab_h), then output form `form`. base: the policy net's parameters (the live arena, or a held behaviour copy).
+// o: the form's own fields (eps, action, logp; clipped, seed, step, row0) filled in by the caller, the rest zero -- the layer,
+// the output activation and the action limits are set here
+static int enqueue_act_batch(dsact_handle* h, const float* X, int ldx, int m, const float* base, hipStream_t stream, ActBatchOut o,
+                             int form) {
+  const NetDesc& d = h->pd;
+  // on the handle's stream through launch (profiling records), on the acting stream launch_on
+  auto launch_act = [&](const char* name, auto kernel, dim3 grid, const auto& a) {
+    return stream == h->stream ? launch(h, name, kernel, grid, dim3(256), 0, a) : launch_on(h, stream, name, kernel, grid, dim3(256), 0, a);
+  };
+  for (int l = 0; l < h->Lp; ++l) {
+    ActBatchHidden a;
+    a.X = X; a.ldx = ldx; a.W = base + d.w_off[l]; a.b = base + d.b_off[l];
+    a.K = d.in[l]; a.N = d.out[l]; a.half = 0;
+    if (d.nblk == 2 && l > 0) { a.K = d.in[l] / 2; a.half = d.out[l] / 2; }   // two (H x Hprev) blocks
+    a.Y = h->ab_h[l & 1]; a.ldy = d.out[l]; a.n = m; a.act = h->cfg.policy_act;
+    const int seg_n = a.half > 0 ? a.half : a.N;
+    const dim3 grid((unsigned)((a.half > 0 ? 2 : 1) * ((seg_n + 31) / 32)), (unsigned)((m + 31) / 32));
+    TRY(launch_act("act_batch_hidden", k_act_batch_hidden, grid, a));
+    X = a.Y; ldx = a.ldy;
+  }
+  const int A = h->A;
+  o.X = X; o.ldx = ldx; o.W = base + d.w_off[h->Lp]; o.b = base + d.b_off[h->Lp];
+  o.K = d.in[h->Lp]; o.A = A; o.n = m;
+  o.out_act = h->cfg.policy_out_act; o.out_n = h->cfg.policy_std_param ? A : 2 * A;
+  o.scale = h->act_scale; o.center = h->act_center; o.lo_ls = h->cfg.min_log_std; o.hi_ls = h->cfg.max_log_std;
+  o.lo = h->act_lo; o.hi = h->act_hi;
+  return launch_act(kActOutForms[form].name, kActOutForms[form].kernel, dim3((unsigned)((m + 7) / 8)), o);
+}
+
+// the host-row forward of dsact_act_sample_batch / dsact_act_mode_batch (and a held dsact_act_sample): eps != nullptr samples
+// (action, logp), eps == nullptr writes the mode.
 // base: the policy net's parameters (the live arena, or a held behaviour copy); stream: where the copies and launches go and
 // the one stream the call waits for (the handle's stream: behind every enqueued update; the acting stream: behind the hold)
 static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const float* eps, float* action_host, float* logp_host,
@@ -5418,7 +5466,6 @@ static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const flo
   const bool mode = eps == nullptr;
   TRY(alloc_act_batch(h));
   const bool obs_dev = is_device_ptr(obs), eps_dev = !mode && is_device_ptr(eps);
-  const NetDesc& d = h->pd;
   for (int s = 0; s < n; s += R) {
     const int m = n - s < R ? n - s : R;
     float* in_obs = h->ab_in;
@@ -5435,31 +5482,10 @@ static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const flo
         HIPCHK(h, hipMemcpyAsync(in_eps, eps_dev ? eps + (size_t)s * A : h->ab_stage + (size_t)m * O, (size_t)m * A * sizeof(float),
                                  hipMemcpyDefault, stream));
     }
-    const float* X = in_obs;
-    int ldx = O;
-    for (int l = 0; l < h->Lp; ++l) {
-      ActBatchHidden a;
-      a.X = X; a.ldx = ldx; a.W = base + d.w_off[l]; a.b = base + d.b_off[l];
-      a.K = d.in[l]; a.N = d.out[l]; a.half = 0;
-      if (d.nblk == 2 && l > 0) { a.K = d.in[l] / 2; a.half = d.out[l] / 2; }   // two (H x Hprev) blocks
-      a.Y = h->ab_h[l & 1]; a.ldy = d.out[l]; a.n = m; a.act = h->cfg.policy_act;
-      const int seg_n = a.half > 0 ? a.half : a.N;
-      const dim3 grid((unsigned)((a.half > 0 ? 2 : 1) * ((seg_n + 31) / 32)), (unsigned)((m + 31) / 32));
-      TRY(stream == h->stream ? launch(h, "act_batch_hidden", k_act_batch_hidden, grid, dim3(256), 0, a)
-                              : launch_on(h, stream, "act_batch_hidden", k_act_batch_hidden, grid, dim3(256), 0, a));
-      X = a.Y; ldx = a.ldy;
-    }
-    ActBatchOut o;
-    o.X = X; o.ldx = ldx; o.W = base + d.w_off[h->Lp]; o.b = base + d.b_off[h->Lp];
-    o.K = d.in[h->Lp]; o.A = A; o.n = m;
-    o.out_act = h->cfg.policy_out_act; o.out_n = h->cfg.policy_std_param ? A : 2 * A;
-    o.eps = mode ? nullptr : in_eps; o.scale = h->act_scale; o.center = h->act_center; o.lo_ls = h->cfg.min_log_std; o.hi_ls = h->cfg.max_log_std;
-    o.lo = h->act_lo; o.hi = h->act_hi;
+    ActBatchOut o = {};
+    o.eps = mode ? nullptr : in_eps;
     o.action = h->ab_out_dev; o.logp = mode ? nullptr : h->ab_out_dev + (size_t)m * A;
-    const dim3 grid((unsigned)((m + 7) / 8));
-    if (mode) TRY(launch(h, "act_batch_mode", k_act_batch_out<true, false>, grid, dim3(256), 0, o));
-    else if (stream == h->stream) TRY(launch(h, "act_batch_out", k_act_batch_out<false, false>, grid, dim3(256), 0, o));
-    else TRY(launch_on(h, stream, "act_batch_out", k_act_batch_out<false, false>, grid, dim3(256), 0, o));
+    TRY(enqueue_act_batch(h, in_obs, O, m, base, stream, o, mode ? kActOutMode : kActOutSample));
     HIPCHK(h, hipStreamSynchronize(stream));
     (mode ? h->ab_mode_calls : h->ab_calls)++;
     memcpy(action_host + (size_t)s * A, h->ab_out_host, (size_t)m * A * sizeof(float));
@@ -5470,10 +5496,7 @@ static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const flo
 
 int dsact_act_sample_batch(dsact_handle* h, const float* obs, int32_t n, const float* eps, float* action_host, float* logp_host) {
   if (!h || !obs || !eps || !action_host || !logp_host || n < 1) return DSACT_E_INVALID;
-  if (!h->online) return fail(h, DSACT_E_STATE, "arenas not bound");
-  if (!h->limits_set) return fail(h, DSACT_E_STATE, "action limits not set (dsact_set_action_limits)");
-  if (h->cnn) return fail(h, DSACT_E_INVALID, "dsact_act_sample_batch serves MLP policies (CNN: dsact_policy_forward)");
-  if (h->A > 32) return fail(h, DSACT_E_INVALID, "dsact_act_sample_batch serves act_dim <= 32");
+  TRY(act_batch_ready(h, "dsact_act_sample_batch", "dsact_policy_forward"));
   if (h->beh_held) {   // the held behaviour policy (dsact_behaviour_hold) on the acting stream
     h->beh_acts++;
     return act_batch_gpu(h, obs, n, eps, action_host, logp_host, h->beh_dev, h->act_stream);
@@ -5533,9 +5556,7 @@ static void mode_rows(const dsact_handle* h, const float* logits, int n, float* 
 }
 int dsact_act_mode_batch(dsact_handle* h, const float* obs, int32_t n, float* action_host) {
   if (!h || !obs || !action_host || n < 1) return DSACT_E_INVALID;
-  if (!h->online) return fail(h, DSACT_E_STATE, "arenas not bound");
-  if (!h->limits_set) return fail(h, DSACT_E_STATE, "action limits not set (dsact_set_action_limits)");
-  if (h->A > 32) return fail(h, DSACT_E_INVALID, "dsact_act_mode_batch serves act_dim <= 32");
+  TRY(act_batch_ready(h, "dsact_act_mode_batch", nullptr));   // (CNN policies take the stand-alone forward below)
   HIPCHK(h, hipSetDevice(h->device));
   const int O = h->O, A = h->A;
   if (h->cnn) {
@@ -5568,13 +5589,13 @@ int dsact_set_act_rng(dsact_handle* h, uint64_t seed) {
   return DSACT_OK;
 }
 
+// the two device-resident forms: obs is read IN PLACE (no staging copy), the results land in the caller's device arrays, and
+// nothing waits -- per chunk of kActBatchCap rows the launches of enqueue_act_batch on the handle's stream (the live weights,
+// behind every enqueued update; also under a behaviour hold)
 int dsact_act_sample_device(dsact_handle* h, const float* obs_dev, int32_t n, const float* eps_dev, int64_t step,
                             float* action_dev, float* clipped_dev, float* logp_dev) {
   if (!h || !obs_dev || !action_dev || !clipped_dev || !logp_dev || n < 1) return DSACT_E_INVALID;
-  if (!h->online) return fail(h, DSACT_E_STATE, "arenas not bound");
-  if (!h->limits_set) return fail(h, DSACT_E_STATE, "action limits not set (dsact_set_action_limits)");
-  if (h->cnn) return fail(h, DSACT_E_INVALID, "dsact_act_sample_batch serves MLP policies (CNN: dsact_policy_forward)");
-  if (h->A > 32) return fail(h, DSACT_E_INVALID, "dsact_act_sample_batch serves act_dim <= 32");
+  TRY(act_batch_ready(h, "dsact_act_sample_device", "dsact_policy_forward"));
   if (!eps_dev && h->act_seed == 0)
     return fail(h, DSACT_E_STATE, "eps == NULL draws the noise in the kernel: call dsact_set_act_rng with a non-zero seed first");
   HIPCHK(h, hipSetDevice(h->device));
@@ -5584,34 +5605,13 @@ int dsact_act_sample_device(dsact_handle* h, const float* obs_dev, int32_t n, co
   TRY(check_handoff_counted(h));
   TRY(alloc_act_batch(h));   // (the hidden layers' two activation buffers; the first call allocates)
   const int O = h->O, A = h->A, R = kActBatchCap;
-  const float* base = net_params(h, N_POL);   // the live weights: the launches sit behind every enqueued update
-  const NetDesc& d = h->pd;
   for (int s = 0; s < n; s += R) {
     const int m = n - s < R ? n - s : R;
-    const float* X = obs_dev + (size_t)s * O;   // read in place: no staging copy
-    int ldx = O;
-    for (int l = 0; l < h->Lp; ++l) {
-      ActBatchHidden a;
-      a.X = X; a.ldx = ldx; a.W = base + d.w_off[l]; a.b = base + d.b_off[l];
-      a.K = d.in[l]; a.N = d.out[l]; a.half = 0;
-      if (d.nblk == 2 && l > 0) { a.K = d.in[l] / 2; a.half = d.out[l] / 2; }   // two (H x Hprev) blocks
-      a.Y = h->ab_h[l & 1]; a.ldy = d.out[l]; a.n = m; a.act = h->cfg.policy_act;
-      const int seg_n = a.half > 0 ? a.half : a.N;
-      const dim3 grid((unsigned)((a.half > 0 ? 2 : 1) * ((seg_n + 31) / 32)), (unsigned)((m + 31) / 32));
-      TRY(launch(h, "act_batch_hidden", k_act_batch_hidden, grid, dim3(256), 0, a));
-      X = a.Y; ldx = a.ldy;
-    }
-    ActBatchOut o;
-    memset(&o, 0, sizeof(o));
-    o.X = X; o.ldx = ldx; o.W = base + d.w_off[h->Lp]; o.b = base + d.b_off[h->Lp];
-    o.K = d.in[h->Lp]; o.A = A; o.n = m;
-    o.out_act = h->cfg.policy_out_act; o.out_n = h->cfg.policy_std_param ? A : 2 * A;
+    ActBatchOut o = {};
     o.eps = eps_dev ? eps_dev + (size_t)s * A : nullptr;
-    o.scale = h->act_scale; o.center = h->act_center; o.lo_ls = h->cfg.min_log_std; o.hi_ls = h->cfg.max_log_std;
-    o.lo = h->act_lo; o.hi = h->act_hi;
     o.action = action_dev + (size_t)s * A; o.logp = logp_dev + s; o.clipped = clipped_dev + (size_t)s * A;
     o.seed = h->act_seed; o.step = step; o.row0 = s;
-    TRY(launch(h, "act_batch_out_dev", k_act_batch_out<false, true>, dim3((unsigned)((m + 7) / 8)), dim3(256), 0, o));
+    TRY(enqueue_act_batch(h, obs_dev + (size_t)s * O, O, m, net_params(h, N_POL), h->stream, o, kActOutSampleDev));
     h->act_dev_calls++;
   }
   return check_handoff_counted(h);
@@ -5622,42 +5622,18 @@ int dsact_act_sample_device(dsact_handle* h, const float* obs_dev, int32_t n, co
 // the launches of dsact_act_sample_device with the mode epilogue
 int dsact_act_mode_device(dsact_handle* h, const float* obs_dev, int32_t n, float* action_dev) {
   if (!h || !obs_dev || !action_dev || n < 1) return DSACT_E_INVALID;
-  if (!h->online) return fail(h, DSACT_E_STATE, "arenas not bound");
-  if (!h->limits_set) return fail(h, DSACT_E_STATE, "action limits not set (dsact_set_action_limits)");
-  if (h->cnn) return fail(h, DSACT_E_INVALID, "dsact_act_mode_device serves MLP policies (CNN: dsact_act_mode_batch)");
-  if (h->A > 32) return fail(h, DSACT_E_INVALID, "dsact_act_mode_device serves act_dim <= 32");
+  TRY(act_batch_ready(h, "dsact_act_mode_device", "dsact_act_mode_batch"));
   HIPCHK(h, hipSetDevice(h->device));
   if (!on_handle_gpu(h, obs_dev) || !on_handle_gpu(h, action_dev))
     return fail(h, DSACT_E_INVALID, "dsact_act_mode_device takes device pointers on the handle's GPU (host rows: dsact_act_mode_batch)");
   TRY(check_handoff_counted(h));
   TRY(alloc_act_batch(h));   // (the hidden layers' two activation buffers; the first call allocates)
   const int O = h->O, A = h->A, R = kActBatchCap;
-  const float* base = net_params(h, N_POL);   // the live weights, also under a behaviour hold (like dsact_act_mode_batch)
-  const NetDesc& d = h->pd;
   for (int s = 0; s < n; s += R) {
     const int m = n - s < R ? n - s : R;
-    const float* X = obs_dev + (size_t)s * O;   // read in place: no staging copy
-    int ldx = O;
-    for (int l = 0; l < h->Lp; ++l) {
-      ActBatchHidden a;
-      a.X = X; a.ldx = ldx; a.W = base + d.w_off[l]; a.b = base + d.b_off[l];
-      a.K = d.in[l]; a.N = d.out[l]; a.half = 0;
-      if (d.nblk == 2 && l > 0) { a.K = d.in[l] / 2; a.half = d.out[l] / 2; }   // two (H x Hprev) blocks
-      a.Y = h->ab_h[l & 1]; a.ldy = d.out[l]; a.n = m; a.act = h->cfg.policy_act;
-      const int seg_n = a.half > 0 ? a.half : a.N;
-      const dim3 grid((unsigned)((a.half > 0 ? 2 : 1) * ((seg_n + 31) / 32)), (unsigned)((m + 31) / 32));
-      TRY(launch(h, "act_batch_hidden", k_act_batch_hidden, grid, dim3(256), 0, a));
-      X = a.Y; ldx = a.ldy;
-    }
-    ActBatchOut o;
-    memset(&o, 0, sizeof(o));
-    o.X = X; o.ldx = ldx; o.W = base + d.w_off[h->Lp]; o.b = base + d.b_off[h->Lp];
-    o.K = d.in[h->Lp]; o.A = A; o.n = m;
-    o.out_act = h->cfg.policy_out_act; o.out_n = h->cfg.policy_std_param ? A : 2 * A;
-    o.scale = h->act_scale; o.center = h->act_center; o.lo_ls = h->cfg.min_log_std; o.hi_ls = h->cfg.max_log_std;
-    o.lo = h->act_lo; o.hi = h->act_hi;
+    ActBatchOut o = {};
     o.action = action_dev + (size_t)s * A;
-    TRY(launch(h, "act_batch_mode_dev", k_act_batch_out<true, true>, dim3((unsigned)((m + 7) / 8)), dim3(256), 0, o));
+    TRY(enqueue_act_batch(h, obs_dev + (size_t)s * O, O, m, net_params(h, N_POL), h->stream, o, kActOutModeDev));
     h->act_mode_dev_calls++;
   }
   return check_handoff_counted(h);

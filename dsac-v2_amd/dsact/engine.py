@@ -564,14 +564,18 @@ class DsactEngine:
             self._chk(rc)
         return self._act_out, self._act_lp
 
+    def _addr_fn(self, attr: str, symbol: str, argtypes):
+        """a second binding of `symbol` whose pointer arguments are void* (plain integer addresses cross without a ctypes pointer
+        object per call), cached as self.<attr> by the first call"""
+        f = self._lib[symbol]          # a fresh function object: its argtypes are its own
+        f.restype, f.argtypes = C.c_int, argtypes
+        setattr(self, attr, f)
+        return f
+
     def act_sample_addr(self, obs_addr: int, eps_addr: int, act_addr: int, logp_addr: int):
         """dsact_act_sample on plain integer addresses (the sampler's per-step call: no array or pointer objects are made;
         results land in the caller's rows). A second binding of the same symbol whose arguments are void*."""
-        f = getattr(self, "_act_addr_fn", None)
-        if f is None:
-            f = self._lib["dsact_act_sample"]          # a fresh function object: its argtypes are its own
-            f.restype, f.argtypes = C.c_int, [C.c_void_p] * 5
-            self._act_addr_fn = f
+        f = getattr(self, "_act_addr_fn", None) or self._addr_fn("_act_addr_fn", "dsact_act_sample", [C.c_void_p] * 5)
         rc = f(self._h, obs_addr, eps_addr, act_addr, logp_addr)
         if rc != 0:
             self._chk(rc)
@@ -593,11 +597,8 @@ class DsactEngine:
     def act_sample_batch_addr(self, obs_addr: int, n: int, eps_addr: int, act_addr: int, logp_addr: int):
         """dsact_act_sample_batch on plain integer addresses (the vectorised sampler's per-step call; results land in the
         caller's rows). A second binding of the same symbol whose pointer arguments are void*."""
-        f = getattr(self, "_act_batch_addr_fn", None)
-        if f is None:
-            f = self._lib["dsact_act_sample_batch"]    # a fresh function object: its argtypes are its own
-            f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-            self._act_batch_addr_fn = f
+        f = getattr(self, "_act_batch_addr_fn", None) or self._addr_fn(
+            "_act_batch_addr_fn", "dsact_act_sample_batch", [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
         rc = f(self._h, obs_addr, n, eps_addr, act_addr, logp_addr)
         if rc != 0:
             self._chk(rc)
@@ -620,16 +621,18 @@ class DsactEngine:
     def act_mode_batch_addr(self, obs_addr: int, n: int, act_addr: int):
         """dsact_act_mode_batch on plain integer addresses (the vectorised evaluator's per-step call; the actions land in the
         caller's rows). A second binding of the same symbol whose pointer arguments are void*."""
-        f = getattr(self, "_act_mode_addr_fn", None)
-        if f is None:
-            f = self._lib["dsact_act_mode_batch"]      # a fresh function object: its argtypes are its own
-            f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-            self._act_mode_addr_fn = f
+        f = getattr(self, "_act_mode_addr_fn", None) or self._addr_fn(
+            "_act_mode_addr_fn", "dsact_act_mode_batch", [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p])
         rc = f(self._h, obs_addr, n, act_addr)
         if rc != 0:
             self._chk(rc)
 
     # ---- device-resident sampling (DESIGN.md section 15): everything stays on the GPU, nothing waits -------------------------
+    @staticmethod
+    def _rows(t) -> int:
+        """the leading dimension of a tensor argument (0 for anything else: _dev then refuses it by name)"""
+        return int(t.shape[0]) if hasattr(t, "shape") and len(t.shape) else 0
+
     def _dev(self, t, shape, dtypes, name):
         """address of a torch tensor the asynchronous entry points may read or write: on this engine's GPU, contiguous, of
         the given shape and one of `dtypes`"""
@@ -656,7 +659,7 @@ class DsactEngine:
         `step` (set_act_rng). float32 contiguous tensors on this engine's GPU. Asynchronous on the engine's stream: issue the
         torch work that produces obs / consumes the results under `torch.cuda.stream(engine.torch_stream)`."""
         f32 = (self.torch.float32,)
-        n = int(obs.shape[0]) if hasattr(obs, "shape") and len(obs.shape) else 0
+        n = self._rows(obs)
         O, A = self.obs_dim, self.act_dim
         po = self._dev(obs, (n, O), f32, "obs")
         pe = self._dev(eps, (n, A), f32, "eps") if eps is not None else None
@@ -671,7 +674,7 @@ class DsactEngine:
         terminated / truncated [n] bool (or uint8). Asynchronous on the engine's stream."""
         torch = self.torch
         f32, flag = (torch.float32,), (torch.bool, torch.uint8)
-        n = int(rew.shape[0]) if hasattr(rew, "shape") and len(rew.shape) else 0
+        n = self._rows(rew)
         O, A = self.obs_dim, self.act_dim
         ptrs = [self._dev(obs, (n, O), f32, "obs"), self._dev(act, (n, A), f32, "act"), self._dev(rew, (n,), f32, "rew"),
                 self._dev(obs2, (n, O), f32, "obs2"), self._dev(terminated, (n,), flag, "terminated"),
@@ -686,7 +689,7 @@ class DsactEngine:
         GPU. Asynchronous on the engine's stream: issue the torch work that produces obs / consumes action under
         `torch.cuda.stream(engine.torch_stream)`."""
         f32 = (self.torch.float32,)
-        n = int(obs.shape[0]) if hasattr(obs, "shape") and len(obs.shape) else 0
+        n = self._rows(obs)
         po, pa = self._dev(obs, (n, self.obs_dim), f32, "obs"), self._dev(action, (n, self.act_dim), f32, "action")
         rc = self._lib.dsact_act_mode_device(self._h, po, n, pa)
         if rc != 0:
@@ -705,7 +708,7 @@ class DsactEngine:
         f32, flag = (torch.float32,), (torch.bool, torch.uint8)
         n = getattr(self, "_eval_n", None)
         if n is None:
-            n = int(reward.shape[0]) if hasattr(reward, "shape") and len(reward.shape) else 0   # (the library refuses: E_STATE)
+            n = self._rows(reward)   # (the library refuses: E_STATE)
         ptrs = [self._dev(reward, (n,), f32, "reward"), self._dev(terminated, (n,), flag, "terminated"),
                 self._dev(truncated, (n,), flag, "truncated"), self._dev(ended, (n,), flag, "ended")]
         rc = self._lib.dsact_eval_commit(self._h, *ptrs)

@@ -1,0 +1,162 @@
+"""What the samplers and evaluators share: HipOffSampler, HipVecOffSampler, HipTensorEnvSampler, HipEvaluator, HipVecEvaluator
+and HipTensorEnvEvaluator. Plain functions -- constructor steps (each class calls them at its own point: the container build
+consumes the torch generator), the question "which engine stands behind this policy", and the tensor-environment setup.
+Nothing here runs per environment step.
+"""
+import contextlib
+
+import numpy as np
+import torch
+
+MLP_POLICY = ("HipStochaPolicy",)
+ANY_POLICY = ("HipStochaPolicy", "HipCnnStochaPolicy")
+
+
+def _container(**kwargs):
+    """`__import__(algorithm.lower()).ApproxContainer(**kwargs)` -- the reference's rule (off_sampler.py:19-23,
+    evaluator.py:16-20): a plain CPU torch module until the learner's attached container replaces it"""
+    module = __import__(kwargs["algorithm"].lower())
+    return getattr(module, "ApproxContainer")(**kwargs)
+
+
+def _reset(env):
+    out = env.reset()
+    if isinstance(out, tuple) and len(out) == 2 and isinstance(out[1], dict):
+        return out
+    return out, {}
+
+
+# ---- constructor steps ------------------------------------------------------------------------------------------------------
+def sample_batch_size(kwargs):
+    return kwargs["batch_size_per_sampler"] if "batch_size_per_sampler" in kwargs else kwargs["sample_batch_size"]
+
+
+def refuse_noise(kwargs):
+    if kwargs.get("noise_params") is not None:
+        raise NotImplementedError("exploration noise is not part of the DSAC-T path (default None)")
+
+
+def networks_of(kwargs):
+    """`networks`, else the reference's own throw-away container (off_sampler.py:19-23, evaluator.py:16-20) -- the trainer replaces
+    it with the learner's (trainer.py:24-26), but its random initialisation consumes the torch global generator, so a run from
+    the same seed only follows the reference's trajectory if this one is built too"""
+    networks = kwargs.get("networks")
+    if networks is None and "algorithm" in kwargs:
+        networks = _container(**kwargs)
+    return networks
+
+
+def env_count(kwargs, envs_key, count_key, noun="environments"):
+    """(kwargs[envs_key] as a list or None, N): N is the list's length, else kwargs[count_key], else 1"""
+    envs, n = kwargs.get(envs_key), kwargs.get(count_key)
+    if envs is not None:
+        envs = list(envs)
+        if n is not None and int(n) != len(envs):
+            raise ValueError("%s=%s but %d %s were passed" % (count_key, n, len(envs), noun))
+        n = len(envs)
+    n = int(n) if n is not None else 1
+    if n < 1:
+        raise ValueError("%s must be >= 1 (got %d)" % (count_key, n))
+    return envs, n
+
+
+def make_envs(kwargs, envs, n):
+    """the N environments of a lockstep class from env_count's answer: `envs`, or `create_env(**kwargs)` n times; environment i is
+    seeded with `seed + i` (the single-environment classes seed theirs with the plain seed: environment 0 here)"""
+    from plugin import create_env
+
+    seed = kwargs.get("seed")
+    if envs is None:
+        envs = []
+        for i in range(n):
+            kw_i = dict(kwargs)
+            if seed is not None:
+                kw_i["seed"] = seed + i
+            envs.append(create_env(**kw_i))
+    if seed is not None:
+        for i, e in enumerate(envs):
+            if hasattr(e, "seed"):
+                e.seed(seed + i)
+    return envs
+
+
+# ---- the engine behind a policy ---------------------------------------------------------------------------------------------
+def attached_engine(networks, action_type, policy_classes):
+    """the engine behind an ATTACHED policy of one of `policy_classes` (by class name) that acts continuously, else None. A CNN
+    engine counts only where HipCnnStochaPolicy is among the classes."""
+    pol = getattr(networks, "policy", None)
+    eng = getattr(pol, "_engine", None)
+    if eng is None or action_type != "continu" or type(pol).__name__ not in policy_classes:
+        return None
+    if getattr(eng, "conv_type", None) and "HipCnnStochaPolicy" not in policy_classes:
+        return None
+    return eng
+
+
+def act_fast_ok(cache, eng):
+    """the library's own gate of dsact_act_sample (act_fast_ok, csrc/dsact_api.hip): MLP policy, observation <= 768 floats, at most
+    4 hidden layers, act_dim <= 32, DSACT_NO_FAST_ACT unset -- asked once per engine (`cache`: {id(engine): bool}), never restated"""
+    ok = cache.get(id(eng))
+    if ok is None:
+        try:
+            ok = eng.debug_get("act_fast") == 1.0
+        except Exception:
+            ok = False
+        cache[id(eng)] = ok
+    return ok
+
+
+# ---- tensor environments (hip_tensor_sampler.py, hip_tensor_evaluator.py) ---------------------------------------------------------
+# who -> (what serves the refused setups instead, the library call `who` acts through)
+_TENSOR_CLASSES = {"hip_tensor_env_sampler": ("hip_vec_off_sampler", "dsact_act_sample_device"),
+                   "hip_tensor_env_evaluator": ("hip_eval_env_num", "dsact_act_mode_device")}
+
+
+def require_tensor_engine(who, networks, action_type, env):
+    """the engine behind the ATTACHED MLP policy; every other setup is refused"""
+    instead, call = _TENSOR_CLASSES[who]
+    pol = getattr(networks, "policy", None)
+    eng = getattr(pol, "_engine", None)
+    if eng is None:
+        raise NotImplementedError("%s needs a policy attached to a DsactEngine (the learner's networks); an "
+                                  "unattached container acts through the module forward: use %s" % (who, instead))
+    if getattr(eng, "conv_type", None):
+        raise NotImplementedError("%s serves MLP policies (%s); CNN policies: %s" % (who, call, instead))
+    if action_type != "continu":
+        raise NotImplementedError("%s serves continuous actions" % who)
+    low = torch.as_tensor(env.action_low)
+    if low.device != torch.device(eng.device):
+        raise ValueError("the environment lives on %s, the engine on %s: %s moves nothing between devices"
+                         % (low.device, eng.device, who))
+    return eng
+
+
+def tensor_limits(env, eng, n):
+    """(low[n, A], high[n, A], same): the environment's action limits as device rows, and whether they are the policy's own
+    (dsact_set_action_limits) -- then what the library clips to is what the environment accepts"""
+    f = dict(dtype=torch.float32, device=torch.device(eng.device))
+    low = torch.as_tensor(env.action_low, **f).expand(n, eng.act_dim).contiguous()
+    high = torch.as_tensor(env.action_high, **f).expand(n, eng.act_dim).contiguous()
+    e_lo, e_hi = getattr(eng, "act_low", None), getattr(eng, "act_high", None)
+    lo_h, hi_h = low.cpu().numpy(), high.cpu().numpy()
+    same = bool(e_lo is not None and e_hi is not None and (lo_h == np.asarray(e_lo)[None, :]).all()
+                and (hi_h == np.asarray(e_hi)[None, :]).all())
+    return low, high, same
+
+
+def engine_stream(eng):
+    """the torch stream the engine's launches go to (None off the GPU)"""
+    return getattr(eng, "torch_stream", None) if torch.device(eng.device).type == "cuda" else None
+
+
+def on_stream(stream):
+    """torch ops issued inside are ordered with the engine's launches without any synchronisation"""
+    return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+
+
+def hand_over(eng):
+    """once per engine: buffers, the environment's state and its first observation were produced on torch's current stream; from
+    here on everything runs on the engine's. The only wait a tensor-environment class makes on its own."""
+    dev = torch.device(eng.device)
+    if dev.type == "cuda":
+        torch.cuda.current_stream(dev).synchronize()

@@ -48,14 +48,15 @@ def _check_supported(alg, sampler):
     from training.hip_sampler import HipOffSampler
     from training.hip_vec_sampler import HipVecOffSampler
 
-    one = sampler
     if isinstance(sampler, HipVecOffSampler):
         route = sampler.route()
         if route == "module":
             raise NotImplementedError("hip_off_async_trainer: this HipVecOffSampler acts through the module forward (the live "
                                       "weights); a held behaviour policy serves its 'host' and 'gpu' routes only")
-        one = sampler._single if route == "single" else None
-    if one is not None and not (isinstance(one, HipOffSampler) and one._fast_engine() is eng):
+        held = route != "single" or sampler.per_row_engine() is eng
+    else:
+        held = isinstance(sampler, HipOffSampler) and sampler.per_row_engine() is eng
+    if not held:
         raise NotImplementedError("hip_off_async_trainer: the sampler does not act through dsact_act_sample (general path, or an "
                                   "unknown sampler class): it would act with the live weights")
 

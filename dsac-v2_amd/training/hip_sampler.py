@@ -16,23 +16,12 @@ import time
 import numpy as np
 import torch
 
+from training.hip_acting_common import (MLP_POLICY, _container, _reset, act_fast_ok, attached_engine, networks_of,  # noqa: F401
+                                        refuse_noise, sample_batch_size)
+
 __all__ = ["HipOffSampler", "create_sampler"]
 
 SAMPLER_TIME_KEY = "Time/Sampler time [ms]-RL iter"  # reference utils/tensorboard_setup.py:150
-
-
-def _container(**kwargs):
-    """`__import__(algorithm.lower()).ApproxContainer(**kwargs)` -- the reference's rule (off_sampler.py:19-23,
-    evaluator.py:16-20): a plain CPU torch module until the learner's attached container replaces it"""
-    module = __import__(kwargs["algorithm"].lower())
-    return getattr(module, "ApproxContainer")(**kwargs)
-
-
-def _reset(env):
-    out = env.reset()
-    if isinstance(out, tuple) and len(out) == 2 and isinstance(out[1], dict):
-        return out
-    return out, {}
 
 
 class SampleBatch(list):
@@ -51,17 +40,10 @@ class HipOffSampler:
         if kwargs.get("seed") is not None and hasattr(self.env, "seed"):
             self.env.seed(kwargs["seed"])  # reference set_seed(..., env) seeds with the plain seed
         self.obs, self.info = _reset(self.env)
-        # The reference builds its own ApproxContainer here (off_sampler.py:19-23) -- the trainer replaces it with the
-        # learner's (trainer.py:24-26), but its random initialisation consumes the torch global generator, so a run
-        # from the same seed only follows the reference's trajectory if this one is built too.
-        self.networks = kwargs.get("networks")
-        if self.networks is None and "algorithm" in kwargs:
-            self.networks = _container(**kwargs)
-        self.noise_params = kwargs.get("noise_params")
-        if self.noise_params is not None:
-            raise NotImplementedError("exploration noise is not part of the DSAC-T path (default None)")
-        self.sample_batch_size = kwargs["batch_size_per_sampler"] if "batch_size_per_sampler" in kwargs \
-            else kwargs["sample_batch_size"]
+        self.networks = networks_of(kwargs)   # (the reference's throw-away container: built for its use of the torch generator)
+        refuse_noise(kwargs)
+        self.noise_params = None
+        self.sample_batch_size = sample_batch_size(kwargs)
         self.action_type = kwargs.get("action_type", "continu")
         self.reward_scale = kwargs.get("reward_scale", 1)
         self.total_sample_number = 0
@@ -79,22 +61,13 @@ class HipOffSampler:
         .cpu().numpy() (145 -> ~50 us per step, bench.py `e2e`). None: the general path below."""
         if self.general_path:
             return None
-        pol = getattr(self.networks, "policy", None)
-        eng = getattr(pol, "_engine", None)
-        if eng is None or self.action_type != "continu" or getattr(eng, "conv_type", None):
-            return None
-        if type(pol).__name__ != "HipStochaPolicy":
-            return None
-        # the library's own gate (act_fast_ok, csrc/dsact_api.hip): MLP policy, observation <= 768 floats, at most 4 hidden
-        # layers, act_dim <= 32, DSACT_NO_FAST_ACT unset -- asked once per engine, never restated here
-        ok = self._fast_ok.get(id(eng))
-        if ok is None:
-            try:
-                ok = eng.debug_get("act_fast") == 1.0
-            except Exception:
-                ok = False
-            self._fast_ok[id(eng)] = ok
-        return eng if ok else None
+        eng = attached_engine(self.networks, self.action_type, MLP_POLICY)
+        return eng if eng is not None and act_fast_ok(self._fast_ok, eng) else None
+
+    def per_row_engine(self):
+        """the engine this sampler's dsact_act_sample calls go to, None on the general path (what the overlapped trainer asks:
+        only those calls follow a held behaviour policy)"""
+        return self._fast_engine()
 
     def _sample_fast(self, eng):
         """same step order and the same generator consumption as the loop in sample() (ONE torch.randn(1, A) per step:

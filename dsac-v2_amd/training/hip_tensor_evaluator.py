@@ -47,10 +47,10 @@ non-continuous actions, an environment on another device than the engine, num_ev
 Evaluation draws nothing from the torch or NumPy generators and enqueues no update: the training state is not touched.
 After run_evaluation, `returns` (float64[E]), `lengths` (int32[E]) and `steps` (lockstep steps made) describe the last run.
 """
-import contextlib
-
 import numpy as np
 import torch
+
+from training.hip_acting_common import engine_stream, hand_over, networks_of, on_stream, require_tensor_engine, tensor_limits
 
 __all__ = ["HipTensorEnvEvaluator"]
 
@@ -79,12 +79,8 @@ class HipTensorEnvEvaluator:
         self.returns = None       # its episode returns, float64[E] in episode-index order
         self.lengths = None       # its episode lengths, int32[E]
         self._ready = None        # id of the engine the buffers / clip route were set up for
-        given = kwargs.get("networks")
-        self.networks = given
-        if given is None and "algorithm" in kwargs:   # evaluator.py:16-20: the generator is consumed as HipEvaluator's
-            from training.hip_sampler import _container
-            self.networks = _container(**kwargs)
-        if given is not None:
+        self.networks = networks_of(kwargs)   # evaluator.py:16-20: the generator is consumed as HipEvaluator's
+        if kwargs.get("networks") is not None:
             self._engine()        # an explicit policy is checked right away
 
     def load_state_dict(self, state_dict):
@@ -92,21 +88,7 @@ class HipTensorEnvEvaluator:
 
     def _engine(self):
         """the engine behind the ATTACHED MLP policy; every other setup is refused"""
-        pol = getattr(self.networks, "policy", None)
-        eng = getattr(pol, "_engine", None)
-        if eng is None:
-            raise NotImplementedError("hip_tensor_env_evaluator needs a policy attached to a DsactEngine (the learner's networks); an "
-                                      "unattached container acts through the module forward: use hip_eval_env_num")
-        if getattr(eng, "conv_type", None):
-            raise NotImplementedError("hip_tensor_env_evaluator serves MLP policies (dsact_act_mode_device); CNN policies: "
-                                      "hip_eval_env_num")
-        if self.action_type != "continu":
-            raise NotImplementedError("hip_tensor_env_evaluator serves continuous actions")
-        low = torch.as_tensor(self.env.action_low)
-        if low.device != torch.device(eng.device):
-            raise ValueError("the environment lives on %s, the engine on %s: hip_tensor_env_evaluator moves nothing between devices"
-                             % (low.device, eng.device))
-        return eng
+        return require_tensor_engine("hip_tensor_env_evaluator", self.networks, self.action_type, self.env)
 
     def _setup(self, eng):
         """once per engine: the [N, .] buffers and whether the policy's limits are the environment's"""
@@ -116,17 +98,8 @@ class HipTensorEnvEvaluator:
         self._obs, self._act, self._clip = torch.zeros(N, O, **f), torch.zeros(N, A, **f), torch.zeros(N, A, **f)
         self._rew = torch.zeros(N, **f)
         self._term, self._trunc, self._ended = (torch.zeros(N, dtype=torch.bool, device=dev) for _ in range(3))
-        low = torch.as_tensor(self.env.action_low, **f)
-        high = torch.as_tensor(self.env.action_high, **f)
-        self._low, self._high = low.expand(N, A).contiguous(), high.expand(N, A).contiguous()
-        e_lo, e_hi = getattr(eng, "act_low", None), getattr(eng, "act_high", None)
-        lo_h, hi_h = self._low.cpu().numpy(), self._high.cpu().numpy()
-        self._policy_clip = bool(e_lo is not None and e_hi is not None and (lo_h == np.asarray(e_lo)[None, :]).all()
-                                 and (hi_h == np.asarray(e_hi)[None, :]).all())
-        if dev.type == "cuda":
-            # the buffers and the environment's own state were produced on torch's current stream; from here on everything runs on
-            # the engine's. Once per engine.
-            torch.cuda.current_stream(dev).synchronize()
+        self._low, self._high, self._policy_clip = tensor_limits(self.env, eng, N)
+        hand_over(eng)
         self._ready = id(eng)
 
     def run_evaluation(self, iteration):
@@ -138,9 +111,8 @@ class HipTensorEnvEvaluator:
             eng.note_torch_writes(pol.parameters())   # (weights written with torch ops since the last call)
         N, E, P, env = self.n_envs, self.num_eval_episode, self.poll_steps, self.env
         obs, act, clip, rew, term, trunc, ended = self._obs, self._act, self._clip, self._rew, self._term, self._trunc, self._ended
-        stream = getattr(eng, "torch_stream", None) if torch.device(eng.device).type == "cuda" else None
         self.steps, remaining = 0, E
-        with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()), torch.no_grad():
+        with on_stream(engine_stream(eng)), torch.no_grad():
             eng.eval_begin(N, E)
             obs.copy_(env.reset().reshape(N, -1))
             while self.steps < self.max_steps:

@@ -44,14 +44,15 @@ sample() returns (DeviceSampleBatch, {sampler time}). The time is the HOST time 
 sampler's own preallocated [S, .] buffers: they are valid until the next sample() call (add_batch consumes them in stream
 order before that).
 """
-import contextlib
 import time
 
 import numpy as np
 import torch
 
+from training.hip_acting_common import (engine_stream, hand_over, networks_of, on_stream, refuse_noise, require_tensor_engine,
+                                        sample_batch_size, tensor_limits)
 from training.hip_replay_buffer import act_seed_from
-from training.hip_sampler import SAMPLER_TIME_KEY, _container
+from training.hip_sampler import SAMPLER_TIME_KEY
 
 __all__ = ["HipTensorEnvSampler", "DeviceSampleBatch", "act_noise_words", "act_noise_reference"]
 
@@ -119,8 +120,7 @@ class DeviceSampleBatch:
     def _host(self):
         if self._tuples is None:
             S, O, A = len(self), self.obs.shape[1], self.act.shape[1]
-            ctx = torch.cuda.stream(self.stream) if self.stream is not None else contextlib.nullcontext()
-            with ctx:
+            with on_stream(self.stream):
                 flat = torch.cat([self.obs, self.obs2, self.act, self.rew[:, None], self.logp[:, None],
                                   self.terminated[:, None].to(torch.float32), self.truncated[:, None].to(torch.float32)], dim=1)
                 h = flat.cpu().numpy()     # the one copy
@@ -139,8 +139,7 @@ class DeviceSampleBatch:
 
 class HipTensorEnvSampler:
     def __init__(self, index=0, **kwargs):
-        if kwargs.get("noise_params") is not None:
-            raise NotImplementedError("exploration noise is not part of the DSAC-T path (default None)")
+        refuse_noise(kwargs)
         if kwargs.get("strict_rng", False):
             raise ValueError("hip_tensor_env_sampler with strict_rng=True: the acting noise is drawn in the kernel (Philox), not "
                              "from torch.randn's stream; a parity run wants hip_vec_off_sampler")
@@ -150,8 +149,7 @@ class HipTensorEnvSampler:
             env = create_env(**kwargs)
         self.env = env
         self.n_envs = int(env.num_envs)
-        self.sample_batch_size = kwargs["batch_size_per_sampler"] if "batch_size_per_sampler" in kwargs \
-            else kwargs["sample_batch_size"]
+        self.sample_batch_size = sample_batch_size(kwargs)
         if self.n_envs < 1 or self.sample_batch_size % self.n_envs:
             raise ValueError("the sample batch size %d is not a multiple of the environment's num_envs %d"
                              % (self.sample_batch_size, self.n_envs))
@@ -165,12 +163,8 @@ class HipTensorEnvSampler:
         self.total_sample_number = 0
         self._ready = None                # id of the engine the buffers / seed / clip route were set up for
         self._started = False             # env.reset() has been called
-        # the reference's own throw-away container (off_sampler.py:19-23), built for its use of the torch generator
-        given = kwargs.get("networks")
-        self.networks = given
-        if given is None and "algorithm" in kwargs:
-            self.networks = _container(**kwargs)
-        if given is not None:
+        self.networks = networks_of(kwargs)   # (the reference's throw-away container: built for its use of the torch generator)
+        if kwargs.get("networks") is not None:
             self._engine()                # an explicit policy is checked right away
 
     def load_state_dict(self, state_dict):
@@ -181,21 +175,7 @@ class HipTensorEnvSampler:
 
     def _engine(self):
         """the engine behind the ATTACHED MLP policy; every other setup is refused"""
-        pol = getattr(self.networks, "policy", None)
-        eng = getattr(pol, "_engine", None)
-        if eng is None:
-            raise NotImplementedError("hip_tensor_env_sampler needs a policy attached to a DsactEngine (the learner's networks); an "
-                                      "unattached container acts through the module forward: use hip_vec_off_sampler")
-        if getattr(eng, "conv_type", None):
-            raise NotImplementedError("hip_tensor_env_sampler serves MLP policies (dsact_act_sample_device); CNN policies: "
-                                      "hip_vec_off_sampler")
-        if self.action_type != "continu":
-            raise NotImplementedError("hip_tensor_env_sampler serves continuous actions")
-        low = torch.as_tensor(self.env.action_low)
-        if low.device != torch.device(eng.device):
-            raise ValueError("the environment lives on %s, the engine on %s: hip_tensor_env_sampler moves nothing between devices"
-                             % (low.device, eng.device))
-        return eng
+        return require_tensor_engine("hip_tensor_env_sampler", self.networks, self.action_type, self.env)
 
     def _setup(self, eng):
         """once per engine: the [S, .] buffers, the acting seed, and whether the kernel's clip is the environment's"""
@@ -208,21 +188,12 @@ class HipTensorEnvSampler:
         self._term_b = torch.zeros(S, dtype=torch.bool, device=dev)
         self._trunc_b = torch.zeros(S, dtype=torch.bool, device=dev)
         self._obs = torch.zeros(N, O, **f)
-        low = torch.as_tensor(self.env.action_low, **f)
-        high = torch.as_tensor(self.env.action_high, **f)
-        self._low, self._high = low.expand(N, A).contiguous(), high.expand(N, A).contiguous()
-        e_lo, e_hi = getattr(eng, "act_low", None), getattr(eng, "act_high", None)
-        lo_h, hi_h = self._low.cpu().numpy(), self._high.cpu().numpy()
-        self._kernel_clip = bool(e_lo is not None and e_hi is not None and (lo_h == np.asarray(e_lo)[None, :]).all()
-                                 and (hi_h == np.asarray(e_hi)[None, :]).all())
+        self._low, self._high, self._kernel_clip = tensor_limits(self.env, eng, N)
         eng.set_act_rng(self.act_seed)
         if not self._started:
             self._obs.copy_(self.env.reset().reshape(N, O))
             self._started = True
-        if dev.type == "cuda":
-            # the buffers, the environment's state and its first observation were produced on torch's current stream; from here on
-            # everything runs on the engine's. The only wait this sampler ever makes, once.
-            torch.cuda.current_stream(dev).synchronize()
+        hand_over(eng)   # (the only wait this sampler ever makes, once)
         self._ready = id(eng)
 
     def sample(self):
@@ -234,8 +205,8 @@ class HipTensorEnvSampler:
         env = self.env
         obs_b, obs2_b, act_b, clip_b = self._obs_b, self._obs2_b, self._act_b, self._clip_b
         rew_b, logp_b, term_b, trunc_b = self._rew_b, self._logp_b, self._term_b, self._trunc_b
-        stream = getattr(eng, "torch_stream", None) if torch.device(eng.device).type == "cuda" else None
-        with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()), torch.no_grad():
+        stream = engine_stream(eng)
+        with on_stream(stream), torch.no_grad():
             obs_b[0:N].copy_(self._obs)
             for t in range(S // N):
                 r0, r1 = t * N, (t + 1) * N

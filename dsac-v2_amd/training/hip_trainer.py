@@ -20,6 +20,8 @@ import time
 
 import torch
 
+from training.hip_acting_common import _reset, networks_of
+
 __all__ = ["HipOffSerialTrainer", "HipEvaluator", "create_trainer", "create_evaluator", "save_tb_to_csv", "TB_TAGS"]
 
 TB_TAGS = {  # the reference's tag set, same keys and strings (utils/tensorboard_setup.py:142-153)
@@ -120,15 +122,11 @@ class HipEvaluator:
         self.env = kwargs.get("eval_env") or kwargs.get("env") or create_env(**kwargs)
         if kwargs.get("seed") is not None and hasattr(self.env, "seed"):
             self.env.seed(kwargs["seed"])  # reference evaluator.py:15: set_seed(..., env) seeds with the plain seed
-        self.networks = kwargs.get("networks")
-        if self.networks is None and "algorithm" in kwargs:   # evaluator.py:16-20: consumes the torch generator like the reference
-            from training.hip_sampler import _container
-            self.networks = _container(**kwargs)
+        self.networks = networks_of(kwargs)   # evaluator.py:16-20: consumes the torch generator like the reference
         self.num_eval_episode = kwargs.get("num_eval_episode", 5)
 
     def run_an_episode(self):
-        out = self.env.reset()
-        obs = out[0] if isinstance(out, tuple) else out
+        obs = _reset(self.env)[0]
         rewards, done = [], False
         while not done:
             with torch.no_grad():

@@ -23,41 +23,16 @@ Evaluation draws nothing from the torch generator and enqueues no update: the tr
 import numpy as np
 import torch
 
+from training.hip_acting_common import ANY_POLICY, _reset, attached_engine, env_count, make_envs, networks_of
+
 __all__ = ["HipVecEvaluator"]
 
 
 class HipVecEvaluator:
     def __init__(self, index=0, **kwargs):
-        from plugin import create_env
-
-        envs = kwargs.get("eval_envs")
-        n = kwargs.get("hip_eval_env_num")
-        if envs is not None:
-            envs = list(envs)
-            if n is not None and int(n) != len(envs):
-                raise ValueError("hip_eval_env_num=%s but %d evaluation environments were passed" % (n, len(envs)))
-            n = len(envs)
-        n = int(n) if n is not None else 1
-        if n < 1:
-            raise ValueError("hip_eval_env_num must be >= 1 (got %d)" % n)
-        seed = kwargs.get("seed")
-        if envs is None:
-            envs = []
-            for i in range(n):
-                kw_i = dict(kwargs)
-                if seed is not None:
-                    kw_i["seed"] = seed + i
-                envs.append(create_env(**kw_i))
-        if seed is not None:
-            for i, e in enumerate(envs):
-                if hasattr(e, "seed"):
-                    e.seed(seed + i)   # (HipEvaluator seeds its environment with the plain seed: environment 0 here)
-        self.envs = envs
-        self.n_envs = n
-        self.networks = kwargs.get("networks")
-        if self.networks is None and "algorithm" in kwargs:   # evaluator.py:16-20: the generator is consumed as HipEvaluator's
-            from training.hip_sampler import _container
-            self.networks = _container(**kwargs)
+        envs, self.n_envs = env_count(kwargs, "eval_envs", "hip_eval_env_num", noun="evaluation environments")
+        self.envs = make_envs(kwargs, envs, self.n_envs)
+        self.networks = networks_of(kwargs)   # evaluator.py:16-20: the generator is consumed as HipEvaluator's
         self.num_eval_episode = kwargs.get("num_eval_episode", 5)
         self.action_type = kwargs.get("action_type", "continu")
         self.steps = 0        # lockstep steps of the last run_evaluation
@@ -68,13 +43,8 @@ class HipVecEvaluator:
 
     def _engine(self):
         """the engine behind an ATTACHED policy that dsact_act_mode_batch serves, else None"""
-        pol = getattr(self.networks, "policy", None)
-        eng = getattr(pol, "_engine", None)
-        if eng is None or self.action_type != "continu" or eng.act_dim > 32:
-            return None
-        if type(pol).__name__ not in ("HipStochaPolicy", "HipCnnStochaPolicy"):
-            return None
-        return eng
+        eng = attached_engine(self.networks, self.action_type, ANY_POLICY)
+        return eng if eng is not None and eng.act_dim <= 32 else None
 
     def route(self):
         """'engine' | 'module': how the next run_evaluation() acts (see the module docstring)"""
@@ -94,9 +64,7 @@ class HipVecEvaluator:
         episode, rewards, obs = {}, {}, {}
 
         def begin(i, e):
-            out = envs[i].reset()
-            o = out[0] if isinstance(out, tuple) else out
-            episode[i], rewards[i], obs[i] = e, [], o
+            episode[i], rewards[i], obs[i] = e, [], _reset(envs[i])[0]
 
         for i in range(min(N, E)):
             begin(i, i)

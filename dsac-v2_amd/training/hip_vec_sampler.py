@@ -33,7 +33,9 @@ import time
 import numpy as np
 import torch
 
-from training.hip_sampler import SAMPLER_TIME_KEY, HipOffSampler, SampleBatch, _container, _reset
+from training.hip_acting_common import (MLP_POLICY, _reset, act_fast_ok, attached_engine, env_count, make_envs, networks_of,
+                                        refuse_noise, sample_batch_size)
+from training.hip_sampler import SAMPLER_TIME_KEY, HipOffSampler, SampleBatch
 
 __all__ = ["HipVecOffSampler", "DEFAULT_GPU_MIN_ENVS"]
 
@@ -43,25 +45,12 @@ DEFAULT_GPU_MIN_ENVS = 32
 
 class HipVecOffSampler:
     def __init__(self, index=0, **kwargs):
-        from plugin import create_env
-
-        envs = kwargs.get("envs")
-        n = kwargs.get("vector_env_num")
-        if envs is not None:
-            envs = list(envs)
-            if n is not None and int(n) != len(envs):
-                raise ValueError("vector_env_num=%s but %d environments were passed" % (n, len(envs)))
-            n = len(envs)
-        n = int(n) if n is not None else 1
-        if n < 1:
-            raise ValueError("vector_env_num must be >= 1 (got %d)" % n)
+        envs, n = env_count(kwargs, "envs", "vector_env_num")
         self.n_envs = n
-        self.sample_batch_size = kwargs["batch_size_per_sampler"] if "batch_size_per_sampler" in kwargs \
-            else kwargs["sample_batch_size"]
+        self.sample_batch_size = sample_batch_size(kwargs)
         if self.sample_batch_size % n:
             raise ValueError("the sample batch size %d is not a multiple of vector_env_num %d" % (self.sample_batch_size, n))
-        if kwargs.get("noise_params") is not None:
-            raise NotImplementedError("exploration noise is not part of the DSAC-T path (default None)")
+        refuse_noise(kwargs)
         self.act_mode = kwargs.get("hip_vec_act", "auto")
         if self.act_mode not in ("auto", "gpu", "host"):
             raise ValueError("hip_vec_act must be 'auto', 'gpu' or 'host' (got %r)" % (self.act_mode,))
@@ -75,29 +64,14 @@ class HipVecOffSampler:
             self._single = HipOffSampler(index, **one)
             return
         self._single = None
-        seed = kwargs.get("seed")
-        if envs is None:
-            envs = []
-            for i in range(n):
-                kw_i = dict(kwargs)
-                if seed is not None:
-                    kw_i["seed"] = seed + i
-                envs.append(create_env(**kw_i))
-        if seed is not None:
-            for i, e in enumerate(envs):
-                if hasattr(e, "seed"):
-                    e.seed(seed + i)   # (HipOffSampler seeds its environment with the plain seed: environment 0 here)
-        self.envs = envs
+        self.envs = envs = make_envs(kwargs, envs, n)
         first = [_reset(e) for e in envs]
         self.obs_shape = np.shape(first[0][0])
         self.obs_dim = int(np.prod(self.obs_shape))
         self.obs = np.empty((n, self.obs_dim), np.float32)
         self.obs[...] = [np.reshape(o, -1) for o, _ in first]
         self.infos = [i for _, i in first]
-        # the reference's own throw-away container (off_sampler.py:19-23), built for its use of the torch generator
-        self.networks = kwargs.get("networks")
-        if self.networks is None and "algorithm" in kwargs:
-            self.networks = _container(**kwargs)
+        self.networks = networks_of(kwargs)   # (the reference's throw-away container: built for its use of the torch generator)
         self.action_type = kwargs.get("action_type", "continu")
         self.reward_scale = kwargs.get("reward_scale", 1)
         self.total_sample_number = 0
@@ -128,13 +102,12 @@ class HipVecOffSampler:
 
     def _engine(self):
         """the engine behind an ATTACHED MLP policy (dsact_act_sample_batch serves every one), else None"""
-        pol = getattr(self.networks, "policy", None)
-        eng = getattr(pol, "_engine", None)
-        if eng is None or self.action_type != "continu" or getattr(eng, "conv_type", None):
-            return None
-        if type(pol).__name__ != "HipStochaPolicy":
-            return None
-        return eng
+        return attached_engine(self.networks, self.action_type, MLP_POLICY)
+
+    def per_row_engine(self):
+        """the engine the 'single' route's per-row dsact_act_sample calls go to (HipOffSampler.per_row_engine of the wrapped
+        sampler); None on every other route. What the overlapped trainer asks before it holds the behaviour policy."""
+        return self._single.per_row_engine() if self._single is not None else None
 
     def route(self):
         """'single' | 'gpu' | 'host' | 'module': how the next sample() acts (see the module docstring)"""
@@ -145,14 +118,7 @@ class HipVecOffSampler:
             return "module"
         if self.act_mode == "gpu" or (self.act_mode == "auto" and self.n_envs >= self.gpu_min_envs):
             return "gpu"
-        ok = self._fast_ok.get(id(eng))
-        if ok is None:   # the library's own gate of dsact_act_sample (act_fast_ok)
-            try:
-                ok = eng.debug_get("act_fast") == 1.0
-            except Exception:
-                ok = False
-            self._fast_ok[id(eng)] = ok
-        return "host" if ok else "gpu"
+        return "host" if act_fast_ok(self._fast_ok, eng) else "gpu"
 
     def sample(self):
         if self._single is not None:
