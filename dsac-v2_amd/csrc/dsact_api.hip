@@ -182,7 +182,6 @@ struct dsact_handle {
   int n_cu = 256;                       // compute units of the device (hipDeviceAttributeMultiprocessorCount)
   bool env_no_dcol_ident = false;       // DSACT_NO_DCOL_IDENT: keep dCol + col2im on the layer whose col2im is the identity (round 6 fuses the mask into the product)
   bool mirror_w0 = false;      // set while the merged-gather graph is being captured (see FusedOpt::mir_*)
-  bool merged_graph = false;   // the captured graph uses the merged-gather flow
   bool have_local_tail = false;   // the gradient arena's tail holds mean_std of a gradient computed HERE and not yet committed
   long long dev_it_next = -1;  // host shadow of DevState::it_next after graph replays (-1: unknown, upload it)
   hipEvent_t tev0 = nullptr, tev1 = nullptr;   // dsact_time_steps' events, created once
@@ -215,25 +214,8 @@ struct dsact_handle {
   uint64_t idx_seed = 0;   // dsact_set_index_rng: 0 = the caller draws the replay indices (np.random.randint)
   bool have_batch = false;
   bool limits_set = false;
-  // graph
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t graph_exec = nullptr;
-  int graph_steps = 0;
-  uint32_t graph_flags = 0;
-  // dsact_run_group: captured graphs of OTHER lengths / noise modes than the active one stay instantiated (a trainer's
-  // groups between two sampler calls come in a few lengths: sample_interval, and what log / eval / save iterations cut off)
-  struct GraphSet {
-    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-    hipGraph_t pgraph[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipGraphExec_t pexec[4] = {nullptr, nullptr, nullptr, nullptr};
-    void* pargs[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool pipe = false, merged = false, noise_table = false;
-    int steps = 0; uint32_t flags = 0;
-  };
-  std::vector<GraphSet> graph_cache;
-  bool graph_noise_table = false;       // the ACTIVE graph's gathers read the noise table (strict RNG) instead of drawing Philox noise
-  bool noise_table_on = false;          // set while such a graph is being captured (noise_args)
-  bool build_keeps_cache = false;       // set by dsact_run_group around dsact_graph_build: the previous graphs are stashed, not destroyed
+  // graph (the captured graphs themselves: GraphSet below)
+  bool noise_table_on = false;          // set by build_graph while it captures a graph whose gathers read the noise table (noise_args, pipe_eligible)
   float* noise_table = nullptr;         // [idx_rows][2*B*A + 2*B]: eps_new | eps_2 | z5 | z6 per replayed update
   char* grp_pin[4] = {nullptr, nullptr, nullptr, nullptr};   // pinned staging of dsact_run_group (index rows + noise rows), 4 slots
   size_t grp_pin_bytes = 0;
@@ -374,20 +356,30 @@ struct dsact_handle {
   PipeSet pset[kPipeSets];
   char* pipe_ws = nullptr;
   unsigned long long* pipe_hand[2] = {nullptr, nullptr};   // tagged hand-over buffers [B][32] (value, tag): new_act, act2
-  bool pipe_defer_now = false;          // set while the update being enqueued defers its (discarded) policy backward
   // merged critic backward + critic tiles + close (k_chain_bwd_qt) on the updates that defer their policy backward
   int* bqt_cnt = nullptr;               // arrival counters [2 critics][8 x kArriveStride], zeroed by the forward launch's bookkeeping block
   int* bqt_tab = nullptr; int bqt_tab_blocks = 0;   // block -> tile table (classes of layers in arrival order, dealt to the XCDs)
   bool env_no_bqt = false;              // DSACT_NO_BQT_MERGE: critics' backward and their tiles stay two launches (A/B)
-  bool bqt_now = false;                 // set while such an update is being enqueued
   // k_chain_bwd_qpt: the whole backward of a policy-moving update of the pipelined graph as one launch
   unsigned long long* bqp_pairs[2] = {nullptr, nullptr};   // dL/d new_act through q1 / q2 as (value, tag) pairs [B][32]
   bool env_no_bqp = false;              // DSACT_NO_BQP_MERGE: critics' backward and policy backward stay two launches on those updates (A/B)
-  bool bqp_now = false;
-  bool pipe_graph = false;              // the captured graphs are the pipelined ones (pgraph / pexec, one per phase)
-  hipGraph_t pgraph[kPipePhases] = {nullptr, nullptr, nullptr, nullptr};
-  hipGraphExec_t pexec[kPipePhases] = {nullptr, nullptr, nullptr, nullptr};
-  PipeFwd* pargs[kPipePhases] = {nullptr, nullptr, nullptr, nullptr};   // device: one PipeFwd per captured forward launch
+  // one captured graph of `steps` updates: the plain one (graph / exec) or, when `pipe`, the pipelined ones (one per phase).
+  // `active` is what the replays launch; dsact_run_group keeps the graphs of OTHER lengths / noise modes instantiated in
+  // graph_cache (a trainer's groups between two sampler calls come in a few lengths: sample_interval, and what log / eval /
+  // save iterations cut off)
+  struct GraphSet {
+    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
+    hipGraph_t pgraph[kPipePhases] = {nullptr, nullptr, nullptr, nullptr};
+    hipGraphExec_t pexec[kPipePhases] = {nullptr, nullptr, nullptr, nullptr};
+    PipeFwd* pargs[kPipePhases] = {nullptr, nullptr, nullptr, nullptr};   // device: one PipeFwd per captured forward launch
+    bool pipe = false;          // the pipelined graphs (pgraph / pexec)
+    bool merged = false;        // captured with the merged-gather flow (debug name "merged_graph": 0 again once the graph is dropped)
+    bool noise_table = false;   // its gathers read the noise table (strict RNG) instead of drawing Philox noise
+    int steps = 0; uint32_t flags = 0;
+    bool present() const { return exec != nullptr || pipe; }
+  };
+  GraphSet active;
+  std::vector<GraphSet> graph_cache;
   bool env_no_pipe_defer = false;       // DSACT_NO_PIPE_DEFER: the discarded policy backward stays in its own update's last launch (A/B)
   std::string env_pipe_map;             // DSACT_PIPE_MAP: XCD lists per unit (experiments), see pipe_xcds
   // native collective (RCCL): communicator of this rank, see dsact_comm_init
@@ -398,6 +390,11 @@ struct dsact_handle {
   bool auto_std_sums = false;
   float* std_sums_own = nullptr;
 };
+
+// dsact_graph_build's body, defined beside it: check_handoff and dsact_run_group say what they capture
+extern "C" {
+static int build_graph(dsact_handle* h, int steps_per_graph, uint32_t flags, bool noise_table, bool keep_cache);
+}
 
 namespace {
 
@@ -2712,12 +2709,31 @@ int enqueue_chain_bwd_qpt(dsact_handle* h, bool fused, const RideArgs* ride) {
   return launch(h, "chain_bwd_qpt", k_chain_bwd_qpt<4, 1, 2>, dim3(grid), dim3(kThreads), lds, a);
 }
 
+// which part of an update enqueue_grads enqueues
+enum GradPhase {
+  PH_ALL = 0,        // everything
+  PH_FORWARD = 1,    // forward part up to the local {sum std1, sum std2} (strict data-parallel mode: the caller all-reduces those two floats)
+  PH_BACKWARD = 2,   // loss + backward (+ fused update)
+  // data-parallel overlap, unfused: the caller starts the all-reduce of the first segment between the two
+  PH_DP_CRITIC = 3,  // everything up to and including the critics' gradients (q1 | q2 segment of the arena final)
+  PH_DP_ACTOR = 4,   // actor part (policy | log_alpha | mean_std tail)
+};
+// launch form of the chain backward of one update of the pipelined graph (chosen per update by plan_updates_pipe)
+enum BwdForm {
+  BWD_PLAIN = 0,     // critics' backward, then the policy backward with the tiles and the close
+  BWD_DEFER_PI,      // the (discarded) policy backward rides in the next forward launch: enqueue_chain_bwd_pi_close
+  BWD_QT,            // ... and the critics' backward + their tiles + close are one launch: enqueue_chain_bwd_qt
+  BWD_QPT,           // update that moves the policy: the whole backward as one launch, enqueue_chain_bwd_qpt
+};
+static bool defers_pi(BwdForm f) { return f == BWD_DEFER_PI || f == BWD_QT; }
+static bool merged_bwd(BwdForm f) { return f == BWD_QT || f == BWD_QPT; }   // (its bookkeeping rides in its forward launch)
+
 // same contract as enqueue_grads (phases, fused optimiser, riders of the loss launch)
-int enqueue_grads_chain(dsact_handle* h, bool actor_backward, bool fused, int phase, const RideArgs* ride) {
+int enqueue_grads_chain(dsact_handle* h, bool actor_backward, bool fused, GradPhase phase, const RideArgs* ride, BwdForm form) {
   const int* off = h->dw2_off;
-  const bool one_dfeat = h->twin && actor_backward && (phase == 0 || phase == 2) && h->dw_chunks == 1;
-  if (phase == 4) goto actor_part;
-  if (phase != 2) {
+  const bool one_dfeat = h->twin && actor_backward && (phase == PH_ALL || phase == PH_BACKWARD) && h->dw_chunks == 1;
+  if (phase == PH_DP_ACTOR) goto actor_part;
+  if (phase != PH_BACKWARD) {
     if (h->cnn) TRY(enqueue_conv_forward(h));
     if (h->twin) {
       TRY(enqueue_chain_fwd_twin(h, 0));
@@ -2734,11 +2750,11 @@ int enqueue_grads_chain(dsact_handle* h, bool actor_backward, bool fused, int ph
       TRY(launch(h, "std_sums", k_std_sums, dim3(1), dim3(kThreads), 0, s));
     }
   }
-  if (phase == 1) return DSACT_OK;
+  if (phase == PH_FORWARD) return DSACT_OK;
   // pipelined graph, update whose policy backward rides in the next forward launch: critics' backward + their tiles + close
-  if (h->bqt_now && h->pipe_defer_now && actor_backward && phase == 2) return enqueue_chain_bwd_qt(h, fused, ride);
+  if (form == BWD_QT && actor_backward && phase == PH_BACKWARD) return enqueue_chain_bwd_qt(h, fused, ride);
   // ... update that moves the policy: the whole backward as one launch
-  if (h->bqp_now && !h->pipe_defer_now && actor_backward && phase == 2) return enqueue_chain_bwd_qpt(h, fused, ride);
+  if (form == BWD_QPT && actor_backward && phase == PH_BACKWARD) return enqueue_chain_bwd_qpt(h, fused, ride);
   TRY(enqueue_chain_bwd_q(h, (actor_backward ? 2 : 1) * h->nq, ride));
   // CNN nets (batch <= 1024: one gradient arena): dL/d features = dZ0 . W0[:, :F] right behind the chains that produce dZ0 and
   // before the launch whose tiles update W0; the conv stacks' backward follows the MLP part (enqueue_grads' order)
@@ -2754,13 +2770,13 @@ int enqueue_grads_chain(dsact_handle* h, bool actor_backward, bool fused, int ph
     if (fused) return enqueue_adam(h, true);
     return sum_parts(h, 0, (size_t)h->nq * h->n_q);
   }
-  if (phase == 3) {
+  if (phase == PH_DP_CRITIC) {
     TRY(run_dw2(h, off[0], off[2], false, false));
     if (h->cnn) TRY(enqueue_conv_backward(h, h->nq, false));
     return sum_parts(h, 0, (size_t)h->nq * h->n_q);
   }
 actor_part:
-  if (phase == 4) {
+  if (phase == PH_DP_ACTOR) {
     TRY(enqueue_chain_bwd_pi(h, 0, 0, false));
     if (h->cnn) TRY(run_stage(h, h->dfeat_pi));
     TRY(run_dw2(h, h->dw2_off[2], h->dw2_off[3], false, false));
@@ -2773,7 +2789,7 @@ actor_part:
     // batch <= 256: the policy's own tiles and the closing block ride in the same launch behind the riders and wait for
     // the chain's arrival counter (k_chain_bwd_pi, merge_dw) -- one launch and one kernel boundary less per update
     if (h->pi_merge && h->dw_chunks == 1 && ride_end == h->dw2_off[2]) {
-      if (h->pipe_defer_now) return enqueue_chain_bwd_pi_close(h, fused);   // the policy backward rides in the next forward launch
+      if (defers_pi(form)) return enqueue_chain_bwd_pi_close(h, fused);   // the policy backward rides in the next forward launch
       return enqueue_chain_bwd_pi(h, h->dw2_off[0], ride_end, fused, true);
     }
     if (one_dfeat) {
@@ -2796,21 +2812,18 @@ actor_part:
   return sum_parts(h, 0, h->n_online - 1);
 }
 
-// phase 0: everything; 1: forward part up to the local {sum std1, sum std2} (strict data-parallel mode: the
-// caller all-reduces those two floats); 2: loss + backward (+ fused update);
-// 3 / 4 (data-parallel overlap, unfused): 3 = everything up to and including the critics' gradients (q1 | q2
-// segment of the arena final), 4 = actor part (policy | log_alpha | mean_std tail) -- the caller starts the
-// all-reduce of the first segment between the two
 // `ride` (graph replays with the merged gather): nullptr, or the riders of the loss launch -- this update's
 // bookkeeping and, when ride->n_gather > 0, the next update's gather into the other batch set
-int enqueue_grads(dsact_handle* h, bool actor_backward, bool fused, int phase = 0, const RideArgs* ride = nullptr) {
+// `form` (pipelined graph on the chains): see BwdForm
+int enqueue_grads(dsact_handle* h, bool actor_backward, bool fused, GradPhase phase = PH_ALL, const RideArgs* ride = nullptr,
+                  BwdForm form = BWD_PLAIN) {
   h->have_local_tail = true;
   h->uev_valid = false;   // dsact_step / dsact_compute_grads set it again once their closing event is recorded
-  if (h->chain_ok) return enqueue_grads_chain(h, actor_backward, fused, phase, ride);
+  if (h->chain_ok) return enqueue_grads_chain(h, actor_backward, fused, phase, ride, form);
   const int B = h->B, A = h->A;
   const int Lq = h->Lq, Lp = h->Lp;   // hidden layers of the critics / the policy nets (equal unless policy_n_hidden is set)
-  if (phase == 4) goto actor_part;
-  if (phase != 2) {
+  if (phase == PH_DP_ACTOR) goto actor_part;
+  if (phase != PH_BACKWARD) {
   if (h->cnn) TRY(enqueue_conv_forward(h));
   for (size_t l = 0; l < h->fwd1.size(); ++l) TRY(run_stage(h, h->fwd1[l]));
   {
@@ -2852,8 +2865,8 @@ int enqueue_grads(dsact_handle* h, bool actor_backward, bool fused, int phase = 
     s.qstd_c[0] = h->qstd_c[0]; s.qstd_c[1] = h->qstd_c[1]; s.B = B; s.out = h->std_sums;
     TRY(launch(h, "std_sums", k_std_sums, dim3(1), dim3(kThreads), 0, s));
   }
-  }  // phase != 2
-  if (phase == 1) return DSACT_OK;
+  }  // phase != PH_BACKWARD
+  if (phase == PH_FORWARD) return DSACT_OK;
   {
   const int L = Lq;   // the loss kernels read the critics' last hidden layer
   if (h->nq == 1) {
@@ -2936,7 +2949,7 @@ int enqueue_grads(dsact_handle* h, bool actor_backward, bool fused, int phase = 
   }
   for (size_t i = 0; i < h->bwdq.size(); ++i) TRY(run_stage(h, h->bwdq[i]));
   if (h->cnn) TRY(run_stage(h, h->dfeat_q));   // reads the step's padded copy of W0: safe against the fused Adam below
-  if (phase == 3) {
+  if (phase == PH_DP_CRITIC) {
     TRY(run_dw(h, h->dw_off[0], h->dw_off[2], false, false));
     if (h->cnn) TRY(enqueue_conv_backward(h, h->nq, false));
     TRY(sum_parts(h, 0, (size_t)h->nq * h->n_q));
@@ -2951,7 +2964,7 @@ actor_part:
   // tiles that may ride: the critics' + (behind heads_bwd only) the policy's output layer
   const int ride_end = h->bwdpi.empty() ? h->dw_off[2] : h->dw_pol_rest;
   int ride_hb = 0;
-  if (phase == 0) {
+  if (phase == PH_ALL) {
     ride_hb = (ride_end - h->dw_off[0]) / n_carriers;
     if (ride_hb > crit_tiles) ride_hb = crit_tiles;
   }
@@ -2980,7 +2993,7 @@ actor_part:
     NCH_DISPATCH(a.WL, CALL_HBWD);
   }
   const size_t np = h->bwdpi.size();
-  if (phase == 4) {
+  if (phase == PH_DP_ACTOR) {
     for (size_t i = 0; i < np; ++i) TRY(run_stage(h, h->bwdpi[i]));
     if (h->cnn) TRY(run_stage(h, h->dfeat_pi));
     TRY(run_dw(h, h->dw_off[2], h->dw_off[3], false, false));
@@ -3054,60 +3067,30 @@ static void destroy_graph_set(dsact_handle::GraphSet& g) {
 }
 // the active graph (if any) moves into the cache; nothing is destroyed
 static void stash_graph(dsact_handle* h) {
-  if (!(h->graph_exec != nullptr || h->pipe_graph)) return;
-  dsact_handle::GraphSet g;
-  g.graph = h->graph; g.exec = h->graph_exec;
-  for (int p = 0; p < dsact_handle::kPipePhases; ++p) { g.pgraph[p] = h->pgraph[p]; g.pexec[p] = h->pexec[p]; g.pargs[p] = h->pargs[p]; }
-  g.pipe = h->pipe_graph; g.merged = h->merged_graph; g.noise_table = h->graph_noise_table;
-  g.steps = h->graph_steps; g.flags = h->graph_flags;
-  h->graph_cache.push_back(g);
-  h->graph = nullptr; h->graph_exec = nullptr;
-  for (int p = 0; p < dsact_handle::kPipePhases; ++p) { h->pgraph[p] = nullptr; h->pexec[p] = nullptr; h->pargs[p] = nullptr; }
-  h->pipe_graph = false; h->graph_steps = 0; h->graph_noise_table = false;
+  if (!h->active.present()) return;
+  h->graph_cache.push_back(h->active);
+  h->active = dsact_handle::GraphSet();
 }
 // a cached graph of that shape becomes the active one (the caller stashed the previous one); false: none cached
 static bool activate_graph(dsact_handle* h, int steps, uint32_t flags, bool noise_table) {
   for (size_t i = 0; i < h->graph_cache.size(); ++i) {
-    dsact_handle::GraphSet& g = h->graph_cache[i];
+    const dsact_handle::GraphSet& g = h->graph_cache[i];
     if (g.steps != steps || g.flags != flags || g.noise_table != noise_table) continue;
-    h->graph = g.graph; h->graph_exec = g.exec;
-    for (int p = 0; p < dsact_handle::kPipePhases; ++p) { h->pgraph[p] = g.pgraph[p]; h->pexec[p] = g.pexec[p]; h->pargs[p] = (PipeFwd*)g.pargs[p]; }
-    h->pipe_graph = g.pipe; h->merged_graph = g.merged; h->graph_noise_table = g.noise_table;
-    h->graph_steps = g.steps; h->graph_flags = g.flags;
+    h->active = g;
     h->graph_cache.erase(h->graph_cache.begin() + (long)i);
     return true;
   }
   return false;
 }
-// every captured graph goes: the active one and the cached ones (they bake in pointers, hyper-parameters, launch forms)
 // the ACTIVE graph only (a failed or abandoned capture): cached graphs of other shapes stay valid
-static void drop_active_graph(dsact_handle* h) {
-  if (h->graph_exec) { hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-  if (h->graph) { hipGraphDestroy(h->graph); h->graph = nullptr; }
-  for (int p = 0; p < dsact_handle::kPipePhases; ++p) {
-    if (h->pexec[p]) { hipGraphExecDestroy(h->pexec[p]); h->pexec[p] = nullptr; }
-    if (h->pgraph[p]) { hipGraphDestroy(h->pgraph[p]); h->pgraph[p] = nullptr; }
-    if (h->pargs[p]) { hipFree(h->pargs[p]); h->pargs[p] = nullptr; }
-  }
-  h->pipe_graph = false;
-  h->graph_steps = 0;
-  h->graph_noise_table = false;
-}
+static void drop_active_graph(dsact_handle* h) { destroy_graph_set(h->active); }
+// every captured graph goes: the active one and the cached ones (they bake in pointers, hyper-parameters, launch forms)
 void drop_graphs(dsact_handle* h) {
-  if (h->graph_exec) { hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-  if (h->graph) { hipGraphDestroy(h->graph); h->graph = nullptr; }
-  for (int p = 0; p < dsact_handle::kPipePhases; ++p) {
-    if (h->pexec[p]) { hipGraphExecDestroy(h->pexec[p]); h->pexec[p] = nullptr; }
-    if (h->pgraph[p]) { hipGraphDestroy(h->pgraph[p]); h->pgraph[p] = nullptr; }
-    if (h->pargs[p]) { hipFree(h->pargs[p]); h->pargs[p] = nullptr; }
-  }
+  destroy_graph_set(h->active);
   for (auto& g : h->graph_cache) destroy_graph_set(g);
   h->graph_cache.clear();
-  h->pipe_graph = false;
-  h->graph_steps = 0;
-  h->graph_noise_table = false;
 }
-bool have_graph(const dsact_handle* h) { return h->graph_exec != nullptr || h->pipe_graph; }
+bool have_graph(const dsact_handle* h) { return h->active.present(); }
 // active OR cached: what the "baked into the captured graph" refusals have to look at (dsact_run_group keeps graphs of other
 // group lengths in the cache, and a failed build may leave no active graph beside them)
 bool any_graph(const dsact_handle* h) { return have_graph(h) || !h->graph_cache.empty(); }
@@ -3138,9 +3121,9 @@ int check_handoff(dsact_handle* h) {
                 e_sync != hipSuccess ? "; HIP also reported: " : "", e_sync != hipSuccess ? hipGetErrorString(e_sync) : "");
   }
   const bool had_graph = have_graph(h);
-  const int steps = had_graph ? h->graph_steps : h->want_graph_steps;
-  const uint32_t gflags = had_graph ? h->graph_flags : h->want_graph_flags;
-  const bool noise_tab = h->graph_noise_table;
+  const int steps = had_graph ? h->active.steps : h->want_graph_steps;
+  const uint32_t gflags = had_graph ? h->active.flags : h->want_graph_flags;
+  const bool noise_tab = h->active.noise_table;
   h->fwd_merge = false;
   h->pi_merge = false;
   h->handoff_failures += 1;
@@ -3159,16 +3142,13 @@ int check_handoff(dsact_handle* h) {
   if (wanted && twin_rc == DSACT_OK) {
     // (the re-capture must not trip over an earlier, still unacknowledged timeout: capturing launches nothing)
     h->state_invalid = false;
-    h->noise_table_on = noise_tab;
-    rebuilt = dsact_graph_build(h, steps, gflags);
-    h->noise_table_on = false;
-    if (rebuilt == DSACT_OK) h->graph_noise_table = noise_tab;
+    rebuilt = build_graph(h, steps, gflags, noise_tab, false);
   }
   // not re-captured: remembered, and built by the first replay after the caller's acknowledgement
   h->want_graph_steps = (wanted && rebuilt != DSACT_OK) ? steps : 0;
   h->want_graph_flags = gflags;
   h->in_handoff = false;
-  h->state_invalid = true;   // (after the re-capture: dsact_graph_build itself is an entry point that refuses an invalid state)
+  h->state_invalid = true;   // (after the re-capture: build_graph makes an entry point's checks and refuses an invalid state)
   const hipError_t e_hip = e_dev != hipSuccess ? e_dev : e_sync != hipSuccess ? e_sync : e_set;
   return fail(h, DSACT_E_HIP,
               "an in-launch hand-over timed out: a workgroup waited > 0.1 s for its producers' ready flags, so every result "
@@ -3185,7 +3165,7 @@ static int ensure_wanted_graph(dsact_handle* h) {
   if (have_graph(h) || h->want_graph_steps <= 0) return DSACT_OK;
   const int steps = h->want_graph_steps;
   h->want_graph_steps = 0;
-  return dsact_graph_build(h, steps, h->want_graph_flags);
+  return dsact_graph_build(h, steps, h->want_graph_flags);   // (the noise mode of a wanted graph is not remembered: Philox)
 }
 
 bool has_ring(const dsact_handle* h) { return h->rb_act != nullptr; }
@@ -3209,13 +3189,19 @@ int check_codes(dsact_handle* h) {
               h->miss_rec.count, (double)v, bits, h->miss_rec.row);
 }
 
-int check_ready(dsact_handle* h, bool need_batch) {
+// what every update entry point asks first: no pending hand-over timeout, no codebook miss, no unacknowledged invalid state
+static int check_usable(dsact_handle* h) {
   if (!h) return DSACT_E_INVALID;
   TRY(check_handoff(h));
   TRY(check_codes(h));
   if (h->state_invalid)
     return fail(h, DSACT_E_STATE, "device state is invalid after a hand-over timeout: restore parameters / optimiser state, then "
                                   "call dsact_set_state or dsact_bind_arenas");
+  return DSACT_OK;
+}
+
+int check_ready(dsact_handle* h, bool need_batch) {
+  TRY(check_usable(h));
   if (!h->online || !h->grads) return fail(h, DSACT_E_STATE, "arenas not bound (dsact_bind_arenas)");
   if (!h->limits_set) return fail(h, DSACT_E_STATE, "action limits not set (dsact_set_action_limits)");
   if (need_batch && !h->have_batch) return fail(h, DSACT_E_STATE, "no minibatch staged (dsact_gather / dsact_load_batch)");
@@ -4369,9 +4355,9 @@ static int enqueue_allreduce(dsact_handle* h, float* buf, size_t count, int op) 
 static int enqueue_graph_step_dp(dsact_handle* h) {
   TRY(enqueue_gather(h, h->idx_table, h->idx_rows, 1, 0, 0));
   if (h->use_std_sums) {
-    TRY(enqueue_grads(h, true, false, 1));
+    TRY(enqueue_grads(h, true, false, PH_FORWARD));
     TRY(enqueue_allreduce(h, h->std_sums, 2, kNcclSum));
-    TRY(enqueue_grads(h, true, false, 2));
+    TRY(enqueue_grads(h, true, false, PH_BACKWARD));
   } else {
     TRY(enqueue_grads(h, true, false));
   }
@@ -4414,11 +4400,11 @@ static int capture_updates(dsact_handle* h, int n, uint32_t flags, bool merged, 
       if (flags & DSACT_F_DATA_PARALLEL) {
         // local gradients (the next update's gather and this one's bookkeeping ride in the loss launch as on the single-GPU
         // path) -> all-reduce -> streaming Adam/Polyak -> packed weight copies rebuilt for the next forward
-        rc = enqueue_grads(h, true, false, 0, &ride);
+        rc = enqueue_grads(h, true, false, PH_ALL, &ride);
         if (rc == DSACT_OK) rc = enqueue_allreduce(h, h->grads, h->n_online + 2, kNcclAvg);
         if (rc == DSACT_OK) rc = enqueue_adam_pack(h);
       } else {
-        rc = enqueue_grads(h, actor, true, 0, &ride);
+        rc = enqueue_grads(h, actor, true, PH_ALL, &ride);
       }
     }
     select_set(h, 0);
@@ -4440,12 +4426,11 @@ static int capture_updates(dsact_handle* h, int n, uint32_t flags, bool merged, 
 // The forward launches read their unit tables from `dev_args` (n PipeFwd, filled here BEFORE anything is enqueued).
 struct PipePlan {
   std::vector<PipeFwd> host; std::vector<char> pre, dop;
-  std::vector<char> defer;        // update s leaves the policy alone and has a successor: its policy backward rides in launch s + 1
-  std::vector<BwdPiArgs> bp;      // [s]: the deferred policy backward of update s - 1 (valid when defer[s - 1])
+  std::vector<BwdForm> form;      // [s]: launch form of update s's backward. defers_pi: the update leaves the policy alone and has a
+                                  // successor, its policy backward rides in launch s + 1; merged_bwd: its bookkeeping rides in its forward
+  std::vector<BwdPiArgs> bp;      // [s]: the deferred policy backward of update s - 1 (valid when defers_pi(form[s - 1]))
   std::vector<int> bp_rg;
   bool dp = false;                // local gradients -> all-reduce -> k_adam_pack instead of the fused optimiser
-  std::vector<char> bqt;          // update s: critics' backward + their tiles + close as one launch (its bookkeeping rides in its forward)
-  std::vector<char> bqp;          // update s (moves the policy): critics' + policy backward + all tiles + close as one launch
   bool skip = false;              // DSACT_F_SKIP_ACTOR_ON_OFF_ITERS: the discarded policy backward is not computed at all
   std::vector<char> leaves;       // update s leaves policy / alpha / targets alone
 };
@@ -4454,7 +4439,7 @@ static int plan_updates_pipe(dsact_handle* h, int n, int phase, PipePlan& plan, 
   const int D = h->cfg.delay_update;
   auto set_of = [&](int s) { return (s - (n - 1)) & (dsact_handle::kPipeSets - 1); };
   plan.host.resize((size_t)n); plan.pre.resize((size_t)n); plan.dop.resize((size_t)n);
-  plan.defer.assign((size_t)n, 0); plan.bp.resize((size_t)n); plan.bp_rg.assign((size_t)n, 2);
+  plan.form.assign((size_t)n, BWD_PLAIN); plan.bp.resize((size_t)n); plan.bp_rg.assign((size_t)n, 2);
   // the discarded policy backward can move when it is the merged launch's (chain + its own tiles behind the arrival counter)
   const int rg_pi = h->B >= 8 ? h->cRG : 1;
   // (data parallel: the same -- on those updates k_adam_pack leaves the policy alone, so the policy segment of the all-reduced
@@ -4463,8 +4448,6 @@ static int plan_updates_pipe(dsact_handle* h, int n, int phase, PipePlan& plan, 
   plan.dp = (flags & DSACT_F_DATA_PARALLEL) != 0;
   plan.skip = (flags & DSACT_F_SKIP_ACTOR_ON_OFF_ITERS) != 0 && !plan.dp;
   plan.leaves.assign((size_t)n, 0);
-  plan.bqt.assign((size_t)n, 0);
-  plan.bqp.assign((size_t)n, 0);
   const bool bqt = bqt_ok(h);   // (data-parallel graphs too: the tiles then store gradients and the closing block closes nothing)
   // (4-row critic slices, 8-row policy slices: the instantiation k_chain_bwd_qpt is built for)
   const bool bqp = bqt && h->nq == 2 && !h->env_no_bqp && chain_rg(h, 4, true) == 1 && rg_pi == 2;
@@ -4477,7 +4460,7 @@ static int plan_updates_pipe(dsact_handle* h, int n, int phase, PipePlan& plan, 
     const bool do_pre = s + 1 < n && leaves_policy;
     plan.leaves[(size_t)s] = leaves_policy;
     const BwdPiArgs* bp = nullptr;
-    if (s > 0 && plan.defer[(size_t)s - 1]) {
+    if (s > 0 && defers_pi(plan.form[(size_t)s - 1])) {
       apply_pipe_set(h, set_of(s - 1));   // the deferred backward works on the PREVIOUS update's minibatch
       BwdPiArgs& a = plan.bp[(size_t)s];
       // (the deferred chain shares its launch with forward chains, not with ~500 riding tiles: 4-row slices by default)
@@ -4488,10 +4471,10 @@ static int plan_updates_pipe(dsact_handle* h, int n, int phase, PipePlan& plan, 
       a.dw.store_g = 0;                   // nothing reads this gradient (fused: no optimiser step on that update either)
       bp = &a;
     }
-    plan.defer[(size_t)s] = do_pre && can_defer && !plan.skip;   // (skip: there is no policy backward to move)
-    plan.bqt[(size_t)s] = plan.defer[(size_t)s] && bqt;
-    plan.bqp[(size_t)s] = !leaves_policy && bqp;
-    rc = pipe_fwd_build(h, set_of(s), set_of(s + 1), pre, do_pre, plan.host[(size_t)s], bp, plan.bqt[(size_t)s] != 0 || plan.bqp[(size_t)s] != 0);
+    const bool defer = do_pre && can_defer && !plan.skip;   // (skip: there is no policy backward to move)
+    const BwdForm form = defer ? (bqt ? BWD_QT : BWD_DEFER_PI) : (!leaves_policy && bqp) ? BWD_QPT : BWD_PLAIN;
+    plan.form[(size_t)s] = form;
+    rc = pipe_fwd_build(h, set_of(s), set_of(s + 1), pre, do_pre, plan.host[(size_t)s], bp, merged_bwd(form));
     plan.pre[(size_t)s] = pre; plan.dop[(size_t)s] = do_pre;
     pre = do_pre;
   }
@@ -4526,7 +4509,7 @@ static int enqueue_updates_pipe(dsact_handle* h, int n, const PipePlan& plan, Pi
   }
   for (int s = 0; s < n && rc == DSACT_OK; ++s) {
     apply_pipe_set(h, set_of(s));
-    const bool carries = s > 0 && plan.defer[(size_t)s - 1];
+    const bool carries = s > 0 && defers_pi(plan.form[(size_t)s - 1]);
     rc = launch_chain_fwd_pipe(h, pipe_fwd_name(pre_v[(size_t)s], do_v[(size_t)s]), host[(size_t)s], dev_args + s,
                                carries ? &plan.bp[(size_t)s] : nullptr, plan.bp_rg[(size_t)s]);
     if (rc != DSACT_OK) break;
@@ -4542,26 +4525,15 @@ static int enqueue_updates_pipe(dsact_handle* h, int n, const PipePlan& plan, Pi
       ride.g = gather_args(h, h->idx_table, h->idx_rows, 1, 0, 1);   // (st / hp of the bookkeeping block)
       ride.n_gather = 0;
     }
-    ride.bookkeeping = (plan.bqt[(size_t)s] || plan.bqp[(size_t)s]) ? 0 : 1;   // (merged backward launches: the forward launch did the bookkeeping)
+    const BwdForm form = plan.form[(size_t)s];
+    ride.bookkeeping = merged_bwd(form) ? 0 : 1;   // (merged backward launches: the forward launch did the bookkeeping)
     if (plan.dp) {
-      h->pipe_defer_now = plan.defer[(size_t)s] != 0;
-      h->bqt_now = plan.bqt[(size_t)s] != 0;
-      h->bqp_now = plan.bqp[(size_t)s] != 0;
-      rc = enqueue_grads(h, true, false, 2, &ride);
-      h->pipe_defer_now = false;
-      h->bqt_now = false;
-      h->bqp_now = false;
+      rc = enqueue_grads(h, true, false, PH_BACKWARD, &ride, form);
       if (rc == DSACT_OK) rc = enqueue_allreduce(h, h->grads, h->n_online + 2, kNcclAvg);
       if (rc == DSACT_OK) rc = enqueue_adam_pack(h);
       continue;
     }
-    h->pipe_defer_now = plan.defer[(size_t)s] != 0;
-    h->bqt_now = plan.bqt[(size_t)s] != 0;
-    h->bqp_now = plan.bqp[(size_t)s] != 0;
-    rc = enqueue_grads(h, !(plan.skip && plan.leaves[(size_t)s]), true, 2, &ride);
-    h->pipe_defer_now = false;
-    h->bqt_now = false;
-    h->bqp_now = false;
+    rc = enqueue_grads(h, !(plan.skip && plan.leaves[(size_t)s]), true, PH_BACKWARD, &ride, form);
   }
   apply_pipe_set(h, 0);
   h->mirror_w0 = false;
@@ -4593,7 +4565,9 @@ static bool pipe_eligible(const dsact_handle* h, int steps_per_graph, uint32_t f
          D <= dsact_handle::kPipePhases && steps_per_graph >= 2;
 }
 
-int dsact_graph_build(dsact_handle* h, int32_t steps_per_graph, uint32_t flags) {
+// dsact_graph_build's body. noise_table: the graph's gathers read the noise table of dsact_run_group (else device Philox noise /
+// the staged noise); keep_cache: the previous active graph is stashed, not destroyed, and cached graphs survive a failure
+static int build_graph(dsact_handle* h, int steps_per_graph, uint32_t flags, bool noise_table, bool keep_cache) {
   TRY(check_ready(h, false));
   if (steps_per_graph < 1) return fail(h, DSACT_E_INVALID, "steps_per_graph must be >= 1");
   if (!h->idx_table) return fail(h, DSACT_E_STATE, "upload an index table first (dsact_upload_index_table)");
@@ -4603,7 +4577,7 @@ int dsact_graph_build(dsact_handle* h, int32_t steps_per_graph, uint32_t flags) 
     return fail(h, DSACT_E_INVALID, "with DSACT_F_SKIP_ACTOR_ON_OFF_ITERS steps_per_graph must be a multiple of delay_update");
   if ((flags & DSACT_F_DATA_PARALLEL) && !h->comm) return fail(h, DSACT_E_STATE, "DSACT_F_DATA_PARALLEL needs dsact_comm_init");
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->build_keeps_cache) stash_graph(h); else drop_graphs(h);
+  if (keep_cache) stash_graph(h); else drop_graphs(h);
   h->want_graph_steps = 0;
   if (h->flags_dirty && h->chain_flags) {   // not inside the graph: the captured updates clear the flags themselves
     HIPCHK(h, hipMemset(h->chain_flags, 0, kChainFlags * sizeof(int)));
@@ -4616,18 +4590,19 @@ int dsact_graph_build(dsact_handle* h, int32_t steps_per_graph, uint32_t flags) 
   // (data parallel: only on the chain path, whose packed copies k_pack can rebuild after the streaming optimiser)
   const bool merged = !h->cnn && h->use_w1p && h->dw_chunks == 1 && !h->use_std_sums && h->alt_ws != nullptr &&
                       (!(flags & DSACT_F_DATA_PARALLEL) || h->chain_ok);
-  h->merged_graph = merged;
   // Pipelined graph (fused single-GPU update on the row-slice chains with both in-launch hand-overs available, device RNG,
   // 2 <= delay_update <= 4, at least 2 updates per graph): one graph per phase first_iteration % delay_update
   const int D = h->cfg.delay_update;
+  dsact_handle::GraphSet& g = h->active;   // (empty: stashed or dropped above)
+  h->noise_table_on = noise_table;         // read below the captures (noise_args, pipe_eligible); no return until it is cleared
   const bool pipe = pipe_eligible(h, steps_per_graph, flags);
   const bool was_prof = h->profiling;
   h->profiling = false;
   int rc = DSACT_OK;
   if (pipe) {
     rc = alloc_pipe_sets(h);
-    for (int ph = 0; ph < D && rc == DSACT_OK; ++ph) rc = capture_updates_pipe(h, steps_per_graph, ph, &h->pgraph[ph], &h->pexec[ph], &h->pargs[ph], flags);
-    h->pipe_graph = rc == DSACT_OK;
+    for (int ph = 0; ph < D && rc == DSACT_OK; ++ph) rc = capture_updates_pipe(h, steps_per_graph, ph, &g.pgraph[ph], &g.pexec[ph], &g.pargs[ph], flags);
+    g.pipe = rc == DSACT_OK;
     if (rc != DSACT_OK) {   // (e.g. out of memory for the extra minibatch sets): the plain graph serves the same contract
       drop_active_graph(h);   // the partially built pipelined graph only: cached graphs of other shapes stay
       (void)hipGetLastError();
@@ -4635,31 +4610,36 @@ int dsact_graph_build(dsact_handle* h, int32_t steps_per_graph, uint32_t flags) 
       rc = DSACT_OK;
     }
   }
-  if (!h->pipe_graph) {
-    rc = capture_updates(h, steps_per_graph, flags, merged, &h->graph, &h->graph_exec);
+  if (!g.pipe) {
+    rc = capture_updates(h, steps_per_graph, flags, merged, &g.graph, &g.exec);
   }
   h->profiling = was_prof;
-  if (rc != DSACT_OK) { if (h->build_keeps_cache) drop_active_graph(h); else drop_graphs(h); return rc; }
-  h->graph_steps = steps_per_graph;
-  h->graph_flags = flags;
+  h->noise_table_on = false;
+  if (rc != DSACT_OK) { if (keep_cache) drop_active_graph(h); else drop_graphs(h); return rc; }
+  g.merged = merged; g.noise_table = noise_table;
+  g.steps = steps_per_graph;
+  g.flags = flags;
   h->have_batch = true;
   return DSACT_OK;
 }
+
+int dsact_graph_build(dsact_handle* h, int32_t steps_per_graph, uint32_t flags) { return build_graph(h, steps_per_graph, flags, false, false); }
 
 // n_groups back-to-back replays of the captured updates
 static int launch_groups(dsact_handle* h, int64_t first_iteration, int64_t n_groups) {
   h->uev_valid = false;
   int64_t i = 0;
-  if (h->pipe_graph) {
-    // the pipelined graphs are captured per phase of the delayed update: replay i starts at first_iteration + i * graph_steps
+  const dsact_handle::GraphSet& g = h->active;
+  if (g.pipe) {
+    // the pipelined graphs are captured per phase of the delayed update: replay i starts at first_iteration + i * steps
     const int D = h->cfg.delay_update;
     for (; i < n_groups; ++i) {
-      const int ph = (int)(((first_iteration + i * h->graph_steps) % D + D) % D);
-      HIPCHK(h, hipGraphLaunch(h->pexec[ph], h->stream));
+      const int ph = (int)(((first_iteration + i * g.steps) % D + D) % D);
+      HIPCHK(h, hipGraphLaunch(g.pexec[ph], h->stream));
     }
     return DSACT_OK;
   }
-  for (; i < n_groups; ++i) HIPCHK(h, hipGraphLaunch(h->graph_exec, h->stream));
+  for (; i < n_groups; ++i) HIPCHK(h, hipGraphLaunch(g.exec, h->stream));
   return DSACT_OK;
 }
 
@@ -4673,20 +4653,15 @@ static int set_device_iteration(dsact_handle* h, long long it) {
 }
 
 int dsact_graph_run(dsact_handle* h, int64_t first_iteration, int64_t n_steps) {
-  if (!h) return DSACT_E_INVALID;
-  TRY(check_handoff(h));
-  TRY(check_codes(h));
-  if (h->state_invalid)
-    return fail(h, DSACT_E_STATE, "device state is invalid after a hand-over timeout: restore parameters / optimiser state, then "
-                                  "call dsact_set_state or dsact_bind_arenas");
+  TRY(check_usable(h));   // (not check_ready: a replay skips its other checks and keeps dev_it_next)
   TRY(ensure_wanted_graph(h));
   if (!have_graph(h)) return fail(h, DSACT_E_STATE, "dsact_graph_build first");
-  if (n_steps % h->graph_steps) return fail(h, DSACT_E_INVALID, "n_steps must be a multiple of steps_per_graph");
-  if ((h->graph_flags & DSACT_F_SKIP_ACTOR_ON_OFF_ITERS) && first_iteration % h->cfg.delay_update)
+  if (n_steps % h->active.steps) return fail(h, DSACT_E_INVALID, "n_steps must be a multiple of steps_per_graph");
+  if ((h->active.flags & DSACT_F_SKIP_ACTOR_ON_OFF_ITERS) && first_iteration % h->cfg.delay_update)
     return fail(h, DSACT_E_INVALID, "first_iteration must be a multiple of delay_update for a graph captured with DSACT_F_SKIP_ACTOR_ON_OFF_ITERS");
   HIPCHK(h, hipSetDevice(h->device));
   TRY(set_device_iteration(h, first_iteration));
-  TRY(launch_groups(h, first_iteration, n_steps / h->graph_steps));
+  TRY(launch_groups(h, first_iteration, n_steps / h->active.steps));
   h->dev_it_next = first_iteration + n_steps;
   return policy_moved(h);
 }
@@ -4723,17 +4698,10 @@ int dsact_run_group(dsact_handle* h, int64_t first_iteration, int32_t n_steps, c
   }
   // ---- the graph of this shape: active, cached, or captured now
   const bool want_table = noise != nullptr;
-  if (!(have_graph(h) && h->graph_steps == n_steps && h->graph_flags == flags && h->graph_noise_table == want_table)) {
+  const dsact_handle::GraphSet& g = h->active;
+  if (!(g.present() && g.steps == n_steps && g.flags == flags && g.noise_table == want_table)) {
     stash_graph(h);
-    if (!activate_graph(h, n_steps, flags, want_table)) {
-      h->build_keeps_cache = true;
-      h->noise_table_on = want_table;
-      const int rc = dsact_graph_build(h, n_steps, flags);
-      h->noise_table_on = false;
-      h->build_keeps_cache = false;
-      TRY(rc);
-      h->graph_noise_table = want_table;
-    }
+    if (!activate_graph(h, n_steps, flags, want_table)) TRY(build_graph(h, n_steps, flags, want_table, true));
   }
   // ---- rows -> pinned slot -> tables (stream-ordered; the slot is reused four groups later)
   // idx == nullptr (dsact_set_index_rng): no staging, conversion or H2D of index rows -- k_draw_indices fills the table rows on the
@@ -4799,14 +4767,14 @@ int dsact_dp_enqueue_grads_critic(dsact_handle* h, uint32_t flags) {
   (void)flags;
   TRY(enqueue_gather(h, h->idx_table, h->idx_rows, 1, 0, 0));
   h->have_batch = true;
-  return enqueue_grads(h, true, false, 3);
+  return enqueue_grads(h, true, false, PH_DP_CRITIC);
 }
 
 int dsact_dp_enqueue_grads_actor(dsact_handle* h, uint32_t flags) {
   TRY(check_ready(h, true));
   HIPCHK(h, hipSetDevice(h->device));
   (void)flags;
-  return enqueue_grads(h, true, false, 4);
+  return enqueue_grads(h, true, false, PH_DP_ACTOR);
 }
 
 int dsact_dp_set_strict(dsact_handle* h, float* std_sums_dev) {
@@ -4828,7 +4796,7 @@ int dsact_dp_enqueue_forward(dsact_handle* h, uint32_t flags) {
   (void)flags;
   TRY(enqueue_gather(h, h->idx_table, h->idx_rows, 1, 0, 0));
   h->have_batch = true;
-  return enqueue_grads(h, true, false, 1);
+  return enqueue_grads(h, true, false, PH_FORWARD);
 }
 
 int dsact_dp_enqueue_backward(dsact_handle* h, uint32_t flags) {
@@ -4836,7 +4804,7 @@ int dsact_dp_enqueue_backward(dsact_handle* h, uint32_t flags) {
   if (!h->use_std_sums) return fail(h, DSACT_E_STATE, "dsact_dp_set_strict first");
   HIPCHK(h, hipSetDevice(h->device));
   (void)flags;
-  return enqueue_grads(h, true, false, 2);
+  return enqueue_grads(h, true, false, PH_BACKWARD);
 }
 
 int dsact_dp_enqueue_apply(dsact_handle* h) {
@@ -4954,10 +4922,10 @@ int dsact_time_steps(dsact_handle* h, int64_t first_iteration, int64_t n_steps, 
   if (use_graph) {
     TRY(ensure_wanted_graph(h));
     if (!have_graph(h)) return fail(h, DSACT_E_STATE, "dsact_graph_build first");
-    if (n_steps % h->graph_steps) return fail(h, DSACT_E_INVALID, "n_steps must be a multiple of steps_per_graph");
-    if ((h->graph_flags & DSACT_F_SKIP_ACTOR_ON_OFF_ITERS) && first_iteration % h->cfg.delay_update)
+    if (n_steps % h->active.steps) return fail(h, DSACT_E_INVALID, "n_steps must be a multiple of steps_per_graph");
+    if ((h->active.flags & DSACT_F_SKIP_ACTOR_ON_OFF_ITERS) && first_iteration % h->cfg.delay_update)
       return fail(h, DSACT_E_INVALID, "first_iteration must be a multiple of delay_update");
-    TRY(launch_groups(h, first_iteration, n_steps / h->graph_steps));
+    TRY(launch_groups(h, first_iteration, n_steps / h->active.steps));
     h->dev_it_next = first_iteration + n_steps;
   } else {
     h->dev_it_next = -1;
@@ -5279,9 +5247,9 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "act_wait_us")) *value = h->act_wait_us;
   else if (!strcmp(name, "fat")) *value = (h->fat ? 1.0 : 0.0) + (h->fat_bwd ? 2.0 : 0.0);
   else if (!strcmp(name, "handoff_failures")) *value = (double)h->handoff_failures;
-  else if (!strcmp(name, "graph_steps")) *value = (double)h->graph_steps;
-  else if (!strcmp(name, "pipe_graph")) *value = h->pipe_graph ? 1.0 : 0.0;   // the captured graphs are the pipelined ones
-  else if (!strcmp(name, "merged_graph")) *value = h->merged_graph ? 1.0 : 0.0;   // captured with the merged gather (else one enqueue_graph_step per update)
+  else if (!strcmp(name, "graph_steps")) *value = (double)h->active.steps;
+  else if (!strcmp(name, "pipe_graph")) *value = h->active.pipe ? 1.0 : 0.0;   // the captured graphs are the pipelined ones
+  else if (!strcmp(name, "merged_graph")) *value = h->active.merged ? 1.0 : 0.0;   // captured with the merged gather (else one enqueue_graph_step per update)
   else if (!strcmp(name, "state_invalid")) *value = h->state_invalid ? 1.0 : 0.0;
   else if (!strcmp(name, "act_batch_calls")) *value = (double)h->ab_calls;   // dsact_act_sample_batch chunks launched on the GPU
   else if (!strcmp(name, "act_mode_calls")) *value = (double)h->ab_mode_calls;   // dsact_act_mode_batch chunks launched on the GPU
@@ -5294,7 +5262,7 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "eval_polls")) *value = (double)h->eval_polls;                   // dsact_eval_poll waits
   else if (!strcmp(name, "act_fast")) *value = act_fast_ok(h) ? 1.0 : 0.0;     // dsact_act_sample / the one-launch acting forward serve this handle
   else if (!strcmp(name, "graph_cache")) *value = (double)h->graph_cache.size();   // inactive captured graphs kept by dsact_run_group
-  else if (!strcmp(name, "graph_noise_table")) *value = h->graph_noise_table ? 1.0 : 0.0;
+  else if (!strcmp(name, "graph_noise_table")) *value = h->active.noise_table ? 1.0 : 0.0;
   else if (!strcmp(name, "twin_par")) *value = (h->twin_par ? 1.0 : 0.0) + (h->twin_merged ? 2.0 : 0.0);   // CNN nets: trunks as own workgroups (+2: one launch)
   else return DSACT_E_INVALID;
   return DSACT_OK;
