@@ -304,6 +304,12 @@ struct dsact_handle {
   int ev_n = 0, ev_e = 0;                 // the running evaluation's N and E (0: no dsact_eval_begin yet)
   unsigned long long act_mode_dev_calls = 0;   // dsact_act_mode_device chunks launched
   unsigned long long eval_commit_calls = 0, eval_polls = 0;
+  // episode statistics of the training environments (dsact_track_*): ONE device block of tk_n rows laid out
+  // as eight 8-byte columns (cur_ret, episodes, terminated, ret_sum, ret_min, ret_max, len_sum, last_ret) and two 4-byte
+  // columns (cur_len, last_len), kTrackRowBytes per row, and its pinned landing place (dsact_track_read)
+  unsigned char* tk_dev = nullptr; unsigned char* tk_host = nullptr;
+  int tk_cap = 0, tk_n = 0;               // rows allocated; the running statistics' N (0: no dsact_track_begin yet)
+  unsigned long long track_commit_calls = 0, track_reads = 0;
   int mode_host_rows = kModeHostRows;   // dsact_act_mode_batch's host / GPU crossover (debug switch "mode_host_rows": measurements)
   unsigned long long act_host_calls = 0, act_copies = 0;
   // behaviour policy (dsact_behaviour_hold): a device copy of the policy net taken on the handle's stream
@@ -3570,6 +3576,8 @@ int dsact_destroy(dsact_handle* h) {
   for (void* p : {(void*)h->ev_ep, (void*)h->ev_acc, (void*)h->ev_len, (void*)h->ev_returns, (void*)h->ev_lengths, (void*)h->ev_remaining})
     if (p) hipFree(p);
   if (h->ev_remaining_host) hipHostFree(h->ev_remaining_host);
+  if (h->tk_dev) hipFree(h->tk_dev);
+  if (h->tk_host) hipHostFree(h->tk_host);
   for (int i = 0; i < 2; ++i) if (h->ab_h[i]) hipFree(h->ab_h[i]);
   if (h->pol_host) hipHostFree(h->pol_host);
   if (h->pol_ev) hipEventDestroy(h->pol_ev);
@@ -5260,6 +5268,8 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "act_mode_dev_calls")) *value = (double)h->act_mode_dev_calls;   // dsact_act_mode_device chunks launched
   else if (!strcmp(name, "eval_commit_calls")) *value = (double)h->eval_commit_calls;     // dsact_eval_commit launches
   else if (!strcmp(name, "eval_polls")) *value = (double)h->eval_polls;                   // dsact_eval_poll waits
+  else if (!strcmp(name, "track_commit_calls")) *value = (double)h->track_commit_calls;   // dsact_track_commit launches
+  else if (!strcmp(name, "track_reads")) *value = (double)h->track_reads;                 // dsact_track_read waits
   else if (!strcmp(name, "act_fast")) *value = act_fast_ok(h) ? 1.0 : 0.0;     // dsact_act_sample / the one-launch acting forward serve this handle
   else if (!strcmp(name, "graph_cache")) *value = (double)h->graph_cache.size();   // inactive captured graphs kept by dsact_run_group
   else if (!strcmp(name, "graph_noise_table")) *value = h->active.noise_table ? 1.0 : 0.0;
@@ -5688,6 +5698,83 @@ int dsact_eval_read(dsact_handle* h, double* returns, int32_t* lengths, int32_t 
     return fail(h, DSACT_E_STATE, "dsact_eval_read: %d of %d episodes have not ended", *h->ev_remaining_host, h->ev_e);
   HIPCHK(h, hipMemcpy(returns, h->ev_returns, (size_t)n_episodes * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(h, hipMemcpy(lengths, h->ev_lengths, (size_t)n_episodes * sizeof(int), hipMemcpyDeviceToHost));
+  return check_handoff(h);
+}
+
+// ---- episode statistics of the training environments ------------------------------------------------
+// the state block's columns for n rows: eight 8-byte columns, then two 4-byte columns (the 8-byte columns are 8-byte aligned; the int
+// columns 4-byte aligned: last_len starts at 8 * col + 4 n, which is no multiple of 8 when n is odd)
+constexpr size_t kTrackRowBytes = 8 * 8 + 2 * 4;
+static TrackArgs track_args(unsigned char* base, int n) {
+  TrackArgs a;
+  memset(&a, 0, sizeof(a));
+  const size_t col = (size_t)n * 8;
+  a.cur_ret = (double*)(base + 0 * col); a.episodes = (long long*)(base + 1 * col); a.terminated = (long long*)(base + 2 * col);
+  a.ret_sum = (double*)(base + 3 * col); a.ret_min = (double*)(base + 4 * col); a.ret_max = (double*)(base + 5 * col);
+  a.len_sum = (long long*)(base + 6 * col); a.last_ret = (double*)(base + 7 * col);
+  a.cur_len = (int*)(base + 8 * col); a.last_len = (int*)(base + 8 * col + (size_t)n * 4);
+  a.N = n;
+  return a;
+}
+static int track_init(dsact_handle* h, int all) {
+  return launch(h, "track_init", k_track_init, dim3((unsigned)((h->tk_n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                track_args(h->tk_dev, h->tk_n), all);
+}
+
+int dsact_track_begin(dsact_handle* h, int32_t n_envs) {
+  if (!h) return DSACT_E_INVALID;
+  if (n_envs < 1) return fail(h, DSACT_E_INVALID, "dsact_track_begin: n_envs = %d must be >= 1", (int)n_envs);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (n_envs > h->tk_cap) {
+    // the commits enqueued so far (if any) write the old block: they finish before it goes
+    h->tk_n = 0;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->tk_dev) HIPCHK(h, hipFree(h->tk_dev));
+    if (h->tk_host) HIPCHK(h, hipHostFree(h->tk_host));
+    h->tk_dev = nullptr; h->tk_host = nullptr; h->tk_cap = 0;
+    HIPCHK(h, hipMalloc((void**)&h->tk_dev, (size_t)n_envs * kTrackRowBytes));
+    HIPCHK(h, hipHostMalloc((void**)&h->tk_host, (size_t)n_envs * kTrackRowBytes, hipHostMallocDefault));
+    h->tk_cap = n_envs;
+  }
+  h->tk_n = n_envs;
+  return track_init(h, 1);
+}
+
+int dsact_track_commit(dsact_handle* h, const float* reward_dev, const uint8_t* terminated_dev, const uint8_t* truncated_dev,
+                       int32_t n_steps) {
+  if (!h || !reward_dev || !terminated_dev || !truncated_dev) return DSACT_E_INVALID;
+  if (h->tk_n < 1) return fail(h, DSACT_E_STATE, "dsact_track_commit before dsact_track_begin");
+  if (n_steps < 1) return fail(h, DSACT_E_INVALID, "dsact_track_commit: n_steps = %d must be >= 1", (int)n_steps);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!on_handle_gpu(h, reward_dev) || !on_handle_gpu(h, terminated_dev) || !on_handle_gpu(h, truncated_dev))
+    return fail(h, DSACT_E_INVALID, "dsact_track_commit takes device pointers on the handle's GPU");
+  TRY(check_handoff_counted(h));
+  TrackArgs a = track_args(h->tk_dev, h->tk_n);
+  a.reward = reward_dev; a.term = terminated_dev; a.trunc = truncated_dev; a.T = n_steps;
+  TRY(launch(h, "track_commit", k_track_commit, dim3((unsigned)((h->tk_n + kThreads - 1) / kThreads)), dim3(kThreads), 0, a));
+  h->track_commit_calls++;
+  return DSACT_OK;
+}
+
+// the one wait of the feature: the whole block behind everything enqueued so far, then (clear) the totals' initialisation
+int dsact_track_read(dsact_handle* h, int32_t n_envs, int64_t* episodes, int64_t* terminated, double* ret_sum, double* ret_min,
+                     double* ret_max, int64_t* len_sum, double* last_ret, int32_t* last_len, double* cur_ret, int32_t* cur_len,
+                     int32_t clear) {
+  if (!h || !episodes || !terminated || !ret_sum || !ret_min || !ret_max || !len_sum || !last_ret || !last_len || !cur_ret || !cur_len)
+    return DSACT_E_INVALID;
+  if (h->tk_n < 1) return fail(h, DSACT_E_STATE, "dsact_track_read before dsact_track_begin");
+  if (n_envs != h->tk_n) return fail(h, DSACT_E_INVALID, "dsact_track_read: n_envs = %d, the statistics have %d rows", (int)n_envs, h->tk_n);
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t n = (size_t)h->tk_n;
+  HIPCHK(h, hipMemcpyAsync(h->tk_host, h->tk_dev, n * kTrackRowBytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->track_reads++;
+  const TrackArgs s = track_args(h->tk_host, h->tk_n);
+  memcpy(cur_ret, s.cur_ret, n * 8); memcpy(episodes, s.episodes, n * 8); memcpy(terminated, s.terminated, n * 8);
+  memcpy(ret_sum, s.ret_sum, n * 8); memcpy(ret_min, s.ret_min, n * 8); memcpy(ret_max, s.ret_max, n * 8);
+  memcpy(len_sum, s.len_sum, n * 8); memcpy(last_ret, s.last_ret, n * 8);
+  memcpy(cur_len, s.cur_len, n * 4); memcpy(last_len, s.last_len, n * 4);
+  if (clear) TRY(track_init(h, 0));
   return check_handoff(h);
 }
 

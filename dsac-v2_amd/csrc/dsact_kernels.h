@@ -735,6 +735,71 @@ __global__ void __launch_bounds__(kThreads) k_eval_init(EvalCommitArgs a) {
 }
 #endif
 
+// k_track_commit: the episode statistics of the device-resident sampler's TRAINING environments (training/hip_tensor_sampler.py
+// with hip_episode_stats, dsact_track_commit) -- one launch folds the T lockstep steps of a sample() into
+// state that persists across calls. reward / term / trunc are the sampler's step-major [T * N] buffers (element t * N + i is
+// row i's step t; the reward is the environment's own, before reward_scale; the flags one byte each, non-zero = set). One thread
+// per environment row i < N. State (owned by the handle, initialised by k_track_init):
+//   the episode in progress   cur_ret[i] (fp64), cur_len[i]
+//   the totals over the episodes of row i that ended since the totals were last cleared
+//                             episodes[i], terminated[i] (ended with `terminated` set: both flags in one step count here),
+//                             ret_sum[i], ret_min[i] (+inf when none), ret_max[i] (-inf when none), len_sum[i], last_ret[i], last_len[i]
+// The thread loads its row's state, walks t = 0 .. T-1 (ret += (double)reward, len += 1; at terminated | truncated the episode
+// is folded into the totals and the running pair cleared) and stores the state back.
+//   * the return is the fp64 sum of the fp32 rewards in step order: k_eval_commit's rule;
+//   * min / max move on a strict comparison (ret < ret_min, ret > ret_max): a return that compares equal, or a NaN, leaves them;
+//   * a row writes its own slots only: no atomics, no LDS, no cross-row reduction -- every number is a pure function of the
+//     row's own reward and flag sequence, whatever N, T or the split of the steps into launches;
+//   * the loads of a step are coalesced across rows (consecutive i: consecutive addresses).
+// Plain C++, vector loads / stores only.
+struct TrackArgs {
+  const float* reward; const unsigned char* term; const unsigned char* trunc;
+  double* cur_ret; int* cur_len;
+  long long* episodes; long long* terminated; double* ret_sum; double* ret_min; double* ret_max; long long* len_sum;
+  double* last_ret; int* last_len;
+  int N, T;
+};
+#ifndef DSACT_FAMILY_UNIT   // plain kernels: compiled in dsact_api.hip only (dsact_tu.h)
+__global__ void __launch_bounds__(kThreads) k_track_commit(TrackArgs a) {
+  const int i = (int)blockIdx.x * kThreads + (int)threadIdx.x;
+  if (i >= a.N) return;
+  double ret = a.cur_ret[i]; int len = a.cur_len[i];
+  long long episodes = a.episodes[i], terminated = a.terminated[i], len_sum = a.len_sum[i];
+  double ret_sum = a.ret_sum[i], ret_min = a.ret_min[i], ret_max = a.ret_max[i], last_ret = a.last_ret[i];
+  int last_len = a.last_len[i];
+  for (int t = 0; t < a.T; ++t) {
+    const size_t k = (size_t)t * (size_t)a.N + (size_t)i;
+    ret += (double)a.reward[k];
+    len += 1;
+    const bool term = a.term[k] != 0, trunc = a.trunc[k] != 0;   // (both loaded: no load behind a divergent branch)
+    if (term | trunc) {
+      episodes += 1;
+      terminated += term ? 1 : 0;
+      ret_sum += ret;
+      if (ret < ret_min) ret_min = ret;
+      if (ret > ret_max) ret_max = ret;
+      len_sum += len;
+      last_ret = ret; last_len = len;
+      ret = 0.0; len = 0;
+    }
+  }
+  a.cur_ret[i] = ret; a.cur_len[i] = len;
+  a.episodes[i] = episodes; a.terminated[i] = terminated; a.len_sum[i] = len_sum;
+  a.ret_sum[i] = ret_sum; a.ret_min[i] = ret_min; a.ret_max[i] = ret_max; a.last_ret[i] = last_ret;
+  a.last_len[i] = last_len;
+}
+// the state's initialisation in stream order: all != 0 everything (dsact_track_begin), else the totals only (a clearing
+// dsact_track_read: the episode in progress goes on)
+__global__ void __launch_bounds__(kThreads) k_track_init(TrackArgs a, int all) {
+  const int i = (int)blockIdx.x * kThreads + (int)threadIdx.x;
+  if (i >= a.N) return;
+  if (all) { a.cur_ret[i] = 0.0; a.cur_len[i] = 0; }
+  a.episodes[i] = 0; a.terminated[i] = 0; a.len_sum[i] = 0;
+  a.ret_sum[i] = 0.0; a.ret_min[i] = __builtin_huge_val(); a.ret_max[i] = -__builtin_huge_val(); a.last_ret[i] = 0.0;
+  a.last_len[i] = 0;
+}
+#endif
+
 // ---------------------------------------------------------------------------------------------
 // k_tiles: C[m][n] (+epilogue) = sum_k P(m,k) * Q(n,k) on 32x32 tiles, BK = 64
 //   operand storage: KC  element (row,k) at base[row*ld + k]   (k contiguous)

@@ -132,6 +132,9 @@ SYMBOLS = [
     ("dsact_eval_commit", C.c_int, [_P, _P, _P, _P, _P]),
     ("dsact_eval_poll", C.c_int, [_P, _P]),
     ("dsact_eval_read", C.c_int, [_P, _P, _P, C.c_int32]),
+    ("dsact_track_begin", C.c_int, [_P, C.c_int32]),
+    ("dsact_track_commit", C.c_int, [_P, _P, _P, _P, C.c_int32]),
+    ("dsact_track_read", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32]),
 ]
 
 _lib = None

@@ -730,6 +730,38 @@ class DsactEngine:
         self._chk(self._lib.dsact_eval_read(self._h, returns.ctypes.data_as(C.c_void_p), lengths.ctypes.data_as(C.c_void_p), E))
         return returns, lengths
 
+    # ---- episode statistics of the training environments: one launch per commit, one wait in track_read ---
+    TRACK_COLUMNS = (("episodes", np.int64), ("terminated", np.int64), ("ret_sum", np.float64), ("ret_min", np.float64),
+                     ("ret_max", np.float64), ("len_sum", np.int64), ("last_ret", np.float64), ("last_len", np.int32),
+                     ("cur_ret", np.float64), ("cur_len", np.int32))     # dsact_track_read's arrays, in its argument order
+
+    def track_begin(self, n_envs: int):
+        """dsact_track_begin: new episode statistics for n_envs lockstep rows, initialised in stream order"""
+        self._chk(self._lib.dsact_track_begin(self._h, int(n_envs)))
+        self._track_n = int(n_envs)
+
+    def track_commit(self, reward, terminated, truncated, n_steps: int):
+        """dsact_track_commit: n_steps lockstep steps of the bookkeeping in one launch. reward[n_steps * N] float32 (before any
+        reward scale), terminated / truncated [n_steps * N] bool (or uint8), step-major. Asynchronous on the engine's stream."""
+        torch = self.torch
+        f32, flag = (torch.float32,), (torch.bool, torch.uint8)
+        T = int(n_steps)
+        n = getattr(self, "_track_n", None)
+        rows = T * n if n is not None and T > 0 else self._rows(reward)   # (the library refuses: E_STATE / E_INVALID)
+        ptrs = [self._dev(reward, (rows,), f32, "reward"), self._dev(terminated, (rows,), flag, "terminated"),
+                self._dev(truncated, (rows,), flag, "truncated")]
+        rc = self._lib.dsact_track_commit(self._h, *ptrs, T)
+        if rc != 0:
+            self._chk(rc)
+
+    def track_read(self, clear: bool = True) -> dict:
+        """dsact_track_read: {name: array[N]} of TRACK_COLUMNS behind everything enqueued so far. WAITS for the engine's stream.
+        clear: the totals start again afterwards (the episodes in progress, cur_ret / cur_len, go on)."""
+        n = getattr(self, "_track_n", None) or 0
+        out = {k: np.empty(max(n, 1), dt) for k, dt in self.TRACK_COLUMNS}   # (n = 0: the library refuses, E_STATE)
+        self._chk(self._lib.dsact_track_read(self._h, n, *[a.ctypes.data_as(C.c_void_p) for a in out.values()], 1 if clear else 0))
+        return {k: a[:n] for k, a in out.items()}
+
     def behaviour_hold(self):
         """dsact_behaviour_hold: from now on act_sample / act_sample_batch act with a copy of the policy taken on the engine's
         stream behind everything enqueued so far -- without waiting for anything enqueued later (act_mode_batch and

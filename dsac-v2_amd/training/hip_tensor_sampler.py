@@ -40,10 +40,22 @@ Refused (NotImplementedError / ValueError, before an environment step or an engi
 strict_rng=True, noise_params, S not a multiple of N, an environment on another device than the engine. The overlapped
 trainer (hip_off_async_trainer) refuses this sampler as an unknown sampler class: held-behaviour acting is not built for it.
 
+Episode statistics (`hip_episode_stats=True`; default off: exactly the calls above): how the N TRAINING
+environments' episodes are going, kept on the device. _setup starts them (dsact_track_begin: a new engine starts new
+statistics), and sample() ends with ONE more launch, dsact_track_commit over the [S] reward / terminated / truncated buffers as
+they are (S / N lockstep steps; the environment's own reward, before reward_scale) -- still no wait. `episode_statistics()` is
+the one call that waits: it reads the per-row state (dsact_track_read) and aggregates it on the host. With
+`hip_episode_stats_every=K` (K > 0) every K-th sample() makes that read itself (a clearing one) and adds `Sampler/episodes`,
+`Sampler/episode return mean` / `min` / `max`, `Sampler/episode length mean` and `Sampler/terminated share` to the dict it
+returns: the only case in which sample() waits. The count is `sample_calls` (0 at construction, +1 per sample(), assignable
+like act_step) and includes the calls a trainer makes to warm the buffer up; a read whose dict nobody writes down is still a
+clearing read. INTEGRATION.md says how to line the reads up with HipOffSerialTrainer's log iterations.
+
 sample() returns (DeviceSampleBatch, {sampler time}). The time is the HOST time of issuing the work. The batch's tensors are the
 sampler's own preallocated [S, .] buffers: they are valid until the next sample() call (add_batch consumes them in stream
 order before that).
 """
+import math
 import time
 
 import numpy as np
@@ -54,7 +66,8 @@ from training.hip_acting_common import (engine_stream, hand_over, networks_of, o
 from training.hip_replay_buffer import act_seed_from
 from training.hip_sampler import SAMPLER_TIME_KEY
 
-__all__ = ["HipTensorEnvSampler", "DeviceSampleBatch", "act_noise_words", "act_noise_reference"]
+__all__ = ["HipTensorEnvSampler", "DeviceSampleBatch", "act_noise_words", "act_noise_reference", "aggregate_episode_rows",
+           "EPISODE_TB_KEYS"]
 
 ACT_STREAM = 5    # the acting noise's Philox stream id (include/dsact.h: 1 .. 3 the update noise, 4 the index draw)
 _M32 = 0xFFFFFFFF
@@ -94,6 +107,29 @@ def act_noise_reference(seed, step, n_rows, act_dim):
     ra, rb = np.sqrt(-2.0 * np.log(u[0])), np.sqrt(-2.0 * np.log(u[2]))
     z = np.stack([ra * np.cos(2 * np.pi * u[1]), ra * np.sin(2 * np.pi * u[1]), rb * np.cos(2 * np.pi * u[3]), rb * np.sin(2 * np.pi * u[3])], axis=1)
     return np.ascontiguousarray(z.reshape(n_rows, per_row * 4)[:, :act_dim])
+
+
+# hip_episode_stats_every: the keys a K-th sample() adds to its dict, and the aggregate behind each
+EPISODE_TB_KEYS = (("Sampler/episodes", "episodes"), ("Sampler/episode return mean", "return_mean"),
+                   ("Sampler/episode return min", "return_min"), ("Sampler/episode return max", "return_max"),
+                   ("Sampler/episode length mean", "length_mean"), ("Sampler/terminated share", "terminated_share"))
+
+
+def aggregate_episode_rows(rows):
+    """the per-row totals of dsact_track_read ({name: array[N]}) as one dict: `episodes` (int), `terminated_share`,
+    `return_mean`, `return_min`, `return_max`, `length_mean`, and `rows` (the arrays themselves, the episodes in progress
+    included). The means are math.fsum of the per-row sums over the total count -- fsum is exactly rounded, so the result
+    does not depend on a summation order. No finished episode: the means, min and max are nan."""
+    n = int(rows["episodes"].sum())
+    nan = float("nan")
+    done = rows["episodes"] > 0
+    return {"episodes": n,
+            "terminated_share": int(rows["terminated"].sum()) / n if n else nan,
+            "return_mean": math.fsum(rows["ret_sum"][done].tolist()) / n if n else nan,
+            "return_min": float(rows["ret_min"][done].min()) if n else nan,
+            "return_max": float(rows["ret_max"][done].max()) if n else nan,
+            "length_mean": int(rows["len_sum"].sum()) / n if n else nan,
+            "rows": rows}
 
 
 class DeviceSampleBatch:
@@ -143,6 +179,14 @@ class HipTensorEnvSampler:
         if kwargs.get("strict_rng", False):
             raise ValueError("hip_tensor_env_sampler with strict_rng=True: the acting noise is drawn in the kernel (Philox), not "
                              "from torch.randn's stream; a parity run wants hip_vec_off_sampler")
+        self.episode_stats = bool(kwargs.get("hip_episode_stats", False))
+        every = kwargs.get("hip_episode_stats_every", 0)
+        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 0:
+            raise ValueError("hip_episode_stats_every must be an integer >= 0 (sample() calls; 0: only on request), got %r" % (every,))
+        if every > 0 and not self.episode_stats:
+            raise ValueError("hip_episode_stats_every=%d needs hip_episode_stats=True" % every)
+        self.episode_stats_every = int(every)
+        self.sample_calls = 0             # sample() calls made: the K-th-call read counts these (assignable, like act_step)
         env = kwargs.get("env")
         if env is None:
             from plugin import create_env
@@ -190,6 +234,8 @@ class HipTensorEnvSampler:
         self._obs = torch.zeros(N, O, **f)
         self._low, self._high, self._kernel_clip = tensor_limits(self.env, eng, N)
         eng.set_act_rng(self.act_seed)
+        if self.episode_stats:
+            eng.track_begin(N)            # (a new engine starts new statistics)
         if not self._started:
             self._obs.copy_(self.env.reset().reshape(N, O))
             self._started = True
@@ -222,6 +268,26 @@ class HipTensorEnvSampler:
                 # the next step's observations: this step's, with every environment that ended restarted on its own
                 nxt = env.reset(term_b[r0:r1] | trunc_b[r0:r1])
                 (obs_b[r1:r1 + N] if r1 < S else self._obs).copy_(nxt.reshape(N, -1))
+            if self.episode_stats:
+                eng.track_commit(rew_b, term_b, trunc_b, S // N)    # the S / N steps in one launch
         self.total_sample_number += S
+        self.sample_calls += 1
         batch = DeviceSampleBatch(obs_b, act_b, rew_b, obs2_b, term_b, trunc_b, logp_b, self.reward_scale, stream=stream)
-        return batch, {SAMPLER_TIME_KEY: (time.perf_counter() - t0) * 1000}
+        tb = {}
+        if self.episode_stats_every and self.sample_calls % self.episode_stats_every == 0:
+            stats = self.episode_statistics(clear=True)             # (the only wait sample() ever makes)
+            tb = {key: stats[name] for key, name in EPISODE_TB_KEYS}
+        tb[SAMPLER_TIME_KEY] = (time.perf_counter() - t0) * 1000
+        return batch, tb
+
+    def episode_statistics(self, clear=True):
+        """the training environments' finished episodes since the last clearing read (or since the statistics began), over all
+        rows: aggregate_episode_rows of ONE dsact_track_read, which waits for the engine's stream. clear: the totals start again
+        (an episode in progress is never cut: it is counted whole when it ends). Before the first sample() the set-up of
+        sample() is made here, and the answer is zero episodes."""
+        if not self.episode_stats:
+            raise RuntimeError("episode_statistics() needs a sampler built with hip_episode_stats=True")
+        eng = self._engine()
+        if self._ready != id(eng):
+            self._setup(eng)
+        return aggregate_episode_rows(eng.track_read(clear))

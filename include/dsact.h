@@ -537,6 +537,41 @@ int dsact_eval_commit(dsact_handle* h, const float* reward_dev, const uint8_t* t
 int dsact_eval_poll(dsact_handle* h, int32_t* remaining);
 int dsact_eval_read(dsact_handle* h, double* returns, int32_t* lengths, int32_t n_episodes);
 
+/* ---- Episode statistics of the training environments (training/hip_tensor_sampler.py) ------------------
+ * Returns and lengths of the episodes the device-resident sampler's N TRAINING environments play, kept on the device across
+ * sample() calls: one launch per sample(), no wait unless the numbers are asked for. Per environment row i < n_envs the handle
+ * keeps the episode in progress -- cur_ret[i] (fp64), cur_len[i] -- and the totals over the episodes of row i that ended since
+ * the totals were last cleared: episodes[i], terminated[i] (episodes that ended with `terminated` set; both flags in one step
+ * count here), ret_sum[i], ret_min[i] (+inf while none), ret_max[i] (-inf while none), len_sum[i], last_ret[i], last_len[i].
+ *   dsact_track_begin              allocates the state for n_envs rows (or reallocates it when n_envs grows, after draining the
+ *                                  handle's stream) and initialises ALL of it in stream order: new statistics.
+ *                                  n_envs < 1: DSACT_E_INVALID.
+ *   dsact_track_commit             n_steps lockstep steps in ONE launch: reward[n_steps * n_envs] fp32 (the environment's own
+ *                                  reward, before any reward_scale), terminated / truncated [n_steps * n_envs] one byte each
+ *                                  (non-zero = set), step-major (element t * n_envs + i is row i's step t: the sampler's
+ *                                  buffers as they are). A row adds each reward to its fp64 running return in step order
+ *                                  (dsact_eval_commit's rule) and counts the step; at terminated | truncated the episode is
+ *                                  folded into the row's totals (min / max by strict comparison) and the running pair
+ *                                  cleared. A row touches its own slots only -- no atomics, no reduction: every number is a
+ *                                  pure function of the row's reward and flag sequence, however the steps are split into
+ *                                  calls. ASYNCHRONOUS: no stream synchronisation, no host copy. DSACT_E_STATE before
+ *                                  dsact_track_begin; n_steps < 1: DSACT_E_INVALID; device pointers of the handle's GPU only
+ *                                  (host and pinned memory: DSACT_E_INVALID).
+ *   dsact_track_read               copies the state to the host behind everything enqueued so far and WAITS for it -- the only
+ *                                  wait of the feature -- into the caller's ten arrays of n_envs elements each. clear != 0:
+ *                                  the totals' initialisation is then enqueued (counters and sums 0, ret_min = +inf, ret_max =
+ *                                  -inf, last_* = 0); the episode in progress (cur_ret, cur_len) is NEVER cleared, so an
+ *                                  episode that spans a read is counted whole. n_envs must be dsact_track_begin's
+ *                                  (DSACT_E_INVALID); DSACT_E_STATE before dsact_track_begin.
+ * dsact_destroy frees the state. dsact_debug_get: "track_commit_calls" (dsact_track_commit launches), "track_reads"
+ * (dsact_track_read waits); "act_dev_syncs" stays 0 across dsact_track_commit too. */
+int dsact_track_begin(dsact_handle* h, int32_t n_envs);
+int dsact_track_commit(dsact_handle* h, const float* reward_dev, const uint8_t* terminated_dev, const uint8_t* truncated_dev,
+                       int32_t n_steps);
+int dsact_track_read(dsact_handle* h, int32_t n_envs, int64_t* episodes, int64_t* terminated, double* ret_sum, double* ret_min,
+                     double* ret_max, int64_t* len_sum, double* last_ret, int32_t* last_len, double* cur_ret, int32_t* cur_len,
+                     int32_t clear);
+
 #ifdef __cplusplus
 }
 #endif
