@@ -2394,7 +2394,7 @@ int pipe_fwd_build(dsact_handle* h, int set_own, int set_next, bool pre, bool do
   P.n_blocks = (int)(8 * rounds);
   for (size_t r = 0; r < rounds; ++r)
     for (int x = 0; x < 8; ++x) P.blk[8 * r + x] = r < q[x].size() ? q[x][r] : -1;
-  // (P.warm stays zero: no L2 warm-up touches -- measured slower, 60.4 vs 59.6 us)
+  // (the forward kernels do not touch the packed weights ahead of their stream: DESIGN.md 4b has the measurements)
   h->n_heads_parts = h->B / 4;
   return DSACT_OK;
 }

@@ -73,9 +73,15 @@ __device__ __forceinline__ void stream_prologue(WStr& ws, const float* cur, int 
 // lasts, then from `nxt` starting at its step nxt_s0 (has_nxt == false: the stream ends; spare slots re-read a valid
 // address). lds + xs: this lane's LDS operand (row lane&3 of group 0; group g is 4g rows further; step s is 4s floats
 // further), read one step ahead.
-template <int RG>
+// TAIL (the critics' backward of the merged launches): where the stream ends (has_nxt == false) and `tail` is set, the
+// first 8 slots of the drained last trip fetch the style-16 fragment blocks the caller multiplies next instead of a dummy --
+// slot 4 t + c = block (t, c) of `tail`, tile t = min(t, tail_nt - 1) is tail_c blocks further (narrow_load's addresses for
+// this wave, in narrow_mma's order; one tile: slots 4 .. 7 re-read tile 0). They arrive under the trip's own MFMAs.
+template <int RG, bool TAIL = false>
 __device__ __forceinline__ void gemm44_seg(WStr& ws, const float* cur, int s_lo, int s_hi, const float* nxt, int nxt_s0,
-                                           bool has_nxt, const float* lds, int xs, int ld, int lane4, f32x4 (&acc)[RG][2]) {
+                                           bool has_nxt, const float* lds, int xs, int ld, int lane4, f32x4 (&acc)[RG][2],
+                                           const float* tail = nullptr, int tail_c = 0, int tail_nt = 0) {
+  static_assert(!TAIL || kPD >= 8, "the tail takes 8 slots of the stream");
   f32x4 a0[RG], a1[RG];
 #pragma unroll
   for (int g = 0; g < RG; ++g) a0[g] = *(const f32x4*)(lds + xs + 4 * g * ld + 4 * s_lo);
@@ -84,6 +90,10 @@ __device__ __forceinline__ void gemm44_seg(WStr& ws, const float* cur, int s_lo,
     // is uniform: the next kPD steps of `cur`, or (last trip) the first kPD steps of what follows
     const float* src = s0 + kPD < s_hi ? cur + (size_t)(s0 + kPD) * 256
                                        : (has_nxt ? nxt + (size_t)nxt_s0 * 256 : cur + (size_t)s_lo * 256);
+    // slots 0 .. 7: block (u >> 2) * tq + (u & 3) of src8 -- the stream's own next steps (tq = 4), or the tail's fragments
+    const bool at_tail = TAIL && tail != nullptr && !has_nxt && !(s0 + kPD < s_hi);   // wave-uniform
+    const float* src8 = at_tail ? tail : src;
+    const int tq = at_tail ? (tail_nt > 1 ? tail_c : 0) : 4;
 #pragma unroll
     for (int u = 0; u < kPD; ++u) {
       const int s = s0 + u;
@@ -100,7 +110,8 @@ __device__ __forceinline__ void gemm44_seg(WStr& ws, const float* cur, int s_lo,
           acc[g][e & 1] = __builtin_amdgcn_mfma_f32_4x4x1f32((u & 1) ? a1[g][e] : a0[g][e], ws.b[u][e], acc[g][e & 1], 0, 0, 0);
         if (e == 1) __builtin_amdgcn_sched_barrier(0);   // keeps MFMAs on one accumulator 2*RG instructions apart
       }
-      ws.b[u] = gload4(src + (size_t)u * 256 + lane4);
+      if (TAIL && u < 8) ws.b[u] = gload4(src8 + (size_t)((u >> 2) * tq + (u & 3)) * 256 + lane4);
+      else ws.b[u] = gload4(src + (size_t)u * 256 + lane4);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
@@ -633,7 +644,7 @@ struct FwdUnit {
                                     // of its net (ACT_*, dsact_math.h). (shorts: two FwdArgs must fit the 4 KB of kernel arguments)
   // (late_wait sits at a DWORD-ALIGNED offset, in front of n_slices: a 16-bit field at +2 of a dword of a unit table in device
   //  memory -- k_chain_fwdp / fwdpb / fwdt -- is no scalar load but `global_load_ushort` + `s_waitcnt vmcnt(0)`: the wait drained
-  //  the weight stream's prologue and the warm-up touches BEFORE the input rows were requested, one memory round trip of every
+  //  the weight stream's prologue BEFORE the input rows were requested, one memory round trip of every
   //  chain's start-up; an aligned 16-bit field is widened to s_load_dword. Round 6, ISA.)
   short late_wait;                  // bit 0 (HW_LATE): wait for the producers AFTER the observation segment (only the action columns
                                     // are handed over): the wait hides under this unit's own first 3/4 of a layer.
@@ -756,13 +767,8 @@ inline int fwd_grid(const FwdArgs& a) {
 // `a`: the launch's common fields (its unit table is not read here); `u`: the unit -- an element of a.u (k_chain_fwd /
 // k_chain_fwd2, kernel arguments) or of the pipelined graph's unit table in device memory (k_chain_fwdp)
 // (AT / UT: FwdArgs / FwdUnit, or their constant-address-space qualified forms -- every field stays a scalar load)
-// warm_cnt > 0 (pipelined launches): this workgroup is number warm_idx of the warm_cnt workgroups that run this unit on
-// this XCD, and touches its share of the unit's packed weights (one dword per 128-byte line) right after its own stream
-// has started: every launch begins with cold L2s (the weights were rewritten by the previous update's Adam tiles on other
-// XCDs), the workgroups of a unit stream in lockstep, and 16 steps of look-ahead (~0.6 us) do not cover a miss to the
-// memory side -- the first layer ran at 112 cycles per step against 81 for the later ones (profiles/r04_pipe_timeline.txt).
-template <int NW, int RG, bool GA = false, typename AT = FwdArgs, typename UT = FwdUnit, bool WARM = false>
-__device__ __forceinline__ void chain_fwd_body(const AT& a, const UT& u, int unit, int slice, float* lds, int warm_idx = 0, int warm_cnt = 0) {
+template <int NW, int RG, bool GA = false, typename AT = FwdArgs, typename UT = FwdUnit>
+__device__ __forceinline__ void chain_fwd_body(const AT& a, const UT& u, int unit, int slice, float* lds) {
   constexpr int W = 64 * NW, SH = W / 4, R = 4 * RG, NTHR = 64 * NW, TPR = NTHR / R;
   int* const done_flag = (u.done && !(a.debug_withhold && unit == 0 && slice == 0)) ? u.done + slice : nullptr;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -785,35 +791,6 @@ __device__ __forceinline__ void chain_fwd_body(const AT& a, const UT& u, int uni
   WStr ws;
   const float* w0 = u.wf[0] + (size_t)wave * (S0 + a.tpad) * 256;
   stream_prologue(ws, w0, do_obs ? 0 : a.s_obs, lane4);
-  constexpr int NWARM = 4;
-  float wt[NWARM] = {0.f, 0.f, 0.f, 0.f};
-  if (WARM) {   // (no branch on warm_cnt: with 0 every lane re-reads line 0 -- a branch here would cost the stream a vmcnt(0))
-    const int n0 = NW * S0 * 8, nh = NW * SH * 8;                     // 128-byte lines of the first layer / of a hidden layer
-    const int nhead = head == HEAD_NONE ? 0 : (head == HEAD_POLICY ? (2 * A + 15) >> 4 : 1) * (W / 16) * 8;
-    const int total = warm_cnt > 0 ? n0 + (L - 1) * nh + nhead : 0;
-    const int share = (total + warm_cnt - 1) / (warm_cnt > 0 ? warm_cnt : 1);
-    const int lo = warm_idx * share, hi = lo + share < total ? lo + share : total;
-    // (branch-free: a scalar branch between the stream prologue's loads and their use makes the compiler wait vmcnt(0))
-    const float* wb[kChMaxL + 1];
-#pragma unroll
-    for (int l = 0; l <= kChMaxL; ++l) wb[l] = u.wf[l <= L ? l : L];
-#pragma unroll
-    for (int q = 0; q < NWARM; ++q) {
-      int i = lo + tid + q * NTHR;
-      i = i < hi ? i : lo;
-      const float* base = wb[0];
-      int off = i;
-#pragma unroll
-      for (int l = 1; l <= kChMaxL; ++l) {
-        const int start = n0 + (l - 1) * nh;              // first line of layer l (the head follows the last hidden layer)
-        const bool in = l <= L && i >= start;
-        base = in ? wb[l] : base;
-        off = in ? i - start : off;
-      }
-      wt[q] = *(const __attribute__((address_space(1))) float*)(base + (size_t)off * 32);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
   float bq[kChMaxL];
 #pragma unroll
   for (int l = 0; l < kChMaxL; ++l) bq[l] = u.bias[l < L ? l : 0][n];
@@ -958,10 +935,6 @@ __device__ __forceinline__ void chain_fwd_body(const AT& a, const UT& u, int uni
       if (u.zdone) chain_publish(u.zdone + slice);   // drains this wave's prefetch queue once (~1 us) -- off the critical path
     }
     CTL(a.timeline, 2);
-    if (WARM) {   // the touched values are dead; naming them here keeps the loads where they were issued
-      const float wsum = (wt[0] + wt[1]) + (wt[2] + wt[3]);
-      asm volatile("" : : "v"(wsum));
-    }
     if (u.seg == SEG_OBS_ONLY) { CTLR(a.timeline, 15); chain_publish(done_flag); return; }
     if (u.seg == SEG_FULL_SPLIT) {   // what zsave -> zinit carries from an obs-only unit to its SEG_ACT_FROM_SAVED consumer
 #pragma unroll
@@ -1145,7 +1118,6 @@ struct PipeFwd {
   // state before they wait
   DevState* book_st; StepHyper book_hp; int* book_cnt; int book_ncnt;
   int blk[kPipeMaxBlocks];          // (unit << 16) | slice, or -1: padding block
-  int warm[kPipeMaxBlocks];         // (index << 16) | count among the workgroups of the same unit on the same XCD; 0: no warm-up (pipe_fwd_build leaves every entry 0)
 };
 constexpr int kPipeRoleBook = 13;
 // the bookkeeping block of a forward launch (see PipeFwd::book_*): one thread
@@ -1173,11 +1145,10 @@ __global__ void __launch_bounds__(64 * NW, 2) k_chain_fwdp(const PipeFwd* __rest
 #ifdef DSACT_TIMELINE
   if (p->c.timeline && threadIdx.x == 0 && blockIdx.x < 512) p->c.timeline[blockIdx.x * 16 + 11] = unit + 1;   // who ran here
 #endif
-  const int wm = p->warm[blockIdx.x];
   typedef __attribute__((address_space(4))) const FwdArgs KA;
   typedef __attribute__((address_space(4))) const FwdUnit KU;
-  if (p->u[unit].rg == 1) chain_fwd_body<NW, 1, GA, KA, KU, true>(p->c, p->u[unit], unit, slice, lds, wm >> 16, wm & 0xffff);
-  else chain_fwd_body<NW, 2, GA, KA, KU, true>(p->c, p->u[unit], unit, slice, lds, wm >> 16, wm & 0xffff);
+  if (p->u[unit].rg == 1) chain_fwd_body<NW, 1, GA, KA, KU>(p->c, p->u[unit], unit, slice, lds);
+  else chain_fwd_body<NW, 2, GA, KA, KU>(p->c, p->u[unit], unit, slice, lds);
 }
 
 // k_chain_fwdt: a forward launch of TWIN-trunk nets (the CNN approximators' mean / log_std MLPs over the conv features).
@@ -1198,8 +1169,8 @@ __global__ void __launch_bounds__(64 * NW, 2) k_chain_fwdt(const PipeFwd* __rest
 #pragma nounroll
   for (int t = 0; t < nt; ++t) {
     if (t) lds_barrier();
-    if (p->u[unit + t].rg == 1) chain_fwd_body<NW, 1, GA, KA, KU, false>(p->c, p->u[unit + t], unit + t, slice, lds);
-    else chain_fwd_body<NW, 2, GA, KA, KU, false>(p->c, p->u[unit + t], unit + t, slice, lds);
+    if (p->u[unit + t].rg == 1) chain_fwd_body<NW, 1, GA, KA, KU>(p->c, p->u[unit + t], unit + t, slice, lds);
+    else chain_fwd_body<NW, 2, GA, KA, KU>(p->c, p->u[unit + t], unit + t, slice, lds);
   }
 }
 
@@ -1466,11 +1437,14 @@ __device__ __forceinline__ void bwd_q_body(const QA& a, int block, float* lds) {
     const float* wl = u.wb[l] + (size_t)wave * SH * 256;
     const float* wn = u.wb[has_nxt ? l - 1 : l] + (size_t)wave * SH * 256;
     const int xop = (cur ? S.off_h1 : S.off_h0) + (lane & 3) * S.ld_h;
-    gemm44_seg<RG>(ws, wl, 0, SH, wn, 0, has_nxt, lds, xop, S.ld_h, lane4, acc);
+    // (merged launches: the kernel has to fit 168 registers -- three workgroups per CU, the chain's and two waiting tiles -- so
+    //  the 32 fragment registers of dL/da are not loaded beside the stream as in k_chain_bwd_q below. The last product's stream
+    //  has no successor: its drained last trip fetches them into the stream's own first 8 slots, under that trip's MFMAs. The
+    //  end of the q_p chains is waited for: in k_chain_bwd_qpt the policy chain's 32 slices poll the pairs stored below, the
+    //  policy's tiles wait for the policy chain and the kernel end for the tiles; in k_chain_bwd_qt nobody waits for it.)
+    gemm44_seg<RG, MRG>(ws, wl, 0, SH, wn, 0, has_nxt, lds, xop, S.ld_h, lane4, acc,
+                        u.w1at ? u.w1at + (size_t)wave * 4 * 256 : nullptr, c1at, nta);
     CTL(a.timeline, 3 + 2 * (L - 1 - l));
-    // (merged launch: the 32 fragment registers of dL/da are loaded AFTER the last epilogue -- one L2 round trip on a chain
-    //  whose end nobody in this launch waits for -- so that the kernel fits 168 registers: three workgroups per CU, the
-    //  chain's and two waiting tiles)
     if (l == 1 && u.w1at && !MRG) narrow_load<2>(af, u.w1at, c1at, nta, wave, lane4);
     const int hn = cur ? S.off_h0 : S.off_h1;
 #pragma unroll
@@ -1487,7 +1461,14 @@ __device__ __forceinline__ void bwd_q_body(const QA& a, int block, float* lds) {
     CTL(a.timeline, 4 + 2 * (L - 1 - l));
   }
   if (!u.w1at) { CTLR(a.timeline, 15); return; }
-  if (MRG) narrow_load<2>(af, u.w1at, c1at, nta, wave, lane4);
+  if (MRG) {
+    if (L > 1) {   // the last product's tail left them in the stream's slots
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) af.w[t][c] = ws.b[4 * t + c];
+    } else narrow_load<2>(af, u.w1at, c1at, nta, wave, lane4);   // one hidden layer: no stream
+  }
   // ---- dL/d new_act through this critic: dZ0 . W0[:, F:F+A]   (contraction over the hidden units, split over waves)
   narrow_mma<2>(af, nta, wave, lds, (cur ? S.off_h1 : S.off_h0) + ((lane & 15) & (R - 1)) * S.ld_h + 4 * (lane >> 4), red, lane);
   lds_barrier();
@@ -1938,11 +1919,10 @@ __global__ void __launch_bounds__(256, 2) k_chain_fwdpb(const PipeFwd* __restric
   }
   if (unit == kPipeRoleBook) { pipe_book(p); return; }
   if ((int)threadIdx.x >= 64 * NW) return;      // narrow nets: the launch is 256 wide for the tiles
-  const int wm = p->warm[blockIdx.x];
   typedef __attribute__((address_space(4))) const FwdArgs KA;
   typedef __attribute__((address_space(4))) const FwdUnit KU;
-  if (p->u[unit].rg == 1) chain_fwd_body<NW, 1, GA, KA, KU, true>(p->c, p->u[unit], unit, slice, lds, wm >> 16, wm & 0xffff);
-  else chain_fwd_body<NW, 2, GA, KA, KU, true>(p->c, p->u[unit], unit, slice, lds, wm >> 16, wm & 0xffff);
+  if (p->u[unit].rg == 1) chain_fwd_body<NW, 1, GA, KA, KU>(p->c, p->u[unit], unit, slice, lds);
+  else chain_fwd_body<NW, 2, GA, KA, KU>(p->c, p->u[unit], unit, slice, lds);
 }
 
 }  // namespace dsact
