@@ -139,6 +139,7 @@ def make_pair(O, A, hid, B, act_limit=0.4, seed=0, init=None, **over):
                          policy_std_type=over.get("policy_std_type", "mlp_shared"),
                          value_out_act=over.get("value_output_activation", "linear"), policy_out_act=over.get("policy_output_activation", "linear"),
                          policy_hidden=over.get("policy_hidden_sizes"),
+                         **{k[len("policy_"):]: over[k] for k in ("policy_min_log_std", "policy_max_log_std") if k in over},
                          **{k: over[k] for k in ("auto_alpha", "alpha", "delay_update") if k in over})
     cfg["pad_to"] = getattr(alg.engine.layout, "pad_to", None)   # stored widths of the HIP arenas: the oracle's FLAT views follow them
     orc = DsactOracle(cfg, state_dict={k: v.cpu() for k, v in alg.networks.state_dict().items()})
@@ -230,7 +231,11 @@ def compare_intermediates(rep, alg, orc, L, B, A, Lp=None):
             rep.cmp("dZ.%s.%d" % (ch, l), dl("dZ.%s.%d" % (ch, l), I[key][l]), I[key][l], 1e-10, 2e-4)
 
 
-def run_case(title, O, A, hid, B, steps, act_limit=0.4, init=None, golden=None, **over):
+def run_case(title, O, A, hid, B, steps, act_limit=0.4, init=None, golden=None, prepare=None, resync_last=False, **over):
+    """prepare(it, data, noise) -> (data, noise): a hook that changes (or replaces) the inputs of update `it` (tests/stress_cases.py).
+    resync_last: take the last update's intermediates and gradients from a copy of the oracle AT the engine's parameters, as the
+    non-gelu activations below do (nets with an output row scaled by 10^2: the gradients, and their rounding noise, scale with
+    it while Adam's step does not -- more elements whose gradient is within that noise of zero take their 2 * lr sign flip)"""
     rep = Report(title)
     alg, orc = make_pair(O, A, hid, B, act_limit=act_limit, init=init, **over)
     e = alg.engine
@@ -249,6 +254,8 @@ def run_case(title, O, A, hid, B, steps, act_limit=0.4, init=None, golden=None, 
             data = synth_batch(rng, B, O, A, lim=act_limit, p_done=0.05)
             torch.manual_seed(1000 + it)
             noise = draw_noise(B, A)
+        if prepare is not None:
+            data, noise = prepare(it, data, noise)
         keep = it in (0, steps - 1)
         e.load_batch(*(data[k].numpy() for k in ("obs", "act", "rew", "obs2", "done")))
         e.set_noise(noise["eps_new"].numpy(), noise["eps_2"].numpy(), noise["z5"].numpy(), noise["z6"].numpy())
@@ -257,7 +264,7 @@ def run_case(title, O, A, hid, B, steps, act_limit=0.4, init=None, golden=None, 
         if cfg["value_act"] in KINKED or cfg["policy_act"] in KINKED:
             orc.act_sides = hip_act_sides(e, cfg, L, B, Lp)
         orc_chk = orc
-        if (cfg["value_act"], cfg["policy_act"]) != ("gelu", "gelu") and it == steps - 1 and it > 0:
+        if (resync_last or (cfg["value_act"], cfg["policy_act"]) != ("gelu", "gelu")) and it == steps - 1 and it > 0:
             # The intermediates and gradients of the last step are a per-kernel check at tight tolerances, so THEY are taken
             # from a copy of the oracle evaluated AT the parameters the engine holds: after two updates the two trajectories
             # differ by the (enumerated, bounded) Adam noise of the steps before, which the tanh / sigmoid nets' O(1)

@@ -23,13 +23,15 @@ def make_pair(O, A, hid, B, act_limit=0.4, seed=0, init=None, td_bound=10.0, **o
     if init is not None:
         alg.networks.load_state_dict(init)
     cfg = default_config(O, A, hid, act_limit=act_limit, TD_bound=td_bound, bound=over.get("bound", True),
-                         policy_hidden=over.get("policy_hidden_sizes"))
+                         policy_hidden=over.get("policy_hidden_sizes"),
+                         **{k[len("policy_"):]: over[k] for k in ("policy_min_log_std", "policy_max_log_std") if k in over})
     cfg["pad_to"] = getattr(alg.engine.layout, "pad_to", None)   # stored widths of the HIP arenas: the oracle's FLAT views follow them
     orc = DsacV1Oracle(cfg, state_dict={k: v.cpu() for k, v in alg.networks.state_dict().items()})
     return alg, orc
 
 
-def run_case(title, O, A, hid, B, steps, act_limit=0.4, init=None, golden=None, **over):
+def run_case(title, O, A, hid, B, steps, act_limit=0.4, init=None, golden=None, prepare=None, **over):
+    """prepare(it, data, noise) -> (data, noise): a hook that changes (or replaces) the inputs of update `it` (tests/stress_cases.py)"""
     rep = Report(title)
     alg, orc = make_pair(O, A, hid, B, act_limit=act_limit, init=init, **over)
     e = alg.engine
@@ -47,6 +49,8 @@ def run_case(title, O, A, hid, B, steps, act_limit=0.4, init=None, golden=None, 
             data = synth_batch(rng, B, O, A, lim=act_limit, p_done=0.05)
             torch.manual_seed(3000 + it)
             noise = draw_noise_v1(B, A)
+        if prepare is not None:
+            data, noise = prepare(it, data, noise)
         tb_ref = orc.compute_gradient(data, noise)
         e.load_batch(*(data[k].numpy() for k in ("obs", "act", "rew", "obs2", "done")))
         e.set_noise(noise["eps_new"].numpy(), noise["eps_2"].numpy(), noise["z_t"].numpy(), noise["z_t"].numpy())
