@@ -1803,8 +1803,13 @@ int run_dw2(dsact_handle* h, int x0, int x1, bool fused, bool finalize) {
   } while (0)
 
 // Row groups (of 4 rows) per chain workgroup of one launch. A workgroup streams its unit's whole weight set whatever
-// its row count, and a step costs ~45 cycles on top of its 32 * RG MFMA cycles: 4-row workgroups finish a layer in
-// 0.75x the time of 8-row ones -- as long as every workgroup still gets a CU of its own (n_units * B/4 <= 256 CUs).
+// its row count, and a step (4 KB of weights, 32 * RG cycles of MFMA) is not the sum of the two but close to it: measured
+// with 192 - 256 workgroups streaming (profiles/gemm44_step_ubench.txt, cycles per step at 2.4 GHz) 78 - 80 at 4 rows,
+// 102 - 104 at 8, 207 - 210 at 16 (one workgroup alone: 69 / 84 / 193). The 4-row step is the stream itself (4 KB at the
+// CU's ~64 B/clk from L2): fetching the LDS operand up to four steps ahead, filling the accumulator hazard slot and
+// scalar stream addresses each measured nothing there; the 8- and 16-row steps lost 8 / 11 cycles of vector address
+// arithmetic to scalar stream bases (gemm44_seg). 4-row workgroups finish a layer in 0.76 - 0.78x the time of 8-row ones
+// (0.72x before the 8-row step shrank) -- as long as every workgroup still gets a CU of its own (n_units * B/4 <= 256 CUs).
 // Large batches: 16-row workgroups (RG 4) halve the weight bytes per FLOP. Measured at batch 4096 / 1024: the critics'
 // backward gains (81.5 -> 63.7 us / 21.8 -> 20.3 us), the forward launches lose (209 -> 228 us: one fat workgroup per CU
 // hides less latency than two 8-row ones), the policy backward is even -- so only the critics' backward asks for it

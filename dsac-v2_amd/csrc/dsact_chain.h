@@ -29,7 +29,11 @@
 //   * loads are issued between MFMA groups (a wave issues in order) and run kPD steps ahead ACROSS layer boundaries:
 //     the weight stream never drains at an epilogue or barrier (raw s_barrier: __syncthreads() waits for vmcnt(0));
 //     LDS operands are addressed by OFFSET into the LDS array (a generic pointer makes them flat loads, which count
-//     on vmcnt), and are read one step ahead.
+//     on vmcnt), and are read one step ahead (deeper look-ahead measured nothing: profiles/gemm44_step_ubench.txt).
+//   * f32 MFMAs of this shape hold the SIMD's vector issue for their whole 8 cycles, so with one wave per SIMD every VALU
+//     instruction between them adds its 4 cycles to the step: the stream's refills of the 8- and 16-row forms take their
+//     addresses from scalar bases (gemm44_seg); the 4-row step is bound by the stream (4 KB per ~64 cycles) and keeps
+//     the compiler's mixed addressing, which measured the same there.
 #pragma once
 #include "dsact_kernels.h"
 
@@ -67,12 +71,27 @@ __device__ __forceinline__ void stream_prologue(WStr& ws, const float* cur, int 
   for (int u = 0; u < kPD; ++u) ws.b[u] = gload4(cur + (size_t)(s_lo + u) * 256 + lane4);
 }
 
+// a wave-uniform pointer as an SGPR pair: the first lane's value where the compiler cannot prove uniformity (free where it can)
+__device__ __forceinline__ const float* uniform_ptr(const float* p) {
+  const unsigned long long v = (unsigned long long)p;
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return (const float*)(((unsigned long long)hi << 32) | lo);
+}
+// ... and opaque to instruction selection, which keeps base + 4 KB * k a scalar add (hipcc otherwise folds the constant into
+// a 64-bit VGPR address: v_lshl_add_u64 + v_add_co / v_addc_co pairs and their s_nops between the MFMAs of a step)
+__device__ __forceinline__ const float* sgpr_ptr(const float* p) { p = uniform_ptr(p); asm("" : "+s"(p)); return p; }
+
 // acc[g][p] += X[rows 4g..4g+3][4 k of step s] (x) W[64 outputs of the wave][same k] over steps [s_lo, s_hi) of `cur`
 // ((s_hi - s_lo) % kPD == 0; two accumulators per row group, k parity p, keep dependent MFMAs 4 instructions apart).
 // After a step's MFMAs its buffer is refilled with the step kPD positions further down the stream: from `cur` while it
 // lasts, then from `nxt` starting at its step nxt_s0 (has_nxt == false: the stream ends; spare slots re-read a valid
-// address). lds + xs: this lane's LDS operand (row lane&3 of group 0; group g is 4g rows further; step s is 4s floats
-// further), read one step ahead.
+// address). RG >= 2 (SB): every refill of a trip is  global_load_dwordx4 v, v_lane4, s[base:base+1] offset:imm  off kPD / 4
+// scalar bases (the 13-bit immediate reaches the 4 steps behind each), chosen with scalar selects at the head of the trip:
+// no vector address arithmetic between the MFMAs (scripts/ubench/slice_gemm44.hip, profiles/gemm44_step_ubench.txt: 7 % of
+// an 8-row step, 5 % of a 16-row one). RG == 1 keeps the addresses the compiler forms from `src` (a quarter of them scalar):
+// its step is the stream itself, scalar bases measured nothing there and cost its unrolled last trip two s_nops a step.
+// lds + xs: this lane's LDS operand (row lane&3 of group 0; group g is 4g rows further; step s is 4s floats further),
+// read one step ahead (two to four steps ahead measured no different at any row count: same profile).
 // TAIL (the critics' backward of the merged launches): where the stream ends (has_nxt == false) and `tail` is set, the
 // first 8 slots of the drained last trip fetch the style-16 fragment blocks the caller multiplies next instead of a dummy --
 // slot 4 t + c = block (t, c) of `tail`, tile t = min(t, tail_nt - 1) is tail_c blocks further (narrow_load's addresses for
@@ -82,6 +101,8 @@ __device__ __forceinline__ void gemm44_seg(WStr& ws, const float* cur, int s_lo,
                                            bool has_nxt, const float* lds, int xs, int ld, int lane4, f32x4 (&acc)[RG][2],
                                            const float* tail = nullptr, int tail_c = 0, int tail_nt = 0) {
   static_assert(!TAIL || kPD >= 8, "the tail takes 8 slots of the stream");
+  static_assert(kPD % 4 == 0, "one scalar base per 4 steps");
+  constexpr bool SB = RG >= 2;   // scalar stream bases
   f32x4 a0[RG], a1[RG];
 #pragma unroll
   for (int g = 0; g < RG; ++g) a0[g] = *(const f32x4*)(lds + xs + 4 * g * ld + 4 * s_lo);
@@ -94,6 +115,11 @@ __device__ __forceinline__ void gemm44_seg(WStr& ws, const float* cur, int s_lo,
     const bool at_tail = TAIL && tail != nullptr && !has_nxt && !(s0 + kPD < s_hi);   // wave-uniform
     const float* src8 = at_tail ? tail : src;
     const int tq = at_tail ? (tail_nt > 1 ? tail_c : 0) : 4;
+    const float* sb[kPD / 4];   // SB: base of slots 4 k .. 4 k + 3
+    if (SB) {
+#pragma unroll
+      for (int k = 0; k < kPD / 4; ++k) sb[k] = sgpr_ptr(TAIL && k < 2 ? src8 + (size_t)(k * tq) * 256 : src + (size_t)k * 1024);
+    }
 #pragma unroll
     for (int u = 0; u < kPD; ++u) {
       const int s = s0 + u;
@@ -110,7 +136,8 @@ __device__ __forceinline__ void gemm44_seg(WStr& ws, const float* cur, int s_lo,
           acc[g][e & 1] = __builtin_amdgcn_mfma_f32_4x4x1f32((u & 1) ? a1[g][e] : a0[g][e], ws.b[u][e], acc[g][e & 1], 0, 0, 0);
         if (e == 1) __builtin_amdgcn_sched_barrier(0);   // keeps MFMAs on one accumulator 2*RG instructions apart
       }
-      if (TAIL && u < 8) ws.b[u] = gload4(src8 + (size_t)((u >> 2) * tq + (u & 3)) * 256 + lane4);
+      if (SB) ws.b[u] = gload4(sb[u >> 2] + (size_t)(u & 3) * 256 + lane4);
+      else if (TAIL && u < 8) ws.b[u] = gload4(src8 + (size_t)((u >> 2) * tq + (u & 3)) * 256 + lane4);
       else ws.b[u] = gload4(src + (size_t)u * 256 + lane4);
       __builtin_amdgcn_sched_barrier(0);
     }
