@@ -294,11 +294,17 @@ constexpr int dw2_lds_floats(int nwv) { return nwv * 4 * 64 * 4 + nwv * 2 * 64; 
 // `wait`: called between the loads of everything the tile needs from EARLIER launches (the X-side fragments, the Adam /
 // Polyak operands) and the first load of the dZ-side fragments -- the policy's tiles of the merged policy-backward
 // launch wait there for the policy chain's arrival counter with their other operands already in flight.
-struct NoWait { __device__ __forceinline__ void operator()() const {} };
+struct NoWait {
+  __device__ __forceinline__ void operator()() const {}
+  __device__ __forceinline__ void stamp_class(int) const {}
+};
 // NWV = waves per tile: the contraction of a round (4 * NWV chunks) is split over them; NWV = 8 (k_dw2 as its own launch
 // at batch >= 1024, one tile per CU: two waves per SIMD instead of one hide each other's operand waits) -- the first four
 // waves finish the tile as before, summing 8 partial blocks instead of 4 (fixed order).
-template <int NSET = 2, typename Wait = NoWait, int NWV = 4>
+// RAGPRE: the ragged quad of a row (N % 4 valid columns) fetches its Adam / Polyak operands in front of the wait like a full
+// one; false (k_chain_bwd_qpt<1, 1, 2> only): after the contraction -- with both that instantiation reaches its 168-register
+// bound and hipcc keeps the kernel-argument struct in scratch (3.7 KB per lane).
+template <int NSET = 2, typename Wait = NoWait, int NWV = 4, bool RAGPRE = true>
 __device__ __forceinline__ void dw2_tile(const Dw2Args& a, int t, float* lds, Wait wait = Wait()) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -312,6 +318,10 @@ __device__ __forceinline__ void dw2_tile(const Dw2Args& a, int t, float* lds, Wa
   const int local = bt - (pi ? a.p[pi - 1].tile_end : 0);
   const int mt = local / P.tiles_n, nt = local - mt * P.tiles_n;
   const int m0 = 32 * mt, n0 = 32 * nt;
+#ifdef DSACT_TIMELINE
+  wait.stamp_class(((nt == 0 && P.b_idx >= 0) ? 1 << 8 : 0) | (((P.N & 3) && (P.N & ~3) >= n0 && (P.N & ~3) < n0 + 32) ? 1 << 9 : 0) |
+                   ((int)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 15) << 12) | (pi << 16));   // (XCC_ID)
+#endif
   // ---- the contraction runs in rounds of <= 16 chunks (256 batch rows); in a round the 4 waves split the chunks (wave w:
   //      chunks cb + w*cw + q, q < cw <= 4). The fragments travel in NSET register sets of two chunks each (half rounds):
   //      all are loaded up front -- batch <= 256 is exactly two of them, one round -- and a set is refilled with the half
@@ -362,15 +372,35 @@ __device__ __forceinline__ void dw2_tile(const Dw2Args& a, int t, float* lds, Wa
   bool o_delayed = false, o_upd = false;
   float o_ss = 0.f, o_bc2 = 1.f;
   f32x4 op = {0.f, 0.f, 0.f, 0.f}, om = op, ov = op, ot = op;
+  // bias tiles: thread tid < 32 finishes the bias of row m0 + tid and holds its Adam / Polyak operands from here on
+  const bool bias = nt == 0 && P.b_idx >= 0;
+  const bool b_row = bias && tid < 32 && m0 + tid < P.M;
+  const long long bi = P.b_idx + m0 + tid;
+  float b_p = 0.f, b_m = 0.f, b_v = 0.f, b_t = 0.f;
   if (fused) {
     const bool is_q = P.w_idx < a.fo.n_q2;
     o_delayed = a.fo.st->do_delayed != 0;
     o_ss = is_q ? a.fo.st->ss_q : a.fo.st->ss_pi;
     o_bc2 = is_q ? a.fo.st->bc2_q : a.fo.st->bc2_pi;
     o_upd = is_q || o_delayed;
-    if (o_upd && in_range && full) {
-      op = *(const f32x4u*)(a.fo.online + oi); om = *(const f32x4u*)(a.fo.adam_m + oi); ov = *(const f32x4u*)(a.fo.adam_v + oi);
-      if (o_delayed) ot = *(const f32x4u*)(a.fo.target + oi);
+    if (o_upd && in_range) {
+      if (full) {
+        op = *(const f32x4u*)(a.fo.online + oi); om = *(const f32x4u*)(a.fo.adam_m + oi); ov = *(const f32x4u*)(a.fo.adam_v + oi);
+        if (o_delayed) ot = *(const f32x4u*)(a.fo.target + oi);
+      } else if (RAGPRE) {
+        // the ragged quad: element by element, nothing at or past column N is touched --
+        // the last row's would lie beyond the tensor (and, for the last tensor, beyond the arena); those elements stay 0
+#pragma unroll
+        for (int e = 0; e < 3; ++e)
+          if (n + e < P.N) {
+            op[e] = a.fo.online[oi + e]; om[e] = a.fo.adam_m[oi + e]; ov[e] = a.fo.adam_v[oi + e];
+            if (o_delayed) ot[e] = a.fo.target[oi + e];
+          }
+      }
+    }
+    if (o_upd && b_row) {
+      b_p = a.fo.online[bi]; b_m = a.fo.adam_m[bi]; b_v = a.fo.adam_v[bi];
+      if (o_delayed) b_t = a.fo.target[bi];
     }
   }
   wait();
@@ -446,7 +476,6 @@ __device__ __forceinline__ void dw2_tile(const Dw2Args& a, int t, float* lds, Wa
     last_halves(0);
   }
   // ---- partial blocks -> LDS -> block `wave`
-  const bool bias = nt == 0 && P.b_idx >= 0;
 #pragma unroll
   for (int bm = 0; bm < 2; ++bm)
 #pragma unroll
@@ -477,13 +506,19 @@ __device__ __forceinline__ void dw2_tile(const Dw2Args& a, int t, float* lds, Wa
         *(f32x4u*)(a.fo.online + oi) = op; *(f32x4u*)(a.fo.adam_m + oi) = om; *(f32x4u*)(a.fo.adam_v + oi) = ov;
         if (o_delayed) *(f32x4u*)(a.fo.target + oi) = ot;
       } else {
-        for (int e = 0; e < 4 && n + e < P.N; ++e) {
-          float pe = a.fo.online[oi + e], me = a.fo.adam_m[oi + e], ve = a.fo.adam_v[oi + e];
-          adam_update(pe, me, ve, v[e], a.fo.b1w, a.fo.beta2, a.fo.b2w, o_ss, o_bc2, a.fo.eps);
-          a.fo.online[oi + e] = pe; a.fo.adam_m[oi + e] = me; a.fo.adam_v[oi + e] = ve;
-          op[e] = pe;
-          if (o_delayed) { ot[e] = polyak_update(a.fo.target[oi + e], pe, a.fo.polyak, a.fo.one_minus_polyak); a.fo.target[oi + e] = ot[e]; }
-        }
+#pragma unroll
+        for (int e = 0; e < 3; ++e)   // (RAGPRE: operands loaded in front of the wait)
+          if (n + e < P.N) {
+            if (!RAGPRE) {
+              op[e] = a.fo.online[oi + e]; om[e] = a.fo.adam_m[oi + e]; ov[e] = a.fo.adam_v[oi + e];
+              if (o_delayed) ot[e] = a.fo.target[oi + e];
+            }
+            float pe = op[e], me = om[e], ve = ov[e];
+            adam_update(pe, me, ve, v[e], a.fo.b1w, a.fo.beta2, a.fo.b2w, o_ss, o_bc2, a.fo.eps);
+            a.fo.online[oi + e] = pe; a.fo.adam_m[oi + e] = me; a.fo.adam_v[oi + e] = ve;
+            op[e] = pe;
+            if (o_delayed) { ot[e] = polyak_update(ot[e], pe, a.fo.polyak, a.fo.one_minus_polyak); a.fo.target[oi + e] = ot[e]; }
+          }
       }
     }
   }
@@ -493,22 +528,18 @@ __device__ __forceinline__ void dw2_tile(const Dw2Args& a, int t, float* lds, Wa
     mirror_store4_quad(*P.mir, m, n, P.N, P.M, in_range, in_range ? op : zero, o_delayed, ot, lane);
   }
   // ---- bias gradient of rows m0 .. m0+31: sum of the 4 waves' x 4 lane groups' row sums
-  if (bias && tid < 32) {
-    const int mb = m0 + tid;
-    if (mb < P.M) {
-      float sbias = 0.f;
+  if (b_row) {
+    float sbias = 0.f;
 #pragma unroll
-      for (int w = 0; w < NWV; ++w)
+    for (int w = 0; w < NWV; ++w)
 #pragma unroll
-        for (int gg = 0; gg < 4; ++gg) sbias += lds[PB + (w * 2 + (tid >> 4)) * 64 + gg * 16 + (tid & 15)];
-      const long long bi = P.b_idx + mb;
-      if (a.store_g) C[bi] = sbias;
-      if (fused && o_upd) {
-        float pe = a.fo.online[bi], me = a.fo.adam_m[bi], ve = a.fo.adam_v[bi];
-        adam_update(pe, me, ve, sbias, a.fo.b1w, a.fo.beta2, a.fo.b2w, o_ss, o_bc2, a.fo.eps);
-        a.fo.online[bi] = pe; a.fo.adam_m[bi] = me; a.fo.adam_v[bi] = ve;
-        if (o_delayed) a.fo.target[bi] = polyak_update(a.fo.target[bi], pe, a.fo.polyak, a.fo.one_minus_polyak);
-      }
+      for (int gg = 0; gg < 4; ++gg) sbias += lds[PB + (w * 2 + (tid >> 4)) * 64 + gg * 16 + (tid & 15)];
+    if (a.store_g) C[bi] = sbias;
+    if (fused && o_upd) {
+      float pe = b_p, me = b_m, ve = b_v;   // (loaded in front of the wait)
+      adam_update(pe, me, ve, sbias, a.fo.b1w, a.fo.beta2, a.fo.b2w, o_ss, o_bc2, a.fo.eps);
+      a.fo.online[bi] = pe; a.fo.adam_m[bi] = me; a.fo.adam_v[bi] = ve;
+      if (o_delayed) a.fo.target[bi] = polyak_update(b_t, pe, a.fo.polyak, a.fo.one_minus_polyak);
     }
   }
 }
@@ -756,6 +787,7 @@ struct ArriveWait {
   const int* cnt; int need; int* timeout;
   long long* tl = nullptr;                       // instrumented builds: chip-wide stamp when the wait ended (slot 13)
   int quick = 0;                                 // 1: short naps between polls (k_chain_bwd_qt: the waiters sit on the critical path)
+  int kind = 0;                                  // instrumented builds: low byte of the tile's class stamp (slot 11)
   __device__ __forceinline__ void operator()() const {
     if (threadIdx.x == 0) {
       const int* c = cnt + ((int)blockIdx.x & 7) * kArriveStride;
@@ -768,6 +800,8 @@ struct ArriveWait {
     asm volatile("s_barrier" ::: "memory");   // the waves keep their operand loads in flight (no vmcnt wait here)
     CTLR(tl, 13);
   }
+  // instrumented builds, slot 11: kind | bias tile << 8 | tile holds a ragged quad << 9 | XCD << 12 | problem << 16
+  __device__ __forceinline__ void stamp_class(int v) const { CTLV(tl, 11, kind | v); }
 };
 
 // block -> (unit, slice) of a forward launch; false: padding block
@@ -1804,8 +1838,7 @@ __global__ void __launch_bounds__(256, DSACT_BQT_OCC) k_chain_bwd_qt(BwdQtArgs a
     const int net = pi / (L + 1), l = pi - net * (L + 1);
     const int* cnt = a.q.arrive + net * 8 * kArriveStride;
     CTLR(a.q.timeline, 14);
-    CTLV(a.q.timeline, 11, 10 + (l < L ? l : L - 1));   // tile class
-    dw2_tile<2, ArriveWait>(a.dw, t, lds, ArriveWait{cnt, a.need, a.spin_timeout, a.q.timeline, 0});
+    dw2_tile<2, ArriveWait>(a.dw, t, lds, ArriveWait{cnt, a.need, a.spin_timeout, a.q.timeline, 0, 10 + (l < L ? l : L - 1) /* tile class */});
     CTLR(a.q.timeline, 15);
     return;
   }
@@ -1870,7 +1903,7 @@ __global__ void __launch_bounds__(256, DSACT_BQT_OCC) k_chain_bwd_qpt(BwdQpArgs 
     // through xcd_chunk and wait for the policy chain
     int t;
     const int* cnt;
-    int need;
+    int need, kind;
     if (idx < a.n_tile_blocks) {
       t = ((const __attribute__((address_space(4))) int*)(unsigned long long)a.tile_tab)[idx];
       if (t < 0) return;
@@ -1880,16 +1913,16 @@ __global__ void __launch_bounds__(256, DSACT_BQT_OCC) k_chain_bwd_qpt(BwdQpArgs 
         if (q + 1 < a.pi.dw.n_prob && t >= a.pi.dw.tile_ends[q]) pi = q + 1;
       cnt = a.q.arrive + (pi / (L + 1)) * 8 * kArriveStride;
       need = a.need_c;
-      CTLV(a.q.timeline, 11, 10);      // critics' tile
+      kind = 10;                       // critics' tile (class stamp of instrumented builds)
     } else {
       if (!xcd_chunk(idx - a.n_tile_blocks, a.pi.n_pi_tiles, t)) return;
       t += a.pi.pi_tile0;
       cnt = a.pi.cnt_pi;
       need = a.pi.n_slices;
-      CTLV(a.q.timeline, 11, 11);      // policy tile
+      kind = 11;                       // policy tile
     }
     CTLR(a.q.timeline, 14);
-    dw2_tile<2, ArriveWait>(a.pi.dw, t, lds, ArriveWait{cnt, need, a.spin_timeout, a.q.timeline});
+    dw2_tile<2, ArriveWait, 4, !(NW == 1 && RGP == 2)>(a.pi.dw, t, lds, ArriveWait{cnt, need, a.spin_timeout, a.q.timeline, 0, kind});
     CTLR(a.q.timeline, 15);
     return;
   }
