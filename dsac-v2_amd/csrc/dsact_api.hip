@@ -92,7 +92,26 @@ constexpr int kChainFlags = 10 * kChainFlagSlices;  // done[6 units] + zdone[q1c
 constexpr int kChainCounters = kChMaxL * 8 * kArriveStride;   // behind the flags (+128 ints of padding): per-layer arrival counters (8 replicas each) of the merged policy backward
 constexpr int kChainFlagInts = kChainFlags + 128 + kChainCounters;
 
-struct dsact_handle {
+// Everything that exists once per staged minibatch. The handle derives from it: h->X0, h->fwd1 ... are the SELECTED set's
+// (select_set copies one of dsact_handle::sets over them), so every enqueue function and args builder reads the handle.
+// A field a set has no storage of its own for holds the workspace's pointer (carve).
+struct BatchBufs {
+  float *X0 = nullptr, *XP = nullptr, *X2 = nullptr, *rew = nullptr, *done = nullptr;
+  float *eps_new = nullptr, *eps_2 = nullptr, *z5 = nullptr, *z6 = nullptr;
+  float* Xc[N_CHAIN] = {};              // MLP input rows per chain
+  float* Hb[N_CHAIN][DSACT_MAX_HIDDEN_LAYERS] = {};   // (only the policy chain's, [C_PI], exist per set)
+  float* Gb[N_CHAIN][DSACT_MAX_HIDDEN_LAYERS] = {};
+  float *logits_pi = nullptr, *logits_pit = nullptr, *logp_new = nullptr, *logp2 = nullptr;
+  float* qout_t[2] = {};
+  float* part_heads = nullptr;
+  float* X0t = nullptr;                 // transposed pack of the staged minibatch [roundup32(F+A) x B]
+  float* W1aT[2] = {};                  // transposed zero-padded action columns of q1 / q2's first layer  [32][w0]
+  // task tables of the tile-stage path: they bake the set's pointers (build_tasks builds them for the selected set)
+  std::vector<Stage> fwd1, fwd2;
+  GemmProb* d_tiles = nullptr;          // per-tile table of the weight/bias-gradient tiles: [q1 | q2 | policy]
+};
+
+struct dsact_handle : BatchBufs {
   dsact_config cfg;
   int device = 0;
   char err[512] = {0};
@@ -120,27 +139,20 @@ struct dsact_handle {
   float *aimg, *aact[kMaxConv];         // stand-alone policy forward
   float* stage_img = nullptr;           // device staging of a host minibatch's images (dsact_load_batch)
   int* idx_iota = nullptr;
-  float* Xc[8];                         // MLP input rows per chain
   int w[DSACT_MAX_HIDDEN_LAYERS];     // activation row widths: the wider of the two families per layer (buffer sizes)
   int Lq = 0, Lp = 0;   // hidden layers of the critics / of the policy nets (L = the larger; they differ only with policy_n_hidden)
   int wq[DSACT_MAX_HIDDEN_LAYERS], wp[DSACT_MAX_HIDDEN_LAYERS];   // ... of the critics / of the policy nets (equal unless policy_hidden is set)
   // workspace
   char* ws = nullptr;
   size_t ws_bytes = 0;
-  float *X0, *XP, *X2, *rew, *done;
-  float *eps_new, *eps_2, *z5, *z6;
-  float* Hb[N_CHAIN][DSACT_MAX_HIDDEN_LAYERS];
-  float* Gb[N_CHAIN][DSACT_MAX_HIDDEN_LAYERS];
   float* dZ[5][DSACT_MAX_HIDDEN_LAYERS];
-  float *logits_pi, *logits_pit, *logp_new, *logp2;
-  float *qout_c[2], *qout_t[2], *qout_p[2], *qstd_c[2];
+  float *qout_c[2], *qout_p[2], *qstd_c[2];
   float* W1p[4];  // zero-padded first-layer weights of q1, q2, q1_target, q2_target  [w0 x ldx]
   bool use_w1p = true;   // false for very wide first layers: copying them every step costs more than unaligned rows
   float* dout[4];
   float *dout_pi, *d_new_act;
   float* qdmean[2] = {nullptr, nullptr}; float* pi_dact = nullptr;   // GELU output layers: the heads' stored d y / d z (carve)
-  float* W1aT[2];  // transposed zero-padded action columns of q1 / q2's first layer  [32][w0]
-  float *part_loss, *part_heads, *stats, *ones, *std_sums;
+  float *part_loss, *stats, *ones, *std_sums;
   long long* timeline;  // [512][8] stamps of the stage named by DSACT_TIMELINE_STAGE (instrumented builds)
   float *act_scale, *act_center;
   float *act_lo, *act_hi;   // the action limits themselves (the mode of a GaussDistribution clamps to them; act_scale is 0 there)
@@ -152,7 +164,6 @@ struct dsact_handle {
   // stand-alone policy forward
   float *Xact, *Hact[DSACT_MAX_HIDDEN_LAYERS], *Gact, *act_out;
   // tasks
-  GemmProb* d_tiles = nullptr;   // per-tile table of the weight/bias-gradient tiles: [q1 | q2 | policy]
   int n_dw_tiles = 0;
   int dw_off[4] = {0, 0, 0, 0};  // start of q1, q2, policy tiles, end
   int dw_pol_rest = 0;           // the policy's OUTPUT-layer tiles come first in its range ([dw_off[2], dw_pol_rest)): they
@@ -161,21 +172,17 @@ struct dsact_handle {
   int dw_chunks = 1;
   float* dw_parts = nullptr;     // [dw_chunks][dw_part_stride]
   size_t dw_part_stride = 0;
-  std::vector<Stage> fwd1, fwd2, bwdq, bwdq_critic, bwdpi, actf;
+  std::vector<Stage> bwdq, bwdq_critic, bwdpi, actf;
   Stage dfeat_q, dfeat_pi, dfeat_all;
-  // Second batch set (MLP nets): graph replays stage update s+1's minibatch while update s still reads its own
-  // (the gather rides in the loss launch, see RideArgs). `alt` holds the set that is NOT selected; select_set()
-  // swaps the two, so every enqueue function keeps reading h->X0, h->fwd1, h->d_tiles ... of the selected set.
-  struct BatchSet {
-    float *X0 = nullptr, *XP = nullptr, *X2 = nullptr, *rew = nullptr, *done = nullptr;
-    float *eps_new = nullptr, *eps_2 = nullptr, *z5 = nullptr, *z6 = nullptr;
-    float* Xc[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    float* W1aT[2] = {nullptr, nullptr};
-    std::vector<Stage> fwd1, fwd2;
-    GemmProb* d_tiles = nullptr;
-  } alt;
+  // Batch sets: graph replays stage a later update's minibatch while update s still reads its own (the gather rides in the
+  // loss / critic-backward launch, see RideArgs). Set 0 is the workspace's own buffers -- the one selected outside of graph
+  // capture, and the one every graph's LAST update works on. kAltSet is the plain graph's second set (MLP nets, alt_ws: rows,
+  // noise and W1aT); kPipeSet + 1..3 are the pipelined graph's sets 1..3 (pipe_ws: rows, noise and the policy forward's outputs).
+  static constexpr int kAltSet = 1, kPipeSet = 1, kPipeSets = 4, kSets = kPipeSet + kPipeSets;
+  static constexpr int pipe_set(int k) { return k ? kPipeSet + k : 0; }   // set k of the pipelined graph in `sets`
+  BatchBufs sets[kSets];
   char* alt_ws = nullptr;
-  int cur_set = 0;             // 0 outside of graph capture
+  int cur_set = 0;             // the selected set; 0 outside of graph capture
   // environment switches, read once at dsact_create (getenv walks the whole environment: ~20 calls per eager update
   // were host time on the launch path)
   std::string env_timeline_stage;   // DSACT_TIMELINE_STAGE
@@ -342,24 +349,12 @@ struct dsact_handle {
   PipeFwd* d_fwdt[2] = {nullptr, nullptr};           // k_chain_fwdt tables (group A, group B), built by dsact_bind_arenas
   PipeFwd* fwdt_host[2] = {nullptr, nullptr};
   float* doutT[3];                      // transposed packs of dL/d(out): q1, q2 [32 x B], policy [roundup32(2A) x B]
-  float* X0t = nullptr;                 // transposed pack of the staged minibatch [roundup32(F+A) x B]
   int dw2_off[4] = {0, 0, 0, 0};        // tile ranges of q1, q2, policy in the dw2 problem list
   int dw2_mid = 0;                      // twin trunks: the critics' FIRST-layer tiles are [dw2_mid, dw2_off[2]) (behind their other tiles)
   int n_heads_parts = 0;                // partial (tanh, sigma) sums the last forward wrote
   // pipelined graph (delayed-update-aware software pipelining, k_chain_fwdp): per-minibatch buffers in kPipeSets copies
   // (set 0 = the workspace's own), one captured graph per phase first_iteration % delay_update
-  struct PipeSet {
-    float *X0 = nullptr, *XP = nullptr, *X2 = nullptr, *rew = nullptr, *done = nullptr;
-    float *eps_new = nullptr, *eps_2 = nullptr, *z5 = nullptr, *z6 = nullptr;
-    float *logits_pi = nullptr, *logits_pit = nullptr, *logp_new = nullptr, *logp2 = nullptr;
-    float* Hpi[DSACT_MAX_HIDDEN_LAYERS]; float* Gpi[DSACT_MAX_HIDDEN_LAYERS];
-    float* qout_t[2] = {nullptr, nullptr};
-    float* part_heads = nullptr;
-    float* X0t = nullptr;
-  };
-  static constexpr int kPipeSets = 4;
   static constexpr int kPipePhases = 4;
-  PipeSet pset[kPipeSets];
   char* pipe_ws = nullptr;
   unsigned long long* pipe_hand[2] = {nullptr, nullptr};   // tagged hand-over buffers [B][32] (value, tag): new_act, act2
   // merged critic backward + critic tiles + close (k_chain_bwd_qt) on the updates that defer their policy backward
@@ -552,22 +547,37 @@ struct Carver {
   }
 };
 
-void carve(dsact_handle* h, Carver& c) {
+// what a batch set has storage of its own for, beyond its rows and noise (which every set has): the policy forward's outputs
+// + q_target's heads + X0t; the W1aT copies; SET_WS: the workspace itself = set 0 with everything that exists only once
+enum : unsigned { SET_FWD = 1, SET_W1AT = 2, SET_WS = 4 | SET_FWD | SET_W1AT };
+
+// The one carve routine: set `s` gets storage for the groups named and keeps the workspace's pointers (set 0's) for every
+// other field. The takes are in the workspace's order, so its layout -- and every allocation's size: the last take of an
+// allocation is not padded -- is fixed here.
+void carve(dsact_handle* h, Carver& c, BatchBufs& s, unsigned groups) {
   const size_t B = h->B;
   const int A = h->A, L = h->L;
-  h->st = c.take<DevState>(1);
-  h->X0 = c.take<float>(B * h->ldx);
-  h->XP = c.take<float>(B * h->ldx);
-  h->X2 = c.take<float>(B * h->ldx);
+  const bool ws = (groups & SET_WS) == SET_WS, fwd = groups & SET_FWD;
+  auto chain_acts = [&](int ch) {
+    for (int l = 0; l < L; ++l) {
+      s.Hb[ch][l] = c.take<float>(B * h->w[l]);
+      s.Gb[ch][l] = c.take<float>(B * h->w[l]);
+    }
+  };
+  if (ws) h->st = c.take<DevState>(1);
+  else s = h->sets[0];
+  s.X0 = c.take<float>(B * h->ldx);
+  s.XP = c.take<float>(B * h->ldx);
+  s.X2 = c.take<float>(B * h->ldx);
   if (!h->cnn) {
     // MLP nets read the observation itself: chains on the same (obs, action) source share one row buffer
-    h->Xc[C_PI] = h->Xc[C_Q1C] = h->Xc[C_Q2C] = h->X0;
-    h->Xc[C_PIT] = h->Xc[C_Q1T] = h->Xc[C_Q2T] = h->X2;
-    h->Xc[C_Q1P] = h->Xc[C_Q2P] = h->XP;
+    s.Xc[C_PI] = s.Xc[C_Q1C] = s.Xc[C_Q2C] = s.X0;
+    s.Xc[C_PIT] = s.Xc[C_Q1T] = s.Xc[C_Q2T] = s.X2;
+    s.Xc[C_Q1P] = s.Xc[C_Q2P] = s.XP;
   } else {
-    // CNN nets: every net has its own encoder, so every chain has its own [features | action] rows
-    h->Xc[C_Q1C] = h->X0; h->Xc[C_Q1P] = h->XP; h->Xc[C_Q1T] = h->X2;
-    for (int ch : {C_PI, C_PIT, C_Q2C, C_Q2T, C_Q2P}) h->Xc[ch] = c.take<float>(B * h->ldx);
+    // CNN nets (the workspace only): every net has its own encoder, so every chain has its own [features | action] rows
+    s.Xc[C_Q1C] = s.X0; s.Xc[C_Q1P] = s.XP; s.Xc[C_Q1T] = s.X2;
+    for (int ch : {C_PI, C_PIT, C_Q2C, C_Q2T, C_Q2P}) s.Xc[ch] = c.take<float>(B * h->ldx);
     const size_t R = h->Brows;
     h->img[0] = c.take<float>(B * h->O);
     h->img[1] = c.take<float>(B * h->O);
@@ -589,53 +599,63 @@ void carve(dsact_handle* h, Carver& c) {
     h->aimg = c.take<float>((size_t)kActRows * h->O);
     h->idx_iota = c.take<int>(R);
   }
-  h->rew = c.take<float>(B);
-  h->done = c.take<float>(B);
-  h->eps_new = c.take<float>(B * A);
-  h->eps_2 = c.take<float>(B * A);
-  h->z5 = c.take<float>(B);
-  h->z6 = c.take<float>(B);
-  for (int ch = 0; ch < N_CHAIN; ++ch)
-    for (int l = 0; l < L; ++l) {
-      h->Hb[ch][l] = c.take<float>(B * h->w[l]);
-      h->Gb[ch][l] = c.take<float>(B * h->w[l]);
-    }
-  for (int s = 0; s < 5; ++s)
-    for (int l = 0; l < L; ++l) h->dZ[s][l] = c.take<float>(B * h->w[l]);
-  h->logits_pi = c.take<float>(B * 2 * A);
-  h->logits_pit = c.take<float>(B * 2 * A);
-  h->logp_new = c.take<float>(B);
-  h->logp2 = c.take<float>(B);
-  for (int i = 0; i < 2; ++i) {
-    h->qout_c[i] = c.take<float>(B * 2);
-    h->qout_t[i] = c.take<float>(B * 2);
-    h->qout_p[i] = c.take<float>(B * 2);
-    h->qstd_c[i] = c.take<float>(B * 2);
+  s.rew = c.take<float>(B);
+  s.done = c.take<float>(B);
+  s.eps_new = c.take<float>(B * A);
+  s.eps_2 = c.take<float>(B * A);
+  s.z5 = c.take<float>(B);
+  s.z6 = c.take<float>(B);
+  if (ws) {
+    for (int ch = 0; ch < N_CHAIN; ++ch) chain_acts(ch);
+    for (int k = 0; k < 5; ++k)
+      for (int l = 0; l < L; ++l) h->dZ[k][l] = c.take<float>(B * h->w[l]);
   }
-  for (int i = 0; i < 4; ++i) h->dout[i] = c.take<float>(B * 2);
-  h->dout_pi = c.take<float>(B * 2 * A);
-  h->d_new_act = c.take<float>(B * A);
-  // GELU output layers (tile-stage kernels only): d y / d z of the heads that are differentiated later
-  for (int i = 0; i < 2; ++i) h->qdmean[i] = h->cfg.value_out_act == OUT_ACT_GELU ? c.take<float>(B) : nullptr;
-  h->pi_dact = h->cfg.policy_out_act == OUT_ACT_GELU ? c.take<float>(B * 2 * A) : nullptr;
-  h->W1aT[0] = c.take<float>((size_t)32 * h->w[0]);
-  h->W1aT[1] = c.take<float>((size_t)32 * h->w[0]);
-  h->part_loss = c.take<float>(B * kLossPart);
-  for (int i = 0; i < 4; ++i) h->W1p[i] = c.take<float>(h->use_w1p ? (size_t)h->w[0] * h->ldx : 4);
-  h->part_heads = c.take<float>((size_t)h->n_heads_wg * 2);
-  h->stats = c.take<float>(16 * (1 + DSACT_STATS_SLOTS));   // [0]: dsact_read_stats; [1 + slot]: the snapshot ring
-  h->ones = c.take<float>(B);
-  h->std_sums = c.take<float>(2);
-  h->timeline = c.take<long long>(1024 * 16);
-  h->dw_parts = c.take<float>(h->dw_chunks > 1 ? (size_t)h->dw_chunks * h->dw_part_stride : 4);
-  for (int i = 0; i < 4; ++i) h->zobs[i] = c.take<float>(B * h->w[0]);
-  h->chain_flags = c.take<int>(kChainFlagInts);   // [unit 0..5][slice] ready flags of the merged forward launch, then the spin-timeout word
-  for (int i = 0; i < 4; ++i) h->dAq[i] = c.take<float>(B * 32);
-  for (int i = 0; i < 2; ++i) h->doutT[i] = c.take<float>(B * 32);
-  h->doutT[2] = c.take<float>(B * (size_t)((2 * A + 31) / 32 * 32));
-  h->X0t = c.take<float>(B * (size_t)((h->F + A + 31) / 32 * 32));
+  if (fwd) {
+    s.logits_pi = c.take<float>(B * 2 * A);
+    s.logits_pit = c.take<float>(B * 2 * A);
+    s.logp_new = c.take<float>(B);
+    s.logp2 = c.take<float>(B);
+    if (!ws) chain_acts(C_PI);   // (a further set has the policy chain's only)
+  }
+  for (int i = 0; i < 2; ++i) {
+    if (ws) h->qout_c[i] = c.take<float>(B * 2);
+    if (fwd) s.qout_t[i] = c.take<float>(B * 2);
+    if (ws) {
+      h->qout_p[i] = c.take<float>(B * 2);
+      h->qstd_c[i] = c.take<float>(B * 2);
+    }
+  }
+  if (ws) {
+    for (int i = 0; i < 4; ++i) h->dout[i] = c.take<float>(B * 2);
+    h->dout_pi = c.take<float>(B * 2 * A);
+    h->d_new_act = c.take<float>(B * A);
+    // GELU output layers (tile-stage kernels only): d y / d z of the heads that are differentiated later
+    for (int i = 0; i < 2; ++i) h->qdmean[i] = h->cfg.value_out_act == OUT_ACT_GELU ? c.take<float>(B) : nullptr;
+    h->pi_dact = h->cfg.policy_out_act == OUT_ACT_GELU ? c.take<float>(B * 2 * A) : nullptr;
+  }
+  if (groups & SET_W1AT)
+    for (int i = 0; i < 2; ++i) s.W1aT[i] = c.take<float>((size_t)32 * h->w[0]);
+  if (ws) {
+    h->part_loss = c.take<float>(B * kLossPart);
+    for (int i = 0; i < 4; ++i) h->W1p[i] = c.take<float>(h->use_w1p ? (size_t)h->w[0] * h->ldx : 4);
+  }
+  if (fwd) s.part_heads = c.take<float>((size_t)h->n_heads_wg * 2);
+  if (ws) {
+    h->stats = c.take<float>(16 * (1 + DSACT_STATS_SLOTS));   // [0]: dsact_read_stats; [1 + slot]: the snapshot ring
+    h->ones = c.take<float>(B);
+    h->std_sums = c.take<float>(2);
+    h->timeline = c.take<long long>(1024 * 16);
+    h->dw_parts = c.take<float>(h->dw_chunks > 1 ? (size_t)h->dw_chunks * h->dw_part_stride : 4);
+    for (int i = 0; i < 4; ++i) h->zobs[i] = c.take<float>(B * h->w[0]);
+    h->chain_flags = c.take<int>(kChainFlagInts);   // [unit 0..5][slice] ready flags of the merged forward launch, then the spin-timeout word
+    for (int i = 0; i < 4; ++i) h->dAq[i] = c.take<float>(B * 32);
+    for (int i = 0; i < 2; ++i) h->doutT[i] = c.take<float>(B * 32);
+    h->doutT[2] = c.take<float>(B * (size_t)((2 * A + 31) / 32 * 32));
+  }
+  if (fwd) s.X0t = c.take<float>(B * (size_t)((h->F + A + 31) / 32 * 32));
+  if (!ws) return;
   if (h->twin) {
-    h->X0t_net[0] = h->X0t;
+    h->X0t_net[0] = s.X0t;
     for (int i = 1; i < 3; ++i) h->X0t_net[i] = c.take<float>(B * (size_t)((h->F + A + 31) / 32 * 32));
     for (int i = 0; i < 3; ++i) h->dz0row[i] = c.take<float>(B * h->w[0]);
     for (int i = 0; i < 8; ++i) h->twin_part[i] = c.take<float>(B * 64);
@@ -651,6 +671,14 @@ void carve(dsact_handle* h, Carver& c) {
   for (int l = 0; l < L; ++l) wmax = h->w[l] > wmax ? h->w[l] : wmax;
   h->Gact = c.take<float>((size_t)kActRows * wmax);
   h->act_out = c.take<float>((size_t)kActRows * 2 * A);
+  static_cast<BatchBufs&>(*h) = s;   // the handle starts on set 0
+}
+
+// the handle's per-minibatch pointers and task tables := set k; 0 restores the workspace's own
+void select_set(dsact_handle* h, int k) {
+  if (k == h->cur_set) return;
+  static_cast<BatchBufs&>(*h) = h->sets[k];
+  h->cur_set = k;
 }
 
 // ---- stage descriptions ---------------------------------------------------------------------------
@@ -705,40 +733,20 @@ void fwd_probs(const dsact_handle* h, int ch, int l, const float* x0, int ldx0, 
 }
 
 
-void select_set(dsact_handle* h, int set) {
-  if (set == h->cur_set) return;
-  dsact_handle::BatchSet& a = h->alt;
-  std::swap(h->X0, a.X0); std::swap(h->XP, a.XP); std::swap(h->X2, a.X2); std::swap(h->rew, a.rew); std::swap(h->done, a.done);
-  std::swap(h->eps_new, a.eps_new); std::swap(h->eps_2, a.eps_2); std::swap(h->z5, a.z5); std::swap(h->z6, a.z6);
-  for (int i = 0; i < 8; ++i) std::swap(h->Xc[i], a.Xc[i]);
-  for (int i = 0; i < 2; ++i) std::swap(h->W1aT[i], a.W1aT[i]);
-  h->fwd1.swap(a.fwd1); h->fwd2.swap(a.fwd2);
-  std::swap(h->d_tiles, a.d_tiles);
-  h->cur_set = set;
-}
-
-// the second batch set's buffers (MLP nets only); zeroed like the workspace
+// the plain graph's second batch set (MLP nets only); zeroed like the workspace
 int alloc_alt_set(dsact_handle* h) {
   if (h->cnn || h->alt_ws) return DSACT_OK;
-  const size_t B = h->B;
-  const int A = h->A;
+  BatchBufs& a = h->sets[dsact_handle::kAltSet];
   for (int pass = 0; pass < 2; ++pass) {
     Carver c;
     c.base = pass ? h->alt_ws : nullptr;
-    dsact_handle::BatchSet& a = h->alt;
-    a.X0 = c.take<float>(B * h->ldx); a.XP = c.take<float>(B * h->ldx); a.X2 = c.take<float>(B * h->ldx);
-    a.rew = c.take<float>(B); a.done = c.take<float>(B);
-    a.eps_new = c.take<float>(B * A); a.eps_2 = c.take<float>(B * A); a.z5 = c.take<float>(B); a.z6 = c.take<float>(B);
-    a.W1aT[0] = c.take<float>((size_t)32 * h->w[0]); a.W1aT[1] = c.take<float>((size_t)32 * h->w[0]);
+    carve(h, c, a, SET_W1AT);
     if (!pass) {
       HIPCHK(h, hipMalloc((void**)&h->alt_ws, c.off + 256));
       HIPCHK(h, hipMemset(h->alt_ws, 0, c.off + 256));
     }
   }
-  dsact_handle::BatchSet& a = h->alt;
-  a.Xc[C_PI] = a.Xc[C_Q1C] = a.Xc[C_Q2C] = a.X0;
-  a.Xc[C_PIT] = a.Xc[C_Q1T] = a.Xc[C_Q2T] = a.X2;
-  a.Xc[C_Q1P] = a.Xc[C_Q2P] = a.XP;
+  a.fwd1.clear(); a.fwd2.clear(); a.d_tiles = nullptr;   // its task tables are its own: dsact_bind_arenas builds them
   return DSACT_OK;
 }
 
@@ -1087,10 +1095,13 @@ int build_tasks(dsact_handle* h) {
       add_tiles(t);
     }
   }
-  if (h->d_tiles) { hipFree(h->d_tiles); h->d_tiles = nullptr; }
+  BatchBufs& own = h->sets[h->cur_set];   // the tables bake the selected set's pointers: they stay with it
+  if (own.d_tiles) { hipFree(own.d_tiles); own.d_tiles = h->d_tiles = nullptr; }
   h->n_dw_tiles = (int)tiles.size();
   h->dw_off[3] = h->n_dw_tiles;
-  HIPCHK(h, hipMalloc(&h->d_tiles, tiles.size() * sizeof(GemmProb)));
+  HIPCHK(h, hipMalloc(&own.d_tiles, tiles.size() * sizeof(GemmProb)));
+  h->d_tiles = own.d_tiles;
+  own.fwd1 = h->fwd1; own.fwd2 = h->fwd2;
   HIPCHK(h, hipMemcpy(h->d_tiles, tiles.data(), tiles.size() * sizeof(GemmProb), hipMemcpyHostToDevice));
   return DSACT_OK;
 }
@@ -1121,7 +1132,7 @@ FusedOpt fused_opt(const dsact_handle* h, bool enable) {
     for (int i = 0; i < h->nq; ++i) {
       f.mir_lo[i] = (long long)(net_grads(h, on[i]) - h->grads) + (long long)h->qd.w_off[0];
       f.mir_w[i] = h->W1p[i]; f.mir_wt[i] = h->W1p[2 + i];
-      f.mir_at[i] = h->alt.W1aT[i];   // the NEXT update's copy (this one is being read by k_heads_bwd)
+      f.mir_at[i] = h->sets[h->cur_set ^ 1].W1aT[i];   // the NEXT update's copy, in the plain graph's other set (this one is being read by k_heads_bwd)
     }
   }
   return f;
@@ -1840,6 +1851,20 @@ FwdUnit fwd_unit(const dsact_handle* h, int ch, int seg, int head) {
   return u;
 }
 
+// the shape-wide fields of a forward launch's arguments, whatever its form (direct arguments, twin-trunk table, pipelined
+// table); `name`: the launch's timeline name. Fat mode counts the first layer's segments in its own chunks (the table forms
+// never run in fat mode)
+void fill_fwd_shape(dsact_handle* h, FwdArgs& a, const char* name) {
+  a.B = h->B; a.F = h->F; a.A = h->A; a.L = h->L; a.ldx = h->ldx;
+  a.s_obs = h->fat ? h->c_obs : h->s_obs; a.s_act = h->fat ? h->c_act : h->s_act; a.v1_stats = h->nq == 1; a.Cb = h->B / 16;
+  a.act_scale = h->act_scale; a.act_center = h->act_center; a.lo_ls = h->cfg.min_log_std; a.hi_ls = h->cfg.max_log_std;
+  a.timeline = tl_for(h, name);
+  a.spin_timeout = h->handoff_dev;
+  a.debug_withhold = h->debug_withhold == 1;   // tests: a producer never raises slice 0's flag
+  // the forward packs have no padding steps; FwdArgs::tpad stays (always 0) so that the chain kernels' code is unchanged
+  a.tpad = 0;
+}
+
 // rg: rows per workgroup / 4 of every unit that has not chosen its own (FwdUnit::rg != 0); map: nullptr = uniform placement
 void fill_fwd_common(dsact_handle* h, FwdArgs& a, int rg, const char* name, const XcdMap* map = nullptr) {
   for (int k = 0; k < a.n_units; ++k) {
@@ -1847,25 +1872,23 @@ void fill_fwd_common(dsact_handle* h, FwdArgs& a, int rg, const char* name, cons
     a.u[k].n_slices = (short)(h->B / (4 * a.u[k].rg));
   }
   a.map = map ? *map : xcd_map_uniform(a.n_units);
-  a.B = h->B; a.F = h->F; a.A = h->A; a.L = h->L; a.ldx = h->ldx;
-  a.s_obs = h->fat ? h->c_obs : h->s_obs; a.s_act = h->fat ? h->c_act : h->s_act; a.v1_stats = h->nq == 1; a.Cb = h->B / 16;
-  a.act_scale = h->act_scale; a.act_center = h->act_center; a.lo_ls = h->cfg.min_log_std; a.hi_ls = h->cfg.max_log_std;
-  a.timeline = tl_for(h, name);
-  a.spin_timeout = h->handoff_dev;
-  a.debug_withhold = h->debug_withhold == 1;
-  // the forward packs have no padding steps; FwdArgs::tpad stays (always 0, here and in the zeroed PipeFwd of the pipelined
-  // forward) so that the chain kernels' code is unchanged
-  a.tpad = 0;
+  fill_fwd_shape(h, a, name);
+}
+
+// what makes the units of policy(obs) and policy_target(obs2) policy units, on the selected batch set: each head writes its
+// sampled action into the rows of the critic chains that read it. The caller adds its hand-over fields.
+void policy_pair(const dsact_handle* h, FwdUnit& pi, FwdUnit& pt) {
+  pi.logits = h->logits_pi; pi.logp = h->logp_new; pi.eps = h->eps_new; pi.xact = h->Xc[C_Q1P]; pi.part_heads = h->part_heads;
+  pt.logits = h->logits_pit; pt.logp = h->logp2; pt.eps = h->eps_2; pt.xact = h->Xc[C_Q1T];
+  for (int l = 0; l < h->L; ++l) pt.G[l] = nullptr;   // never differentiated
 }
 
 // group A: policy(obs), policy_target(obs2), q1/q2(obs,act) + observation part of q1_t/q2_t(obs2, .)
 void fwd_args_a(dsact_handle* h, FwdArgs& a) {
   memset(&a, 0, sizeof(a));
-  FwdUnit& pi = a.u[0] = fwd_unit(h, C_PI, SEG_FULL, HEAD_POLICY);
-  pi.logits = h->logits_pi; pi.logp = h->logp_new; pi.eps = h->eps_new; pi.xact = h->Xc[C_Q1P]; pi.part_heads = h->part_heads;
-  FwdUnit& pt = a.u[1] = fwd_unit(h, C_PIT, SEG_FULL, HEAD_POLICY);
-  pt.logits = h->logits_pit; pt.logp = h->logp2; pt.eps = h->eps_2; pt.xact = h->Xc[C_Q1T];
-  for (int l = 0; l < h->L; ++l) pt.G[l] = nullptr;   // never differentiated
+  a.u[0] = fwd_unit(h, C_PI, SEG_FULL, HEAD_POLICY);
+  a.u[1] = fwd_unit(h, C_PIT, SEG_FULL, HEAD_POLICY);
+  policy_pair(h, a.u[0], a.u[1]);
   const int nq = h->nq;      // 2 critics (DSAC_V2) or 1 (DSAC_V1): units [pi, pit, q_c x nq, q_t(obs) x nq]
   for (int i = 0; i < nq; ++i) {
     FwdUnit& qc = a.u[2 + i] = fwd_unit(h, C_Q1C + i, SEG_FULL_SAVE, HEAD_Q);
@@ -1930,18 +1953,14 @@ int build_twin_fwd(dsact_handle* h) {
     };
     if (grp == 0) {
       FwdUnit* pi = add(C_PI, HEAD_POLICY);
-      for (int t = 0; t < 2; ++t) {
-        pi[t].logits = h->logits_pi; pi[t].logp = h->logp_new; pi[t].eps = h->eps_new;
-        pi[t].xact = h->Xc[C_Q1P]; pi[t].xact2 = nq == 2 ? h->Xc[C_Q2P] : nullptr;
-      }
-      pi[1].part_heads = h->part_heads;
-      pi[0].x0t = h->X0t_net[2];
       FwdUnit* pt = add(C_PIT, HEAD_POLICY);
-      for (int t = 0; t < 2; ++t) {
-        pt[t].logits = h->logits_pit; pt[t].logp = h->logp2; pt[t].eps = h->eps_2;
-        pt[t].xact = h->Xc[C_Q1T]; pt[t].xact2 = nq == 2 ? h->Xc[C_Q2T] : nullptr;
-        for (int l = 0; l < L; ++l) pt[t].G[l] = nullptr;   // never differentiated
+      for (int t = 0; t < 2; ++t) {   // (every critic has input rows of its own: the second one's take the action too)
+        policy_pair(h, pi[t], pt[t]);
+        pi[t].xact2 = nq == 2 ? h->Xc[C_Q2P] : nullptr;
+        pt[t].xact2 = nq == 2 ? h->Xc[C_Q2T] : nullptr;
       }
+      pi[0].part_heads = nullptr;   // the head runs in the second trunk's unit
+      pi[0].x0t = h->X0t_net[2];
       for (int i = 0; i < nq; ++i) {
         FwdUnit* qc = add(C_Q1C + i, HEAD_Q);
         for (int t = 0; t < 2; ++t) { qc[t].qout = h->qout_c[i]; qc[t].qstd = h->qstd_c[i]; }
@@ -1979,12 +1998,7 @@ int build_twin_fwd(dsact_handle* h) {
     FwdArgs& c = P.c;
     c.n_units = 2 * n_nets;
     for (int k = 0; k < c.n_units; ++k) { P.u[k].rg = (short)rg; P.u[k].n_slices = (short)(h->B / (4 * rg)); }
-    c.B = h->B; c.F = h->F; c.A = h->A; c.L = L; c.ldx = h->ldx;
-    c.s_obs = h->s_obs; c.s_act = h->s_act; c.v1_stats = nq == 1; c.Cb = h->B / 16;
-    c.act_scale = h->act_scale; c.act_center = h->act_center; c.lo_ls = h->cfg.min_log_std; c.hi_ls = h->cfg.max_log_std;
-    c.timeline = tl_for(h, name);
-    c.spin_timeout = h->handoff_dev;
-    c.debug_withhold = h->debug_withhold == 1;   // tests: the first trunk of the policy never raises slice 0's flag
+    fill_fwd_shape(h, c, name);
     const int n_slices = h->B / (4 * rg);
     if (par) {
       // XCDs 0-3 run the first trunks, 4-7 the second ones; the nets share each half (rep XCDs per net, slices dealt
@@ -2183,55 +2197,19 @@ int enqueue_chain_fwd_merged(dsact_handle* h) {
 // LAST update on set 0 = the workspace's own buffers, so whatever reads the handle after a replay -- statistics, debug
 // reads, dsact_read_batch -- sees the last update as after eager updates), update s's forward launch may also fill set
 // s + 1 (policy units of the next minibatch), and the gather riding in update s's critic-backward launch fills set s + 2.
+// The sets are derived again on every call: they share set 0's task tables, which change with the arenas.
 int alloc_pipe_sets(dsact_handle* h) {
-  if (h->pipe_ws) return DSACT_OK;
-  const size_t B = h->B;
-  const int A = h->A, L = h->L;
-  for (int pass = 0; pass < 2; ++pass) {
+  for (int pass = h->pipe_ws ? 1 : 0; pass < 2; ++pass) {
     Carver c;
-    c.base = pass ? h->pipe_ws : nullptr;
-    for (int k = 1; k < dsact_handle::kPipeSets; ++k) {
-      dsact_handle::PipeSet& p = h->pset[k];
-      p.X0 = c.take<float>(B * h->ldx); p.XP = c.take<float>(B * h->ldx); p.X2 = c.take<float>(B * h->ldx);
-      p.rew = c.take<float>(B); p.done = c.take<float>(B);
-      p.eps_new = c.take<float>(B * A); p.eps_2 = c.take<float>(B * A); p.z5 = c.take<float>(B); p.z6 = c.take<float>(B);
-      p.logits_pi = c.take<float>(B * 2 * A); p.logits_pit = c.take<float>(B * 2 * A);
-      p.logp_new = c.take<float>(B); p.logp2 = c.take<float>(B);
-      for (int l = 0; l < L; ++l) { p.Hpi[l] = c.take<float>(B * h->w[l]); p.Gpi[l] = c.take<float>(B * h->w[l]); }
-      for (int i = 0; i < 2; ++i) p.qout_t[i] = c.take<float>(B * 2);
-      p.part_heads = c.take<float>((size_t)h->n_heads_wg * 2);
-      p.X0t = c.take<float>(B * (size_t)((h->F + A + 31) / 32 * 32));
-    }
-    for (int i = 0; i < 2; ++i) h->pipe_hand[i] = c.take<unsigned long long>(B * 32);
+    c.base = h->pipe_ws;
+    for (int k = 1; k < dsact_handle::kPipeSets; ++k) carve(h, c, h->sets[dsact_handle::pipe_set(k)], SET_FWD);
+    for (int i = 0; i < 2; ++i) h->pipe_hand[i] = c.take<unsigned long long>((size_t)h->B * 32);
     if (!pass) {
       HIPCHK(h, hipMalloc((void**)&h->pipe_ws, c.off + 256));
       HIPCHK(h, hipMemset(h->pipe_ws, 0, c.off + 256));
     }
   }
-  dsact_handle::PipeSet& p0 = h->pset[0];
-  p0.X0 = h->X0; p0.XP = h->XP; p0.X2 = h->X2; p0.rew = h->rew; p0.done = h->done;
-  p0.eps_new = h->eps_new; p0.eps_2 = h->eps_2; p0.z5 = h->z5; p0.z6 = h->z6;
-  p0.logits_pi = h->logits_pi; p0.logits_pit = h->logits_pit; p0.logp_new = h->logp_new; p0.logp2 = h->logp2;
-  for (int l = 0; l < L; ++l) { p0.Hpi[l] = h->Hb[C_PI][l]; p0.Gpi[l] = h->Gb[C_PI][l]; }
-  for (int i = 0; i < 2; ++i) p0.qout_t[i] = h->qout_t[i];
-  p0.part_heads = h->part_heads;
-  p0.X0t = h->X0t;
   return DSACT_OK;
-}
-
-// the handle's per-minibatch pointers := set k (every args builder reads the handle); k = 0 restores the workspace's own
-void apply_pipe_set(dsact_handle* h, int k) {
-  const dsact_handle::PipeSet& p = h->pset[k];
-  h->X0 = p.X0; h->XP = p.XP; h->X2 = p.X2; h->rew = p.rew; h->done = p.done;
-  h->eps_new = p.eps_new; h->eps_2 = p.eps_2; h->z5 = p.z5; h->z6 = p.z6;
-  h->logits_pi = p.logits_pi; h->logits_pit = p.logits_pit; h->logp_new = p.logp_new; h->logp2 = p.logp2;
-  for (int l = 0; l < h->L; ++l) { h->Hb[C_PI][l] = p.Hpi[l]; h->Gb[C_PI][l] = p.Gpi[l]; }
-  for (int i = 0; i < 2; ++i) h->qout_t[i] = p.qout_t[i];
-  h->part_heads = p.part_heads;
-  h->X0t = p.X0t;
-  h->Xc[C_PI] = h->Xc[C_Q1C] = h->Xc[C_Q2C] = h->X0;
-  h->Xc[C_PIT] = h->Xc[C_Q1T] = h->Xc[C_Q2T] = h->X2;
-  h->Xc[C_Q1P] = h->Xc[C_Q2P] = h->XP;
 }
 
 const char* pipe_fwd_name(bool pre, bool do_pre) {
@@ -2322,17 +2300,16 @@ int pipe_fwd_build(dsact_handle* h, int set_own, int set_next, bool pre, bool do
   };
   // in-launch hand-over of the sampled actions: (value, tag) pairs, the data is the flag (pipe_hand[0]: new_act, [1]: act2)
   auto policy_units = [&](int r_pi, int r_pit, bool hand_over) {
-    FwdUnit pi = fwd_unit(h, C_PI, SEG_FULL, HEAD_POLICY);
-    pi.logits = h->logits_pi; pi.logp = h->logp_new; pi.eps = h->eps_new; pi.xact = h->Xc[C_Q1P]; pi.part_heads = h->part_heads;
-    if (hand_over) { pi.xact2 = (float*)h->pipe_hand[0]; pi.late_wait |= HW_PAIRS_OUT; }
+    FwdUnit pi = fwd_unit(h, C_PI, SEG_FULL, HEAD_POLICY), pt = fwd_unit(h, C_PIT, SEG_FULL, HEAD_POLICY);
+    policy_pair(h, pi, pt);
+    if (hand_over) {
+      pi.xact2 = (float*)h->pipe_hand[0]; pi.late_wait |= HW_PAIRS_OUT;
+      pt.xact2 = (float*)h->pipe_hand[1]; pt.late_wait |= HW_PAIRS_OUT;
+    }
     put(r_pi, pi);
-    FwdUnit pt = fwd_unit(h, C_PIT, SEG_FULL, HEAD_POLICY);
-    pt.logits = h->logits_pit; pt.logp = h->logp2; pt.eps = h->eps_2; pt.xact = h->Xc[C_Q1T];
-    for (int l = 0; l < h->L; ++l) pt.G[l] = nullptr;   // never differentiated
-    if (hand_over) { pt.xact2 = (float*)h->pipe_hand[1]; pt.late_wait |= HW_PAIRS_OUT; }
     put(r_pit, pt);
   };
-  apply_pipe_set(h, set_own);
+  select_set(h, set_own);
   if (!pre) policy_units(PR_PI, PR_PIT, true);
   // q(obs, new_act): eager updates run it as "saved observation part of q(obs, act)'s first layer + action part". A unit
   // that computes the observation part itself and merges the accumulators where the hand-over would have (SEG_FULL_SPLIT)
@@ -2359,19 +2336,14 @@ int pipe_fwd_build(dsact_handle* h, int set_own, int set_next, bool pre, bool do
     put(PR_Q1T + i, qt);
   }
   if (do_pre) {
-    apply_pipe_set(h, set_next);
+    select_set(h, set_next);
     policy_units(PR_PIN, PR_PITN, false);
-    apply_pipe_set(h, set_own);
+    select_set(h, set_own);
   }
   // common fields
   FwdArgs& a = P.c;
   a.n_units = PR_N;
-  a.B = h->B; a.F = h->F; a.A = h->A; a.L = h->L; a.ldx = h->ldx;
-  a.s_obs = h->s_obs; a.s_act = h->s_act; a.v1_stats = h->nq == 1; a.Cb = h->B / 16;
-  a.act_scale = h->act_scale; a.act_center = h->act_center; a.lo_ls = h->cfg.min_log_std; a.hi_ls = h->cfg.max_log_std;
-  a.timeline = tl_for(h, pipe_fwd_name(pre, do_pre));
-  a.spin_timeout = h->handoff_dev;
-  a.debug_withhold = h->debug_withhold == 1;
+  fill_fwd_shape(h, a, pipe_fwd_name(pre, do_pre));
   a.tagp = &h->st->tag_seq;
   // block table: every XCD's queue is filled role by role (the enum is the priority order), a role's slices are dealt
   // round-robin over its XCDs; block 8 r + x = entry r of XCD x's queue (the dispatcher places block b on XCD b % 8)
@@ -3425,13 +3397,13 @@ int dsact_create(const dsact_config* cfg, int device, dsact_handle** out) {
     h->pi_merge = ok && !h->cnn && h->B <= 512 && !h->fat_bwd && getenv("DSACT_NO_PI_MERGE") == nullptr;
   }
   Carver c0;
-  carve(h, c0);
+  carve(h, c0, h->sets[0], SET_WS);
   h->ws_bytes = c0.off + 256;
   HIPCHK(h, hipMalloc(&h->ws, h->ws_bytes));
   HIPCHK(h, hipMemset(h->ws, 0, h->ws_bytes));
   Carver c1;
   c1.base = h->ws;
-  carve(h, c1);
+  carve(h, c1, h->sets[0], SET_WS);
   {
     DevState st0;
     memset(&st0, 0, sizeof(st0));
@@ -3593,8 +3565,7 @@ int dsact_destroy(dsact_handle* h) {
   if (h->beh_host_ev) hipEventDestroy(h->beh_host_ev);
   free(h->act_buf);
   delete h->act_pool;
-  if (h->d_tiles) hipFree(h->d_tiles);
-  if (h->alt.d_tiles) hipFree(h->alt.d_tiles);
+  for (int k : {0, (int)dsact_handle::kAltSet}) if (h->sets[k].d_tiles) hipFree(h->sets[k].d_tiles);   // (the other sets share set 0's)
   if (h->alt_ws) hipFree(h->alt_ws);
   if (h->pipe_ws) hipFree(h->pipe_ws);
   if (h->bqt_cnt) hipFree(h->bqt_cnt);
@@ -3669,7 +3640,7 @@ int dsact_bind_arenas(dsact_handle* h, float* online, float* target, float* adam
   if (h->chain_ok) (void)dw2_args(h, false);   // tile ranges of the dw2 problem list
   if (!h->cnn) {   // the same task lists over the second batch set
     TRY(alloc_alt_set(h));
-    select_set(h, 1);
+    select_set(h, dsact_handle::kAltSet);
     int rc = build_tasks(h);
     select_set(h, 0);
     TRY(rc);
@@ -4396,6 +4367,7 @@ static int capture_updates(dsact_handle* h, int n, uint32_t flags, bool merged, 
   if (!merged) {
     for (int s = 0; s < n && rc == DSACT_OK; ++s) rc = enqueue_graph_step(h, s, flags);
   } else {
+    static_assert(dsact_handle::kAltSet == 1, "the plain graph alternates between sets 0 and kAltSet by parity");
     h->mirror_w0 = true;
     select_set(h, (n - 1) & 1);
     rc = enqueue_gather(h, h->idx_table, h->idx_rows, 1, 0, 1, /*bookkeeping=*/0);
@@ -4450,7 +4422,7 @@ struct PipePlan {
 // unit tables of the n forward launches -> plan.host and (synchronous copy: call it BEFORE a stream capture begins) dev_args
 static int plan_updates_pipe(dsact_handle* h, int n, int phase, PipePlan& plan, PipeFwd* dev_args, uint32_t flags = 0) {
   const int D = h->cfg.delay_update;
-  auto set_of = [&](int s) { return (s - (n - 1)) & (dsact_handle::kPipeSets - 1); };
+  auto set_of = [&](int s) { return dsact_handle::pipe_set((s - (n - 1)) & (dsact_handle::kPipeSets - 1)); };
   plan.host.resize((size_t)n); plan.pre.resize((size_t)n); plan.dop.resize((size_t)n);
   plan.form.assign((size_t)n, BWD_PLAIN); plan.bp.resize((size_t)n); plan.bp_rg.assign((size_t)n, 2);
   // the discarded policy backward can move when it is the merged launch's (chain + its own tiles behind the arrival counter)
@@ -4474,7 +4446,7 @@ static int plan_updates_pipe(dsact_handle* h, int n, int phase, PipePlan& plan, 
     plan.leaves[(size_t)s] = leaves_policy;
     const BwdPiArgs* bp = nullptr;
     if (s > 0 && defers_pi(plan.form[(size_t)s - 1])) {
-      apply_pipe_set(h, set_of(s - 1));   // the deferred backward works on the PREVIOUS update's minibatch
+      select_set(h, set_of(s - 1));   // the deferred backward works on the PREVIOUS update's minibatch
       BwdPiArgs& a = plan.bp[(size_t)s];
       // (the deferred chain shares its launch with forward chains, not with ~500 riding tiles: 4-row slices by default)
       // (fused = false: the tiles compute, apply nothing and store nothing -- and never read the step state, which the
@@ -4492,13 +4464,13 @@ static int plan_updates_pipe(dsact_handle* h, int n, int phase, PipePlan& plan, 
     pre = do_pre;
   }
   h->mirror_w0 = false;
-  apply_pipe_set(h, 0);
+  select_set(h, 0);
   TRY(rc);
   HIPCHK(h, hipMemcpy(dev_args, plan.host.data(), (size_t)n * sizeof(PipeFwd), hipMemcpyHostToDevice));
   return DSACT_OK;
 }
 static int enqueue_updates_pipe(dsact_handle* h, int n, const PipePlan& plan, PipeFwd* dev_args) {
-  auto set_of = [&](int s) { return (s - (n - 1)) & (dsact_handle::kPipeSets - 1); };
+  auto set_of = [&](int s) { return dsact_handle::pipe_set((s - (n - 1)) & (dsact_handle::kPipeSets - 1)); };
   const std::vector<PipeFwd>& host = plan.host;
   const std::vector<char>&pre_v = plan.pre, &do_v = plan.dop;
   int rc = DSACT_OK;
@@ -4506,14 +4478,14 @@ static int enqueue_updates_pipe(dsact_handle* h, int n, const PipePlan& plan, Pi
   {
     // the first two minibatches (+ the packed-copy refresh: anything may have written the arenas since the last replay)
     Gather2Args g;
-    apply_pipe_set(h, set_of(0));
+    select_set(h, set_of(0));
     g.a = gather_args(h, h->idx_table, h->idx_rows, 1, 0, 1);
     g.a.bookkeeping = 0;
     g.a.rp = repack_args(h, repack_blocks(h));
     g.b = g.a;
     g.b.n_gather_blocks = 0;
     if (n > 1) {
-      apply_pipe_set(h, set_of(1));
+      select_set(h, set_of(1));
       g.b = gather_args(h, h->idx_table, h->idx_rows, 1, 0, 1);
       g.b.bookkeeping = 0; g.b.lookahead = 1;
       g.b.rp = repack_args(h, 0);
@@ -4521,7 +4493,7 @@ static int enqueue_updates_pipe(dsact_handle* h, int n, const PipePlan& plan, Pi
     rc = launch(h, "gather", k_gather2, dim3(g.a.n_gather_blocks + g.b.n_gather_blocks + g.a.rp.n_blocks), dim3(kThreads), 0, g);
   }
   for (int s = 0; s < n && rc == DSACT_OK; ++s) {
-    apply_pipe_set(h, set_of(s));
+    select_set(h, set_of(s));
     const bool carries = s > 0 && defers_pi(plan.form[(size_t)s - 1]);
     rc = launch_chain_fwd_pipe(h, pipe_fwd_name(pre_v[(size_t)s], do_v[(size_t)s]), host[(size_t)s], dev_args + s,
                                carries ? &plan.bp[(size_t)s] : nullptr, plan.bp_rg[(size_t)s]);
@@ -4529,11 +4501,11 @@ static int enqueue_updates_pipe(dsact_handle* h, int n, const PipePlan& plan, Pi
     RideArgs ride;
     memset(&ride, 0, sizeof(ride));
     if (s + 2 < n) {
-      apply_pipe_set(h, set_of(s + 2));   // destination of the riding gather
+      select_set(h, set_of(s + 2));   // destination of the riding gather
       ride.g = gather_args(h, h->idx_table, h->idx_rows, 1, 0, 1);
       ride.g.lookahead = 2;
       ride.n_gather = ride.g.n_gather_blocks;
-      apply_pipe_set(h, set_of(s));
+      select_set(h, set_of(s));
     } else {
       ride.g = gather_args(h, h->idx_table, h->idx_rows, 1, 0, 1);   // (st / hp of the bookkeeping block)
       ride.n_gather = 0;
@@ -4548,7 +4520,7 @@ static int enqueue_updates_pipe(dsact_handle* h, int n, const PipePlan& plan, Pi
     }
     rc = enqueue_grads(h, !(plan.skip && plan.leaves[(size_t)s]), true, PH_BACKWARD, &ride, form);
   }
-  apply_pipe_set(h, 0);
+  select_set(h, 0);
   h->mirror_w0 = false;
   h->n_heads_parts = h->B / 4;
   return rc;
@@ -4619,7 +4591,7 @@ static int build_graph(dsact_handle* h, int steps_per_graph, uint32_t flags, boo
     if (rc != DSACT_OK) {   // (e.g. out of memory for the extra minibatch sets): the plain graph serves the same contract
       drop_active_graph(h);   // the partially built pipelined graph only: cached graphs of other shapes stay
       (void)hipGetLastError();
-      if (h->pipe_ws) apply_pipe_set(h, 0);   // (set 0 = the workspace's own buffers, recorded once the extra sets exist)
+      select_set(h, 0);
       rc = DSACT_OK;
     }
   }
@@ -5201,7 +5173,8 @@ int dsact_debug_set(dsact_handle* h, const char* name, double value) {
     // does not see -- its producer's stores then computes on `value` (tests pass NaN).
     const float v = (float)value;
     for (int i = 0; i < 4; ++i) TRY(debug_fill(h, h->zobs[i], 1, 0, 0, h->B * h->w[0], v));
-    float* rows[4] = {h->XP, h->X2, h->alt.XP, h->alt.X2};
+    const BatchBufs& alt = h->sets[dsact_handle::kAltSet];
+    float* rows[4] = {h->XP, h->X2, alt.XP, alt.X2};
     for (float* r : rows) TRY(debug_fill(h, r, h->B, h->ldx, h->F, h->A, v));
     for (int i = 0; i < 2; ++i) TRY(debug_fill(h, h->dAq[i], 1, 0, 0, h->B * 32, v));
     // merged policy backward: the policy's dZ packs its weight-gradient tiles wait for
