@@ -301,6 +301,7 @@ struct dsact_handle : BatchBufs {
   uint64_t act_seed = 0;                 // dsact_set_act_rng: 0 = no in-kernel draw (eps must be passed)
   unsigned long long act_dev_calls = 0;  // dsact_act_sample_device chunks launched
   unsigned long long ring_commit_rows = 0;   // transitions written by dsact_buffer_add_device
+  unsigned long long* digest_dev = nullptr;  // dsact_buffer_digest: the six 64-bit sums k_ring_digest adds into (allocated by the first call)
   unsigned long long act_dev_syncs = 0;  // stream synchronisations made inside those two entry points (stays 0)
   // device-resident evaluation (dsact_act_mode_device / dsact_eval_*): the episode bookkeeping's state
   int* ev_ep = nullptr; double* ev_acc = nullptr; int* ev_len = nullptr;   // [ev_cap_n]
@@ -3554,6 +3555,7 @@ int dsact_destroy(dsact_handle* h) {
     if (p) hipFree(p);
   if (h->ev_remaining_host) hipHostFree(h->ev_remaining_host);
   if (h->tk_dev) hipFree(h->tk_dev);
+  if (h->digest_dev) hipFree(h->digest_dev);
   if (h->tk_host) hipHostFree(h->tk_host);
   for (int i = 0; i < 2; ++i) if (h->ab_h[i]) hipFree(h->ab_h[i]);
   if (h->pol_host) hipHostFree(h->pol_host);
@@ -3974,6 +3976,141 @@ int dsact_buffer_add_device(dsact_handle* h, int64_t n, const float* obs, const 
   h->size = h->size + n > h->cap ? h->cap : h->size + n;
   h->ring_commit_rows += (unsigned long long)n;
   return DSACT_OK;
+}
+
+// ---- ring snapshots: the ring's stored form out of and into HBM, its cursor, and an integrity digest ----
+namespace {
+// the six columns in the SoA order of DESIGN.md section 3: device base, bytes per row
+struct RingColumn { char* base; size_t row_bytes; };
+void ring_columns(const dsact_handle* h, RingColumn c[6]) {
+  const size_t O = (size_t)h->O, A = (size_t)h->A;
+  if (h->rb_code) {
+    c[0] = {(char*)h->rb_code, O};
+    c[1] = {(char*)h->rb_code + (size_t)h->cap * O, O};
+  } else {
+    c[0] = {(char*)h->rb_obs, O * sizeof(float)};
+    c[1] = {(char*)h->rb_obs2, O * sizeof(float)};
+  }
+  c[2] = {(char*)h->rb_act, A * sizeof(float)};
+  c[3] = {(char*)h->rb_rew, sizeof(float)};
+  c[4] = {(char*)h->rb_done, sizeof(float)};
+  c[5] = {(char*)h->rb_logp, sizeof(float)};
+}
+// what the four synchronous ring entry points ask before they look at their arguments' values: a ring, no stream capture
+int ring_entry(dsact_handle* h, const char* what) {
+  if (!has_ring(h)) return fail(h, DSACT_E_STATE, "%s: buffer not created", what);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  HIPCHK(h, hipStreamIsCapturing(h->stream, &cap));
+  if (cap != hipStreamCaptureStatusNone) return fail(h, DSACT_E_STATE, "%s under stream capture", what);
+  return DSACT_OK;
+}
+// ... and after the arguments passed: drain the stream, with the hand-over word looked at on both sides of the wait
+int ring_drain(dsact_handle* h) {
+  HIPCHK(h, hipSetDevice(h->device));
+  TRY(check_handoff(h));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  TRY(check_handoff(h));
+  return check_codes(h);
+}
+}  // namespace
+
+int dsact_buffer_export(dsact_handle* h, int64_t row0, int64_t n, void* obs, void* obs2, float* act, float* rew, float* done,
+                        float* logp) {
+  if (!h) return DSACT_E_INVALID;
+  TRY(ring_entry(h, "dsact_buffer_export"));
+  if (row0 < 0 || n < 0 || row0 > h->size || n > h->size - row0)
+    return fail(h, DSACT_E_INVALID, "dsact_buffer_export: rows [%lld, %lld + %lld) are not inside the %lld live rows", (long long)row0,
+                (long long)row0, (long long)n, h->size);
+  TRY(ring_drain(h));
+  if (n == 0) return DSACT_OK;
+  RingColumn c[6];
+  ring_columns(h, c);
+  void* dst[6] = {obs, obs2, act, rew, done, logp};
+  for (int k = 0; k < 6; ++k)
+    if (dst[k]) HIPCHK(h, hipMemcpy(dst[k], c[k].base + (size_t)row0 * c[k].row_bytes, (size_t)n * c[k].row_bytes, hipMemcpyDeviceToHost));
+  return DSACT_OK;
+}
+
+int dsact_buffer_import(dsact_handle* h, int64_t row0, int64_t n, const void* obs, const void* obs2, const float* act,
+                        const float* rew, const float* done, const float* logp) {
+  if (!h) return DSACT_E_INVALID;
+  TRY(ring_entry(h, "dsact_buffer_import"));
+  if (!obs || !obs2 || !act || !rew || !done || !logp) return fail(h, DSACT_E_INVALID, "dsact_buffer_import: a source column is NULL");
+  if (row0 < 0 || n < 0 || row0 > h->cap || n > h->cap - row0)
+    return fail(h, DSACT_E_INVALID, "dsact_buffer_import: rows [%lld, %lld + %lld) are not inside the capacity %lld", (long long)row0,
+                (long long)row0, (long long)n, h->cap);
+  if (h->rb_code && h->n_codes < 256) {
+    // every code must name a table entry -- looked at here, before the first byte goes up: a refused import leaves the ring as it was
+    const size_t cnt = (size_t)n * (size_t)h->O;
+    const unsigned char* src[2] = {(const unsigned char*)obs, (const unsigned char*)obs2};
+    for (int w = 0; w < 2; ++w)
+      for (size_t i = 0; i < cnt; ++i)
+        if (src[w][i] >= h->n_codes)
+          return fail(h, DSACT_E_INVALID, "dsact_buffer_import: %s code %d at row %lld, element %lld is not below the codebook's %d entries",
+                      w ? "obs2" : "obs", (int)src[w][i], (long long)(row0 + (int64_t)(i / (size_t)h->O)), (long long)(i % (size_t)h->O), h->n_codes);
+  }
+  TRY(ring_drain(h));
+  if (n == 0) return DSACT_OK;
+  RingColumn c[6];
+  ring_columns(h, c);
+  const void* src[6] = {obs, obs2, act, rew, done, logp};
+  for (int k = 0; k < 6; ++k)
+    HIPCHK(h, hipMemcpy(c[k].base + (size_t)row0 * c[k].row_bytes, src[k], (size_t)n * c[k].row_bytes, hipMemcpyHostToDevice));
+  return DSACT_OK;
+}
+
+int dsact_buffer_set_cursor(dsact_handle* h, int64_t size, int64_t ptr) {
+  if (!h) return DSACT_E_INVALID;
+  TRY(ring_entry(h, "dsact_buffer_set_cursor"));
+  // the states replay_buffer.py:58-79 can reach: filling (ptr == size), or full with the cursor anywhere
+  const bool ok = size >= 0 && size <= h->cap && (size < h->cap ? ptr == size % h->cap : (ptr >= 0 && ptr < h->cap));
+  if (!ok)
+    return fail(h, DSACT_E_INVALID, "dsact_buffer_set_cursor: (size %lld, ptr %lld) is no state a ring of %lld rows reaches", (long long)size,
+                (long long)ptr, h->cap);
+  TRY(ring_drain(h));
+  h->size = size; h->ptr = ptr;
+  return DSACT_OK;
+}
+
+int dsact_buffer_digest(dsact_handle* h, int64_t row0, int64_t n, uint64_t out[6]) {
+  if (!h) return DSACT_E_INVALID;
+  TRY(ring_entry(h, "dsact_buffer_digest"));
+  if (!out) return fail(h, DSACT_E_INVALID, "dsact_buffer_digest: out is NULL");
+  if (row0 < 0 || n < 0 || row0 > h->size || n > h->size - row0)
+    return fail(h, DSACT_E_INVALID, "dsact_buffer_digest: rows [%lld, %lld + %lld) are not inside the %lld live rows", (long long)row0,
+                (long long)row0, (long long)n, h->size);
+  TRY(ring_drain(h));
+  for (int k = 0; k < 6; ++k) out[k] = 0;
+  if (n == 0) return DSACT_OK;
+  if (!h->digest_dev) HIPCHK(h, hipMalloc(&h->digest_dev, 6 * sizeof(unsigned long long)));
+  RingColumn c[6];
+  ring_columns(h, c);
+  RingDigestArgs a;
+  unsigned long long most = 0;
+  for (int k = 0; k < 6; ++k) {
+    const int eb = (k < 2 && h->rb_code) ? 1 : 4;
+    const unsigned long long w = (unsigned long long)(c[k].row_bytes / (size_t)eb);   // w_c: O, O, A, 1, 1, 1
+    a.col[k].base = c[k].base;
+    a.col[k].g0 = (unsigned long long)row0 * w;          // 64 bits from the first product
+    a.col[k].count = (unsigned long long)n * w;
+    a.col[k].elem_bytes = eb;
+    const unsigned long long loads = a.col[k].count / (eb == 4 ? 4u : 16u);
+    if (loads > most) most = loads;
+  }
+  a.out = h->digest_dev;
+  // enough workgroups for every 16-byte load of the widest column to have a lane, capped at eight per compute unit (the
+  // kernel strides over the rest)
+  unsigned long long gx = (most + kThreads - 1) / kThreads;
+  const unsigned long long gmax = (unsigned long long)(h->n_cu > 0 ? h->n_cu : 256) * 8;
+  if (gx > gmax) gx = gmax;
+  if (gx < 1) gx = 1;
+  HIPCHK(h, hipMemsetAsync(h->digest_dev, 0, 6 * sizeof(unsigned long long), h->stream));
+  TRY(launch(h, "ring_digest", k_ring_digest, dim3((unsigned)gx, 6), dim3(kThreads), 0, a));
+  unsigned long long got[6];
+  HIPCHK(h, hipMemcpyAsync(got, h->digest_dev, sizeof(got), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int k = 0; k < 6; ++k) out[k] = (uint64_t)got[k];
+  return check_handoff(h);
 }
 
 int dsact_gather(dsact_handle* h, const int64_t* idx_host, int32_t batch) {

@@ -690,6 +690,83 @@ __global__ void __launch_bounds__(kThreads) k_ring_commit(RingCommitArgs a) {
 }
 #endif
 
+// k_ring_digest: the integrity digest of ring rows [row0, row0 + n) (dsact_buffer_digest, include/dsact.h has the definition;
+// DESIGN.md section 18) -- six 64-bit sums, one per column c = 0..5 (obs, obs2, act, rew, done, logp), over the column's elements
+// of the row range: element (row r, position j) has the index g = r * w_c + j (64 bits from the first product: the host computes
+// g0 = row0 * w_c in 64 bits and the kernel only adds to it), v = its stored bits zero-extended (the float's 32 bits, or the code
+// byte of a coded ring), and contributes digest_mix(g, c + 1, v). The sum is an integer sum mod 2^64: no order to choose, and
+// the digest of a range is the sum of the digests of its parts.
+//   layout: the SoA ring keeps a column's rows back to back, so the row range is ONE contiguous run of `count` = n * w_c elements
+//           that starts at element g0 of the column -- the kernel never sees rows. blockIdx.y is the column, blockIdx.x strides
+//           over the run. The part of the run that starts at the first 16-byte boundary is read 16 bytes per lane (one dwordx4:
+//           4 floats, or 16 codes); the up to 3 floats (15 codes) in front of it and behind its last whole 16 bytes are read one
+//           element per lane (dword / ubyte) by the first lanes of the grid. Obs width 17 with an odd row0 starts off a boundary;
+//           376-float rows and whole code planes start on one. Every load is inside [g0, g0 + count).
+//   sums:   a lane keeps one 64-bit partial in registers, a wave folds its 64 partials with six shuffles, and lane 0 adds the
+//           wave's sum to out[c] with one 64-bit vector atomic add (integer: exact, order-free). out[0..6) is zeroed by the host
+//           in stream order before the launch. A wave whose sum is 0 (it had no element) adds nothing. No LDS, no scratch.
+struct DigestCol {
+  const void* base;                 // the column's first element (row 0)
+  unsigned long long g0, count;     // first element index of the run, elements in it
+  int elem_bytes;                   // 4 (float32 bits) or 1 (code byte)
+};
+struct RingDigestArgs {
+  DigestCol col[6];
+  unsigned long long* out;          // [6], zero before the launch
+};
+__device__ __forceinline__ unsigned long long digest_mix(unsigned long long g, unsigned c1, unsigned v) {
+  unsigned long long x = g * 0x9E3779B97F4A7C15ull + (((unsigned long long)c1 << 32) | (unsigned long long)v);
+  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27; x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+#ifndef DSACT_FAMILY_UNIT   // plain kernel: compiled in dsact_api.hip only (dsact_tu.h)
+__global__ void __launch_bounds__(kThreads) k_ring_digest(RingDigestArgs a) {
+  const unsigned c = blockIdx.y;
+  const DigestCol col = a.col[c];
+  const unsigned per = col.elem_bytes == 4 ? 4u : 16u;                      // elements per 16-byte load
+  const unsigned long long addr = (unsigned long long)(uintptr_t)col.base + col.g0 * (unsigned)col.elem_bytes;
+  unsigned long long head = ((16u - (unsigned)(addr & 15u)) & 15u) / (unsigned)col.elem_bytes;   // elements in front of the first 16-byte boundary
+  if (head > col.count) head = col.count;
+  const unsigned long long wide = (col.count - head) / per;                 // whole 16-byte loads
+  const unsigned long long tail0 = head + wide * per, tail = col.count - tail0;
+  const unsigned long long tid = (unsigned long long)blockIdx.x * kThreads + threadIdx.x;
+  const unsigned long long nthreads = (unsigned long long)gridDim.x * kThreads;
+  if ((unsigned long long)blockIdx.x * kThreads >= (wide > 16 ? wide : 16)) return;   // (workgroup-uniform: nothing left for it)
+  const unsigned c1 = c + 1;
+  unsigned long long sum = 0;
+  if (col.elem_bytes == 4) {
+    const unsigned* p = reinterpret_cast<const unsigned*>(col.base) + col.g0;
+    if (tid < head) sum += digest_mix(col.g0 + tid, c1, p[tid]);
+    if (tid < tail) sum += digest_mix(col.g0 + tail0 + tid, c1, p[tail0 + tid]);
+    const uint4* q = reinterpret_cast<const uint4*>(p + head);
+    for (unsigned long long k = tid; k < wide; k += nthreads) {
+      const uint4 v = q[k];
+      const unsigned long long g = col.g0 + head + 4 * k;
+      sum += digest_mix(g, c1, v.x) + digest_mix(g + 1, c1, v.y) + digest_mix(g + 2, c1, v.z) + digest_mix(g + 3, c1, v.w);
+    }
+  } else {
+    const unsigned char* p = reinterpret_cast<const unsigned char*>(col.base) + col.g0;
+    if (tid < head) sum += digest_mix(col.g0 + tid, c1, p[tid]);
+    if (tid < tail) sum += digest_mix(col.g0 + tail0 + tid, c1, p[tail0 + tid]);
+    const uint4* q = reinterpret_cast<const uint4*>(p + head);
+    for (unsigned long long k = tid; k < wide; k += nthreads) {
+      const uint4 v = q[k];
+      const unsigned long long g = col.g0 + head + 16 * k;
+      const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) sum += digest_mix(g + 4 * i + b, c1, (w[i] >> (8 * b)) & 0xFFu);   // little-endian: byte b of word i
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+  if ((threadIdx.x & 63) == 0 && sum != 0) atomicAdd(a.out + c, sum);
+}
+#endif
+
 // k_eval_commit: the episode bookkeeping of the device-resident evaluator (training/hip_tensor_evaluator.py, dsact_eval_commit)
 // -- what Evaluator.run_an_episode / run_n_episodes keep in Python lists (training/evaluator.py:34-84: reward_list.append,
 // sum(reward_list), the episode counter) for N environments that step in lockstep, one launch per lockstep step, one thread per

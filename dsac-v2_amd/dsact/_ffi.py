@@ -76,6 +76,10 @@ SYMBOLS = [
     ("dsact_buffer_create_coded", C.c_int, [_P, C.c_int64, _FP, C.c_int32]),
     ("dsact_buffer_check", C.c_int, [_P]),
     ("dsact_buffer_bytes", C.c_int64, [_P]),
+    ("dsact_buffer_export", C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    ("dsact_buffer_import", C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    ("dsact_buffer_set_cursor", C.c_int, [_P, C.c_int64, C.c_int64]),
+    ("dsact_buffer_digest", C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(C.c_uint64)]),
     ("dsact_gather", C.c_int, [_P, _I64P, C.c_int32]),
     ("dsact_read_batch", C.c_int, [_P, _FP, _FP, _FP, _FP, _FP, _FP]),
     ("dsact_load_batch", C.c_int, [_P, _FP, _FP, _FP, _FP, _FP]),

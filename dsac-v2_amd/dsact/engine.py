@@ -28,6 +28,40 @@ def _f32(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float32))
 
 
+RING_COLUMNS = ("obs", "obs2", "act", "rew", "done", "logp")   # the ring's SoA order: digest column c = index
+_M64 = (1 << 64) - 1
+
+
+def ring_digest_reference(cols, row0, widths=None):
+    """dsact_buffer_digest restated in NumPy uint64 arithmetic (include/dsact.h has the definition; no GPU, no library call): the
+    six column sums, as Python ints, of `cols` = {obs, obs2, act, rew, done, logp} holding ring rows [row0, row0 + n) in stored
+    form (float32, or uint8 codes for obs / obs2 of a coded ring). widths: (O, O, A, 1, 1, 1); None reads them off the arrays."""
+    out = []
+    u = np.uint64
+    with np.errstate(over="ignore"):
+        for c, key in enumerate(RING_COLUMNS):
+            a = np.ascontiguousarray(cols[key])
+            n = int(a.shape[0])
+            if a.dtype == np.uint8:
+                v = a.reshape(-1).astype(np.uint64)
+            elif a.dtype == np.float32:
+                v = a.reshape(-1).view(np.uint32).astype(np.uint64)
+            else:
+                raise ValueError("ring column %s must be float32 or uint8 (got %s)" % (key, a.dtype))
+            w = int(widths[c]) if widths is not None else (v.size // n if n else 1)
+            if v.size != n * w:
+                raise ValueError("ring column %s holds %d elements, expected %d rows x %d" % (key, v.size, n, w))
+            g = u((int(row0) * w) & _M64) + np.arange(v.size, dtype=np.uint64)
+            x = g * u(0x9E3779B97F4A7C15) + ((u(c + 1) << u(32)) | v)
+            x ^= x >> u(30)
+            x *= u(0xBF58476D1CE4E5B9)
+            x ^= x >> u(27)
+            x *= u(0x94D049BB133111EB)
+            x ^= x >> u(31)
+            out.append(int(x.sum(dtype=np.uint64)) & _M64)
+    return tuple(out)
+
+
 class DsactEngine:
     def __init__(self, obs_dim: int, act_dim: int, hidden: Sequence[int], batch: int, *,
                  gamma=0.99, tau=0.005, tau_b=None, auto_alpha=True, alpha=0.2, delay_update=2,
@@ -163,6 +197,7 @@ class DsactEngine:
         self._graph_steps = 0
         self.stage_serial = 0
         self.buffer_capacity = 0
+        self.buffer_coded = False
         self.rows_added = 0      # rows ever written to the ring (HipBatch tokens detect overwritten rows with it)
         self.fill_epoch = 0      # bumped by buffer_fill_device (writes at an arbitrary row: outstanding tokens become invalid)
         self.index_seed = 0      # set_index_rng: 0 = the replay indices are the caller's host draws
@@ -244,6 +279,58 @@ class DsactEngine:
             book = np.ascontiguousarray(codebook, dtype=np.float32)
             self._chk(self._lib.dsact_buffer_create_coded(self._h, int(capacity), _ffi.fptr(book), int(book.shape[0])))
         self.buffer_capacity = int(capacity)
+        self.buffer_coded = codebook is not None
+
+    # ---- ring snapshots: stored form out of / into HBM, the cursor, the device-side digest. Synchronous. ---
+    ring_digest_reference = staticmethod(ring_digest_reference)
+
+    @property
+    def ring_widths(self):
+        """(O, O, A, 1, 1, 1): elements per row of the six ring columns"""
+        return (self.obs_dim, self.obs_dim, self.act_dim, 1, 1, 1)
+
+    def _ring_dtypes(self):
+        o = np.uint8 if getattr(self, "buffer_coded", False) else np.float32
+        return (o, o, np.float32, np.float32, np.float32, np.float32)
+
+    def buffer_export(self, row0: int, n: int) -> Dict[str, np.ndarray]:
+        """dsact_buffer_export: ring rows [row0, row0 + n) in stored form -- {obs, obs2: [n, O] float32 (uint8 codes on a coded
+        ring), act: [n, A], rew, done, logp: [n]}. row0 + n <= buffer_size (DsactError otherwise)."""
+        rows = max(int(n), 0)
+        out = {k: np.empty((rows, w) if i < 3 else (rows,), dt)
+               for i, (k, w, dt) in enumerate(zip(RING_COLUMNS, self.ring_widths, self._ring_dtypes()))}
+        self._chk(self._lib.dsact_buffer_export(self._h, int(row0), int(n), *[a.ctypes.data_as(C.c_void_p) for a in out.values()]))
+        return out
+
+    def buffer_import(self, row0: int, cols):
+        """dsact_buffer_import: writes ring rows [row0, row0 + n) from `cols` in stored form (buffer_export's dict; n = rows of
+        `rew`); row0 + n <= capacity. Moves neither size nor ptr (buffer_set_cursor). Counts as a write at an arbitrary row:
+        outstanding HipBatch / HipBatchGroup tokens re-gather or raise as after buffer_fill_device."""
+        n = int(np.shape(cols["rew"])[0])
+        arrs = []
+        for i, (k, w, dt) in enumerate(zip(RING_COLUMNS, self.ring_widths, self._ring_dtypes())):
+            a = np.asarray(cols[k])
+            if a.dtype != dt:
+                raise ValueError("ring column %s must have dtype %s (got %s)" % (k, np.dtype(dt).name, a.dtype))
+            if a.size != n * w:
+                raise ValueError("ring column %s holds %d elements, expected %d rows x %d" % (k, a.size, n, w))
+            arrs.append(np.ascontiguousarray(a))
+        self._chk(self._lib.dsact_buffer_import(self._h, int(row0), n, *[a.ctypes.data_as(C.c_void_p) for a in arrs]))
+        self.fill_epoch += 1
+
+    def buffer_set_cursor(self, size: int, ptr: int):
+        """dsact_buffer_set_cursor: size and ptr, one of the states the reference's store() reaches (DsactError otherwise)"""
+        self._chk(self._lib.dsact_buffer_set_cursor(self._h, int(size), int(ptr)))
+        self.fill_epoch += 1     # (the tokens' bookkeeping is relative to the cursor they were sampled at)
+
+    def buffer_digest(self, row0: int = 0, n: Optional[int] = None):
+        """dsact_buffer_digest: the six 64-bit column digests of ring rows [row0, row0 + n) as Python ints, computed on the
+        device (n None: up to buffer_size). Equals ring_digest_reference(buffer_export(row0, n), row0)."""
+        if n is None:
+            n = self.buffer_size - int(row0)
+        out = (C.c_uint64 * 6)()
+        self._chk(self._lib.dsact_buffer_digest(self._h, int(row0), int(n), out))
+        return tuple(int(v) for v in out)
 
     def buffer_check(self):
         """dsact_buffer_check: drains the stream; raises if a value missing from the codebook was written"""

@@ -160,3 +160,15 @@ def hand_over(eng):
     dev = torch.device(eng.device)
     if dev.type == "cuda":
         torch.cuda.current_stream(dev).synchronize()
+
+
+def require_env_state(env, who):
+    """run_state() / load_run_state() of a sampler carry the environment through two OPTIONAL methods of the environment
+    protocol: state_dict() -> a picklable object, load_state_dict(sd) restores it. An environment without them cannot be
+    resumed exactly, and that is never promised silently."""
+    missing = [m for m in ("state_dict", "load_state_dict") if not callable(getattr(env, m, None))]
+    if missing:
+        raise NotImplementedError("%s: an exact resume needs the environment's state, but %s offers no %s; add state_dict() "
+                                  "(returning a picklable object) and load_state_dict(sd) to it"
+                                  % (who, type(env).__name__, " / ".join(m + "()" if m == "state_dict" else m + "(sd)" for m in missing)))
+    return env

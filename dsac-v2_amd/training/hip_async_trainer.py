@@ -63,6 +63,11 @@ def _check_supported(alg, sampler):
 
 class HipOffAsyncTrainer(HipOffSerialTrainer):
     def __init__(self, alg, sampler, buffer, evaluator, **kwargs):
+        for k in ("hip_save_run_state", "ini_run_state_dir"):
+            if kwargs.get(k):
+                raise NotImplementedError("hip_off_async_trainer: %s is not supported -- between two groups this trainer holds a "
+                                          "behaviour policy one group old, state the run-state format does not carry; use "
+                                          "hip_off_serial_trainer" % k)
         if sampler is not None:
             sampler.networks = alg.networks   # (what the serial trainer does first: the routes below are those of the learner's nets)
         _check_supported(alg, sampler)

@@ -26,14 +26,28 @@ two never share a counter block whatever the seeds.
 `add_batch` also takes a `DeviceSampleBatch` (training/hip_tensor_sampler.py: the transitions of a batched tensor environment,
 already on the GPU) and hands its seven device tensors to the ring in one asynchronous call (dsact_buffer_add_device); every
 other input takes the paths it always took.
+
+`save(path)` / `load(path)` write and read a snapshot of the ring, format "dsact-ring-1" (DESIGN.md section 18): a directory with
+one little-endian file per column -- rows [0, size) in the ring's stored form (float32, or the uint8 codes of a coded ring) --
+and a meta.json holding the cursor, the shapes, the codebook's bit patterns, the per-chunk device digests and the state of the
+device index draw. load() refuses a snapshot of another capacity, shape, coded-ness or codebook before it touches the ring, and
+leaves the ring EMPTY when the digests the device computes over the restored rows are not the saved ones.
 """
+import json
+import os
+import shutil
+import sys
+import tempfile
+
 import numpy as np
 
-from dsact.engine import DsactEngine, current_engine
+from dsact.engine import RING_COLUMNS, DsactEngine, current_engine, ring_digest_reference
 
 __all__ = ["HipReplayBuffer", "parse_obs_codebook", "index_seed_from", "act_seed_from"]
 
 MAX_CODES = 256
+RING_FORMAT = "dsact-ring-1"
+_M64 = (1 << 64) - 1
 
 
 def index_seed_from(seed):
@@ -135,6 +149,157 @@ class HipReplayBuffer:
     def check(self):
         """synchronous: raises DsactError if an observation value missing from `hip_obs_codebook` was stored"""
         self.engine.buffer_check()
+
+    # ---- snapshots (format "dsact-ring-1", DESIGN.md section 18) ---------------------------------------------------------------
+    def _ring_columns(self):
+        """[(name, elements per row, dtype)] of the six columns in stored form"""
+        o = np.dtype(np.uint8) if self.codebook is not None else np.dtype("<f4")
+        f = np.dtype("<f4")
+        return [("obs", self._obs_flat, o), ("obs2", self._obs_flat, o), ("act", int(self.act_dim), f), ("rew", 1, f), ("done", 1, f),
+                ("logp", 1, f)]
+
+    def _snapshot_identity(self):
+        return {"capacity": int(self.max_size), "obs_shape": [int(d) for d in self._obs_shape], "act_dim": int(self.act_dim),
+                "coded": self.codebook is not None,
+                "codebook": None if self.codebook is None else [int(b) for b in np.ascontiguousarray(self.codebook).view(np.uint32)]}
+
+    def save(self, path, chunk_rows=65536, overwrite=False):
+        """Writes the live rows [0, size) and the cursor to the directory `path`. The rows leave HBM chunk by chunk (the host never
+        holds more than `chunk_rows` rows) and each chunk's six digests are taken from the device. Everything is written into a
+        temporary directory beside `path`, meta.json last, and renamed: a snapshot either exists whole or not at all. An
+        existing `path` raises FileExistsError unless overwrite=True. Synchronous."""
+        path = os.path.abspath(os.fspath(path))
+        chunk_rows = int(chunk_rows)
+        if chunk_rows < 1:
+            raise ValueError("chunk_rows must be >= 1 (got %d)" % chunk_rows)
+        if sys.byteorder != "little":
+            raise NotImplementedError("dsact-ring-1 files are little-endian; this host is not")
+        if os.path.lexists(path) and not overwrite:
+            raise FileExistsError("%s exists (pass overwrite=True to replace it)" % path)
+        eng = self.engine
+        if hasattr(eng, "sync"):
+            eng.sync()
+        size, ptr = int(self.size), int(self.ptr)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        tmp = tempfile.mkdtemp(prefix=os.path.basename(path) + ".tmp-", dir=os.path.dirname(path))
+        try:
+            files = {k: open(os.path.join(tmp, k + ".bin"), "wb") for k in RING_COLUMNS}
+            chunks, total = [], [0] * 6
+            try:
+                for r0 in range(0, size, chunk_rows):
+                    n = min(chunk_rows, size - r0)
+                    cols = eng.buffer_export(r0, n)
+                    dig = eng.buffer_digest(r0, n)
+                    for k, _, dt in self._ring_columns():
+                        a = np.ascontiguousarray(cols[k])
+                        if a.dtype != dt:
+                            raise ValueError("the engine exported column %s as %s, the stored form is %s" % (k, a.dtype, dt))
+                        a.tofile(files[k])
+                    chunks.append(["%016x" % v for v in dig])
+                    total = [(t + v) & _M64 for t, v in zip(total, dig)]
+            finally:
+                for f in files.values():
+                    f.close()
+            meta = dict(self._snapshot_identity(), format=RING_FORMAT, size=size, ptr=ptr, chunk_rows=chunk_rows,
+                        digests={"chunks": chunks, "total": ["%016x" % v for v in total]},
+                        index_seed=int(self.index_seed), index_iteration=int(self.index_iteration))
+            with open(os.path.join(tmp, "meta.json"), "w") as f:      # last: a directory without it is not a snapshot
+                json.dump(meta, f, indent=1)
+                f.flush()
+                os.fsync(f.fileno())
+            old = None
+            if os.path.lexists(path):
+                old = tempfile.mkdtemp(prefix=os.path.basename(path) + ".old-", dir=os.path.dirname(path))
+                os.rename(path, os.path.join(old, "d"))
+            os.rename(tmp, path)
+            if old is not None:
+                shutil.rmtree(old, ignore_errors=True)
+        except BaseException:
+            shutil.rmtree(tmp, ignore_errors=True)
+            raise
+        return path
+
+    def _read_snapshot_meta(self, path):
+        """meta.json of a snapshot this ring can take, or ValueError -- nothing here touches the ring"""
+        fn = os.path.join(path, "meta.json")
+        if not os.path.isfile(fn):
+            raise ValueError("%s holds no meta.json: not a complete %s snapshot" % (path, RING_FORMAT))
+        with open(fn) as f:
+            meta = json.load(f)
+        if meta.get("format") != RING_FORMAT:
+            raise ValueError("%s has format %r, this is %s" % (path, meta.get("format"), RING_FORMAT))
+        mine = self._snapshot_identity()
+        why = {"capacity": "a ring of another capacity overwrites other rows from here on: it would not be the same run",
+               "obs_shape": "another observation shape", "act_dim": "another action width",
+               "coded": "a coded ring and an fp32 ring store different bytes", "codebook": "the codebook's bit patterns differ"}
+        for k in ("capacity", "obs_shape", "act_dim", "coded", "codebook"):
+            theirs = meta.get(k)
+            if k == "obs_shape" and theirs is not None:
+                theirs = [int(d) for d in theirs]
+            if theirs != mine[k]:
+                shown = (theirs, mine[k]) if k != "codebook" else ("...", "...")
+                raise ValueError("%s: %s is %r in the snapshot and %r here (%s)" % (path, k, shown[0], shown[1], why[k]))
+        size, ptr, cap, chunk = int(meta["size"]), int(meta["ptr"]), int(self.max_size), int(meta["chunk_rows"])
+        if not (0 <= size <= cap and (ptr == size % cap if size < cap else 0 <= ptr < cap)) or chunk < 1:
+            raise ValueError("%s: (size %d, ptr %d, chunk_rows %d) is no state a ring of %d rows reaches" % (path, size, ptr, chunk, cap))
+        for k, w, dt in self._ring_columns():
+            cf = os.path.join(path, k + ".bin")
+            have = os.path.getsize(cf) if os.path.isfile(cf) else -1
+            if have != size * w * dt.itemsize:
+                raise ValueError("%s: %s.bin holds %d bytes, %d rows x %d bytes are %d" % (path, k, have, size, w * dt.itemsize,
+                                                                                          size * w * dt.itemsize))
+        chunks = meta.get("digests", {}).get("chunks")
+        if not isinstance(chunks, list) or len(chunks) != (size + chunk - 1) // chunk or any(len(c) != 6 for c in chunks):
+            raise ValueError("%s: the digest list does not cover %d rows in chunks of %d" % (path, size, chunk))
+        if self.device_indices and int(meta.get("index_seed", 0)) != int(self.index_seed):
+            raise ValueError("%s was drawn with index seed %#x, this buffer draws with %#x: the resumed run would sample other "
+                             "minibatches" % (path, int(meta.get("index_seed", 0)), int(self.index_seed)))
+        return meta
+
+    def load(self, path):
+        """Restores the snapshot at `path`: rows [0, size), the cursor and `index_iteration` (this buffer keeps its own index
+        seed). Refused with ValueError BEFORE anything touches the ring: no meta.json, another format, capacity, observation shape,
+        action width, coded-ness or codebook, a column file of the wrong length, another index seed while hip_device_indices is
+        on. Then the rows go up chunk by chunk, and the device's digest of every chunk is compared with the file's: on a mismatch
+        the ring is left EMPTY and the ValueError names the chunk and the column. Synchronous."""
+        path = os.path.abspath(os.fspath(path))
+        meta = self._read_snapshot_meta(path)
+        eng = self.engine
+        size, ptr, chunk = int(meta["size"]), int(meta["ptr"]), int(meta["chunk_rows"])
+        spec = self._ring_columns()
+
+        def read_chunk(files, n):
+            return {k: np.fromfile(files[k], dtype=dt, count=n * w).reshape((n, w) if k in ("obs", "obs2", "act") else (n,))
+                    for k, w, dt in spec}
+
+        files = {k: open(os.path.join(path, k + ".bin"), "rb") for k in RING_COLUMNS}
+        try:
+            for r0 in range(0, size, chunk):
+                eng.buffer_import(r0, read_chunk(files, min(chunk, size - r0)))
+        finally:
+            for f in files.values():
+                f.close()
+        eng.buffer_set_cursor(size, ptr)
+        self.index_iteration = int(meta.get("index_iteration", 0))
+        for ci, r0 in enumerate(range(0, size, chunk)):
+            n = min(chunk, size - r0)
+            got = tuple(eng.buffer_digest(r0, n))
+            want = tuple(int(v, 16) for v in meta["digests"]["chunks"][ci])
+            if got != want:
+                eng.buffer_set_cursor(0, 0)
+                c = next(i for i in range(6) if got[i] != want[i])
+                # which side moved: the file (its bytes no longer digest to what save() recorded) or the way to HBM
+                with open(os.path.join(path, RING_COLUMNS[c] + ".bin"), "rb") as f:
+                    k, w, dt = spec[c]
+                    f.seek(r0 * w * dt.itemsize)
+                    a = np.fromfile(f, dtype=dt, count=n * w).reshape(n, w)
+                cols = {kk: (a if kk == k else np.zeros((n, ww), dd)) for kk, ww, dd in spec}
+                of_file = ring_digest_reference(cols, r0, [ww for _, ww, _ in spec])[c]
+                raise ValueError("%s: chunk %d (rows %d .. %d), column %s: the device digests the restored rows to %016x, the snapshot "
+                                 "recorded %016x (%s.bin itself digests to %016x: %s); the ring was left empty"
+                                 % (path, ci, r0, r0 + n - 1, k, got[c], want[c], k, of_file,
+                                    "the file changed after it was saved" if of_file != want[c] else "the rows changed on their way to the device"))
+        return meta
 
     def store(self, obs, info, act, rew, next_obs, done, logp, next_info):
         self.add_batch([(obs, info, act, rew, next_obs, done, logp, next_info)])

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from training.hip_acting_common import (MLP_POLICY, _container, _reset, act_fast_ok, attached_engine, networks_of,  # noqa: F401
-                                        refuse_noise, sample_batch_size)
+                                        refuse_noise, require_env_state, sample_batch_size)
 
 __all__ = ["HipOffSampler", "create_sampler"]
 
@@ -167,6 +167,29 @@ class HipOffSampler:
 
     def get_total_sample_number(self):
         return self.total_sample_number
+
+    RUN_STATE_FORMAT = "dsact-off-sampler-state/1"
+
+    def run_state(self):
+        """What a resumed run needs of this sampler (HipOffSerialTrainer's hip_save_run_state):
+        total_sample_number, the current observation and info, and the environment's state_dict(). The acting noise is the torch
+        global generator's, which the trainer saves itself."""
+        import copy
+
+        env = require_env_state(self.env, "HipOffSampler.run_state")
+        return {"format": self.RUN_STATE_FORMAT, "total_sample_number": int(self.total_sample_number),
+                "obs": np.array(self.obs, copy=True), "info": copy.deepcopy(self.info), "env": env.state_dict()}
+
+    def load_run_state(self, sd):
+        """restores what run_state() saved (named so that it cannot be mistaken for load_state_dict(networks))"""
+        import copy
+
+        env = require_env_state(self.env, "HipOffSampler.load_run_state")
+        if sd.get("format") != self.RUN_STATE_FORMAT:
+            raise ValueError("not a %s object" % self.RUN_STATE_FORMAT)
+        env.load_state_dict(sd["env"])
+        self.obs, self.info = np.array(sd["obs"], copy=True), copy.deepcopy(sd["info"])
+        self.total_sample_number = int(sd["total_sample_number"])
 
 
 def create_sampler(**kwargs):

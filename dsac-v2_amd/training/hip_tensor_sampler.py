@@ -61,8 +61,8 @@ import time
 import numpy as np
 import torch
 
-from training.hip_acting_common import (engine_stream, hand_over, networks_of, on_stream, refuse_noise, require_tensor_engine,
-                                        sample_batch_size, tensor_limits)
+from training.hip_acting_common import (engine_stream, hand_over, networks_of, on_stream, refuse_noise, require_env_state,
+                                        require_tensor_engine, sample_batch_size, tensor_limits)
 from training.hip_replay_buffer import act_seed_from
 from training.hip_sampler import SAMPLER_TIME_KEY
 
@@ -279,6 +279,44 @@ class HipTensorEnvSampler:
             tb = {key: stats[name] for key, name in EPISODE_TB_KEYS}
         tb[SAMPLER_TIME_KEY] = (time.perf_counter() - t0) * 1000
         return batch, tb
+
+    RUN_STATE_FORMAT = "dsact-tensor-sampler-state/1"
+
+    def run_state(self):
+        """What a resumed run needs of this sampler (HipOffSerialTrainer's hip_save_run_state): the counters
+        act_step, sample_calls and total_sample_number, the current [N, O] observations as a CPU tensor, and the environment's
+        state_dict(). Waits for the engine's stream. The acting noise needs nothing: it is a function of (hip_act_seed,
+        act_step, row). Episode statistics (hip_episode_stats) are NOT carried: they start anew after load_run_state."""
+        env = require_env_state(self.env, "hip_tensor_env_sampler.run_state")
+        eng = self._engine()
+        if self._ready != id(eng):
+            self._setup(eng)
+        with on_stream(engine_stream(eng)), torch.no_grad():
+            obs = self._obs.detach().cpu().clone()
+            env_sd = env.state_dict()
+        eng.sync()
+        return {"format": self.RUN_STATE_FORMAT, "act_step": int(self.act_step), "sample_calls": int(self.sample_calls),
+                "total_sample_number": int(self.total_sample_number), "act_seed": int(self.act_seed), "obs": obs, "env": env_sd}
+
+    def load_run_state(self, sd):
+        """restores what run_state() saved (named so that it cannot be mistaken for load_state_dict(networks))"""
+        env = require_env_state(self.env, "hip_tensor_env_sampler.load_run_state")
+        if sd.get("format") != self.RUN_STATE_FORMAT:
+            raise ValueError("not a %s object" % self.RUN_STATE_FORMAT)
+        if int(sd.get("act_seed", self.act_seed)) != int(self.act_seed):
+            raise ValueError("the saved sampler drew its acting noise with hip_act_seed %#x, this one with %#x: the resumed run would "
+                             "act differently" % (int(sd["act_seed"]), int(self.act_seed)))
+        eng = self._engine()
+        if self._ready != id(eng):
+            self._setup(eng)
+        if tuple(sd["obs"].shape) != tuple(self._obs.shape):
+            raise ValueError("the saved observations have shape %r, this sampler steps %r" % (tuple(sd["obs"].shape), tuple(self._obs.shape)))
+        with on_stream(engine_stream(eng)), torch.no_grad():
+            self._obs.copy_(sd["obs"].to(self._obs.device))
+            env.load_state_dict(sd["env"])
+        eng.sync()
+        self.act_step, self.sample_calls = int(sd["act_step"]), int(sd["sample_calls"])
+        self.total_sample_number = int(sd["total_sample_number"])
 
     def episode_statistics(self, clear=True):
         """the training environments' finished episodes since the last clearing read (or since the statistics began), over all

@@ -11,11 +11,19 @@ the per-iteration device ping-pong and without per-step host syncs.
              evaluator.run_evaluation()                       every eval_interval
              torch.save(networks.state_dict())                every apprfunc_save_interval
 
+Whole-run snapshots (additive): `hip_save_run_state=True` makes every save_apprfunc() also write
+apprfunc/run_state_{it}/ -- the replay ring (HipReplayBuffer.save), the networks, the optimiser sidecar and run.pkl (iteration,
+best / last TAR, the sampler's run_state(), the NumPy and torch generator states, a fingerprint of the run) -- and
+`ini_run_state_dir=<such a directory>` makes a new trainer continue that run bit for bit from the iteration after the save.
+
 tensorboard is optional (not installed in every image): scalars always go to <save_folder>/scalars.jsonl,
 and to a SummaryWriter too when one can be imported.
 """
 import json
 import os
+import pickle
+import re
+import shutil
 import time
 
 import torch
@@ -159,6 +167,18 @@ class HipOffSerialTrainer:
         if kwargs.get("ini_optimizer_dir") is not None:
             side = torch.load(kwargs["ini_optimizer_dir"])
             alg.load_optimizer_state_dict(side)
+        # additive: whole-run snapshots (see the module text). Everything the two kwargs need is asked for here, before anything runs
+        self.save_run_state = bool(kwargs.get("hip_save_run_state", False))
+        self.run_state_keep = int(kwargs.get("hip_run_state_keep", 1))
+        resume_dir = kwargs.get("ini_run_state_dir")
+        self._fingerprint = {"algorithm": type(alg).__name__, "replay_batch_size": int(kwargs["replay_batch_size"]),
+                             "sample_interval": int(kwargs.get("sample_interval", 1)), "seed": kwargs.get("seed"),
+                             "strict_rng": bool(kwargs.get("strict_rng", False)),
+                             "hip_device_indices": bool(kwargs.get("hip_device_indices", False))}
+        if self.save_run_state or resume_dir is not None:
+            self._check_run_state_support("hip_save_run_state" if self.save_run_state else "ini_run_state_dir")
+            if self.run_state_keep < 1:
+                raise ValueError("hip_run_state_keep must be >= 1 (got %d)" % self.run_state_keep)
         self.replay_batch_size = kwargs["replay_batch_size"]
         self.max_iteration = kwargs["max_iteration"]
         self.sample_interval = kwargs.get("sample_interval", 1)
@@ -176,13 +196,104 @@ class HipOffSerialTrainer:
         if self.save_folder:
             os.makedirs(os.path.join(self.save_folder, "apprfunc"), exist_ok=True)
         self.writer = _Scalars(self.save_folder)
-        # the reference opens its log with these two at step 0 (training/trainer.py:43-47)
-        self.writer.add_dict({TB_TAGS["alg_time"]: 0, TB_TAGS["sampler_time"]: 0}, 0)
-        self.writer.flush()
+        run = None
+        if resume_dir is not None:
+            # learner, ring, sampler and counters of the saved run: the warm-up loop below then finds the ring warm and samples
+            # nothing. (A run that starts at iteration 0 opens the log; this one continues one.)
+            run = self._restore_run_state(resume_dir)
+        else:
+            # the reference opens its log with these two at step 0 (training/trainer.py:43-47)
+            self.writer.add_dict({TB_TAGS["alg_time"]: 0, TB_TAGS["sampler_time"]: 0}, 0)
+            self.writer.flush()
         while sampler is not None and self.buffer.size < kwargs["buffer_warm_size"]:  # trainer.py:50-52
             samples, _ = sampler.sample()
             self.buffer.add_batch(samples)
         self.start_time = time.time()
+        if run is not None:
+            # the two generator states go LAST: whatever the constructors of the algorithm, sampler, evaluator and this trainer
+            # drew before does not matter
+            import numpy as np
+
+            np.random.set_state(run["numpy_rng"])
+            torch.set_rng_state(run["torch_rng"])
+
+    # ---- whole-run snapshots ------------------------------------------------------------------------
+    RUN_STATE_FORMAT = "dsact-run-state/1"
+
+    def _check_run_state_support(self, kwarg):
+        """NotImplementedError unless every part of the run can be saved and restored: nothing is carried half"""
+        alg, buf, smp = self.alg, self.buffer, self.sampler
+        for obj, names in ((alg, ("optimizer_state_dict", "load_optimizer_state_dict")), (buf, ("save", "load"))):
+            for m in names:
+                if not callable(getattr(obj, m, None)):
+                    raise NotImplementedError("%s: %s has no %s()" % (kwarg, type(obj).__name__, m))
+        if smp is not None:
+            for m in ("run_state", "load_run_state"):
+                if not callable(getattr(smp, m, None)):
+                    raise NotImplementedError("%s: the sampler %s has no %s() (HipOffSampler and HipTensorEnvSampler have)"
+                                              % (kwarg, type(smp).__name__, m))
+        eng = getattr(alg, "engine", None)
+        cfg = getattr(eng, "cfg", None)
+        if eng is not None and ((cfg is not None and int(cfg.global_batch) != int(eng.batch)) or int(getattr(eng, "comm_world", 1)) > 1):
+            raise NotImplementedError("%s: data-parallel handles are not supported (a snapshot holds one shard)" % kwarg)
+
+    def _save_run_state(self, next_iteration):
+        import numpy as np
+
+        root = os.path.join(self.save_folder, "apprfunc")
+        d = os.path.join(root, "run_state_{}".format(self.iteration))
+        if os.path.lexists(d):
+            shutil.rmtree(d)      # (left by an earlier run in this folder: a directory is written whole)
+        os.makedirs(d)
+        self.buffer.save(os.path.join(d, "ring"))
+        torch.save(self.networks.state_dict(), os.path.join(d, "networks.pkl"))
+        torch.save(self.alg.optimizer_state_dict(), os.path.join(d, "optstate.pkl"))
+        run = {"format": self.RUN_STATE_FORMAT, "next_iteration": int(next_iteration), "best_tar": self.best_tar,
+               "last_tar": self.last_tar, "sampler": self.sampler.run_state() if self.sampler is not None else None,
+               "evaluator": self.evaluator.run_state() if callable(getattr(self.evaluator, "run_state", None)) else None,
+               "numpy_rng": np.random.get_state(), "torch_rng": torch.get_rng_state(), "fingerprint": dict(self._fingerprint)}
+        tmp = os.path.join(d, "run.pkl.tmp")
+        with open(tmp, "wb") as f:      # last, and renamed into place: run.pkl is what makes the directory complete
+            pickle.dump(run, f, protocol=pickle.HIGHEST_PROTOCOL)
+            f.flush()
+            os.fsync(f.fileno())
+        os.rename(tmp, os.path.join(d, "run.pkl"))
+        # a ring is gigabytes: once this directory is complete, only the newest `hip_run_state_keep` stay
+        found = []
+        for fn in os.listdir(root):
+            m = re.fullmatch(r"run_state_(\d+)", fn)
+            if m and int(m.group(1)) <= self.iteration and os.path.isdir(os.path.join(root, fn)):
+                found.append((int(m.group(1)), fn))
+        for _, fn in sorted(found)[:-self.run_state_keep]:
+            shutil.rmtree(os.path.join(root, fn), ignore_errors=True)
+
+    def _restore_run_state(self, d):
+        """everything of run_state_{it}/ but the generator states (returned with run.pkl's dict: they are set last)"""
+        fn = os.path.join(d, "run.pkl")
+        if not os.path.isfile(fn):
+            raise ValueError("%s holds no run.pkl: not a complete run-state directory" % d)
+        with open(fn, "rb") as f:
+            run = pickle.load(f)
+        if run.get("format") != self.RUN_STATE_FORMAT:
+            raise ValueError("%s has format %r, this is %s" % (fn, run.get("format"), self.RUN_STATE_FORMAT))
+        theirs = run.get("fingerprint", {})
+        diff = {k: (theirs.get(k), v) for k, v in self._fingerprint.items() if theirs.get(k) != v}
+        if diff:
+            raise ValueError("%s was written by another run: %s" % (d, ", ".join(
+                "%s was %r and is %r" % (k, a, b) for k, (a, b) in sorted(diff.items()))))
+        if (run.get("sampler") is None) != (self.sampler is None):
+            raise ValueError("%s was written %s a sampler, this trainer runs %s one" % (
+                d, "without" if run.get("sampler") is None else "with", "without" if self.sampler is None else "with"))
+        self.networks.load_state_dict(torch.load(os.path.join(d, "networks.pkl")))   # (refreshes the acting snapshot too)
+        self.alg.load_optimizer_state_dict(torch.load(os.path.join(d, "optstate.pkl")))
+        self.buffer.load(os.path.join(d, "ring"))
+        if self.sampler is not None:
+            self.sampler.load_run_state(run["sampler"])
+        if run.get("evaluator") is not None and callable(getattr(self.evaluator, "load_run_state", None)):
+            self.evaluator.load_run_state(run["evaluator"])
+        self.best_tar, self.last_tar = run["best_tar"], run["last_tar"]
+        self.iteration = int(run["next_iteration"])
+        return run
 
     def _has_event(self, it):
         """the host reads device state at the end of iteration `it`: tb_info (log), the policy (evaluation), the networks (save)"""
@@ -260,17 +371,21 @@ class HipOffSerialTrainer:
 
     def _finish(self):
         if self.save_folder:
-            self.save_apprfunc()
+            self.save_apprfunc(final=True)
         self.writer.flush()
         if self.save_folder:
             save_tb_to_csv(self.save_folder)   # what the reference's example scripts do right after train()
 
-    def save_apprfunc(self):
+    def save_apprfunc(self, final=False):
+        """final: called after train()'s last iteration (self.iteration == max_iteration, no update of that number was made)
+        rather than at the end of iteration self.iteration"""
         torch.save(self.networks.state_dict(),
                    os.path.join(self.save_folder, "apprfunc", "apprfunc_{}.pkl".format(self.iteration)))
         if self.save_optimizer_state and hasattr(self.alg, "optimizer_state_dict"):
             side = dict(self.alg.optimizer_state_dict(), iteration=int(self.iteration))
             torch.save(side, os.path.join(self.save_folder, "apprfunc", "apprfunc_{}.optstate.pkl".format(self.iteration)))
+        if self.save_run_state:
+            self._save_run_state(self.iteration if final else self.iteration + 1)
 
 
 def create_trainer(alg, sampler, buffer, evaluator, **kwargs):

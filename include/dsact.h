@@ -218,6 +218,39 @@ int dsact_buffer_create_coded(dsact_handle* h, int64_t capacity, const float* co
 int dsact_buffer_check(dsact_handle* h);
 /* device bytes of the ring: capacity * (2*O + 4*(A+3)) coded, capacity * 4*(2*O + A + 3) fp32; 0 before a create */
 int64_t dsact_buffer_bytes(const dsact_handle* h);
+/* Ring snapshots (training/hip_replay_buffer.py save / load): the ring's STORED FORM out of and into HBM,
+ * its cursor, and an integrity digest computed on the device. Stored form, per column in the SoA order obs, obs2, act, rew,
+ * done, logp: obs / obs2 float32[O] per row on an fp32 ring, uint8[O] codes per row on a coded ring; act float32[A]; rew, done
+ * and logp one float32 each. All four calls are SYNCHRONOUS: every argument is validated on the host before any launch or
+ * copy, the handle's stream is drained first, and the call returns with its work complete. DSACT_E_STATE before a ring was
+ * created or under stream capture.
+ *   dsact_buffer_export      copies ring rows [row0, row0 + n) to HOST arrays in stored form (each column's slice is
+ *                            contiguous in the ring: plain copies, no kernel); any destination may be NULL. 0 <= row0, 0 <= n,
+ *                            row0 + n <= size (DSACT_E_INVALID otherwise); n == 0 is a no-op.
+ *   dsact_buffer_import      writes ring rows [row0, row0 + n) from HOST arrays in stored form, none NULL; row0 + n <= capacity.
+ *                            Moves neither size nor ptr. On a coded ring every code must be < n_codes: checked on the host
+ *                            before the first byte is uploaded -- a refused import leaves the ring untouched.
+ *   dsact_buffer_set_cursor  sets size and ptr to a state replay_buffer.py:58-79 reaches: 0 <= size <= capacity, and
+ *                            ptr == size % capacity while size < capacity, 0 <= ptr < capacity when size == capacity
+ *                            (DSACT_E_INVALID otherwise).
+ *   dsact_buffer_digest      six 64-bit sums, one per column c = 0..5 (obs, obs2, act, rew, done, logp; widths w_c = O, O, A,
+ *                            1, 1, 1), over rows [row0, row0 + n), row0 + n <= size, computed on the device from the stored
+ *                            bits (k_ring_digest). Not cryptographic: it tells whether what reached HBM is what was saved, and
+ *                            compares two rings bit for bit without moving them to the host. For the element at ring row r,
+ *                            position j: g = r * w_c + j as a 64-bit integer, v = the stored value's bits zero-extended (the
+ *                            float's 32 bits, or the code byte), and with all arithmetic mod 2^64
+ *                                x = g * 0x9E3779B97F4A7C15 + (((uint64)(c + 1) << 32) | v)
+ *                                x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31
+ *                                out[c] = sum of x over the column's elements in the row range
+ *                            An integer sum: independent of the order of addition, and the digest of a range is the sum of
+ *                            the digests of its parts. g uses the ABSOLUTE ring row: the same row written at another position
+ *                            digests differently. n == 0 gives six zeros. */
+int dsact_buffer_export(dsact_handle* h, int64_t row0, int64_t n, void* obs, void* obs2, float* act, float* rew, float* done,
+                        float* logp);
+int dsact_buffer_import(dsact_handle* h, int64_t row0, int64_t n, const void* obs, const void* obs2, const float* act,
+                        const float* rew, const float* done, const float* logp);
+int dsact_buffer_set_cursor(dsact_handle* h, int64_t size, int64_t ptr);
+int dsact_buffer_digest(dsact_handle* h, int64_t row0, int64_t n, uint64_t out[6]);
 /* gather rows idx[0..batch) into the handle's minibatch staging area (== sample_batch + .cuda()). idx_host == NULL (an
  * index seed is set, DSACT_E_STATE otherwise): the rows of index-table row 0 as dsact_draw_indices left it, copied device to
  * device behind the draw -- replay_buffer.py:86-90 with no host index at all. */
