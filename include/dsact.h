@@ -294,7 +294,18 @@ int dsact_read_indices(dsact_handle* h, int64_t* out, int32_t rows);
 /* parity mode: inject eps_new[B*A], eps_2[B*A], z5[B], z6[B] (host pointers) for the next step */
 int dsact_set_noise(dsact_handle* h, const float* eps_new, const float* eps_2, const float* z5,
                     const float* z6);
-/* production mode: device Philox4x32-10 + Box-Muller keyed by (seed, iteration); 0 disables */
+/* production mode: device Philox4x32-10 + Box-Muller keyed by (seed, iteration); 0 disables.
+ * Every update's eps_new, eps_2, z5 and z6 are drawn where its minibatch is staged (the prologue of dsact_compute_grads /
+ * dsact_step, the gathers and their riders in graph replays) as a pure function of (seed, iteration, row, action dimension):
+ *   words    Philox4x32-10, counter (index, iteration low, iteration high, stream id), key = seed (low, high word)
+ *   eps_new  stream id 1, eps_2 stream id 2: element [row][d] is normal d % 4 of the call with index row * ceil(A / 4) + d / 4
+ *            (a row's last call is used in part when A % 4 != 0; no call serves two rows)
+ *   z5 | z6  stream id 3, index row: z5[row] is normal 0, z6[row] normal 1 of the call (normals 2 and 3 are not used)
+ *   map      u_k = ((float)(w[k] >> 8) + 0.5f) * 2^-24 in fp32 (the add rounds to even once w >> 8 >= 2^23, so the largest u is
+ *            1.0 and its normals are 0); r(u) = sqrt(-2 ln u); normals 0, 1 = r(u_0) (cos, sin)(2 pi u_1), normals 2, 3 =
+ *            r(u_2) (cos, sin)(2 pi u_3), all in fp32. |normal| <= r(2^-25) = 5.89.
+ * Stream ids 4 (dsact_set_index_rng) and 5 (dsact_set_act_rng) belong to the index draw and the acting noise.
+ * tests/noise_reference.py restates this; tests/test_update_noise_gpu.py holds every drawing site to it. */
 int dsact_set_device_rng(dsact_handle* h, uint64_t seed);
 
 /* ---- the update ----------------------------------------------------------------------------------- */

@@ -44,12 +44,18 @@ def np_of(t):
     return t.detach().cpu().contiguous().numpy()
 
 
-def run_case(title, obs_shape, A, conv_type, B, steps, golden=None, chains=None):
+def run_case(title, obs_shape, A, conv_type, B, steps, golden=None, chains=None, device_noise=None):
+    """device_noise: a Philox key. The update runs in its default mode (strict_rng=False): the noise is drawn in the kernels
+    (set_device_rng once, never set_noise), read back after compute_grads, held to tests/noise_reference.py, and handed to the
+    oracle as that step's noise bit for bit -- everything below it is compared as with uploaded noise, at the same gates."""
     rep = Report(title)
     alg, orc, cfg = make_pair(obs_shape, A, conv_type, B)
     e = alg.engine
     if chains is not None:   # the twin MLP trunks over the conv features as row-slice chain units (batch % 16 == 0, equal widths)
         assert e.chain_active == chains
+    if device_noise is not None:
+        from test_update_noise_gpu import read_device_noise
+        e.set_device_rng(device_noise)
     names = {n: orc._names(n) for n in ("q1", "q2", "policy")}
     orc.keep_conv = True
     lrs = {"q1": orc.cfg["lr_q"], "q2": orc.cfg["lr_q"], "policy": orc.cfg["lr_pi"]}
@@ -61,9 +67,12 @@ def run_case(title, obs_shape, A, conv_type, B, steps, golden=None, chains=None)
         torch.manual_seed(1000 + it)
         noise = draw_noise(B, A)
         e.load_batch(*(data[k].numpy() for k in ("obs", "act", "rew", "obs2", "done")))
-        e.set_noise(noise["eps_new"].numpy(), noise["eps_2"].numpy(), noise["z5"].numpy(), noise["z6"].numpy())
+        if device_noise is None:
+            e.set_noise(noise["eps_new"].numpy(), noise["eps_2"].numpy(), noise["z5"].numpy(), noise["z6"].numpy())
         e.compute_grads(it)
         e.sync()
+        if device_noise is not None:
+            noise = {k: torch.from_numpy(v) for k, v in read_device_noise(e, device_noise, it).items()}
         # ReLU kinks. A pre-activation within rounding noise of 0 lands on either side of the ReLU depending on the
         # summation order, and the gradient is discontinuous there (the whole upstream gradient of that pixel appears or
         # disappears) -- both choices are valid subgradients. The reference is therefore evaluated with the ReLU decisions
@@ -205,6 +214,12 @@ def test_cnn_type2_b16_twin_trunk_chains():
     """smallest batch the chain kernels take: several updates, so the fused Adam / Polyak of the twin-trunk weight-gradient
     tiles (dense first layer, per-trunk hidden blocks, block-diagonal output layer) feeds the next forward passes."""
     run_case("cnn type_2 (3,96,96) B=16 (twin trunks on the chains)", (3, 96, 96), 3, "type_2", 16, steps=4, chains=True)
+
+
+def test_cnn_type2_b16_default_mode_update_against_the_oracle():
+    """strict_rng=False: the kernels' own draws (Philox streams 1 .. 3, tests/noise_reference.py) read back and fed to the CNN
+    oracle bit for bit -- activations, gradients, statistics and parameters at the gates of the uploaded-noise cases"""
+    run_case("cnn type_2 (3,96,96) B=16 device noise", (3, 96, 96), 3, "type_2", 16, steps=2, chains=True, device_noise=0x5DEECE66D1234567)
 
 
 def test_cnn_type2_b16_tile_path_switch(monkeypatch):

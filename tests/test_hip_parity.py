@@ -231,14 +231,24 @@ def compare_intermediates(rep, alg, orc, L, B, A, Lp=None):
             rep.cmp("dZ.%s.%d" % (ch, l), dl("dZ.%s.%d" % (ch, l), I[key][l]), I[key][l], 1e-10, 2e-4)
 
 
-def run_case(title, O, A, hid, B, steps, act_limit=0.4, init=None, golden=None, prepare=None, resync_last=False, **over):
+def run_case(title, O, A, hid, B, steps, act_limit=0.4, init=None, golden=None, prepare=None, resync_last=False, device_noise=None,
+             expect=None, **over):
     """prepare(it, data, noise) -> (data, noise): a hook that changes (or replaces) the inputs of update `it` (tests/stress_cases.py).
     resync_last: take the last update's intermediates and gradients from a copy of the oracle AT the engine's parameters, as the
     non-gelu activations below do (nets with an output row scaled by 10^2: the gradients, and their rounding noise, scale with
-    it while Adam's step does not -- more elements whose gradient is within that noise of zero take their 2 * lr sign flip)"""
+    it while Adam's step does not -- more elements whose gradient is within that noise of zero take their 2 * lr sign flip)
+    device_noise: a Philox key. The update runs in its default mode (strict_rng=False): the noise is drawn in the kernels
+    (set_device_rng once, never set_noise), read back after compute_grads, held to tests/noise_reference.py, and handed to the
+    oracle as that step's noise bit for bit -- everything below it is compared as with uploaded noise, at the same gates.
+    expect(engine): asserts the path the case is meant to take."""
     rep = Report(title)
     alg, orc = make_pair(O, A, hid, B, act_limit=act_limit, init=init, **over)
     e = alg.engine
+    if expect is not None:
+        expect(e)
+    if device_noise is not None:
+        from test_update_noise_gpu import read_device_noise
+        e.set_device_rng(device_noise)
     L = len(hid)
     Lp = len(over.get("policy_hidden_sizes") or hid)
     rng = np.random.default_rng(5)
@@ -258,9 +268,12 @@ def run_case(title, O, A, hid, B, steps, act_limit=0.4, init=None, golden=None, 
             data, noise = prepare(it, data, noise)
         keep = it in (0, steps - 1)
         e.load_batch(*(data[k].numpy() for k in ("obs", "act", "rew", "obs2", "done")))
-        e.set_noise(noise["eps_new"].numpy(), noise["eps_2"].numpy(), noise["z5"].numpy(), noise["z6"].numpy())
+        if device_noise is None:
+            e.set_noise(noise["eps_new"].numpy(), noise["eps_2"].numpy(), noise["z5"].numpy(), noise["z6"].numpy())
         e.compute_grads(it)
         e.sync()  # the engine runs on its own stream; torch reads below are on torch's
+        if device_noise is not None:
+            noise = {k: torch.from_numpy(v) for k, v in read_device_noise(e, device_noise, it).items()}
         if cfg["value_act"] in KINKED or cfg["policy_act"] in KINKED:
             orc.act_sides = hip_act_sides(e, cfg, L, B, Lp)
         orc_chk = orc
@@ -911,6 +924,41 @@ def test_device_rng_is_standard_normal():
     e.step(1)
     b = e.debug_read("eps_new")
     assert not np.array_equal(a[: b.size], b)
+
+
+DEVICE_NOISE_SEED = 0x5DEECE66D1234567     # both key words non-zero
+
+
+def _tiles(e):
+    assert not e.chain_active and e.debug_get("fat") == 0.0
+
+
+def _chains(e):
+    assert e.chain_active and e.debug_get("fat") == 0.0
+
+
+def _throughput(e):
+    assert e.chain_active and e.debug_get("fat") == 1.0
+
+
+@pytest.mark.parametrize("O,A,hid,B,steps,expect,over", [
+    (5, 1, (33,), 7, 3, _tiles, {"act_limit": 2.0}),                        # ragged: a quarter of a call per row, a partial 4-row block
+    (11, 3, (96, 40), 50, 3, _tiles, {}),
+    (16, 4, (64, 64), 64, 3, _chains, {}),
+    (23, 5, (64, 96, 64), 64, 3, _chains, {"hip_pad_widths": True}),        # the plugin's default storage: padded to 128, on the chains
+    (23, 5, (64, 96, 64), 64, 3, _tiles, {}),                               # the exact layout keeps unequal widths on the tile stages
+    (376, 17, (256, 256, 256), 256, 3, _chains, {}),                        # BASELINE
+    (376, 17, (256, 256, 256), 1024, 2, _throughput, {}),
+    (16, 4, (64, 64), 64, 3, _chains, {"policy_act_distribution": "GaussDistribution"}),
+])
+def test_default_mode_update_against_the_oracle(O, A, hid, B, steps, expect, over):
+    """The production configuration (strict_rng=False): eps_new, eps_2, z5, z6 are drawn by k_prologue (Philox streams 1 .. 3 +
+    fp32 Box-Muller), read back, held to tests/noise_reference.py and fed to the oracle bit for bit -- every intermediate,
+    gradient, statistic, parameter, target and Adam moment then at the gates of the uploaded-noise cases. Box-Muller reaches
+    |z| = 5.9 where torch.randn practically never does: more actions saturate, which the per-row budgets (logp_tol,
+    policy_saturation_budget) take from the oracle's own actions."""
+    run_case("device noise O=%d A=%d hid=%s B=%d %s" % (O, A, hid, B, over), O, A, hid, B, steps=steps, device_noise=DEVICE_NOISE_SEED,
+             expect=expect, **over)
 
 
 def test_policy_forward_and_checkpoint_roundtrip(tmp_path):

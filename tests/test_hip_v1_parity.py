@@ -30,11 +30,20 @@ def make_pair(O, A, hid, B, act_limit=0.4, seed=0, init=None, td_bound=10.0, **o
     return alg, orc
 
 
-def run_case(title, O, A, hid, B, steps, act_limit=0.4, init=None, golden=None, prepare=None, **over):
-    """prepare(it, data, noise) -> (data, noise): a hook that changes (or replaces) the inputs of update `it` (tests/stress_cases.py)"""
+def run_case(title, O, A, hid, B, steps, act_limit=0.4, init=None, golden=None, prepare=None, device_noise=None, expect=None, **over):
+    """prepare(it, data, noise) -> (data, noise): a hook that changes (or replaces) the inputs of update `it` (tests/stress_cases.py)
+    device_noise: a Philox key. The update runs in its default mode (strict_rng=False): the noise is drawn in the kernels
+    (set_device_rng once, never set_noise), read back after compute_grads, held to tests/noise_reference.py, and handed to the
+    oracle bit for bit -- its z_t is z5, the buffer k_loss_v1 and the V1 row phase of the chains read; z6 is drawn and unused.
+    expect(engine): asserts the path the case is meant to take."""
     rep = Report(title)
     alg, orc = make_pair(O, A, hid, B, act_limit=act_limit, init=init, **over)
     e = alg.engine
+    if expect is not None:
+        expect(e)
+    if device_noise is not None:
+        from test_update_noise_gpu import read_device_noise
+        e.set_device_rng(device_noise)
     lay = e.layout
     assert lay.n_online == orc.flat_params().numel()
     rng = np.random.default_rng(9)
@@ -51,11 +60,17 @@ def run_case(title, O, A, hid, B, steps, act_limit=0.4, init=None, golden=None, 
             noise = draw_noise_v1(B, A)
         if prepare is not None:
             data, noise = prepare(it, data, noise)
-        tb_ref = orc.compute_gradient(data, noise)
+        if device_noise is None:
+            tb_ref = orc.compute_gradient(data, noise)
         e.load_batch(*(data[k].numpy() for k in ("obs", "act", "rew", "obs2", "done")))
-        e.set_noise(noise["eps_new"].numpy(), noise["eps_2"].numpy(), noise["z_t"].numpy(), noise["z_t"].numpy())
+        if device_noise is None:
+            e.set_noise(noise["eps_new"].numpy(), noise["eps_2"].numpy(), noise["z_t"].numpy(), noise["z_t"].numpy())
         e.compute_grads(it)
         e.sync()
+        if device_noise is not None:
+            drawn = read_device_noise(e, device_noise, it)
+            noise = {"eps_new": torch.from_numpy(drawn["eps_new"]), "eps_2": torch.from_numpy(drawn["eps_2"]), "z_t": torch.from_numpy(drawn["z5"])}
+            tb_ref = orc.compute_gradient(data, noise)
         g, g_ref = e.grads.cpu().numpy(), orc.flat_grads().numpy()
         off = 0
         for net, n in (("q", lay.n_q), ("policy", lay.n_pi), ("log_alpha", 1)):
@@ -124,6 +139,12 @@ def test_v1_runs_on_the_row_slice_chains(monkeypatch):
         assert np.abs(x - y).max() <= 2e-5 * max(1.0, np.abs(y).max()), n
     d = (a1.engine.online - a2.engine.online).abs().max().item()
     assert d < 5e-6, d
+
+
+def test_v1_default_mode_update_against_the_oracle():
+    """strict_rng=False: the kernels' own draws (Philox streams 1 .. 3, tests/noise_reference.py) read back and fed to the V1
+    oracle bit for bit, z_t = z5 -- gradients, statistics, parameters and targets at the gates of the uploaded-noise cases"""
+    run_case("v1 device noise O=11 A=3 (64,64) B=64", 11, 3, (64, 64), 64, steps=3, device_noise=0x5DEECE66D1234567)
 
 
 def test_v1_unbounded_critic_loss():
