@@ -41,8 +41,14 @@
 // output activation and act_mode of <true, false> (a row's action is bitwise dsact_act_mode_batch's GPU route), launched on obs
 // the hidden layers read IN PLACE from the caller's device array (no staging copy) with action[n][A] in the caller's DEVICE
 // memory. No eps is read, no logp, clipped, seed, step or row0: act_mode already clamps the plain Gaussian to the limits.
+//
+// CNN policies (dsact_cnn_acting_enable; training/off_sampler.py:46-56 on image observations,
+// networks/cnn.py:151-240): k_act_frames below turns a chunk of <= kActFrameCap frames into the pixel-major rows k_conv_fwd
+// reads, the conv stack and k_feat_scatter (dsact_conv.h) make the feature rows, and the launches above run the twin trunk
+// (ActBatchHidden::half) and the sample on them.
 #pragma once
 #include "dsact_kernels.h"
+#include "dsact_conv.h"   // fast_div
 
 namespace dsact {
 
@@ -77,6 +83,16 @@ struct ActBatchOut {
   int row0;                            // the first row of this launch in the whole call (the chunk offset)
 };
 constexpr uint32_t kActStream = 5u;
+
+// frame ingest of the CNN acting forward: n frames as the environment delivers them, src[r][c][pix] (C, H, W), into the
+// pixel-major rows of the conv kernels, dst[r][pix][c]. A pure permutation: no index table, no replay columns, no step
+// bookkeeping, noise or weight repack (k_gather_img carries those for the update) -- it may run on any stream
+constexpr int kActFrameCap = 64;     // frames per chunk of the CNN acting forward (the rows of the stand-alone forward)
+struct ActFramesArgs {
+  const float* src; float* dst;
+  int n, C, HW;
+  int chunks;                          // workgroups per frame
+};
 
 #ifdef DSACT_ACT_BATCH_DEFINE   // the kernels themselves: csrc/dsact_tu_act_batch.hip; other units see the declarations
 // 32 rows x 32 features per workgroup; thread (tr, tf) = (tid / 16, tid % 16) owns rows tr, tr + 16 and features tf, tf + 16.
@@ -232,12 +248,55 @@ __global__ void __launch_bounds__(256) k_act_batch_out(ActBatchOut a) {
     a.logp[r0 + tid] = lp;
   }
 }
+// grid: x = frame * chunks + chunk. C == 3 with HW % 4 == 0: a lane takes 4 consecutive pixels -- one 16-byte load per plane
+// (a wave reads 1 KB of each plane back to back), the 3 x 4 block transposed in registers, three 16-byte stores (a wave writes
+// 3 KB back to back): k_gather_img's RGB path for one image. Otherwise a lane per output quad, its 4 floats from <= 4 planes
+// (fast_div by C; C * HW % 4 == 0 is checked when the handle is created)
+__global__ void __launch_bounds__(256) k_act_frames(ActFramesArgs a) {
+  const int r = (int)blockIdx.x / a.chunks, ck = (int)blockIdx.x - r * a.chunks;
+  if (r >= a.n) return;
+  const size_t O = (size_t)a.C * a.HW;
+  const float* so = a.src + (size_t)r * O;
+  float* d0 = a.dst + (size_t)r * O;
+  if (a.C == 3 && (a.HW & 3) == 0) {
+    const int nq = a.HW >> 2;
+    for (int q = ck * 256 + (int)threadIdx.x; q < nq; q += a.chunks * 256) {
+      f32x4 p[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) p[c] = *(const f32x4*)(so + (size_t)c * a.HW + 4 * q);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {     // output quad j holds elements 4j .. 4j+3 of (pixel e, channel c) = e*3 + c
+        f32x4 v;
+#pragma unroll
+        for (int e4 = 0; e4 < 4; ++e4) {
+          const int o = 4 * j + e4;
+          v[e4] = p[o % 3][o / 3];
+        }
+        *(f32x4*)(d0 + (size_t)q * 12 + 4 * j) = v;
+      }
+    }
+    return;
+  }
+  const int n4 = (int)(O >> 2);
+  const float inv_c = 1.0f / (float)a.C;
+  for (int q = ck * 256 + (int)threadIdx.x; q < n4; q += a.chunks * 256) {
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int o = q * 4 + e;
+      const int pix = fast_div(o, a.C, inv_c), c = o - pix * a.C;
+      v[e] = so[(size_t)c * a.HW + pix];
+    }
+    *(f32x4*)(d0 + (size_t)q * 4) = v;
+  }
+}
 template __global__ void k_act_batch_out<false, false>(ActBatchOut);
 template __global__ void k_act_batch_out<true, false>(ActBatchOut);
 template __global__ void k_act_batch_out<false, true>(ActBatchOut);
 template __global__ void k_act_batch_out<true, true>(ActBatchOut);
 #else
 __global__ void k_act_batch_hidden(ActBatchHidden a);
+__global__ void k_act_frames(ActFramesArgs a);
 template <bool kMode, bool kDev>
 __global__ void k_act_batch_out(ActBatchOut a);
 extern template __global__ void k_act_batch_out<false, false>(ActBatchOut);

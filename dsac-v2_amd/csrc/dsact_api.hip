@@ -297,6 +297,16 @@ struct dsact_handle : BatchBufs {
   float* ab_out_host = nullptr; float* ab_out_dev = nullptr;
   unsigned long long ab_calls = 0;
   unsigned long long ab_mode_calls = 0;  // dsact_act_mode_batch chunks launched on the GPU
+  // CNN acting path (dsact_cnn_acting_enable), allocated by the opt-in for kActFrameCap frames per chunk:
+  // pinned staging of a chunk's (frames | eps), its device copy, k_act_frames' pixel-major output, one activation buffer per
+  // conv layer and the feature rows; ab_h and ab_out_* above serve its trunk (kActFrameCap rows on a CNN handle). They are the
+  // path's own -- aimg / aact / Xact stay the stand-alone forward's on `stream`, and nothing an update launch reads or writes
+  // is touched. ONE set serves live calls (on `stream`) and held calls (on act_stream): every entry point that uses it
+  // synchronises its own stream before it returns and CNN handles have no device-resident no-wait form, so two acting calls
+  // never have launches in flight at once
+  bool cnn_act = false;
+  float* ca_stage = nullptr; float* ca_frames = nullptr; float* ca_img = nullptr;
+  float* ca_act[kMaxConv] = {}; float* ca_feat = nullptr;
   // device-resident sampling (dsact_act_sample_device / dsact_buffer_add_device)
   uint64_t act_seed = 0;                 // dsact_set_act_rng: 0 = no in-kernel draw (eps must be passed)
   unsigned long long act_dev_calls = 0;  // dsact_act_sample_device chunks launched
@@ -3551,6 +3561,9 @@ int dsact_destroy(dsact_handle* h) {
   if (h->ab_stage) hipHostFree(h->ab_stage);
   if (h->ab_out_host) hipHostFree(h->ab_out_host);
   if (h->ab_in) hipFree(h->ab_in);
+  if (h->ca_stage) hipHostFree(h->ca_stage);
+  for (float* p : {h->ca_frames, h->ca_img, h->ca_feat}) if (p) hipFree(p);
+  for (int j = 0; j < kMaxConv; ++j) if (h->ca_act[j]) hipFree(h->ca_act[j]);
   for (void* p : {(void*)h->ev_ep, (void*)h->ev_acc, (void*)h->ev_len, (void*)h->ev_returns, (void*)h->ev_lengths, (void*)h->ev_remaining})
     if (p) hipFree(p);
   if (h->ev_remaining_host) hipHostFree(h->ev_remaining_host);
@@ -5385,7 +5398,8 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "eval_polls")) *value = (double)h->eval_polls;                   // dsact_eval_poll waits
   else if (!strcmp(name, "track_commit_calls")) *value = (double)h->track_commit_calls;   // dsact_track_commit launches
   else if (!strcmp(name, "track_reads")) *value = (double)h->track_reads;                 // dsact_track_read waits
-  else if (!strcmp(name, "act_fast")) *value = act_fast_ok(h) ? 1.0 : 0.0;     // dsact_act_sample / the one-launch acting forward serve this handle
+  else if (!strcmp(name, "act_fast")) *value = (act_fast_ok(h) || h->cnn_act) ? 1.0 : 0.0;   // dsact_act_sample serves this handle (the one-launch forward, or the enabled CNN acting path)
+  else if (!strcmp(name, "cnn_act")) *value = h->cnn_act ? 1.0 : 0.0;          // dsact_cnn_acting_enable has been called
   else if (!strcmp(name, "graph_cache")) *value = (double)h->graph_cache.size();   // inactive captured graphs kept by dsact_run_group
   else if (!strcmp(name, "graph_noise_table")) *value = h->active.noise_table ? 1.0 : 0.0;
   else if (!strcmp(name, "twin_par")) *value = (h->twin_par ? 1.0 : 0.0) + (h->twin_merged ? 2.0 : 0.0);   // CNN nets: trunks as own workgroups (+2: one launch)
@@ -5454,13 +5468,15 @@ static bool act_fast_ok(const dsact_handle* h) {
 // TanhGaussDistribution.sample() (utils/act_distribution_cls.py:32-42) with the caller's standard-normal draw eps[A]
 // (torch.randn(1, A) consumes the torch generator exactly as Normal.sample() does and mean + std * eps IS its result):
 // action[A] (inside the action limits by construction of the tanh squashing; the caller clips like the reference) and
-// its log-probability. MLP policies only (DSACT_E_INVALID otherwise: the caller takes dsact_policy_forward).
+// its log-probability. MLP policies, and CNN policies after dsact_cnn_acting_enable (networks/cnn.py:151-240: the batched CNN
+// acting forward at n = 1, live or held); DSACT_E_INVALID otherwise: the caller takes dsact_policy_forward.
 static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const float* eps, float* action_host, float* logp_host,
                         const float* base, hipStream_t stream);
 int dsact_act_sample(dsact_handle* h, const float* obs_host, const float* eps_host, float* action_host, float* logp_host) {
   if (!h || !obs_host || !eps_host || !action_host || !logp_host) return DSACT_E_INVALID;
   if (!h->online) return fail(h, DSACT_E_STATE, "arenas not bound");
   if (!h->limits_set) return fail(h, DSACT_E_STATE, "action limits not set (dsact_set_action_limits)");
+  if (h->cnn_act) return dsact_act_sample_batch(h, obs_host, 1, eps_host, action_host, logp_host);
   if (!act_fast_ok(h)) return fail(h, DSACT_E_INVALID, "dsact_act_sample serves MLP policies with obs <= %d floats", kActMaxObs);
   HIPCHK(h, hipSetDevice(h->device));
   if (h->beh_held) {
@@ -5490,10 +5506,14 @@ static bool is_device_ptr(const void* p) {
 // the batched forward's buffers, allocated by its first call (or by the first dsact_behaviour_hold: no allocation then stands
 // between a held acting call and its launches)
 static int alloc_act_batch(dsact_handle* h) {
-  if (h->ab_in) return DSACT_OK;
-  const int O = h->O, A = h->A, R = kActBatchCap;
-  HIPCHK(h, hipHostMalloc((void**)&h->ab_stage, (size_t)R * (O + A) * sizeof(float), hipHostMallocDefault));
-  HIPCHK(h, hipMalloc((void**)&h->ab_in, (size_t)R * (O + A) * sizeof(float)));
+  if (h->ab_h[0]) return DSACT_OK;
+  // a CNN handle (dsact_cnn_acting_enable) runs chunks of kActFrameCap frames and stages them in buffers of its own (ca_*):
+  // kActBatchCap rows of O floats would be ~113 MB of pinned memory at 3 x 96 x 96
+  const int O = h->O, A = h->A, R = h->cnn ? kActFrameCap : kActBatchCap;
+  if (!h->cnn) {
+    HIPCHK(h, hipHostMalloc((void**)&h->ab_stage, (size_t)R * (O + A) * sizeof(float), hipHostMallocDefault));
+    HIPCHK(h, hipMalloc((void**)&h->ab_in, (size_t)R * (O + A) * sizeof(float)));
+  }
   for (int i = 0; i < 2; ++i) HIPCHK(h, hipMalloc((void**)&h->ab_h[i], (size_t)R * kMaxWidth * sizeof(float)));
   HIPCHK(h, hipHostMalloc((void**)&h->ab_out_host, (size_t)R * (A + 1) * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
   HIPCHK(h, hipHostGetDevicePointer((void**)&h->ab_out_dev, h->ab_out_host, 0));
@@ -5546,6 +5566,58 @@ static int enqueue_act_batch(dsact_handle* h, const float* X, int ldx, int m, co
   return launch_act(kActOutForms[form].name, kActOutForms[form].kernel, dim3((unsigned)((m + 7) / 8)), o);
 }
 
+// one conv layer of the online policy's stack on n pixel-major images as a k_conv_fwd launch: layer j of the policy net whose
+// parameters start at `base`, `in` -> `out`. Shared by the stand-alone forward (enqueue_policy_logits) and the CNN acting path
+static ConvStageArgs act_conv_args(const dsact_handle* h, int j, const float* base, const float* in, float* out, int n) {
+  const NetDesc& d = h->pd;
+  const ConvGeom& g = h->cg[j];
+  ConvStageArgs a;
+  memset(&a, 0, sizeof(a));
+  a.g = g; a.ix = conv_index(g); a.n_prob = 1;
+  ConvGroup& p = a.p[0];
+  p.in = in;
+  p.n_sub = 1;
+  p.w[0] = base + d.cw_off[j]; p.bias[0] = base + d.cb_off[j];
+  p.out[0] = out; p.M = n * g.OH * g.OW; p.tiles_n = tiles_of(g.Cout, TN);
+  p.item_end = tiles_of(p.M, TM) * p.tiles_n;
+  a.n_items = p.item_end;
+  return a;
+}
+// the last conv activation of n images -> the flattened feature columns of n MLP input rows X[n][ldx]
+static FeatArgs act_feat_args(const dsact_handle* h, const float* act, float* X, int n) {
+  FeatArgs f;
+  memset(&f, 0, sizeof(f));
+  f.act[0] = act; f.dst0[0] = X; f.n_stack = 1; f.B = n; f.P = h->cP; f.C = h->cg[h->n_conv - 1].Cout; f.ldx = h->ldx;
+  return f;
+}
+
+// the CNN counterpart of enqueue_act_batch (training/off_sampler.py:46-56 on image observations, networks/cnn.py:151-240):
+// policy(frames) + the output form for one chunk of m <= kActFrameCap frames in the environment's (C, H, W) layout, enqueued on
+// `stream` -- k_act_frames, one k_conv_fwd per conv layer reading its weights at `base`, k_feat_scatter into the feature rows,
+// then the twin trunk and the output launch of enqueue_act_batch. Everything in between lives in the path's own buffers
+// (dsact_cnn_acting_enable). base, o and form as in enqueue_act_batch
+static int enqueue_act_cnn(dsact_handle* h, const float* frames_dev, int m, const float* base, hipStream_t stream, ActBatchOut o, int form) {
+  auto launch_act = [&](const char* name, auto kernel, dim3 grid, const auto& a) {
+    return stream == h->stream ? launch(h, name, kernel, grid, dim3(kThreads), 0, a) : launch_on(h, stream, name, kernel, grid, dim3(kThreads), 0, a);
+  };
+  ActFramesArgs fr;
+  fr.src = frames_dev; fr.dst = h->ca_img; fr.n = m; fr.C = h->cfg.img_c; fr.HW = h->cfg.img_h * h->cfg.img_w;
+  fr.chunks = 8;   // (workgroups per frame as enqueue_gather_img chooses them)
+  if (fr.C == 3 && fr.HW % 4 == 0) {
+    const int per = (fr.HW / 4 + kThreads - 1) / kThreads;
+    fr.chunks = per < 1 ? 1 : (per > 16 ? 16 : per);
+  }
+  TRY(launch_act("act_frames", k_act_frames, dim3((unsigned)(m * fr.chunks)), fr));
+  for (int j = 0; j < h->n_conv; ++j) {
+    const ConvStageArgs a = act_conv_args(h, j, base, j == 0 ? h->ca_img : h->ca_act[j - 1], h->ca_act[j], m);
+    TRY(launch_act("act_conv", k_conv_fwd, dim3(conv_fwd_grid(a.n_items)), a));
+  }
+  const FeatArgs f = act_feat_args(h, h->ca_act[h->n_conv - 1], h->ca_feat, m);
+  const long long ne = (long long)m * h->F;
+  TRY(launch_act("act_feat", k_feat_scatter, dim3((unsigned)((ne + kThreads - 1) / kThreads), 1), f));
+  return enqueue_act_batch(h, h->ca_feat, h->ldx, m, base, stream, o, form);
+}
+
 // the host-row forward of dsact_act_sample_batch / dsact_act_mode_batch (and a held dsact_act_sample): eps != nullptr samples
 // (action, logp), eps == nullptr writes the mode.
 // base: the policy net's parameters (the live arena, or a held behaviour copy); stream: where the copies and launches go and
@@ -5555,30 +5627,35 @@ static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const flo
   HIPCHK(h, hipSetDevice(h->device));
   TRY(check_handoff(h));
   if (stream != h->stream) HIPCHK(h, hipStreamWaitEvent(stream, h->beh_ev, 0));
-  const int O = h->O, A = h->A, R = kActBatchCap;
+  // an enabled CNN handle: rows are frames of O = C * H * W floats, chunks of kActFrameCap through the path's own stage
+  const bool cnn = h->cnn_act;
+  const int O = h->O, A = h->A, R = cnn ? kActFrameCap : kActBatchCap;
   const bool mode = eps == nullptr;
   TRY(alloc_act_batch(h));
+  float* const stage = cnn ? h->ca_stage : h->ab_stage;
+  float* const in = cnn ? h->ca_frames : h->ab_in;
   const bool obs_dev = is_device_ptr(obs), eps_dev = !mode && is_device_ptr(eps);
   for (int s = 0; s < n; s += R) {
     const int m = n - s < R ? n - s : R;
-    float* in_obs = h->ab_in;
-    float* in_eps = h->ab_in + (size_t)m * O;
+    float* in_obs = in;
+    float* in_eps = in + (size_t)m * O;
     // (obs | eps) of this chunk: host rows through the pinned stage in one copy, device rows copied on the stream
-    if (!obs_dev) memcpy(h->ab_stage, obs + (size_t)s * O, (size_t)m * O * sizeof(float));
-    if (!mode && !eps_dev) memcpy(h->ab_stage + (size_t)m * O, eps + (size_t)s * A, (size_t)m * A * sizeof(float));
+    if (!obs_dev) memcpy(stage, obs + (size_t)s * O, (size_t)m * O * sizeof(float));
+    if (!mode && !eps_dev) memcpy(stage + (size_t)m * O, eps + (size_t)s * A, (size_t)m * A * sizeof(float));
     if (!obs_dev && !eps_dev) {
-      HIPCHK(h, hipMemcpyAsync(h->ab_in, h->ab_stage, (size_t)m * (O + (mode ? 0 : A)) * sizeof(float), hipMemcpyHostToDevice,
+      HIPCHK(h, hipMemcpyAsync(in, stage, (size_t)m * (O + (mode ? 0 : A)) * sizeof(float), hipMemcpyHostToDevice,
                                stream));
     } else {
-      HIPCHK(h, hipMemcpyAsync(in_obs, obs_dev ? obs + (size_t)s * O : h->ab_stage, (size_t)m * O * sizeof(float), hipMemcpyDefault, stream));
+      HIPCHK(h, hipMemcpyAsync(in_obs, obs_dev ? obs + (size_t)s * O : stage, (size_t)m * O * sizeof(float), hipMemcpyDefault, stream));
       if (!mode)
-        HIPCHK(h, hipMemcpyAsync(in_eps, eps_dev ? eps + (size_t)s * A : h->ab_stage + (size_t)m * O, (size_t)m * A * sizeof(float),
+        HIPCHK(h, hipMemcpyAsync(in_eps, eps_dev ? eps + (size_t)s * A : stage + (size_t)m * O, (size_t)m * A * sizeof(float),
                                  hipMemcpyDefault, stream));
     }
     ActBatchOut o = {};
     o.eps = mode ? nullptr : in_eps;
     o.action = h->ab_out_dev; o.logp = mode ? nullptr : h->ab_out_dev + (size_t)m * A;
-    TRY(enqueue_act_batch(h, in_obs, O, m, base, stream, o, mode ? kActOutMode : kActOutSample));
+    if (cnn) TRY(enqueue_act_cnn(h, in_obs, m, base, stream, o, mode ? kActOutMode : kActOutSample));
+    else TRY(enqueue_act_batch(h, in_obs, O, m, base, stream, o, mode ? kActOutMode : kActOutSample));
     HIPCHK(h, hipStreamSynchronize(stream));
     (mode ? h->ab_mode_calls : h->ab_calls)++;
     memcpy(action_host + (size_t)s * A, h->ab_out_host, (size_t)m * A * sizeof(float));
@@ -5589,7 +5666,8 @@ static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const flo
 
 int dsact_act_sample_batch(dsact_handle* h, const float* obs, int32_t n, const float* eps, float* action_host, float* logp_host) {
   if (!h || !obs || !eps || !action_host || !logp_host || n < 1) return DSACT_E_INVALID;
-  TRY(act_batch_ready(h, "dsact_act_sample_batch", "dsact_policy_forward"));
+  // (a CNN handle is served after dsact_cnn_acting_enable: chunks of kActFrameCap frames through enqueue_act_cnn)
+  TRY(act_batch_ready(h, "dsact_act_sample_batch", h->cnn_act ? nullptr : "dsact_policy_forward"));
   if (h->beh_held) {   // the held behaviour policy (dsact_behaviour_hold) on the acting stream
     h->beh_acts++;
     return act_batch_gpu(h, obs, n, eps, action_host, logp_host, h->beh_dev, h->act_stream);
@@ -5605,24 +5683,11 @@ static int enqueue_policy_logits(dsact_handle* h, const float* obs_host, int32_t
     if (!h->stage_img) HIPCHK(h, hipMalloc(&h->stage_img, 2 * (size_t)h->Brows * O * sizeof(float)));
     HIPCHK(h, hipMemcpyAsync(h->stage_img, obs_host, (size_t)n * O * 4, hipMemcpyHostToDevice, h->stream));
     TRY(enqueue_gather_img(h, h->stage_img, h->stage_img, h->idx_iota, 1, 0, false, h->aimg, h->aimg, n));
-    const NetDesc& d = h->pd;
     for (int j = 0; j < h->n_conv; ++j) {
-      const ConvGeom& g = h->cg[j];
-      ConvStageArgs a;
-      memset(&a, 0, sizeof(a));
-      a.g = g; a.ix = conv_index(g); a.n_prob = 1;
-      ConvGroup& p = a.p[0];
-      p.in = j == 0 ? h->aimg : h->aact[j - 1];
-      p.n_sub = 1;
-      p.w[0] = net_params(h, N_POL) + d.cw_off[j]; p.bias[0] = net_params(h, N_POL) + d.cb_off[j];
-      p.out[0] = h->aact[j]; p.M = n * g.OH * g.OW; p.tiles_n = tiles_of(g.Cout, TN);
-      p.item_end = tiles_of(p.M, TM) * p.tiles_n;
-      a.n_items = p.item_end;
+      const ConvStageArgs a = act_conv_args(h, j, net_params(h, N_POL), j == 0 ? h->aimg : h->aact[j - 1], h->aact[j], n);
       TRY(launch(h, "act_conv", k_conv_fwd, dim3(conv_fwd_grid(a.n_items)), dim3(kThreads), 0, a));
     }
-    FeatArgs f;
-    memset(&f, 0, sizeof(f));
-    f.act[0] = h->aact[h->n_conv - 1]; f.dst0[0] = h->Xact; f.n_stack = 1; f.B = n; f.P = h->cP; f.C = h->cg[h->n_conv - 1].Cout; f.ldx = h->ldx;
+    const FeatArgs f = act_feat_args(h, h->aact[h->n_conv - 1], h->Xact, n);
     const long long ne = (long long)n * h->F;
     TRY(launch(h, "act_feat", k_feat_scatter, dim3((unsigned)((ne + kThreads - 1) / kThreads), 1), dim3(kThreads), 0, f));
   } else {
@@ -5897,7 +5962,8 @@ int dsact_track_read(dsact_handle* h, int32_t n_envs, int64_t* episodes, int64_t
 int dsact_behaviour_hold(dsact_handle* h) {
   if (!h) return DSACT_E_INVALID;
   if (!h->online) return fail(h, DSACT_E_STATE, "arenas not bound");
-  if (h->cnn) return fail(h, DSACT_E_INVALID, "dsact_behaviour_hold serves MLP policies (the CNN acting forward reads the live weights)");
+  // (after dsact_cnn_acting_enable the CNN acting forward takes its weight base per call: the copy below carries the conv weights)
+  if (h->cnn && !h->cnn_act) return fail(h, DSACT_E_INVALID, "dsact_behaviour_hold serves MLP policies (the CNN acting forward reads the live weights)");
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   HIPCHK(h, hipStreamIsCapturing(h->stream, &cap));
   if (cap != hipStreamCaptureStatusNone) return fail(h, DSACT_E_STATE, "dsact_behaviour_hold under stream capture");
@@ -5932,6 +5998,34 @@ int dsact_behaviour_hold(dsact_handle* h) {
   HIPCHK(h, hipEventRecord(h->beh_host_ev, h->act_stream));
   h->beh_held = true;
   h->beh_holds++;
+  return DSACT_OK;
+}
+
+// ---- CNN acting ------------------------------------------------------------------------------------
+// the opt-in that lets dsact_act_sample_batch, dsact_act_sample and dsact_behaviour_hold serve a CNN handle
+// (training/off_sampler.py:46-56 with the policy of networks/cnn.py:151-240): allocates everything enqueue_act_cnn works in, for
+// kActFrameCap frames per chunk, so that no allocation stands between a held acting call and its launches
+int dsact_cnn_acting_enable(dsact_handle* h) {
+  if (!h) return DSACT_E_INVALID;
+  if (!h->cnn) return fail(h, DSACT_E_INVALID, "dsact_cnn_acting_enable serves CNN policies (an MLP handle acts through dsact_act_sample_batch as it is)");
+  if (h->A > 32) return fail(h, DSACT_E_INVALID, "dsact_cnn_acting_enable serves act_dim <= 32");
+  if (h->cnn_act) return DSACT_OK;
+  static_assert(kActFrameCap == kActRows, "a chunk of the CNN acting path is the stand-alone forward's row count");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t R = kActFrameCap, O = (size_t)h->O, A = (size_t)h->A;
+  if (!h->ca_stage) HIPCHK(h, hipHostMalloc((void**)&h->ca_stage, R * (O + A) * sizeof(float), hipHostMallocDefault));
+  if (!h->ca_frames) HIPCHK(h, hipMalloc((void**)&h->ca_frames, R * (O + A) * sizeof(float)));
+  if (!h->ca_img) HIPCHK(h, hipMalloc((void**)&h->ca_img, R * O * sizeof(float)));
+  for (int j = 0; j < h->n_conv; ++j) {
+    const ConvGeom& g = h->cg[j];
+    if (!h->ca_act[j]) HIPCHK(h, hipMalloc((void**)&h->ca_act[j], R * g.OH * g.OW * g.Cout * sizeof(float)));
+  }
+  if (!h->ca_feat) {
+    HIPCHK(h, hipMalloc((void**)&h->ca_feat, R * h->ldx * sizeof(float)));
+    HIPCHK(h, hipMemset(h->ca_feat, 0, R * h->ldx * sizeof(float)));   // (the columns behind the features are never written)
+  }
+  TRY(alloc_act_batch(h));   // the trunk's two activation buffers and the mapped output rows
+  h->cnn_act = true;
   return DSACT_OK;
 }
 

@@ -163,7 +163,8 @@ class DSAC_V1_HIP(_v2.DSAC_V2_HIP):
             value_act=_v2.ACTIVATIONS[kwargs.get("value_hidden_activation", "gelu")][0],
             policy_act=_v2.ACTIVATIONS[kwargs.get("policy_hidden_activation", "gelu")][0],
             policy_hidden=None if ct else _v2._policy_hidden_sizes(kwargs),
-            pad_widths=bool(kwargs.get("hip_pad_widths", True)))   # ragged / unequal widths on the chains (see DSAC_V2_HIP)
+            pad_widths=bool(kwargs.get("hip_pad_widths", True)),   # ragged / unequal widths on the chains (see DSAC_V2_HIP)
+            cnn_act=bool(kwargs.get("hip_cnn_act", False)))        # CNN acting path, opt-in (see DSAC_V2_HIP)
         if not ct and _v2._policy_hidden_sizes(kwargs) and not self.engine.layout.pad_to:
             raise NotImplementedError("DSAC_V1_HIP: the row-slice chains refused the padded shape of unequal value / policy widths")
         self.networks.attach(self.engine)

@@ -258,6 +258,8 @@ class HipCnnStochaPolicy(nn.Module):
         std = torch.clamp(self.log_std(feature), self.min_log_std, self.max_log_std).exp()
         return torch.cat((self.mean(feature), std), dim=-1)
 
+    # (the default of HipStochaPolicy: DSAC_V1_HIP's container, which sets no class of its own, acts with it on image policies too)
+    action_distribution_cls = HipStochaPolicy.action_distribution_cls
     get_act_dist = HipStochaPolicy.get_act_dist
 
 
@@ -730,7 +732,10 @@ class DSAC_V2_HIP:
             policy_hidden=_policy_hidden_sizes(kwargs),
             # additive: `hip_pad_widths` (default True) -- ragged / unequal hidden widths of the same depth are stored zero-padded to
             # 64 / 128 / 256 when that puts the update on the row-slice chain kernels (dsact/engine.py, dsact/layout.py pad_to)
-            pad_widths=bool(kwargs.get("hip_pad_widths", True)))
+            pad_widths=bool(kwargs.get("hip_pad_widths", True)),
+            # additive: `hip_cnn_act` (default False) -- a CNN policy is served by the batched acting call and under a behaviour
+            # hold (dsact_cnn_acting_enable); nothing with MLP nets
+            cnn_act=bool(kwargs.get("hip_cnn_act", False)))
         self.networks.attach(self.engine)
         register_engine(self.engine)
         # additive: `hip_host_act` (default True) -- the sampler's / evaluator's batch-1 policy forward runs on the host from a

@@ -128,6 +128,7 @@ SYMBOLS = [
     ("dsact_behaviour_hold", C.c_int, [_P]),
     ("dsact_behaviour_release", C.c_int, [_P]),
     ("dsact_stream_idle", C.c_int, [_P]),
+    ("dsact_cnn_acting_enable", C.c_int, [_P]),
     ("dsact_set_act_rng", C.c_int, [_P, C.c_uint64]),
     ("dsact_act_sample_device", C.c_int, [_P, _P, C.c_int32, _P, C.c_int64, _P, _P, _P]),
     ("dsact_buffer_add_device", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_double]),

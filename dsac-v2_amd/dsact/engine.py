@@ -69,9 +69,11 @@ class DsactEngine:
                  global_batch: Optional[int] = None, device: int = 0, conv_type: Optional[str] = None,
                  algo: str = "DSAC_V2", td_bound: float = 20.0, v1_bound: bool = True, value_act: int = 0, policy_act: int = 0, act_dist: int = 0,
                  policy_std_type: str = "mlp_shared", value_out_act: int = 0, policy_out_act: int = 0,
-                 policy_hidden: Optional[Sequence[int]] = None, pad_widths: bool = False):
+                 policy_hidden: Optional[Sequence[int]] = None, pad_widths: bool = False, cnn_act: bool = False):
         """obs_dim: int for the MLP nets; with `conv_type` ("type_1" / "type_2", reference
         networks/cnn.py:173-228) the (C, H, W) image shape, and `hidden` must be that type's MLP widths.
+
+        cnn_act: with `conv_type`, enable the CNN acting path (enable_cnn_acting). Nothing for MLP nets.
 
         pad_widths (round 6): hidden widths the row-slice chain kernels do not take as they are -- ragged ones (96, 40), unequal
         value / policy lists of the same depth -- are STORED zero-padded to one common width of 64 / 128 / 256 when that puts
@@ -87,6 +89,14 @@ class DsactEngine:
         if pad and not self.chain_active:     # the chains refused it (LDS, an environment switch, ...): no reason to carry the padding
             self.close()
             self._init(obs_dim, act_dim, hidden, batch, pad_to=None, **kw)
+        if cnn_act and self.conv_type:
+            self.enable_cnn_acting()
+
+    def enable_cnn_acting(self):
+        """dsact_cnn_acting_enable: from now on act_sample / act_sample_batch and behaviour_hold serve this CNN engine (frames
+        as [n, C, H, W] or [n, O] rows). Allocates the path's buffers; idempotent. Raises DsactError on an MLP engine."""
+        self._chk(self._lib.dsact_cnn_acting_enable(self._h))
+        self.cnn_act = True
 
     @staticmethod
     def _pad_width(hidden, policy_hidden, batch, obs_dim, *, conv_type=None, algo="DSAC_V2", policy_std_type="mlp_shared", value_act=0,
@@ -119,6 +129,7 @@ class DsactEngine:
                              "the DSAC-T update has no CPU fallback")
         self.torch = torch
         self.conv_type = conv_type
+        self.cnn_act = False
         self.algo = algo
         if algo not in ("DSAC_V2", "DSAC_V1"):
             raise DsactError("algo must be DSAC_V2 or DSAC_V1")
@@ -670,7 +681,8 @@ class DsactEngine:
     def act_sample_batch(self, obs, eps):
         """dsact_act_sample_batch: (action float32[N, A], logp float32[N]) of the policy's action distribution sampled for N
         observation rows with the caller's N(0,1) draws eps[N, A] (row i: torch.randn(N, A)[i]). obs / eps: numpy / CPU
-        tensors, or CUDA tensors on this engine's GPU (passed by device address, as load_batch does)"""
+        tensors, or CUDA tensors on this engine's GPU (passed by device address, as load_batch does). A CNN engine with
+        cnn_act takes frames as [N, C, H, W] or [N, O] rows (O = C * H * W)"""
         torch = self.torch
         n = int(np.prod(np.shape(obs))) // self.obs_dim
         srcs = [self._src(obs, n * self.obs_dim), self._src(eps, n * self.act_dim)]

@@ -93,6 +93,15 @@ def attached_engine(networks, action_type, policy_classes):
     return eng
 
 
+def cnn_act_engine(networks, action_type):
+    """attached_engine for a class that was given `hip_cnn_act=True`: an MLP engine as ever, a CNN engine only with the CNN
+    acting path enabled (DsactEngine.cnn_act) -- else None"""
+    eng = attached_engine(networks, action_type, ANY_POLICY)
+    if eng is not None and getattr(eng, "conv_type", None) and not getattr(eng, "cnn_act", False):
+        return None
+    return eng
+
+
 def act_fast_ok(cache, eng):
     """the library's own gate of dsact_act_sample (act_fast_ok, csrc/dsact_api.hip): MLP policy, observation <= 768 floats, at most
     4 hidden layers, act_dim <= 32, DSACT_NO_FAST_ACT unset -- asked once per engine (`cache`: {id(engine): bool}), never restated"""

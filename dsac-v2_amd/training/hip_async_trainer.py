@@ -19,8 +19,12 @@ Holding: an engine-backed algorithm holds through its engine (dsact_behaviour_ho
 policy, which dsact_act_sample / dsact_act_sample_batch act with on a stream of their own). The held snapshot of theta_g
 completes when group g - 1 completes, so at most two groups are in flight. A plain torch algorithm's sampler gets a
 copy.deepcopy of the networks at every hold. Setups in which a held sampler would silently act with the live weights are
-refused (NotImplementedError) before anything runs: CNN policies, samplers that act through the module forward, data-parallel
-handles.
+refused (NotImplementedError) before anything runs: CNN policies without the CNN acting path, samplers that act through the
+module forward, data-parallel handles.
+
+CNN policies: served with `hip_cnn_act=True` in the trainer's kwargs AND an engine whose CNN acting
+path is enabled (DsactEngine.cnn_act -- the algorithm was built with the same kwarg); the sampler checks then apply as they
+stand, so the sampler needs the kwarg too (without it a CNN policy acts through the module forward, which is refused).
 """
 import copy
 
@@ -34,15 +38,18 @@ def _engine_of(alg):
     return eng if eng is not None and hasattr(eng, "behaviour_hold") else None
 
 
-def _check_supported(alg, sampler):
+def _check_supported(alg, sampler, kwargs=None):
     eng = _engine_of(alg)
     if sampler is None or eng is None:
         return
     if not hasattr(alg, "hold_behaviour"):
         raise NotImplementedError("hip_off_async_trainer: %s has an engine but no hold_behaviour()" % type(alg).__name__)
     if getattr(eng, "conv_type", None):
-        raise NotImplementedError("hip_off_async_trainer: CNN policies act through the live weights (the stand-alone CNN forward "
-                                  "holds the arena's weight pointers); use hip_off_serial_trainer")
+        # (the kwarg first: the engine's cnn_act is looked at only when the caller opted in)
+        if not (kwargs or {}).get("hip_cnn_act") or not eng.cnn_act:
+            raise NotImplementedError("hip_off_async_trainer: CNN policies act through the live weights (the stand-alone CNN forward "
+                                      "holds the arena's weight pointers) unless the CNN acting path is enabled: pass "
+                                      "hip_cnn_act=True to the algorithm, the sampler and the trainer, or use hip_off_serial_trainer")
     if int(eng.cfg.global_batch) != int(eng.batch) or int(getattr(eng, "comm_world", 1)) > 1:
         raise NotImplementedError("hip_off_async_trainer: data-parallel handles are not supported")
     from training.hip_sampler import HipOffSampler
@@ -70,7 +77,7 @@ class HipOffAsyncTrainer(HipOffSerialTrainer):
                                           "hip_off_serial_trainer" % k)
         if sampler is not None:
             sampler.networks = alg.networks   # (what the serial trainer does first: the routes below are those of the learner's nets)
-        _check_supported(alg, sampler)
+        _check_supported(alg, sampler, kwargs)
         super().__init__(alg, sampler, buffer, evaluator, **kwargs)
         self._engine = _engine_of(alg)
 

@@ -16,8 +16,8 @@ import time
 import numpy as np
 import torch
 
-from training.hip_acting_common import (MLP_POLICY, _container, _reset, act_fast_ok, attached_engine, networks_of,  # noqa: F401
-                                        refuse_noise, require_env_state, sample_batch_size)
+from training.hip_acting_common import (ANY_POLICY, MLP_POLICY, _container, _reset, act_fast_ok, attached_engine,  # noqa: F401
+                                        cnn_act_engine, networks_of, refuse_noise, require_env_state, sample_batch_size)
 
 __all__ = ["HipOffSampler", "create_sampler"]
 
@@ -50,6 +50,9 @@ class HipOffSampler:
         # additive: `hip_sampler_general_path=True` forces the general loop below (reproducibility comparisons against the
         # reference sampler: the fast path's logits differ from the module forward's in the last bits)
         self.general_path = bool(kwargs.get("hip_sampler_general_path", False))
+        # additive: `hip_cnn_act=True` (default False) -- a CNN policy whose engine has the CNN acting path enabled
+        # (DsactEngine.cnn_act) takes the fast path too: dsact_act_sample on one frame per step
+        self.cnn_act = bool(kwargs.get("hip_cnn_act", False))
         self._fast_ok, self._fast_started = {}, False
 
     def load_state_dict(self, state_dict):
@@ -61,7 +64,10 @@ class HipOffSampler:
         .cpu().numpy() (145 -> ~50 us per step, bench.py `e2e`). None: the general path below."""
         if self.general_path:
             return None
-        eng = attached_engine(self.networks, self.action_type, MLP_POLICY)
+        if self.cnn_act:
+            eng = cnn_act_engine(self.networks, self.action_type)
+        else:
+            eng = attached_engine(self.networks, self.action_type, MLP_POLICY)
         return eng if eng is not None and act_fast_ok(self._fast_ok, eng) else None
 
     def per_row_engine(self):
@@ -76,7 +82,7 @@ class HipOffSampler:
         long run from the same seed may leave the general path's trajectory. `hip_sampler_general_path=True` forces the
         general loop."""
         n, env = self.sample_batch_size, self.env
-        O, A = eng.obs_dim, eng.act_dim
+        O, A = int(np.prod(eng.obs_dim)), eng.act_dim   # (the flat observation size: a CNN engine's frames are rows of C * H * W floats)
         obs_b, obs2_b = np.empty((n, O), np.float32), np.empty((n, O), np.float32)
         act_b = np.empty((n, A), np.float32)
         clip_b = np.empty((n, A), np.float32)

@@ -21,7 +21,10 @@ Acting routes (per sample(), one per lockstep step):
     N rows with ONE torch.randn(N, A) draw (csrc/dsact_act_batch.h);
   * attached MLP policy below the threshold (or hip_vec_act="host"): dsact_act_sample per row (the host acting forward
     HipOffSampler uses), the N rows of ONE torch.randn(N, A) draw as their eps;
-  * CNN policies and unattached containers: the module forward over the [N, ...] batch plus create_action_distributions
+  * hip_cnn_act=True and an attached CNN policy whose engine has the CNN acting path enabled (DsactEngine.cnn_act, DESIGN.md
+    section 19): dsact_act_sample_batch on the N frames for every N >= 2. hip_vec_act and hip_vec_gpu_min_envs do not apply:
+    a CNN policy has no host forward, so there is nothing to cross over to;
+  * other CNN policies and unattached containers: the module forward over the [N, ...] batch plus create_action_distributions
     and its sample() (which consumes the generator as one torch.randn(N, A) draw does).
 A row's action depends only on its observation and its eps row: environment i's trajectory does not depend on how many
 environments run beside it (given the same draws).
@@ -33,8 +36,8 @@ import time
 import numpy as np
 import torch
 
-from training.hip_acting_common import (MLP_POLICY, _reset, act_fast_ok, attached_engine, env_count, make_envs, networks_of,
-                                        refuse_noise, sample_batch_size)
+from training.hip_acting_common import (MLP_POLICY, _reset, act_fast_ok, attached_engine, cnn_act_engine, env_count, make_envs,
+                                        networks_of, refuse_noise, sample_batch_size)
 from training.hip_sampler import SAMPLER_TIME_KEY, HipOffSampler, SampleBatch
 
 __all__ = ["HipVecOffSampler", "DEFAULT_GPU_MIN_ENVS"]
@@ -55,6 +58,7 @@ class HipVecOffSampler:
         if self.act_mode not in ("auto", "gpu", "host"):
             raise ValueError("hip_vec_act must be 'auto', 'gpu' or 'host' (got %r)" % (self.act_mode,))
         self.gpu_min_envs = int(kwargs.get("hip_vec_gpu_min_envs", DEFAULT_GPU_MIN_ENVS))
+        self.cnn_act = bool(kwargs.get("hip_cnn_act", False))   # additive (default False): see the module docstring
         if n == 1:
             # the single-environment sampler as it is: same environment, same container, same per-step calls
             one = dict(kwargs)
@@ -101,7 +105,10 @@ class HipVecOffSampler:
         return self.total_sample_number
 
     def _engine(self):
-        """the engine behind an ATTACHED MLP policy (dsact_act_sample_batch serves every one), else None"""
+        """the engine behind an ATTACHED MLP policy (dsact_act_sample_batch serves every one) -- with hip_cnn_act also behind a
+        CNN policy whose engine has the CNN acting path enabled --, else None"""
+        if self.cnn_act:
+            return cnn_act_engine(self.networks, self.action_type)
         return attached_engine(self.networks, self.action_type, MLP_POLICY)
 
     def per_row_engine(self):
@@ -116,6 +123,8 @@ class HipVecOffSampler:
         eng = self._engine()
         if eng is None:
             return "module"
+        if getattr(eng, "conv_type", None):
+            return "gpu"   # (a CNN policy has no host forward: hip_vec_act / hip_vec_gpu_min_envs do not apply)
         if self.act_mode == "gpu" or (self.act_mode == "auto" and self.n_envs >= self.gpu_min_envs):
             return "gpu"
         return "host" if act_fast_ok(self._fast_ok, eng) else "gpu"

@@ -461,7 +461,9 @@ int dsact_policy_forward(dsact_handle* h, const float* obs_host, int32_t n, floa
  * live weights + TanhGaussDistribution.sample() (utils/act_distribution_cls.py:32-42) in the output layer's epilogue, with
  * the caller's standard-normal draw eps[A] (torch.randn(1, A): it consumes the torch generator exactly as Normal.sample()
  * does, and mean + std * eps is bit for bit what Normal.sample() returns). action[A], logp[1] on the host; MLP policies
- * (DSACT_E_INVALID otherwise -- the caller then takes dsact_policy_forward and samples itself). Synchronous. */
+ * (DSACT_E_INVALID otherwise -- the caller then takes dsact_policy_forward and samples itself). After
+ * dsact_cnn_acting_enable also CNN policies (networks/cnn.py:151-240): obs is one (C, H, W) frame and the call is
+ * dsact_act_sample_batch at n = 1, bit for bit, live or held. Synchronous. */
 int dsact_act_sample(dsact_handle* h, const float* obs_host, const float* eps_host, float* action_host, float* logp_host);
 /* dsact_act_sample for N environments stepped in lockstep (the vectorised sampler, training/hip_vec_sampler.py): the
  * reference's per-step acting (training/off_sampler.py:46-56) for n observation rows at once -- policy(obs) on the live
@@ -470,7 +472,10 @@ int dsact_act_sample(dsact_handle* h, const float* obs_host, const float* eps_ho
  * standard-normal draws eps[n*A] (row i: torch.randn(N, A)[i]). action[n*A] and logp[n] (summed over the action
  * dimensions) on the host. obs[n*O] / eps[n*A] may be host or device pointers (as for dsact_load_batch). A row's results
  * are bitwise independent of n and of its position in the batch. Any n >= 1 (chunked inside the call); MLP policies with
- * act_dim <= 32 (DSACT_E_INVALID for CNN policies). Synchronous. */
+ * act_dim <= 32 (DSACT_E_INVALID for CNN policies that were not enabled). After dsact_cnn_acting_enable a CNN policy
+ * (networks/cnn.py:151-240) is served too: obs holds n frames of O = C*H*W floats in the environment's (C, H, W) layout, and
+ * per chunk of 64 frames the call makes one copy of (frames | eps), the frame ingest, the conv stack, the feature scatter,
+ * the twin trunk and the sampling launch, then one stream synchronisation. Synchronous. */
 int dsact_act_sample_batch(dsact_handle* h, const float* obs, int32_t n, const float* eps, float* action_host,
                            float* logp_host);
 /* The evaluator's acting for N environments stepped in lockstep (training/hip_vec_evaluator.py): the reference's
@@ -491,12 +496,22 @@ int dsact_act_mode_batch(dsact_handle* h, const float* obs, int32_t n, float* ac
  * and ONLY they -- act with that copy: they wait for that event and never for work enqueued after it (held acting runs on a
  * third, non-blocking acting stream; a handle that acts on the host copies the snapshot into a second pinned buffer there).
  * dsact_act_mode_batch and dsact_policy_forward keep acting with the live weights. A second hold replaces the snapshot;
- * dsact_bind_arenas leaves it valid (it is a copy). DSACT_E_INVALID on CNN handles, DSACT_E_STATE under stream capture.
+ * dsact_bind_arenas leaves it valid (it is a copy). DSACT_E_INVALID on CNN handles without dsact_cnn_acting_enable (with it
+ * the snapshot's conv weights feed the held CNN acting forward), DSACT_E_STATE under stream capture.
  * dsact_behaviour_release: back to live acting (the default).
  * dsact_stream_idle: 1 when all work enqueued on the handle's stream has completed, else 0. Never blocks. */
 int dsact_behaviour_hold(dsact_handle* h);
 int dsact_behaviour_release(dsact_handle* h);
 int dsact_stream_idle(dsact_handle* h);
+/* CNN acting, opt-in: lets dsact_act_sample_batch, dsact_act_sample and dsact_behaviour_hold serve a CNN
+ * handle -- the reference's per-step acting (training/off_sampler.py:46-56) with the image policy of networks/cnn.py:151-240,
+ * as a function of (weight base, stream): live on the handle's stream, held on the acting stream with the snapshot's weights.
+ * Allocates the path's own buffers for 64 frames per chunk (pinned frame stage, device frames, pixel-major frames, one
+ * activation buffer per conv layer, feature rows, two trunk buffers, mapped output rows): no allocation stands between a
+ * held acting call and its launches, and nothing an update reads or writes is shared. dsact_policy_forward,
+ * dsact_act_mode_batch and the device-resident forms are unchanged. Idempotent; DSACT_E_INVALID on an MLP handle or with
+ * act_dim > 32. dsact_debug_get "cnn_act" reports the state ("act_fast" is then 1). */
+int dsact_cnn_acting_enable(dsact_handle* h);
 
 /* ---- Device-resident sampling (training/hip_tensor_sampler.py) ----------------------------------------
  * For batched simulators whose observations, rewards and done flags already live on the GPU: one environment step of N
