@@ -45,7 +45,8 @@
 // CNN policies (dsact_cnn_acting_enable; training/off_sampler.py:46-56 on image observations,
 // networks/cnn.py:151-240): k_act_frames below turns a chunk of <= kActFrameCap frames into the pixel-major rows k_conv_fwd
 // reads, the conv stack and k_feat_scatter (dsact_conv.h) make the feature rows, and the launches above run the twin trunk
-// (ActBatchHidden::half) and the sample on them.
+// (ActBatchHidden::half) and the sample on them. The device-resident forms run the same chunks with kDev = true on frames read in
+// place; k_act_frames_u8 is the ingest for byte frames, codes into the coded ring's table.
 #pragma once
 #include "dsact_kernels.h"
 #include "dsact_conv.h"   // fast_div
@@ -92,6 +93,16 @@ struct ActFramesArgs {
   const float* src; float* dst;
   int n, C, HW;
   int chunks;                          // workgroups per frame
+};
+// the same ingest for BYTE frames (dsact_act_sample_device_u8 / dsact_act_mode_device_u8): src[r][c][pix] is
+// one code per element into the coded ring's table, the pixel is book[code] -- the value k_gather_img_coded hands the update for
+// that code, so acting and learning see the same bits
+struct ActFramesU8Args {
+  const uint8_t* src; float* dst;
+  const float* book; int n_codes;
+  int n, C, HW;
+  int chunks;                          // workgroups per frame
+  int grp;                             // C == 3 | 4, HW % 4 == 0 and a 4-byte aligned src: the 4-pixel group form
 };
 
 #ifdef DSACT_ACT_BATCH_DEFINE   // the kernels themselves: csrc/dsact_tu_act_batch.hip; other units see the declarations
@@ -290,6 +301,57 @@ __global__ void __launch_bounds__(256) k_act_frames(ActFramesArgs a) {
     *(f32x4*)(d0 + (size_t)q * 4) = v;
   }
 }
+// k_act_frames for byte frames. The table sits in LDS, padded with 0 beyond n_codes (as k_ring_write_img_coded pads it).
+// grp (CT = 3 | 4 channels): a lane takes a 4-pixel group -- ONE 4-byte load of codes per plane (a wave reads 256 bytes of each
+// plane back to back), CT x 4 table reads, CT 16-byte stores (a wave writes CT KB back to back): the decode and store pattern
+// of k_gather_img_coded<CT>. 16 pixels per lane from one 16-byte load were considered and not taken: the launch moves 4 output
+// bytes per input byte, so a lane of the 4-pixel form already issues CT dwordx4 stores and 4 CT LDS reads per dword load -- the
+// loads are 1 of 1 + 5 CT vector-memory / LDS instructions, and 4x the waves hide the table reads (the reasoning
+// k_ring_write_img_coded records for its search). Otherwise a lane per output quad, its 4 codes read as bytes
+// from <= 4 planes (fast_div by C). Vector loads and stores only; every access is inside frame r < n
+template <int CT>
+__device__ __forceinline__ void act_frames_u8_groups(const ActFramesU8Args& a, const float* tab, const uint8_t* so, float* d0, int ck) {
+  const int nq = a.HW >> 2;
+  for (int q = ck * 256 + (int)threadIdx.x; q < nq; q += a.chunks * 256) {
+    uint32_t w[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) w[c] = *(const uint32_t*)(so + (size_t)c * a.HW + 4 * q);
+#pragma unroll
+    for (int j = 0; j < CT; ++j) {     // output quad j holds elements 4j .. 4j+3 of (pixel e, channel c) = e*CT + c
+      f32x4 v;
+#pragma unroll
+      for (int e4 = 0; e4 < 4; ++e4) {
+        const int o = 4 * j + e4;
+        v[e4] = tab[(w[o % CT] >> (8 * (o / CT))) & 255u];
+      }
+      *(f32x4*)(d0 + (size_t)q * (4 * CT) + 4 * j) = v;
+    }
+  }
+}
+__global__ void __launch_bounds__(256) k_act_frames_u8(ActFramesU8Args a) {
+  __shared__ float tab[256];
+  tab[threadIdx.x] = (int)threadIdx.x < a.n_codes ? a.book[threadIdx.x] : 0.f;
+  __syncthreads();
+  const int r = (int)blockIdx.x / a.chunks, ck = (int)blockIdx.x - r * a.chunks;
+  if (r >= a.n) return;
+  const size_t O = (size_t)a.C * a.HW;
+  const uint8_t* so = a.src + (size_t)r * O;
+  float* d0 = a.dst + (size_t)r * O;
+  if (a.grp && a.C == 3) { act_frames_u8_groups<3>(a, tab, so, d0, ck); return; }
+  if (a.grp && a.C == 4) { act_frames_u8_groups<4>(a, tab, so, d0, ck); return; }
+  const int n4 = (int)(O >> 2);
+  const float inv_c = 1.0f / (float)a.C;
+  for (int q = ck * 256 + (int)threadIdx.x; q < n4; q += a.chunks * 256) {
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int o = q * 4 + e;
+      const int pix = fast_div(o, a.C, inv_c), c = o - pix * a.C;
+      v[e] = tab[so[(size_t)c * a.HW + pix]];
+    }
+    *(f32x4*)(d0 + (size_t)q * 4) = v;
+  }
+}
 template __global__ void k_act_batch_out<false, false>(ActBatchOut);
 template __global__ void k_act_batch_out<true, false>(ActBatchOut);
 template __global__ void k_act_batch_out<false, true>(ActBatchOut);
@@ -297,6 +359,7 @@ template __global__ void k_act_batch_out<true, true>(ActBatchOut);
 #else
 __global__ void k_act_batch_hidden(ActBatchHidden a);
 __global__ void k_act_frames(ActFramesArgs a);
+__global__ void k_act_frames_u8(ActFramesU8Args a);
 template <bool kMode, bool kDev>
 __global__ void k_act_batch_out(ActBatchOut a);
 extern template __global__ void k_act_batch_out<false, false>(ActBatchOut);

@@ -301,10 +301,13 @@ struct dsact_handle : BatchBufs {
   // pinned staging of a chunk's (frames | eps), its device copy, k_act_frames' pixel-major output, one activation buffer per
   // conv layer and the feature rows; ab_h and ab_out_* above serve its trunk (kActFrameCap rows on a CNN handle). They are the
   // path's own -- aimg / aact / Xact stay the stand-alone forward's on `stream`, and nothing an update launch reads or writes
-  // is touched. ONE set serves live calls (on `stream`) and held calls (on act_stream): every entry point that uses it
-  // synchronises its own stream before it returns and CNN handles have no device-resident no-wait form, so two acting calls
-  // never have launches in flight at once
+  // is touched. ONE set serves live calls (on `stream`) and held calls (on act_stream): the host-row entry points synchronise
+  // their own stream before they return; the device-resident forms wait for nothing, run on `stream`
+  // only, and record ca_dev_ev behind their last launch -- a held call makes act_stream wait for it before its first launch,
+  // so two acting calls never have launches on the set at once
   bool cnn_act = false;
+  hipEvent_t ca_dev_ev = nullptr;        // recorded on `stream` behind the last launch of a device-resident CNN acting call
+  bool ca_dev_pending = false;           // ... which has been recorded at least once
   float* ca_stage = nullptr; float* ca_frames = nullptr; float* ca_img = nullptr;
   float* ca_act[kMaxConv] = {}; float* ca_feat = nullptr;
   // device-resident sampling (dsact_act_sample_device / dsact_buffer_add_device)
@@ -3577,6 +3580,7 @@ int dsact_destroy(dsact_handle* h) {
   if (h->beh_dev) hipFree(h->beh_dev);
   if (h->beh_host) hipHostFree(h->beh_host);
   if (h->beh_ev) hipEventDestroy(h->beh_ev);
+  if (h->ca_dev_ev) hipEventDestroy(h->ca_dev_ev);
   if (h->beh_host_ev) hipEventDestroy(h->beh_host_ev);
   free(h->act_buf);
   delete h->act_pool;
@@ -3963,32 +3967,81 @@ static int check_handoff_counted(dsact_handle* h) {
   return rc;
 }
 
-int dsact_buffer_add_device(dsact_handle* h, int64_t n, const float* obs, const float* act, const float* rew, const float* obs2,
-                            const uint8_t* terminated, const uint8_t* truncated, const float* logp, double reward_scale) {
-  if (!h || n < 0 || !obs || !act || !rew || !obs2 || !terminated || !truncated || !logp) return DSACT_E_INVALID;
+// the body of dsact_buffer_add_device and dsact_buffer_add_device_u8. The fp32 MLP ring: one k_ring_commit launch. An enabled CNN
+// handle (dsact_cnn_acting_enable): the two image columns go through k_ring_write_img (fp32 ring),
+// enqueue_ring_encode (fp32 frames into a coded ring) or k_ring_commit_codes (u8: byte frames that are codes already), the
+// narrow columns through k_ring_commit with the observation part switched off (O = 0, as dsact_buffer_add switches k_ring_write's)
+static int ring_add_device(dsact_handle* h, const char* who, int64_t n, const void* obs, bool u8, const float* act, const float* rew,
+                           const void* obs2, const uint8_t* terminated, const uint8_t* truncated, const float* logp, double reward_scale) {
   if (!has_ring(h)) return fail(h, DSACT_E_STATE, "buffer not created");
-  if (h->rb_code) return fail(h, DSACT_E_INVALID, "dsact_buffer_add_device serves the fp32 MLP ring (coded rings: dsact_buffer_add)");
-  if (h->cnn) return fail(h, DSACT_E_INVALID, "dsact_buffer_add_device serves the fp32 MLP ring (image rings: dsact_buffer_add)");
-  if (n > h->cap) return fail(h, DSACT_E_INVALID, "dsact_buffer_add_device: n = %lld exceeds the capacity %lld", (long long)n, (long long)h->cap);
+  if (!h->cnn_act) {
+    if (h->rb_code) return fail(h, DSACT_E_INVALID, "%s serves the fp32 MLP ring (coded rings: dsact_buffer_add)", who);
+    if (h->cnn) return fail(h, DSACT_E_INVALID, "%s serves the fp32 MLP ring (image rings: dsact_buffer_add)", who);
+    if (u8) return fail(h, DSACT_E_INVALID, "%s serves CNN handles after dsact_cnn_acting_enable", who);
+  }
+  if (u8 && !h->rb_code)
+    return fail(h, DSACT_E_STATE, "%s: a byte frame holds codes into the ring's codebook and this handle has no coded ring "
+                                  "(hip_obs_codebook / dsact_buffer_create_coded)", who);
+  if (h->rb_code) TRY(check_codes(h));   // (a mapped host word: no sync)
+  if (n > h->cap) return fail(h, DSACT_E_INVALID, "%s: n = %lld exceeds the capacity %lld", who, (long long)n, (long long)h->cap);
   if (n == 0) return DSACT_OK;
   HIPCHK(h, hipSetDevice(h->device));
   const void* ptrs[7] = {obs, act, rew, obs2, terminated, truncated, logp};
   for (const void* p : ptrs)
     if (!on_handle_gpu(h, p))
-      return fail(h, DSACT_E_INVALID, "dsact_buffer_add_device takes device pointers on the handle's GPU (host rows: dsact_buffer_add)");
+      return fail(h, DSACT_E_INVALID, "%s takes device pointers on the handle's GPU (host rows: dsact_buffer_add)", who);
+  if (h->cnn && !u8 && !h->rb_code && ((uintptr_t)obs % 16 || (uintptr_t)obs2 % 16))   // (k_ring_write_img moves 16 bytes per lane)
+    return fail(h, DSACT_E_INVALID, "%s: image rows must be 16-byte aligned", who);
   TRY(check_handoff_counted(h));
   RingCommitArgs a;
-  a.s_obs = obs; a.s_act = act; a.s_rew = rew; a.s_obs2 = obs2; a.s_term = terminated; a.s_trunc = truncated; a.s_logp = logp;
+  a.s_obs = (const float*)obs; a.s_act = act; a.s_rew = rew; a.s_obs2 = (const float*)obs2; a.s_term = terminated; a.s_trunc = truncated;
+  a.s_logp = logp;
   a.rb_obs = h->rb_obs; a.rb_obs2 = h->rb_obs2; a.rb_act = h->rb_act; a.rb_rew = h->rb_rew; a.rb_done = h->rb_done; a.rb_logp = h->rb_logp;
   a.ptr = h->ptr; a.cap = h->cap; a.n = (int)n; a.O = h->O; a.A = h->A;
   a.wide = (h->O % 4 == 0) && ((uintptr_t)obs % 16 == 0) && ((uintptr_t)obs2 % 16 == 0) && ((uintptr_t)h->rb_obs % 16 == 0) &&
            ((uintptr_t)h->rb_obs2 % 16 == 0);
   a.reward_scale = (float)reward_scale;
+  if (h->cnn) {
+    if (u8) {
+      CodesCommitArgs e;
+      e.s_obs = (const uint8_t*)obs; e.s_obs2 = (const uint8_t*)obs2;
+      e.code0 = h->rb_code; e.code1 = h->rb_code + (size_t)h->cap * h->O;
+      e.n_codes = h->n_codes; e.miss = h->code_miss; e.miss_flag = h->miss_dev;
+      e.ptr = h->ptr; e.cap = h->cap; e.n = (int)n; e.O = h->O;
+      e.wide = (h->O % 16 == 0) && ((uintptr_t)obs % 16 == 0) && ((uintptr_t)obs2 % 16 == 0);
+      const long long per_row = e.wide ? h->O / 16 : h->O;
+      const unsigned gx = (unsigned)std::min<long long>((per_row + kThreads - 1) / kThreads, 64);
+      const unsigned rows = (unsigned)(n < 65535 ? n : 65535);   // (grid y limit: the kernel strides over the rest)
+      TRY(launch(h, "ring_commit_codes", k_ring_commit_codes, dim3(gx, rows, 2), dim3(kThreads), 0, e));
+    } else if (h->rb_code) {
+      TRY(enqueue_ring_encode(h, (const float*)obs, (const float*)obs2, h->ptr, n));
+    } else {
+      const size_t O = (size_t)h->O;
+      for (int64_t s = 0; s < n; s += 65535) {   // (k_ring_write_img takes one row per grid y)
+        ImgScatterArgs w;
+        w.s_obs = (const float*)obs + (size_t)s * O; w.s_obs2 = (const float*)obs2 + (size_t)s * O; w.rb_obs = h->rb_obs; w.rb_obs2 = h->rb_obs2;
+        w.ptr = (h->ptr + s) % h->cap; w.cap = h->cap; w.n = (int)std::min<int64_t>(n - s, 65535); w.O = h->O;
+        TRY(launch(h, "ring_write_img", k_ring_write_img, dim3(8, (unsigned)w.n), dim3(kThreads), 0, w));
+      }
+    }
+    a.O = 0;
+  }
   TRY(launch(h, "ring_commit", k_ring_commit, dim3((unsigned)((n + 3) / 4)), dim3(kThreads), 0, a));
   h->ptr = (h->ptr + n) % h->cap;                           // replay_buffer.py:78-79, n times
   h->size = h->size + n > h->cap ? h->cap : h->size + n;
   h->ring_commit_rows += (unsigned long long)n;
   return DSACT_OK;
+}
+
+int dsact_buffer_add_device(dsact_handle* h, int64_t n, const float* obs, const float* act, const float* rew, const float* obs2,
+                            const uint8_t* terminated, const uint8_t* truncated, const float* logp, double reward_scale) {
+  if (!h || n < 0 || !obs || !act || !rew || !obs2 || !terminated || !truncated || !logp) return DSACT_E_INVALID;
+  return ring_add_device(h, "dsact_buffer_add_device", n, obs, false, act, rew, obs2, terminated, truncated, logp, reward_scale);
+}
+int dsact_buffer_add_device_u8(dsact_handle* h, int64_t n, const uint8_t* obs, const float* act, const float* rew, const uint8_t* obs2,
+                               const uint8_t* terminated, const uint8_t* truncated, const float* logp, double reward_scale) {
+  if (!h || n < 0 || !obs || !act || !rew || !obs2 || !terminated || !truncated || !logp) return DSACT_E_INVALID;
+  return ring_add_device(h, "dsact_buffer_add_device_u8", n, obs, true, act, rew, obs2, terminated, truncated, logp, reward_scale);
 }
 
 // ---- ring snapshots: the ring's stored form out of and into HBM, its cursor, and an integrity digest ----
@@ -5595,19 +5648,29 @@ static FeatArgs act_feat_args(const dsact_handle* h, const float* act, float* X,
 // policy(frames) + the output form for one chunk of m <= kActFrameCap frames in the environment's (C, H, W) layout, enqueued on
 // `stream` -- k_act_frames, one k_conv_fwd per conv layer reading its weights at `base`, k_feat_scatter into the feature rows,
 // then the twin trunk and the output launch of enqueue_act_batch. Everything in between lives in the path's own buffers
-// (dsact_cnn_acting_enable). base, o and form as in enqueue_act_batch
-static int enqueue_act_cnn(dsact_handle* h, const float* frames_dev, int m, const float* base, hipStream_t stream, ActBatchOut o, int form) {
+// (dsact_cnn_acting_enable). base, o and form as in enqueue_act_batch. u8: the frames are bytes, codes into the coded ring's table
+// (k_act_frames_u8) -- only the ingest differs, everything behind it is the fp32 path's
+static int enqueue_act_cnn(dsact_handle* h, const void* frames_dev, bool u8, int m, const float* base, hipStream_t stream, ActBatchOut o,
+                           int form) {
   auto launch_act = [&](const char* name, auto kernel, dim3 grid, const auto& a) {
     return stream == h->stream ? launch(h, name, kernel, grid, dim3(kThreads), 0, a) : launch_on(h, stream, name, kernel, grid, dim3(kThreads), 0, a);
   };
-  ActFramesArgs fr;
-  fr.src = frames_dev; fr.dst = h->ca_img; fr.n = m; fr.C = h->cfg.img_c; fr.HW = h->cfg.img_h * h->cfg.img_w;
-  fr.chunks = 8;   // (workgroups per frame as enqueue_gather_img chooses them)
-  if (fr.C == 3 && fr.HW % 4 == 0) {
-    const int per = (fr.HW / 4 + kThreads - 1) / kThreads;
-    fr.chunks = per < 1 ? 1 : (per > 16 ? 16 : per);
+  const int C = h->cfg.img_c, HW = h->cfg.img_h * h->cfg.img_w;
+  const int per = (HW / 4 + kThreads - 1) / kThreads;
+  const int group_chunks = per < 1 ? 1 : (per > 16 ? 16 : per);   // (workgroups per frame as enqueue_gather_img chooses them)
+  if (u8) {
+    ActFramesU8Args fr;
+    fr.src = (const uint8_t*)frames_dev; fr.dst = h->ca_img; fr.book = h->code_book; fr.n_codes = h->n_codes;
+    fr.n = m; fr.C = C; fr.HW = HW;
+    fr.grp = (C == 3 || C == 4) && HW % 4 == 0 && (uintptr_t)frames_dev % 4 == 0;
+    fr.chunks = fr.grp ? group_chunks : 8;
+    TRY(launch_act("act_frames_u8", k_act_frames_u8, dim3((unsigned)(m * fr.chunks)), fr));
+  } else {
+    ActFramesArgs fr;
+    fr.src = (const float*)frames_dev; fr.dst = h->ca_img; fr.n = m; fr.C = C; fr.HW = HW;
+    fr.chunks = (C == 3 && HW % 4 == 0) ? group_chunks : 8;
+    TRY(launch_act("act_frames", k_act_frames, dim3((unsigned)(m * fr.chunks)), fr));
   }
-  TRY(launch_act("act_frames", k_act_frames, dim3((unsigned)(m * fr.chunks)), fr));
   for (int j = 0; j < h->n_conv; ++j) {
     const ConvStageArgs a = act_conv_args(h, j, base, j == 0 ? h->ca_img : h->ca_act[j - 1], h->ca_act[j], m);
     TRY(launch_act("act_conv", k_conv_fwd, dim3(conv_fwd_grid(a.n_items)), a));
@@ -5627,6 +5690,9 @@ static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const flo
   HIPCHK(h, hipSetDevice(h->device));
   TRY(check_handoff(h));
   if (stream != h->stream) HIPCHK(h, hipStreamWaitEvent(stream, h->beh_ev, 0));
+  // (a device-resident CNN acting call may still have launches on the path's buffers on h->stream: the acting stream waits
+  // for the event behind its last launch, the host does not)
+  if (stream != h->stream && h->ca_dev_pending) HIPCHK(h, hipStreamWaitEvent(stream, h->ca_dev_ev, 0));
   // an enabled CNN handle: rows are frames of O = C * H * W floats, chunks of kActFrameCap through the path's own stage
   const bool cnn = h->cnn_act;
   const int O = h->O, A = h->A, R = cnn ? kActFrameCap : kActBatchCap;
@@ -5654,7 +5720,7 @@ static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const flo
     ActBatchOut o = {};
     o.eps = mode ? nullptr : in_eps;
     o.action = h->ab_out_dev; o.logp = mode ? nullptr : h->ab_out_dev + (size_t)m * A;
-    if (cnn) TRY(enqueue_act_cnn(h, in_obs, m, base, stream, o, mode ? kActOutMode : kActOutSample));
+    if (cnn) TRY(enqueue_act_cnn(h, in_obs, false, m, base, stream, o, mode ? kActOutMode : kActOutSample));
     else TRY(enqueue_act_batch(h, in_obs, O, m, base, stream, o, mode ? kActOutMode : kActOutSample));
     HIPCHK(h, hipStreamSynchronize(stream));
     (mode ? h->ab_mode_calls : h->ab_calls)++;
@@ -5747,32 +5813,66 @@ int dsact_set_act_rng(dsact_handle* h, uint64_t seed) {
   return DSACT_OK;
 }
 
-// the two device-resident forms: obs is read IN PLACE (no staging copy), the results land in the caller's device arrays, and
+// the device-resident forms: obs is read IN PLACE (no staging copy), the results land in the caller's device arrays, and
 // nothing waits -- per chunk of kActBatchCap rows the launches of enqueue_act_batch on the handle's stream (the live weights,
-// behind every enqueued update; also under a behaviour hold)
-int dsact_act_sample_device(dsact_handle* h, const float* obs_dev, int32_t n, const float* eps_dev, int64_t step,
-                            float* action_dev, float* clipped_dev, float* logp_dev) {
-  if (!h || !obs_dev || !action_dev || !clipped_dev || !logp_dev || n < 1) return DSACT_E_INVALID;
-  TRY(act_batch_ready(h, "dsact_act_sample_device", "dsact_policy_forward"));
-  if (!eps_dev && h->act_seed == 0)
+// behind every enqueued update; also under a behaviour hold). An enabled CNN handle (dsact_cnn_acting_enable; DESIGN.md section
+// 20): obs is n frames of O = C*H*W elements in the environment's (C, H, W) layout -- floats, or with u8 bytes that are codes
+// into the coded ring's table --, chunks of kActFrameCap frames through enqueue_act_cnn, and ca_dev_ev recorded behind the
+// last launch (act_batch_gpu: a held call waits for it on the acting stream).
+// mode: dist.mode() (action only) instead of the sample. who / host_form name the entry point and its host-row counterpart
+static int act_device(dsact_handle* h, const char* who, const char* host_form, const char* cnn_route, const void* obs_dev, bool u8,
+                      int32_t n, const float* eps_dev, int64_t step, float* action_dev, float* clipped_dev, float* logp_dev, bool mode) {
+  TRY(act_batch_ready(h, who, h->cnn_act ? nullptr : cnn_route));
+  if (u8 && !h->cnn_act) return fail(h, DSACT_E_INVALID, "%s serves CNN policies after dsact_cnn_acting_enable", who);
+  if (u8 && !h->rb_code)
+    return fail(h, DSACT_E_STATE, "%s: a byte frame holds codes into the ring's codebook and this handle has no coded ring "
+                                  "(hip_obs_codebook / dsact_buffer_create_coded)", who);
+  if (!mode && !eps_dev && h->act_seed == 0)
     return fail(h, DSACT_E_STATE, "eps == NULL draws the noise in the kernel: call dsact_set_act_rng with a non-zero seed first");
   HIPCHK(h, hipSetDevice(h->device));
-  if (!on_handle_gpu(h, obs_dev) || (eps_dev && !on_handle_gpu(h, eps_dev)) || !on_handle_gpu(h, action_dev) ||
-      !on_handle_gpu(h, clipped_dev) || !on_handle_gpu(h, logp_dev))
-    return fail(h, DSACT_E_INVALID, "dsact_act_sample_device takes device pointers on the handle's GPU (host rows: dsact_act_sample_batch)");
+  bool dev = on_handle_gpu(h, obs_dev) && on_handle_gpu(h, action_dev);
+  if (!mode) dev = dev && (!eps_dev || on_handle_gpu(h, eps_dev)) && on_handle_gpu(h, clipped_dev) && on_handle_gpu(h, logp_dev);
+  if (!dev) return fail(h, DSACT_E_INVALID, "%s takes device pointers on the handle's GPU (host rows: %s)", who, host_form);
+  if (h->cnn_act && !u8 && (uintptr_t)obs_dev % 16)   // (k_act_frames reads 16 bytes per lane, in place)
+    return fail(h, DSACT_E_INVALID, "%s: fp32 frames must be 16-byte aligned", who);
   TRY(check_handoff_counted(h));
   TRY(alloc_act_batch(h));   // (the hidden layers' two activation buffers; the first call allocates)
-  const int O = h->O, A = h->A, R = kActBatchCap;
+  const bool cnn = h->cnn_act;
+  const int O = h->O, A = h->A, R = cnn ? kActFrameCap : kActBatchCap;
+  const size_t elem = u8 ? 1 : sizeof(float);
+  const int form = mode ? kActOutModeDev : kActOutSampleDev;
   for (int s = 0; s < n; s += R) {
     const int m = n - s < R ? n - s : R;
     ActBatchOut o = {};
-    o.eps = eps_dev ? eps_dev + (size_t)s * A : nullptr;
-    o.action = action_dev + (size_t)s * A; o.logp = logp_dev + s; o.clipped = clipped_dev + (size_t)s * A;
-    o.seed = h->act_seed; o.step = step; o.row0 = s;
-    TRY(enqueue_act_batch(h, obs_dev + (size_t)s * O, O, m, net_params(h, N_POL), h->stream, o, kActOutSampleDev));
-    h->act_dev_calls++;
+    o.action = action_dev + (size_t)s * A;
+    if (!mode) {
+      o.eps = eps_dev ? eps_dev + (size_t)s * A : nullptr;
+      o.logp = logp_dev + s; o.clipped = clipped_dev + (size_t)s * A;
+      o.seed = h->act_seed; o.step = step; o.row0 = s;
+    }
+    const char* rows = (const char*)obs_dev + (size_t)s * O * elem;
+    if (cnn) TRY(enqueue_act_cnn(h, rows, u8, m, net_params(h, N_POL), h->stream, o, form));
+    else TRY(enqueue_act_batch(h, (const float*)rows, O, m, net_params(h, N_POL), h->stream, o, form));
+    (mode ? h->act_mode_dev_calls : h->act_dev_calls)++;
+  }
+  if (cnn) {
+    HIPCHK(h, hipEventRecord(h->ca_dev_ev, h->stream));
+    h->ca_dev_pending = true;
   }
   return check_handoff_counted(h);
+}
+
+int dsact_act_sample_device(dsact_handle* h, const float* obs_dev, int32_t n, const float* eps_dev, int64_t step,
+                            float* action_dev, float* clipped_dev, float* logp_dev) {
+  if (!h || !obs_dev || !action_dev || !clipped_dev || !logp_dev || n < 1) return DSACT_E_INVALID;
+  return act_device(h, "dsact_act_sample_device", "dsact_act_sample_batch", "dsact_policy_forward", obs_dev, false, n, eps_dev, step,
+                    action_dev, clipped_dev, logp_dev, false);
+}
+int dsact_act_sample_device_u8(dsact_handle* h, const uint8_t* frames_dev, int32_t n, const float* eps_dev, int64_t step,
+                               float* action_dev, float* clipped_dev, float* logp_dev) {
+  if (!h || !frames_dev || !action_dev || !clipped_dev || !logp_dev || n < 1) return DSACT_E_INVALID;
+  return act_device(h, "dsact_act_sample_device_u8", "dsact_act_sample_batch", "dsact_policy_forward", frames_dev, true, n, eps_dev,
+                    step, action_dev, clipped_dev, logp_dev, false);
 }
 
 // ---- device-resident evaluation --------------------------------------------------------------------
@@ -5780,21 +5880,13 @@ int dsact_act_sample_device(dsact_handle* h, const float* obs_dev, int32_t n, co
 // the launches of dsact_act_sample_device with the mode epilogue
 int dsact_act_mode_device(dsact_handle* h, const float* obs_dev, int32_t n, float* action_dev) {
   if (!h || !obs_dev || !action_dev || n < 1) return DSACT_E_INVALID;
-  TRY(act_batch_ready(h, "dsact_act_mode_device", "dsact_act_mode_batch"));
-  HIPCHK(h, hipSetDevice(h->device));
-  if (!on_handle_gpu(h, obs_dev) || !on_handle_gpu(h, action_dev))
-    return fail(h, DSACT_E_INVALID, "dsact_act_mode_device takes device pointers on the handle's GPU (host rows: dsact_act_mode_batch)");
-  TRY(check_handoff_counted(h));
-  TRY(alloc_act_batch(h));   // (the hidden layers' two activation buffers; the first call allocates)
-  const int O = h->O, A = h->A, R = kActBatchCap;
-  for (int s = 0; s < n; s += R) {
-    const int m = n - s < R ? n - s : R;
-    ActBatchOut o = {};
-    o.action = action_dev + (size_t)s * A;
-    TRY(enqueue_act_batch(h, obs_dev + (size_t)s * O, O, m, net_params(h, N_POL), h->stream, o, kActOutModeDev));
-    h->act_mode_dev_calls++;
-  }
-  return check_handoff_counted(h);
+  return act_device(h, "dsact_act_mode_device", "dsact_act_mode_batch", "dsact_act_mode_batch", obs_dev, false, n, nullptr, 0, action_dev,
+                    nullptr, nullptr, true);
+}
+int dsact_act_mode_device_u8(dsact_handle* h, const uint8_t* frames_dev, int32_t n, float* action_dev) {
+  if (!h || !frames_dev || !action_dev || n < 1) return DSACT_E_INVALID;
+  return act_device(h, "dsact_act_mode_device_u8", "dsact_act_mode_batch", "dsact_act_mode_batch", frames_dev, true, n, nullptr, 0,
+                    action_dev, nullptr, nullptr, true);
 }
 
 static EvalCommitArgs eval_args(const dsact_handle* h) {
@@ -6025,6 +6117,7 @@ int dsact_cnn_acting_enable(dsact_handle* h) {
     HIPCHK(h, hipMemset(h->ca_feat, 0, R * h->ldx * sizeof(float)));   // (the columns behind the features are never written)
   }
   TRY(alloc_act_batch(h));   // the trunk's two activation buffers and the mapped output rows
+  if (!h->ca_dev_ev) HIPCHK(h, hipEventCreateWithFlags(&h->ca_dev_ev, hipEventDisableTiming));   // 
   h->cnn_act = true;
   return DSACT_OK;
 }

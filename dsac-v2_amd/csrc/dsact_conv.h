@@ -1399,6 +1399,53 @@ __global__ void __launch_bounds__(kThreads) k_ring_write_img_coded(CodedScatterA
   }
 }
 
+// k_ring_commit_codes: the image columns of dsact_buffer_add_device_u8 -- n transitions whose frames are
+// already codes (one byte per element, device rows, row i at i * O) go straight to code rows (ptr + i) % cap of both columns:
+// no widening to fp32 and no search. grid (x chunks, rows, image) like the encoder. `wide` (O % 16 == 0 and 16-byte aligned
+// sources; code rows are then 16-byte aligned too, the columns being allocation-aligned): a lane moves 16 codes per access,
+// else one byte. A byte >= n_codes names no table entry: it is a miss, recorded through record_code_miss as the encoder records a
+// value that is not in the table (count, the first miss -- the byte as a float -- and its ring row, the mapped flag). n <= cap, so
+// no two transitions of a launch share a ring row; every access is inside source row i < n and ring row dst < cap
+struct CodesCommitArgs {
+  const uint8_t* s_obs; const uint8_t* s_obs2;
+  uint8_t* code0; uint8_t* code1;
+  int n_codes; CodeMiss* miss; int* miss_flag;
+  long long ptr, cap; int n; long long O;
+  int wide;
+};
+__global__ void __launch_bounds__(kThreads) k_ring_commit_codes(CodesCommitArgs a) {
+  const int img = blockIdx.z;
+  const unsigned nc = (unsigned)a.n_codes;
+  const long long nq = a.wide ? a.O >> 4 : a.O;
+  for (int i = blockIdx.y; i < a.n; i += gridDim.y) {
+    const long long dst = (a.ptr + i) % a.cap;
+    const uint8_t* s = (img ? a.s_obs2 : a.s_obs) + (size_t)i * a.O;
+    uint8_t* d = (img ? a.code1 : a.code0) + (size_t)dst * a.O;
+    for (long long q = (long long)blockIdx.x * kThreads + threadIdx.x; q < nq; q += (long long)gridDim.x * kThreads) {
+      unsigned miss = 0, bad = 0;
+      if (a.wide) {
+        const uint4 v = *(const uint4*)(s + 16 * q);
+        *(uint4*)(d + 16 * q) = v;
+        if (nc < 256u) {
+          const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const unsigned b = (w[k] >> (8 * e)) & 255u;
+              if (b >= nc) { bad = miss ? bad : b; ++miss; }
+            }
+        }
+      } else {
+        const unsigned b = s[q];
+        d[q] = (uint8_t)b;
+        if (b >= nc) { bad = b; miss = 1; }
+      }
+      if (miss) record_code_miss(a.miss, a.miss_flag, (float)bad, dst, miss);
+    }
+  }
+}
+
 struct ImgCodedGatherArgs {
   ImgGatherArgs g;              // everything but g.rb_obs / g.rb_obs2 (unused)
   const uint8_t* code0; const uint8_t* code1; const float* book; int n_codes;

@@ -133,6 +133,9 @@ SYMBOLS = [
     ("dsact_act_sample_device", C.c_int, [_P, _P, C.c_int32, _P, C.c_int64, _P, _P, _P]),
     ("dsact_buffer_add_device", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_double]),
     ("dsact_act_mode_device", C.c_int, [_P, _P, C.c_int32, _P]),
+    ("dsact_act_sample_device_u8", C.c_int, [_P, _P, C.c_int32, _P, C.c_int64, _P, _P, _P]),
+    ("dsact_act_mode_device_u8", C.c_int, [_P, _P, C.c_int32, _P]),
+    ("dsact_buffer_add_device_u8", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_double]),
     ("dsact_eval_begin", C.c_int, [_P, C.c_int32, C.c_int32]),
     ("dsact_eval_commit", C.c_int, [_P, _P, _P, _P, _P]),
     ("dsact_eval_poll", C.c_int, [_P, _P]),

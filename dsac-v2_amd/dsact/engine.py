@@ -291,6 +291,7 @@ class DsactEngine:
             self._chk(self._lib.dsact_buffer_create_coded(self._h, int(capacity), _ffi.fptr(book), int(book.shape[0])))
         self.buffer_capacity = int(capacity)
         self.buffer_coded = codebook is not None
+        self.codebook = None if codebook is None else book     # (byte frames of a tensor environment decode through it)
 
     # ---- ring snapshots: stored form out of / into HBM, the cursor, the device-side digest. Synchronous. ---
     ring_digest_reference = staticmethod(ring_digest_reference)
@@ -760,25 +761,44 @@ class DsactEngine:
         f32 = (self.torch.float32,)
         n = self._rows(obs)
         O, A = self.obs_dim, self.act_dim
-        po = self._dev(obs, (n, O), f32, "obs")
+        po, u8 = self._frames(obs, n, "obs")
         pe = self._dev(eps, (n, A), f32, "eps") if eps is not None else None
         pa, pc, pl = self._dev(action, (n, A), f32, "action"), self._dev(clipped, (n, A), f32, "clipped"), self._dev(logp, (n,), f32, "logp")
-        rc = self._lib.dsact_act_sample_device(self._h, po, n, pe, int(step), pa, pc, pl)
+        fn = self._lib.dsact_act_sample_device_u8 if u8 else self._lib.dsact_act_sample_device
+        rc = fn(self._h, po, n, pe, int(step), pa, pc, pl)
         if rc != 0:
             self._chk(rc)
+
+    def _frames(self, t, n, name):
+        """(address, is_uint8) of the observation rows of a device-resident call: [n, O] float32, and on a CNN engine with cnn_act
+         also [n, C, H, W] rows and uint8 tensors of either shape -- byte frames, codes into the coded
+        ring's codebook (the library refuses them on any other handle)"""
+        torch = self.torch
+        O = self.obs_dim
+        shape, dtypes = (n, O), (torch.float32,)
+        if self.conv_type and self.cnn_act:
+            dtypes = (torch.float32, torch.uint8)
+            if hasattr(t, "shape") and len(t.shape) == 4:
+                shape = (n,) + tuple(self.obs_shape)
+        return self._dev(t, shape, dtypes, name), getattr(t, "dtype", None) == torch.uint8
 
     def buffer_add_device(self, obs, act, rew, obs2, terminated, truncated, logp, reward_scale=1.0):
         """dsact_buffer_add_device: n transitions from device tensors into ring rows (ptr + i) % capacity; rew is stored as
         rew * reward_scale, done as terminated & ~truncated. obs / obs2 [n, O], act [n, A], rew / logp [n] float32,
-        terminated / truncated [n] bool (or uint8). Asynchronous on the engine's stream."""
+        terminated / truncated [n] bool (or uint8). Asynchronous on the engine's stream. A CNN engine with cnn_act takes image
+        rows as [n, O] or [n, C, H, W], float32 or -- with a coded ring -- uint8 codes (obs and obs2 in the same dtype)."""
         torch = self.torch
         f32, flag = (torch.float32,), (torch.bool, torch.uint8)
         n = self._rows(rew)
-        O, A = self.obs_dim, self.act_dim
-        ptrs = [self._dev(obs, (n, O), f32, "obs"), self._dev(act, (n, A), f32, "act"), self._dev(rew, (n,), f32, "rew"),
-                self._dev(obs2, (n, O), f32, "obs2"), self._dev(terminated, (n,), flag, "terminated"),
+        A = self.act_dim
+        (po, u8), (po2, u8_2) = self._frames(obs, n, "obs"), self._frames(obs2, n, "obs2")
+        if u8 != u8_2:
+            raise ValueError("obs and obs2 must have the same dtype (got %s and %s)" % (obs.dtype, obs2.dtype))
+        ptrs = [po, self._dev(act, (n, A), f32, "act"), self._dev(rew, (n,), f32, "rew"),
+                po2, self._dev(terminated, (n,), flag, "terminated"),
                 self._dev(truncated, (n,), flag, "truncated"), self._dev(logp, (n,), f32, "logp")]
-        self._chk(self._lib.dsact_buffer_add_device(self._h, n, *ptrs, float(reward_scale)))
+        fn = self._lib.dsact_buffer_add_device_u8 if u8 else self._lib.dsact_buffer_add_device
+        self._chk(fn(self._h, n, *ptrs, float(reward_scale)))
         self.rows_added += n
 
     # ---- device-resident evaluation (DESIGN.md section 16): launches only, one wait in eval_poll ------------------------------
@@ -789,8 +809,8 @@ class DsactEngine:
         `torch.cuda.stream(engine.torch_stream)`."""
         f32 = (self.torch.float32,)
         n = self._rows(obs)
-        po, pa = self._dev(obs, (n, self.obs_dim), f32, "obs"), self._dev(action, (n, self.act_dim), f32, "action")
-        rc = self._lib.dsact_act_mode_device(self._h, po, n, pa)
+        (po, u8), pa = self._frames(obs, n, "obs"), self._dev(action, (n, self.act_dim), f32, "action")
+        rc = (self._lib.dsact_act_mode_device_u8 if u8 else self._lib.dsact_act_mode_device)(self._h, po, n, pa)
         if rc != 0:
             self._chk(rc)
 

@@ -121,16 +121,19 @@ _TENSOR_CLASSES = {"hip_tensor_env_sampler": ("hip_vec_off_sampler", "dsact_act_
                    "hip_tensor_env_evaluator": ("hip_eval_env_num", "dsact_act_mode_device")}
 
 
-def require_tensor_engine(who, networks, action_type, env):
-    """the engine behind the ATTACHED MLP policy; every other setup is refused"""
+def require_tensor_engine(who, networks, action_type, env, hip_cnn_act=False):
+    """the engine behind the ATTACHED MLP policy -- or, for a class that was given `hip_cnn_act=True`, behind a CNN policy whose
+    engine has the CNN acting path enabled (DsactEngine.cnn_act; DESIGN.md section 20: the kwarg is read first, the attribute
+    only when it is set); every other setup is refused"""
     instead, call = _TENSOR_CLASSES[who]
     pol = getattr(networks, "policy", None)
     eng = getattr(pol, "_engine", None)
     if eng is None:
         raise NotImplementedError("%s needs a policy attached to a DsactEngine (the learner's networks); an "
                                   "unattached container acts through the module forward: use %s" % (who, instead))
-    if getattr(eng, "conv_type", None):
-        raise NotImplementedError("%s serves MLP policies (%s); CNN policies: %s" % (who, call, instead))
+    if getattr(eng, "conv_type", None) and not (hip_cnn_act and getattr(eng, "cnn_act", False)):
+        raise NotImplementedError("%s serves MLP policies (%s); CNN policies: %s, or hip_cnn_act=True on the algorithm (the "
+                                  "engine's CNN acting path) and on %s" % (who, call, instead, who))
     if action_type != "continu":
         raise NotImplementedError("%s serves continuous actions" % who)
     low = torch.as_tensor(env.action_low)

@@ -41,7 +41,11 @@ hip_eval_poll_steps (default 16): lockstep steps between two waits. hip_eval_max
 has not finished after that many lockstep steps raises RuntimeError (the handle stays usable) -- an environment that never ends
 an episode must not spin on the GPU forever.
 
-Refused (NotImplementedError / ValueError, before an environment or engine call is made): an unattached or CNN policy,
+Image environments (`hip_cnn_act=True` AND an engine with the CNN acting path): [N, C, H, W] frames, float32
+or uint8 codes into the coded ring's codebook; the observation buffer takes the dtype of the first env.reset().
+
+Refused (NotImplementedError / ValueError, before an environment or engine call is made): an unattached policy, a CNN policy
+outside that gate,
 non-continuous actions, an environment on another device than the engine, num_eval_episode < 1, hip_eval_poll_steps < 1.
 
 Evaluation draws nothing from the torch or NumPy generators and enqueues no update: the training state is not touched.
@@ -75,6 +79,7 @@ class HipTensorEnvEvaluator:
         if self.n_envs < 1:
             raise ValueError("the environment's num_envs must be >= 1 (got %d)" % self.n_envs)
         self.action_type = kwargs.get("action_type", "continu")
+        self.cnn_act = bool(kwargs.get("hip_cnn_act", False))   # image environments on an engine with the CNN acting path
         self.steps = 0            # lockstep steps of the last run_evaluation
         self.returns = None       # its episode returns, float64[E] in episode-index order
         self.lengths = None       # its episode lengths, int32[E]
@@ -87,8 +92,9 @@ class HipTensorEnvEvaluator:
         self.networks.load_state_dict(state_dict)
 
     def _engine(self):
-        """the engine behind the ATTACHED MLP policy; every other setup is refused"""
-        return require_tensor_engine("hip_tensor_env_evaluator", self.networks, self.action_type, self.env)
+        """the engine behind the ATTACHED MLP policy (hip_cnn_act=True: or CNN policy with the CNN acting path); every other
+        setup is refused"""
+        return require_tensor_engine("hip_tensor_env_evaluator", self.networks, self.action_type, self.env, self.cnn_act)
 
     def _setup(self, eng):
         """once per engine: the [N, .] buffers and whether the policy's limits are the environment's"""
@@ -96,6 +102,8 @@ class HipTensorEnvEvaluator:
         dev = torch.device(eng.device)
         f = dict(dtype=torch.float32, device=dev)
         self._obs, self._act, self._clip = torch.zeros(N, O, **f), torch.zeros(N, A, **f), torch.zeros(N, A, **f)
+        if getattr(eng, "conv_type", None):
+            self._obs = None      # image rows [N, C, H, W] in the frame's dtype (float32 or uint8 codes): made at the first reset
         self._rew = torch.zeros(N, **f)
         self._term, self._trunc, self._ended = (torch.zeros(N, dtype=torch.bool, device=dev) for _ in range(3))
         self._low, self._high, self._policy_clip = tensor_limits(self.env, eng, N)
@@ -114,7 +122,12 @@ class HipTensorEnvEvaluator:
         self.steps, remaining = 0, E
         with on_stream(engine_stream(eng)), torch.no_grad():
             eng.eval_begin(N, E)
-            obs.copy_(env.reset().reshape(N, -1))
+            first = env.reset()
+            if obs is None:
+                row = tuple(getattr(eng, "obs_shape", None) or first.shape[1:])
+                odt = torch.uint8 if first.dtype == torch.uint8 else torch.float32
+                obs = self._obs = torch.zeros((N,) + row, dtype=odt, device=first.device)
+            obs.copy_(first.reshape(obs.shape))
             while self.steps < self.max_steps:
                 eng.act_mode_device(obs, act)
                 if self._policy_clip:
@@ -128,7 +141,7 @@ class HipTensorEnvEvaluator:
                 eng.eval_commit(rew, term, trunc, ended)
                 # the next step's observations: this step's, with every environment that ended restarted on its own (rows
                 # without an episode too)
-                obs.copy_(env.reset(ended).reshape(N, -1))
+                obs.copy_(env.reset(ended).reshape(obs.shape))
                 self.steps += 1
                 if self.steps % P == 0:
                     remaining = eng.eval_poll()

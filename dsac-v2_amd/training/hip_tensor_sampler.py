@@ -36,8 +36,12 @@ The clip: the kernel clips to the policy's action limits (dsact_set_action_limit
 -- the usual case -- its `clipped` output is what the environment receives; otherwise the clip is made with two torch ops on
 the device.
 
-Refused (NotImplementedError / ValueError, before an environment step or an engine call is made): an unattached or CNN policy,
-strict_rng=True, noise_params, S not a multiple of N, an environment on another device than the engine. The overlapped
+Image environments (`hip_cnn_act=True` AND an engine with the CNN acting path, DsactEngine.cnn_act): the
+environment returns [N, C, H, W] frames, float32 or uint8. The [S, C, H, W] buffers take the dtype of the first env.reset(); a
+uint8 frame holds codes into the coded ring's codebook (hip_obs_codebook) and the engine's calls dispatch on the dtype.
+
+Refused (NotImplementedError / ValueError, before an environment step or an engine call is made): an unattached policy, a CNN
+policy outside that gate, strict_rng=True, noise_params, S not a multiple of N, an environment on another device than the engine. The overlapped
 trainer (hip_off_async_trainer) refuses this sampler as an unknown sampler class: held-behaviour acting is not built for it.
 
 Episode statistics (`hip_episode_stats=True`; default off: exactly the calls above): how the N TRAINING
@@ -139,11 +143,12 @@ class DeviceSampleBatch:
     (obs, info, act, rew, next_obs, done, logp, next_info) tuples (training/off_sampler.py:74-84): the first such use makes ONE
     device-to-host copy of the whole batch (which waits for the stream that produced it)."""
 
-    def __init__(self, obs, act, rew, obs2, terminated, truncated, logp, reward_scale=1, stream=None):
+    def __init__(self, obs, act, rew, obs2, terminated, truncated, logp, reward_scale=1, stream=None, codebook=None):
         self.obs, self.act, self.rew, self.obs2 = obs, act, rew, obs2
         self.terminated, self.truncated, self.logp = terminated, truncated, logp
         self.reward_scale = reward_scale
         self.stream = stream          # the torch stream the tensors were produced on (None: the current one)
+        self.codebook = codebook      # float32 table of a byte (uint8) image batch: a walked tuple's pixel is codebook[byte]
         self._tuples = None
 
     @property
@@ -155,6 +160,8 @@ class DeviceSampleBatch:
 
     def _host(self):
         if self._tuples is None:
+            if self.obs.dim() != 2 or self.obs.dtype != torch.float32:
+                return self._host_images()
             S, O, A = len(self), self.obs.shape[1], self.act.shape[1]
             with on_stream(self.stream):
                 flat = torch.cat([self.obs, self.obs2, self.act, self.rew[:, None], self.logp[:, None],
@@ -164,6 +171,26 @@ class DeviceSampleBatch:
             rew, logp, term, trunc = (h[:, 2 * O + A + k] for k in range(4))
             self._tuples = [(obs[i], {}, act[i], self.reward_scale * float(rew[i]), obs2[i], bool(term[i]) and not bool(trunc[i]),
                              logp[i], {"TimeLimit.truncated": bool(trunc[i])}) for i in range(S)]
+        return self._tuples
+
+    def _host_images(self):
+        """_host for image batches ([S, C, H, W] rows and / or byte frames): the two image columns are copied as they are -- a
+        byte column as bytes, decoded through the codebook on the host, so the reference's tuples come out as float32 frames"""
+        S, A = len(self), self.act.shape[1]
+        with on_stream(self.stream):
+            narrow = torch.cat([self.act, self.rew[:, None], self.logp[:, None], self.terminated[:, None].to(torch.float32),
+                                self.truncated[:, None].to(torch.float32)], dim=1)
+            h, obs, obs2 = narrow.cpu().numpy(), self.obs.cpu().numpy(), self.obs2.cpu().numpy()
+        if obs.dtype == np.uint8:
+            if self.codebook is None:
+                raise ValueError("a byte (uint8) DeviceSampleBatch needs the ring's codebook to be walked as float32 tuples")
+            book = np.zeros(256, np.float32)
+            book[:len(self.codebook)] = np.asarray(self.codebook, np.float32)
+            obs, obs2 = book[obs], book[obs2]
+        act = h[:, :A]
+        rew, logp, term, trunc = (h[:, A + k] for k in range(4))
+        self._tuples = [(obs[i], {}, act[i], self.reward_scale * float(rew[i]), obs2[i], bool(term[i]) and not bool(trunc[i]),
+                         logp[i], {"TimeLimit.truncated": bool(trunc[i])}) for i in range(S)]
         return self._tuples
 
     def __iter__(self):
@@ -203,6 +230,7 @@ class HipTensorEnvSampler:
         self.act_seed = int(seed) if seed is not None else act_seed_from(kwargs.get("seed"))
         if not 0 < self.act_seed < (1 << 64):
             raise ValueError("hip_act_seed must be in [1, 2^64) (0 switches the in-kernel draw off), got %r" % (seed,))
+        self.cnn_act = bool(kwargs.get("hip_cnn_act", False))   # image environments on an engine with the CNN acting path
         self.act_step = 0                 # the acting-step counter: one per lockstep step (assignable)
         self.total_sample_number = 0
         self._ready = None                # id of the engine the buffers / seed / clip route were set up for
@@ -218,26 +246,36 @@ class HipTensorEnvSampler:
         return self.total_sample_number
 
     def _engine(self):
-        """the engine behind the ATTACHED MLP policy; every other setup is refused"""
-        return require_tensor_engine("hip_tensor_env_sampler", self.networks, self.action_type, self.env)
+        """the engine behind the ATTACHED MLP policy (hip_cnn_act=True: or CNN policy with the CNN acting path); every other
+        setup is refused"""
+        return require_tensor_engine("hip_tensor_env_sampler", self.networks, self.action_type, self.env, self.cnn_act)
 
     def _setup(self, eng):
         """once per engine: the [S, .] buffers, the acting seed, and whether the kernel's clip is the environment's"""
         N, S, O, A = self.n_envs, self.sample_batch_size, eng.obs_dim, eng.act_dim
         dev = torch.device(eng.device)
         f = dict(dtype=torch.float32, device=dev)
-        self._obs_b, self._obs2_b = torch.zeros(S, O, **f), torch.zeros(S, O, **f)
+        # the observation rows: [., O] float32; an image environment on a CNN engine keeps [., C, H, W] rows in the FRAME's dtype
+        # (float32, or uint8: codes into the coded ring's codebook -- DESIGN.md section 20)
+        first = None if self._started else self.env.reset()
+        row, odt = (O,), torch.float32
+        if getattr(eng, "conv_type", None):
+            row = tuple(getattr(eng, "obs_shape", None) or first.shape[1:])
+            odt = torch.uint8 if (first if first is not None else self._obs).dtype == torch.uint8 else torch.float32
+        self._row = row
+        self._obs_b, self._obs2_b = torch.zeros((S,) + row, dtype=odt, device=dev), torch.zeros((S,) + row, dtype=odt, device=dev)
         self._act_b, self._clip_b = torch.zeros(S, A, **f), torch.zeros(S, A, **f)
         self._rew_b, self._logp_b = torch.zeros(S, **f), torch.zeros(S, **f)
         self._term_b = torch.zeros(S, dtype=torch.bool, device=dev)
         self._trunc_b = torch.zeros(S, dtype=torch.bool, device=dev)
-        self._obs = torch.zeros(N, O, **f)
+        if first is not None or tuple(self._obs.shape) != (N,) + row:
+            self._obs = torch.zeros((N,) + row, dtype=odt, device=dev)
         self._low, self._high, self._kernel_clip = tensor_limits(self.env, eng, N)
         eng.set_act_rng(self.act_seed)
         if self.episode_stats:
             eng.track_begin(N)            # (a new engine starts new statistics)
-        if not self._started:
-            self._obs.copy_(self.env.reset().reshape(N, O))
+        if first is not None:
+            self._obs.copy_(first.reshape((N,) + row))
             self._started = True
         hand_over(eng)   # (the only wait this sampler ever makes, once)
         self._ready = id(eng)
@@ -261,18 +299,19 @@ class HipTensorEnvSampler:
                 if not self._kernel_clip:
                     torch.minimum(torch.maximum(act_b[r0:r1], self._low), self._high, out=clip_b[r0:r1])
                 obs2, rew, term, trunc = env.step(clip_b[r0:r1])
-                obs2_b[r0:r1].copy_(obs2.reshape(N, -1))
+                obs2_b[r0:r1].copy_(obs2.reshape((N,) + self._row))
                 rew_b[r0:r1].copy_(rew)
                 term_b[r0:r1].copy_(term)
                 trunc_b[r0:r1].copy_(trunc)
                 # the next step's observations: this step's, with every environment that ended restarted on its own
                 nxt = env.reset(term_b[r0:r1] | trunc_b[r0:r1])
-                (obs_b[r1:r1 + N] if r1 < S else self._obs).copy_(nxt.reshape(N, -1))
+                (obs_b[r1:r1 + N] if r1 < S else self._obs).copy_(nxt.reshape((N,) + self._row))
             if self.episode_stats:
                 eng.track_commit(rew_b, term_b, trunc_b, S // N)    # the S / N steps in one launch
         self.total_sample_number += S
         self.sample_calls += 1
-        batch = DeviceSampleBatch(obs_b, act_b, rew_b, obs2_b, term_b, trunc_b, logp_b, self.reward_scale, stream=stream)
+        batch = DeviceSampleBatch(obs_b, act_b, rew_b, obs2_b, term_b, trunc_b, logp_b, self.reward_scale, stream=stream,
+                                  codebook=getattr(eng, "codebook", None))
         tb = {}
         if self.episode_stats_every and self.sample_calls % self.episode_stats_every == 0:
             stats = self.episode_statistics(clear=True)             # (the only wait sample() ever makes)

@@ -508,8 +508,8 @@ int dsact_stream_idle(dsact_handle* h);
  * as a function of (weight base, stream): live on the handle's stream, held on the acting stream with the snapshot's weights.
  * Allocates the path's own buffers for 64 frames per chunk (pinned frame stage, device frames, pixel-major frames, one
  * activation buffer per conv layer, feature rows, two trunk buffers, mapped output rows): no allocation stands between a
- * held acting call and its launches, and nothing an update reads or writes is shared. dsact_policy_forward,
- * dsact_act_mode_batch and the device-resident forms are unchanged. Idempotent; DSACT_E_INVALID on an MLP handle or with
+ * held acting call and its launches, and nothing an update reads or writes is shared. dsact_policy_forward and
+ * dsact_act_mode_batch are unchanged; the device-resident forms serve the handle from then on (see below). Idempotent; DSACT_E_INVALID on an MLP handle or with
  * act_dim > 32. dsact_debug_get "cnn_act" reports the state ("act_fast" is then 1). */
 int dsact_cnn_acting_enable(dsact_handle* h);
 
@@ -538,7 +538,8 @@ int dsact_cnn_acting_enable(dsact_handle* h);
  *                                  route) -- the inputs must be ready in that stream's order. ASYNCHRONOUS: no stream
  *                                  synchronisation, no host copy. All pointers must be device memory of the handle's GPU
  *                                  (DSACT_E_INVALID otherwise). Any n >= 1 (chunked inside the call); MLP policies with
- *                                  act_dim <= 32 (DSACT_E_INVALID for CNN policies).
+ *                                  act_dim <= 32 (DSACT_E_INVALID for CNN policies without dsact_cnn_acting_enable; with it:
+ *                                  "Device-resident image environments" below).
  *   dsact_buffer_add_device        n x ReplayBuffer.store (training/replay_buffer.py:58-79) fed from device arrays, with the
  *                                  sampler's per-step bookkeeping (training/off_sampler.py:66-73) folded in: transition i goes to
  *                                  ring row (ptr + i) % capacity; rew is stored as rew * reward_scale (ONE fp32 product with
@@ -547,8 +548,9 @@ int dsact_cnn_acting_enable(dsact_handle* h);
  *                                  as non-terminal); terminated / truncated: one byte per transition, non-zero = set. ptr =
  *                                  (ptr + n) % capacity, size = min(size + n, capacity) (replay_buffer.py:78-79), visible to
  *                                  dsact_buffer_size / dsact_buffer_ptr at once like dsact_buffer_add's. n <= capacity.
- *                                  ASYNCHRONOUS on the handle's stream. fp32 MLP rings only (DSACT_E_INVALID on coded rings and
- *                                  CNN handles); device pointers of the handle's GPU only.
+ *                                  ASYNCHRONOUS on the handle's stream. fp32 MLP rings (DSACT_E_INVALID on coded rings and
+ *                                  CNN handles without dsact_cnn_acting_enable; with it: "Device-resident image environments"
+ *                                  below); device pointers of the handle's GPU only.
  * dsact_debug_get: "act_dev_calls" (chunks launched by dsact_act_sample_device), "ring_commit_rows" (transitions written by
  * dsact_buffer_add_device), "act_dev_syncs" (stream synchronisations made inside the two: 0). */
 int dsact_set_act_rng(dsact_handle* h, uint64_t seed);
@@ -567,7 +569,8 @@ int dsact_buffer_add_device(dsact_handle* h, int64_t n, const float* obs, const 
  *                                  update: the LIVE weights, also under a behaviour hold (like dsact_act_mode_batch).
  *                                  ASYNCHRONOUS: no stream synchronisation, no host copy. All pointers must be device memory
  *                                  of the handle's GPU (DSACT_E_INVALID otherwise). Any n >= 1 (chunked inside the call); MLP
- *                                  policies with act_dim <= 32 (DSACT_E_INVALID for CNN policies).
+ *                                  policies with act_dim <= 32 (DSACT_E_INVALID for CNN policies without
+ *                                  dsact_cnn_acting_enable).
  *   dsact_eval_begin               training/evaluator.py:34-84's bookkeeping (lines 40-46 and 77-81: the reward list and the
  *                                  episode loop) moved to the device: allocates (or grows) the state for n_envs rows and n_episodes
  *                                  episodes and initialises it in stream order -- row i plays episode i (none when
@@ -590,6 +593,30 @@ int dsact_buffer_add_device(dsact_handle* h, int64_t n, const float* obs, const 
  * dsact_debug_get: "act_mode_dev_calls" (chunks launched by dsact_act_mode_device), "eval_commit_calls", "eval_polls";
  * "act_dev_syncs" stays 0 across dsact_act_mode_device and dsact_eval_commit too. */
 int dsact_act_mode_device(dsact_handle* h, const float* obs_dev, int32_t n, float* action_dev);
+
+/* ---- Device-resident image environments ----------------------------------------------------------------
+ * After dsact_cnn_acting_enable the device-resident forms above serve a CNN handle too (without it they answer as ever:
+ * DSACT_E_INVALID "serves MLP policies" / "image rings" / "coded rings"):
+ *   dsact_act_sample_device / dsact_act_mode_device   obs_dev holds n frames of O = C*H*W floats in the environment's (C, H, W)
+ *       layout, 16-byte aligned, read in place; chunks of 64 frames run the CNN acting forward of dsact_act_sample_batch (frame
+ *       ingest, conv stack, feature scatter, twin trunk, output launch) on the handle's stream with the live weights. With the
+ *       same eps a row is bit for bit dsact_act_sample_batch's; drawn noise is the same function of (seed, step, row, d). No
+ *       synchronisation, no host copy; every chunk counts in "act_dev_calls" / "act_mode_dev_calls". A held
+ *       dsact_act_sample_batch that follows waits on its acting stream for an event recorded behind the last launch.
+ *   dsact_buffer_add_device   fp32 image ring: the two image columns row by row (16-byte aligned sources), the narrow columns as
+ *       for the MLP ring. Coded ring: the image columns are encoded as dsact_buffer_add encodes them; a value missing from the
+ *       codebook makes the next dsact_buffer_add* / dsact_buffer_check fail, as there.
+ * BYTE FRAMES (the _u8 forms; an enabled CNN handle WITH a coded ring, DSACT_E_STATE naming hip_obs_codebook without one): a frame
+ * is C*H*W bytes in (C, H, W) layout, each a code into the ring's codebook -- the pixel is codebook[byte].
+ *   dsact_act_sample_device_u8 / dsact_act_mode_device_u8   the calls above on byte frames: bit for bit their results on the
+ *       decoded fp32 frames.
+ *   dsact_buffer_add_device_u8   obs / obs2 are byte frames; they go to the code columns as they are (no search). A byte >=
+ *       the codebook's size is a miss, recorded and reported like the encoder's (the byte as the value, its ring row). */
+int dsact_act_sample_device_u8(dsact_handle* h, const uint8_t* frames_dev, int32_t n, const float* eps_dev, int64_t step,
+                               float* action_dev, float* clipped_dev, float* logp_dev);
+int dsact_act_mode_device_u8(dsact_handle* h, const uint8_t* frames_dev, int32_t n, float* action_dev);
+int dsact_buffer_add_device_u8(dsact_handle* h, int64_t n, const uint8_t* obs, const float* act, const float* rew, const uint8_t* obs2,
+                               const uint8_t* terminated, const uint8_t* truncated, const float* logp, double reward_scale);
 int dsact_eval_begin(dsact_handle* h, int32_t n_envs, int32_t n_episodes);
 int dsact_eval_commit(dsact_handle* h, const float* reward_dev, const uint8_t* terminated_dev, const uint8_t* truncated_dev,
                       uint8_t* ended_dev);
