@@ -24,7 +24,8 @@
 #include "dsact_host_act.h"
 #include "dsact_conv.h"
 
-// every listed template-kernel instantiation is compiled in its family's translation unit (csrc/dsact_tu_<group>.hip, dsact_tu.h)
+// every listed template-kernel instantiation is compiled in its family's translation unit (csrc/dsact_tu_<group>.hip, dsact_tu.h);
+// the list follows the kernel instance tables below (struct Kernels), which decide what exists
 #define DSACT_KERNEL(group, ...) extern template __global__ void __VA_ARGS__;
 #include "dsact_instances.inc"
 #undef DSACT_KERNEL
@@ -543,6 +544,145 @@ int launch(dsact_handle* h, const char* name, void (*kernel)(KArgs...), dim3 gri
     int rc_ = (x);        \
     if (rc_ != DSACT_OK) return rc_; \
   } while (0)
+
+// ---- kernel instance tables -------------------------------------------------------------------------------------
+// Which instance of a template kernel a launch runs is decided here and nowhere else. Every family has one table: a cell per
+// instance at the index its template arguments spell (<2, 4, true> sits at [2][4][1]; every other cell stays null), and beside
+// it the dynamic-LDS ceiling dsact_create grants each instance. A launch site names the family and its run-time key and keeps
+// its grid, block size and LDS bytes; a key without an instance is an error, never another instance. csrc/dsact_instances.inc
+// (which unit compiles which instance) follows from these tables: scripts/gen_kernel_instances.py.
+struct KernelFamily {
+  const char* name;
+  int rank;                  // template arguments that key the table
+  int max_lds;               // hipFuncAttributeMaxDynamicSharedMemorySize of every instance; 0: the default 64 KB stays
+  const void* const* cells;  // host handles, null where the family has no instance
+  int n_cells;
+};
+struct KernelKey { int k[4]; };
+
+int no_instance(dsact_handle* h, const KernelFamily& f, const KernelKey& key) {
+  char s[64];
+  int n = 0;
+  for (int d = 0; d < f.rank; ++d) n += snprintf(s + n, sizeof(s) - n, d ? ", %d" : "%d", key.k[d]);
+  return fail(h, DSACT_E_STATE, "%s has no instance <%s>", f.name, s);
+}
+
+template <typename Fn, int D0, int D1 = 1, int D2 = 1, int D3 = 1>
+struct KernelTable : KernelFamily {
+  const void* cell[D0][D1][D2][D3] = {};
+  KernelTable(std::vector<const KernelFamily*>& all, const char* name, int max_lds)
+      : KernelFamily{name, D3 > 1 ? 4 : D2 > 1 ? 3 : D1 > 1 ? 2 : 1, max_lds, &cell[0][0][0][0], D0 * D1 * D2 * D3} {
+    all.push_back(this);
+  }
+  KernelTable(const KernelTable&) = delete;
+  template <int I, int J = 0, int L = 0, int M = 0>
+  void set(Fn* kernel) {
+    static_assert(I >= 0 && I < D0 && J >= 0 && J < D1 && L >= 0 && L < D2 && M >= 0 && M < D3, "cell outside its table");
+    cell[I][J][L][M] = (const void*)kernel;
+  }
+  Fn* find(const KernelKey& key) const {
+    const int* k = key.k;
+    const bool in = (unsigned)k[0] < (unsigned)D0 && (unsigned)k[1] < (unsigned)D1 && (unsigned)k[2] < (unsigned)D2 && (unsigned)k[3] < (unsigned)D3;
+    return in ? (Fn*)cell[k[0]][k[1]][k[2]][k[3]] : nullptr;
+  }
+  template <typename... Args>
+  int launch(dsact_handle* h, const char* launch_name, KernelKey key, dim3 grid, dim3 block, size_t lds, const Args&... args) const {
+    Fn* kernel = find(key);
+    if (!kernel) return no_instance(h, *this, key);
+    return ::launch(h, launch_name, kernel, grid, block, lds, args...);
+  }
+};
+// one set of tokens names the instance and its cell
+#define CELL1(t, k, a) (t).set<a>(k<a>)
+#define CELL2(t, k, a, b) (t).set<a, b>(k<a, b>)
+#define CELL3(t, k, a, b, c) (t).set<a, b, c>(k<a, b, c>)
+#define CELL4(t, k, a, b, c, d) (t).set<a, b, c, d>(k<a, b, c, d>)
+
+struct Kernels {
+  std::vector<const KernelFamily*> all;   // every table below, in declaration order (each adds itself)
+  // chain kernels (dsact_chain.h) <NT = width / 64, RG = rows per workgroup / 4, generic activation>: dsact_create admits
+  // shapes whose 16-row slices take up to 150 KB
+  static constexpr int kChainLds = 155 * 1024;
+  KernelTable<void(FwdArgs), 5, 5, 2> chain_fwd{all, "k_chain_fwd", kChainLds};
+  KernelTable<void(Fwd2Args), 5, 2> chain_fwd2{all, "k_chain_fwd2", kChainLds};
+  KernelTable<void(const PipeFwd*), 5, 2> chain_fwdt{all, "k_chain_fwdt", kChainLds}, chain_fwdp{all, "k_chain_fwdp", kChainLds};
+  KernelTable<void(const PipeFwd*, BwdPiArgs, int), 5, 2> chain_fwdpb{all, "k_chain_fwdpb", kChainLds};
+  KernelTable<void(BwdQArgs), 5, 5> chain_bwd_q{all, "k_chain_bwd_q", kChainLds};
+  KernelTable<void(BwdPiArgs), 5, 5> chain_bwd_pi{all, "k_chain_bwd_pi", kChainLds};
+  // (4- and 8-row slices only: the 16-row instantiations spilled 20-92 B under this kernel's three-workgroups-per-CU register
+  //  bound and were reachable only where bqt_ok() is false -- batch >= 1024, pi_merge off; VERDICT r5)
+  KernelTable<void(BwdQtArgs), 5, 3> chain_bwd_qt{all, "k_chain_bwd_qt", 0};         // 0: RG <= 2 keeps chain_lds(W, W, 4 RG) at <= 44 KB
+  KernelTable<void(BwdQpArgs), 5, 2, 3> chain_bwd_qpt{all, "k_chain_bwd_qpt", 0};    // 0: 4-row critic, <= 8-row policy slices: <= 44 KB
+  // throughput-regime kernels (dsact_fat.h), <NT, RT = rows per workgroup / 16, generic activation>
+  KernelTable<void(FwdArgs), 5, 3, 2> fat_fwd{all, "k_fat_fwd", 0};                  // 0: launch_chain_fwd drops x0_lds above 64 KB
+  KernelTable<void(BwdQArgs), 5, 3> fat_bwd_q{all, "k_fat_bwd_q", 0};                // 0: 32 rows of (W + 4) floats: <= 33 KB
+  KernelTable<void(BwdPiArgs), 5, 3> fat_bwd_pi{all, "k_fat_bwd_pi", 0};             // 0: + 32 rows of 16 c_out + 4 (act_dim <= 32): <= 42 KB
+  // tile stages <P_MC, Q_MC, epilogue, K / 64 of a clean stage or 0>, their 64 x 64 forms <Q_MC, epilogue> and the conv forward's
+  // <MB>; a 32 x 32 tile's operands are fetched up to kMaxPrefetchTiles ahead: 129 KB of the CU's 160 KB
+  const int kTileLds = (int)tile_lds_bytes(BK * kMaxPrefetchTiles), kTile64Lds = (int)tile64_lds_bytes();
+  KernelTable<void(StageArgs), 1, 2, 3, 5> stage{all, "k_stage", kTileLds};
+  KernelTable<void(TableArgs), 1> stage_table{all, "k_stage_table", kTileLds};
+  KernelTable<void(StageArgs), 2, 3> stage64{all, "k_stage64", kTile64Lds};
+  KernelTable<void(ConvStageArgs), 3> conv_fwd64{all, "k_conv_fwd64", kTile64Lds};
+  // row kernels <256-wide chunks of a hidden row> (register arrays are statically indexed); weight-gradient tiles ride in
+  // k_heads_bwd, the others ask for no dynamic LDS
+  KernelTable<void(HeadsArgs), 5> heads{all, "k_heads", 0};
+  KernelTable<void(HeadsBwdArgs), 5> heads_bwd{all, "k_heads_bwd", kTileLds};
+  KernelTable<void(LossArgs), 5> loss{all, "k_loss", 0};
+  KernelTable<void(LossV1Args), 5> loss_v1{all, "k_loss_v1", 0};
+  KernelTable<void(PolicyOutArgs), 5> policy_out{all, "k_policy_out", 0};
+
+  Kernels() {
+    CELL3(chain_fwd, k_chain_fwd, 1, 1, false); CELL3(chain_fwd, k_chain_fwd, 1, 2, false); CELL3(chain_fwd, k_chain_fwd, 1, 4, false);
+    CELL3(chain_fwd, k_chain_fwd, 2, 1, false); CELL3(chain_fwd, k_chain_fwd, 2, 2, false); CELL3(chain_fwd, k_chain_fwd, 2, 4, false);
+    CELL3(chain_fwd, k_chain_fwd, 4, 1, false); CELL3(chain_fwd, k_chain_fwd, 4, 2, false); CELL3(chain_fwd, k_chain_fwd, 4, 4, false);
+    CELL3(chain_fwd, k_chain_fwd, 1, 1, true); CELL3(chain_fwd, k_chain_fwd, 1, 2, true); CELL3(chain_fwd, k_chain_fwd, 1, 4, true);
+    CELL3(chain_fwd, k_chain_fwd, 2, 1, true); CELL3(chain_fwd, k_chain_fwd, 2, 2, true); CELL3(chain_fwd, k_chain_fwd, 2, 4, true);
+    CELL3(chain_fwd, k_chain_fwd, 4, 1, true); CELL3(chain_fwd, k_chain_fwd, 4, 2, true); CELL3(chain_fwd, k_chain_fwd, 4, 4, true);
+    CELL2(chain_fwd2, k_chain_fwd2, 1, false); CELL2(chain_fwd2, k_chain_fwd2, 2, false); CELL2(chain_fwd2, k_chain_fwd2, 4, false);
+    CELL2(chain_fwd2, k_chain_fwd2, 1, true); CELL2(chain_fwd2, k_chain_fwd2, 2, true); CELL2(chain_fwd2, k_chain_fwd2, 4, true);
+    CELL2(chain_fwdt, k_chain_fwdt, 1, false); CELL2(chain_fwdt, k_chain_fwdt, 2, false); CELL2(chain_fwdt, k_chain_fwdt, 4, false);
+    CELL2(chain_fwdt, k_chain_fwdt, 1, true); CELL2(chain_fwdt, k_chain_fwdt, 2, true); CELL2(chain_fwdt, k_chain_fwdt, 4, true);
+    CELL2(chain_fwdp, k_chain_fwdp, 1, false); CELL2(chain_fwdp, k_chain_fwdp, 2, false); CELL2(chain_fwdp, k_chain_fwdp, 4, false);
+    CELL2(chain_fwdp, k_chain_fwdp, 1, true); CELL2(chain_fwdp, k_chain_fwdp, 2, true); CELL2(chain_fwdp, k_chain_fwdp, 4, true);
+    CELL2(chain_fwdpb, k_chain_fwdpb, 1, false); CELL2(chain_fwdpb, k_chain_fwdpb, 2, false); CELL2(chain_fwdpb, k_chain_fwdpb, 4, false);
+    CELL2(chain_fwdpb, k_chain_fwdpb, 1, true); CELL2(chain_fwdpb, k_chain_fwdpb, 2, true); CELL2(chain_fwdpb, k_chain_fwdpb, 4, true);
+    CELL2(chain_bwd_q, k_chain_bwd_q, 1, 1); CELL2(chain_bwd_q, k_chain_bwd_q, 1, 2); CELL2(chain_bwd_q, k_chain_bwd_q, 1, 4);
+    CELL2(chain_bwd_q, k_chain_bwd_q, 2, 1); CELL2(chain_bwd_q, k_chain_bwd_q, 2, 2); CELL2(chain_bwd_q, k_chain_bwd_q, 2, 4);
+    CELL2(chain_bwd_q, k_chain_bwd_q, 4, 1); CELL2(chain_bwd_q, k_chain_bwd_q, 4, 2); CELL2(chain_bwd_q, k_chain_bwd_q, 4, 4);
+    CELL2(chain_bwd_pi, k_chain_bwd_pi, 1, 1); CELL2(chain_bwd_pi, k_chain_bwd_pi, 1, 2); CELL2(chain_bwd_pi, k_chain_bwd_pi, 1, 4);
+    CELL2(chain_bwd_pi, k_chain_bwd_pi, 2, 1); CELL2(chain_bwd_pi, k_chain_bwd_pi, 2, 2); CELL2(chain_bwd_pi, k_chain_bwd_pi, 2, 4);
+    CELL2(chain_bwd_pi, k_chain_bwd_pi, 4, 1); CELL2(chain_bwd_pi, k_chain_bwd_pi, 4, 2); CELL2(chain_bwd_pi, k_chain_bwd_pi, 4, 4);
+    CELL2(chain_bwd_qt, k_chain_bwd_qt, 1, 1); CELL2(chain_bwd_qt, k_chain_bwd_qt, 2, 1); CELL2(chain_bwd_qt, k_chain_bwd_qt, 4, 1);
+    CELL2(chain_bwd_qt, k_chain_bwd_qt, 1, 2); CELL2(chain_bwd_qt, k_chain_bwd_qt, 2, 2); CELL2(chain_bwd_qt, k_chain_bwd_qt, 4, 2);
+    CELL3(chain_bwd_qpt, k_chain_bwd_qpt, 1, 1, 1); CELL3(chain_bwd_qpt, k_chain_bwd_qpt, 2, 1, 1); CELL3(chain_bwd_qpt, k_chain_bwd_qpt, 4, 1, 1);
+    CELL3(chain_bwd_qpt, k_chain_bwd_qpt, 1, 1, 2); CELL3(chain_bwd_qpt, k_chain_bwd_qpt, 2, 1, 2); CELL3(chain_bwd_qpt, k_chain_bwd_qpt, 4, 1, 2);
+    CELL3(fat_fwd, k_fat_fwd, 2, 1, false); CELL3(fat_fwd, k_fat_fwd, 2, 2, false); CELL3(fat_fwd, k_fat_fwd, 4, 1, false); CELL3(fat_fwd, k_fat_fwd, 4, 2, false);
+    CELL3(fat_fwd, k_fat_fwd, 2, 1, true); CELL3(fat_fwd, k_fat_fwd, 2, 2, true); CELL3(fat_fwd, k_fat_fwd, 4, 1, true); CELL3(fat_fwd, k_fat_fwd, 4, 2, true);
+    CELL2(fat_bwd_q, k_fat_bwd_q, 2, 1); CELL2(fat_bwd_q, k_fat_bwd_q, 2, 2); CELL2(fat_bwd_q, k_fat_bwd_q, 4, 1); CELL2(fat_bwd_q, k_fat_bwd_q, 4, 2);
+    CELL2(fat_bwd_pi, k_fat_bwd_pi, 2, 1); CELL2(fat_bwd_pi, k_fat_bwd_pi, 2, 2); CELL2(fat_bwd_pi, k_fat_bwd_pi, 4, 1); CELL2(fat_bwd_pi, k_fat_bwd_pi, 4, 2);
+    CELL1(heads, k_heads, 1); CELL1(heads, k_heads, 2); CELL1(heads, k_heads, 3); CELL1(heads, k_heads, 4);
+    CELL1(heads_bwd, k_heads_bwd, 1); CELL1(heads_bwd, k_heads_bwd, 2); CELL1(heads_bwd, k_heads_bwd, 3); CELL1(heads_bwd, k_heads_bwd, 4);
+    CELL1(loss, k_loss, 1); CELL1(loss, k_loss, 2); CELL1(loss, k_loss, 3); CELL1(loss, k_loss, 4);
+    CELL1(loss_v1, k_loss_v1, 1); CELL1(loss_v1, k_loss_v1, 2); CELL1(loss_v1, k_loss_v1, 3); CELL1(loss_v1, k_loss_v1, 4);
+    CELL1(policy_out, k_policy_out, 1); CELL1(policy_out, k_policy_out, 2); CELL1(policy_out, k_policy_out, 3); CELL1(policy_out, k_policy_out, 4);
+    CELL4(stage, k_stage, false, false, EPI_GELU, 0); CELL4(stage, k_stage, false, false, EPI_GELU, 2); CELL4(stage, k_stage, false, false, EPI_GELU, 4);
+    CELL4(stage, k_stage, false, true, EPI_MULG, 0); CELL4(stage, k_stage, false, true, EPI_MULG, 2); CELL4(stage, k_stage, false, true, EPI_MULG, 4);
+    CELL4(stage, k_stage, false, true, EPI_STORE, 0);
+    stage_table.set<0>(k_stage_table);   // (not a template: a family of one)
+    CELL2(stage64, k_stage64, false, EPI_GELU); CELL2(stage64, k_stage64, true, EPI_MULG); CELL2(stage64, k_stage64, true, EPI_STORE);
+    CELL1(conv_fwd64, k_conv_fwd64, 1); CELL1(conv_fwd64, k_conv_fwd64, 2);
+  }
+};
+#undef CELL1
+#undef CELL2
+#undef CELL3
+#undef CELL4
+// filled on first use (dsact_create), read-only from then on
+const Kernels& kernels() {
+  static const Kernels k;
+  return k;
+}
 
 // pixels per split of a conv weight-gradient contraction (multiple of 64): the SMALLEST the launch may use -- the partial
 // buffers are sized for it
@@ -1161,6 +1301,10 @@ int run_stage(dsact_handle* h, const Stage& s0, int x0 = 0, int x1 = 0, bool fus
   s.args.extra = h->d_tiles + x0;
   s.args.n_extra = x1 > x0 ? x1 - x0 : 0;
   s.args.fo = fused_opt(h, fused);
+  // the tile form of each stage kind: layout of operand Q and the epilogue (kind 3: a plain product whose epilogue applies a ReLU mask)
+  static const struct { bool q_mc; int epi; } kStageForm[4] = {{false, EPI_GELU}, {true, EPI_MULG}, {true, EPI_STORE}, {true, EPI_MULG}};
+  if (s.kind < 0 || s.kind > 3) return fail(h, DSACT_E_STATE, "stage %s: kind %d", s.name.c_str(), s.kind);
+  const auto form = kStageForm[s.kind];
   // large batches: 64x64 tiles (k_stage64) when every problem of the stage allows it and nothing rides along
   // (kind 2, plain store: the conv data gradient's dCol products -- many 32 x 32 tiles with a contraction of only 64-256)
   if (s.args.n_extra == 0 && (s.kind == 0 || s.kind == 1 || (s.kind >= 2 && s.name.compare(0, 9, "conv_dcol") == 0))) {   // (dfeat on 48 such tiles: 14.3 vs 12.3 us)
@@ -1180,30 +1324,15 @@ int run_stage(dsact_handle* h, const Stage& s0, int x0 = 0, int x1 = 0, bool fus
       blocks += (g.M / 64) * g.tiles_n;
       g.tile_end = blocks;
     }
-    if (ok) {
-      if (s.kind == 0) return launch(h, s.name.c_str(), k_stage64<false, EPI_GELU>, dim3(blocks), dim3(kThreads64), tile64_lds_bytes(), a64);
-      if (s.kind == 2) return launch(h, s.name.c_str(), k_stage64<true, EPI_STORE>, dim3(blocks), dim3(kThreads64), tile64_lds_bytes(), a64);
-      return launch(h, s.name.c_str(), k_stage64<true, EPI_MULG>, dim3(blocks), dim3(kThreads64), tile64_lds_bytes(), a64);
-    }
+    if (ok) return kernels().stage64.launch(h, s.name.c_str(), {form.q_mc, form.epi}, dim3(blocks), dim3(kThreads64), tile64_lds_bytes(), a64);
   }
   const int grid = s.n_blocks + s.args.n_extra;
   size_t lds = tile_lds_bytes(s.max_k);
   if (s.args.n_extra && tile_lds_bytes(dw_k(h)) > lds) lds = tile_lds_bytes(dw_k(h));
-  // clean stages (hidden layers of 128 / 256 units at batch sizes that are multiples of 32) use the
+  // clean forward and backward stages (hidden layers of 128 / 256 units at batch sizes that are multiples of 32) use the
   // straight-line specialisations
-#define STAGE_TS(PM, QM, EP)                                                                                     \
-  do {                                                                                                           \
-    if (s.ts == 4) return launch(h, s.name.c_str(), k_stage<PM, QM, EP, 4>, dim3(grid), dim3(kThreads), lds, s.args); \
-    if (s.ts == 2) return launch(h, s.name.c_str(), k_stage<PM, QM, EP, 2>, dim3(grid), dim3(kThreads), lds, s.args); \
-  } while (0)
-  if (s.kind == 0) STAGE_TS(false, false, EPI_GELU);
-  if (s.kind == 1) STAGE_TS(false, true, EPI_MULG);
-#undef STAGE_TS
-  if (s.kind == 0)
-    return launch(h, s.name.c_str(), k_stage<false, false, EPI_GELU>, dim3(grid), dim3(kThreads), lds, s.args);
-  if (s.kind == 2)
-    return launch(h, s.name.c_str(), k_stage<false, true, EPI_STORE>, dim3(grid), dim3(kThreads), lds, s.args);
-  return launch(h, s.name.c_str(), k_stage<false, true, EPI_MULG>, dim3(grid), dim3(kThreads), lds, s.args);   // kinds 1 and 3
+  const int ts = (s.kind <= 1 && (s.ts == 2 || s.ts == 4)) ? s.ts : 0;
+  return kernels().stage.launch(h, s.name.c_str(), {false, form.q_mc, form.epi, ts}, dim3(grid), dim3(kThreads), lds, s.args);
 }
 
 // weight-gradient tiles [x0, x1) as their own launch; `fused`: Adam/Polyak in the tile epilogue;
@@ -1215,7 +1344,7 @@ int run_dw(dsact_handle* h, int x0, int x1, bool fused, bool finalize) {
   a.fo = fused_opt(h, fused);
   a.finalize = finalize ? 1 : 0;
   a.timeline = tl_for(h, "dW");
-  return launch(h, "dW", k_stage_table, dim3(a.n_tiles + (finalize ? 1 : 0)), dim3(kThreads), tile_lds_bytes(dw_k(h)), a);
+  return kernels().stage_table.launch(h, "dW", {0}, dim3(a.n_tiles + (finalize ? 1 : 0)), dim3(kThreads), tile_lds_bytes(dw_k(h)), a);
 }
 
 
@@ -1319,7 +1448,7 @@ int enqueue_conv_forward(dsact_handle* h) {
       for (int q = 0; q < a.n_prob; ++q) { it64 += (M / 64) * (g.Cout / 64); a.p[q].item_end = it64; a.p[q].tiles_n = g.Cout / 64; }
       a.n_items = it64;
       feat_rows(a, j);
-      TRY(launch(h, name.c_str(), k_conv_fwd64<2>, dim3(it64), dim3(kThreads64), tile64_lds_bytes(), a));
+      TRY(kernels().conv_fwd64.launch(h, name.c_str(), {2}, dim3(it64), dim3(kThreads64), tile64_lds_bytes(), a));
       continue;
     }
     // ... 32 x 64 tiles where those would leave CUs idle but the contraction is long (type_2 layer 5: K = 1152, M = batch)
@@ -1328,7 +1457,7 @@ int enqueue_conv_forward(dsact_handle* h) {
       for (int q = 0; q < a.n_prob; ++q) { it += (M / 32) * (g.Cout / 64); a.p[q].item_end = it; a.p[q].tiles_n = g.Cout / 64; }
       a.n_items = it;
       feat_rows(a, j);
-      TRY(launch(h, name.c_str(), k_conv_fwd64<1>, dim3(it), dim3(kThreads64), tile64_lds_bytes(), a));
+      TRY(kernels().conv_fwd64.launch(h, name.c_str(), {1}, dim3(it), dim3(kThreads64), tile64_lds_bytes(), a));
       continue;
     }
     TRY(launch(h, name.c_str(), k_conv_fwd, dim3(conv_fwd_grid(items)), dim3(kThreads), 0, a));
@@ -1597,15 +1726,8 @@ int enqueue_gather_ring_img(dsact_handle* h, const int* table, int rows, int use
   return launch(h, "gather_img_coded", k_gather_img_coded<0>, grid, dim3(kThreads), lds, a);
 }
 
-// dispatch on the number of 256-wide chunks of a hidden row (register arrays are statically indexed)
-#define NCH_DISPATCH(W, CALL)                  \
-  do {                                         \
-    const int nch_ = ((W) + 255) / 256;        \
-    if (nch_ <= 1) { CALL(1); }                \
-    else if (nch_ == 2) { CALL(2); }           \
-    else if (nch_ == 3) { CALL(3); }           \
-    else { CALL(4); }                          \
-  } while (0)
+// key of the row kernels' tables: the number of 256-wide chunks of a hidden row (1..4: widths up to kMaxWidth)
+int row_chunks(int W) { return std::min(std::max((W + 255) / 256, 1), 4); }
 
 StepHyper step_hyper(const dsact_handle* h) {
   StepHyper hp;
@@ -1810,23 +1932,6 @@ int run_dw2(dsact_handle* h, int x0, int x1, bool fused, bool finalize) {
 }
 
 // ---- row-slice fused update (dsact_chain.h) ---------------------------------------------------------------------
-#define CHAIN_NT(CALL, RGV)                    \
-  do {                                         \
-    if ((RGV) == 1) {                          \
-      if (h->cNT == 1) { CALL(1, 1); }         \
-      else if (h->cNT == 2) { CALL(2, 1); }    \
-      else { CALL(4, 1); }                     \
-    } else if ((RGV) == 4) {                   \
-      if (h->cNT == 1) { CALL(1, 4); }         \
-      else if (h->cNT == 2) { CALL(2, 4); }    \
-      else { CALL(4, 4); }                     \
-    } else {                                   \
-      if (h->cNT == 1) { CALL(1, 2); }         \
-      else if (h->cNT == 2) { CALL(2, 2); }    \
-      else { CALL(4, 2); }                     \
-    }                                          \
-  } while (0)
-
 // Row groups (of 4 rows) per chain workgroup of one launch. A workgroup streams its unit's whole weight set whatever
 // its row count, and a step (4 KB of weights, 32 * RG cycles of MFMA) is not the sum of the two but close to it: measured
 // with 192 - 256 workgroups streaming (profiles/gemm44_step_ubench.txt, cycles per step at 2.4 GHz) 78 - 80 at 4 rows,
@@ -2087,12 +2192,7 @@ int enqueue_chain_fwd_twin(dsact_handle* h, int grp) {
   }
   const char* name = h->twin_merged ? "chain_fwd" : grp == 0 ? "chain_fwd_a" : "chain_fwd_b";
   const PipeFwd* dev = h->d_fwdt[grp];
-#define CALL_FT(N) return generic_act(h) ? launch(h, name, k_chain_fwdt<N, true>, dim3(P.n_blocks), dim3(64 * N), lds, dev) \
-                                         : launch(h, name, k_chain_fwdt<N>, dim3(P.n_blocks), dim3(64 * N), lds, dev)
-  if (h->cNT == 1) CALL_FT(1);
-  if (h->cNT == 2) CALL_FT(2);
-  CALL_FT(4);
-#undef CALL_FT
+  return kernels().chain_fwdt.launch(h, name, {h->cNT, generic_act(h)}, dim3(P.n_blocks), dim3(64 * h->cNT), lds, dev);
 }
 
 // fat mode: 32-row workgroups when even those fill the chip twice over, else 16-row ones
@@ -2100,17 +2200,6 @@ int fat_rt(const dsact_handle* h, int n_units) {
   if (h->env_fat_rt) return h->env_fat_rt;
   return (n_units * (h->B / 32) >= 512 && h->B % 32 == 0) ? 2 : 1;
 }
-
-#define FAT_NT(CALL, RTV)                      \
-  do {                                         \
-    if ((RTV) == 2) {                          \
-      if (h->cNT == 2) { CALL(2, 2); }         \
-      else { CALL(4, 2); }                     \
-    } else {                                   \
-      if (h->cNT == 2) { CALL(2, 1); }         \
-      else { CALL(4, 1); }                     \
-    }                                          \
-  } while (0)
 
 int launch_chain_fwd(dsact_handle* h, const char* name, FwdArgs& a) {
   if (h->fat) {
@@ -2123,24 +2212,14 @@ int launch_chain_fwd(dsact_handle* h, const char* name, FwdArgs& a) {
     if (!a.x0_lds) lds = (size_t)fat_lds(h->cW, 16 * rt, 0).total * sizeof(float);
     const int grid = a.n_units * a.u[0].n_slices;
     if (a.u[0].part_heads) h->n_heads_parts = a.u[0].n_slices;
-#define CALL_FF(N, T) return launch(h, name, k_fat_fwd<N, T>, dim3(grid), dim3(64 * N), lds, a)
-#define CALL_FFG(N, T) return launch(h, name, k_fat_fwd<N, T, true>, dim3(grid), dim3(64 * N), lds, a)
-    if (generic_act(h)) FAT_NT(CALL_FFG, rt);
-    FAT_NT(CALL_FF, rt);
-#undef CALL_FF
-#undef CALL_FFG
+    return kernels().fat_fwd.launch(h, name, {h->cNT, rt, generic_act(h)}, dim3(grid), dim3(64 * h->cNT), lds, a);
   }
   const int rg = chain_rg(h, a.n_units);
   fill_fwd_common(h, a, rg, name);
   const int grid = fwd_grid(a);
   const size_t lds = (size_t)chain_lds(4 * (h->s_obs + h->s_act), h->cW, 4 * rg).total * sizeof(float);
   if (a.u[0].part_heads) h->n_heads_parts = h->B / 4;   // one partial per four rows whatever the rows per workgroup (chain_fwd_body)
-#define CALL_CF(N, G) return launch(h, name, k_chain_fwd<N, G>, dim3(grid), dim3(64 * N), lds, a)
-#define CALL_CFG(N, G) return launch(h, name, k_chain_fwd<N, G, true>, dim3(grid), dim3(64 * N), lds, a)
-  if (generic_act(h)) CHAIN_NT(CALL_CFG, rg);
-  CHAIN_NT(CALL_CF, rg);
-#undef CALL_CF
-#undef CALL_CFG
+  return kernels().chain_fwd.launch(h, name, {h->cNT, rg, generic_act(h)}, dim3(grid), dim3(64 * h->cNT), lds, a);
 }
 
 int enqueue_chain_fwd_a(dsact_handle* h) {
@@ -2196,14 +2275,7 @@ int enqueue_chain_fwd_merged(dsact_handle* h) {
   if (h->flags_dirty) HIPCHK(h, hipMemsetAsync(h->chain_flags, 0, kChainFlags * sizeof(int), h->stream));
   h->flags_dirty = true;
   const size_t lds = (size_t)chain_lds(4 * (h->s_obs + h->s_act), h->cW, 4 * (rga > rgb ? rga : rgb)).total * sizeof(float);
-  if (generic_act(h)) {
-    if (h->cNT == 1) return launch(h, "chain_fwd", k_chain_fwd2<1, true>, dim3(grid), dim3(64), lds, m);
-    if (h->cNT == 2) return launch(h, "chain_fwd", k_chain_fwd2<2, true>, dim3(grid), dim3(128), lds, m);
-    return launch(h, "chain_fwd", k_chain_fwd2<4, true>, dim3(grid), dim3(256), lds, m);
-  }
-  if (h->cNT == 1) return launch(h, "chain_fwd", k_chain_fwd2<1>, dim3(grid), dim3(64), lds, m);
-  if (h->cNT == 2) return launch(h, "chain_fwd", k_chain_fwd2<2>, dim3(grid), dim3(128), lds, m);
-  return launch(h, "chain_fwd", k_chain_fwd2<4>, dim3(grid), dim3(256), lds, m);
+  return kernels().chain_fwd2.launch(h, "chain_fwd", {h->cNT, generic_act(h)}, dim3(grid), dim3(64 * h->cNT), lds, m);
 }
 
 // ---- pipelined graph (k_chain_fwdp, dsact_chain.h) ---------------------------------------------------------------
@@ -2400,23 +2472,9 @@ int launch_chain_fwd_pipe(dsact_handle* h, const char* name, const PipeFwd& host
     const size_t lb = (size_t)chain_lds(4 * h->SoT, h->cW, 4 * bp_rg).total * sizeof(float);
     if (lb > lds) lds = lb;
     if (lds < kDw2LdsFloats * sizeof(float)) lds = kDw2LdsFloats * sizeof(float);
-    if (generic_act(h)) {
-      if (h->cNT == 1) return launch(h, name, k_chain_fwdpb<1, true>, dim3(grid), dim3(256), lds, dev, *bp, bp_rg);
-      if (h->cNT == 2) return launch(h, name, k_chain_fwdpb<2, true>, dim3(grid), dim3(256), lds, dev, *bp, bp_rg);
-      return launch(h, name, k_chain_fwdpb<4, true>, dim3(grid), dim3(256), lds, dev, *bp, bp_rg);
-    }
-    if (h->cNT == 1) return launch(h, name, k_chain_fwdpb<1>, dim3(grid), dim3(256), lds, dev, *bp, bp_rg);
-    if (h->cNT == 2) return launch(h, name, k_chain_fwdpb<2>, dim3(grid), dim3(256), lds, dev, *bp, bp_rg);
-    return launch(h, name, k_chain_fwdpb<4>, dim3(grid), dim3(256), lds, dev, *bp, bp_rg);
+    return kernels().chain_fwdpb.launch(h, name, {h->cNT, generic_act(h)}, dim3(grid), dim3(256), lds, dev, *bp, bp_rg);
   }
-  if (generic_act(h)) {
-    if (h->cNT == 1) return launch(h, name, k_chain_fwdp<1, true>, dim3(grid), dim3(64), lds, dev);
-    if (h->cNT == 2) return launch(h, name, k_chain_fwdp<2, true>, dim3(grid), dim3(128), lds, dev);
-    return launch(h, name, k_chain_fwdp<4, true>, dim3(grid), dim3(256), lds, dev);
-  }
-  if (h->cNT == 1) return launch(h, name, k_chain_fwdp<1>, dim3(grid), dim3(64), lds, dev);
-  if (h->cNT == 2) return launch(h, name, k_chain_fwdp<2>, dim3(grid), dim3(128), lds, dev);
-  return launch(h, name, k_chain_fwdp<4>, dim3(grid), dim3(256), lds, dev);
+  return kernels().chain_fwdp.launch(h, name, {h->cNT, generic_act(h)}, dim3(grid), dim3(64 * h->cNT), lds, dev);
 }
 
 // loss + dZ chains of the critics (n_units 2: q1c, q2c only -- off iterations of the delayed update) and of
@@ -2495,14 +2553,10 @@ int enqueue_chain_bwd_q(dsact_handle* h, int n_units, const RideArgs* ride) {
   if (h->fat_bwd) {
     const int rt = rg / 4;
     const size_t flds = (size_t)fat_lds(h->cW, 16 * rt, 0).total * sizeof(float);
-#define CALL_FQ(N, T) return launch(h, "chain_bwd_q", k_fat_bwd_q<N, T>, dim3(a.n_chain_blocks + n_riders), dim3(kThreads), flds, a)
-    FAT_NT(CALL_FQ, rt);
-#undef CALL_FQ
+    return kernels().fat_bwd_q.launch(h, "chain_bwd_q", {h->cNT, rt}, dim3(a.n_chain_blocks + n_riders), dim3(kThreads), flds, a);
   }
   const size_t lds = (size_t)chain_lds(h->cW, h->cW, 4 * rg).total * sizeof(float);
-#define CALL_CQ(N, G) return launch(h, "chain_bwd_q", k_chain_bwd_q<N, G>, dim3(a.n_chain_blocks + n_riders), dim3(kThreads), lds, a)
-  CHAIN_NT(CALL_CQ, rg);
-#undef CALL_CQ
+  return kernels().chain_bwd_q.launch(h, "chain_bwd_q", {h->cNT, rg}, dim3(a.n_chain_blocks + n_riders), dim3(kThreads), lds, a);
 }
 
 // rsample backward + policy dZ chain; weight-gradient tiles [x0, x1) ride along on the other CUs
@@ -2559,16 +2613,13 @@ int enqueue_chain_bwd_pi(dsact_handle* h, int x0, int x1, bool fused, bool merge
     const int rt = rg / 4;
     size_t flds = (size_t)fat_lds(h->cW, 16 * rt, 16 * h->c_out).total * sizeof(float);
     if (flds < kDw2LdsFloats * sizeof(float)) flds = kDw2LdsFloats * sizeof(float);
-#define CALL_FP(N, T) return launch(h, "chain_bwd_pi", k_fat_bwd_pi<N, T>, dim3(a.n_chain_blocks + xcd_chunk_grid(a.n_extra) * h->dw_chunks), dim3(kThreads), flds, a)
-    FAT_NT(CALL_FP, rt);
-#undef CALL_FP
+    const int grid = a.n_chain_blocks + xcd_chunk_grid(a.n_extra) * h->dw_chunks;
+    return kernels().fat_bwd_pi.launch(h, "chain_bwd_pi", {h->cNT, rt}, dim3(grid), dim3(kThreads), flds, a);
   }
   size_t lds = (size_t)chain_lds(4 * h->SoT, h->cW, 4 * rg).total * sizeof(float);
   if (lds < kDw2LdsFloats * sizeof(float)) lds = kDw2LdsFloats * sizeof(float);
   const int tail = merge ? xcd_chunk_grid(a.n_extra) + xcd_chunk_grid(a.n_pi_tiles) + 1 : xcd_chunk_grid(a.n_extra) * h->dw_chunks;
-#define CALL_CP(N, G) return launch(h, "chain_bwd_pi", k_chain_bwd_pi<N, G>, dim3(a.n_chain_blocks + tail), dim3(kThreads), lds, a)
-  CHAIN_NT(CALL_CP, rg);
-#undef CALL_CP
+  return kernels().chain_bwd_pi.launch(h, "chain_bwd_pi", {h->cNT, rg}, dim3(a.n_chain_blocks + tail), dim3(kThreads), lds, a);
 }
 
 // pipelined graph, update whose policy backward is deferred into the next forward launch (k_chain_fwdpb): the last launch
@@ -2580,9 +2631,7 @@ int enqueue_chain_bwd_pi_close(dsact_handle* h, bool fused) {
   a.n_slices = 0; a.n_chain_blocks = 0; a.n_pi_tiles = 0;   // no chain slice arrives, nobody but the closing block waits (for 0 arrivals)
   const size_t lds = kDw2LdsFloats * sizeof(float);
   const int grid = xcd_chunk_grid(a.n_extra) + 1;
-#define CALL_CPC(N, G) return launch(h, "chain_dw_q", k_chain_bwd_pi<N, G>, dim3(grid), dim3(kThreads), lds, a)
-  CHAIN_NT(CALL_CPC, 2);
-#undef CALL_CPC
+  return kernels().chain_bwd_pi.launch(h, "chain_dw_q", {h->cNT, 2}, dim3(grid), dim3(kThreads), lds, a);   // (no slice: any RG does)
 }
 
 // k_chain_bwd_qt (dsact_chain.h): may the critics' backward, their weight-gradient tiles and the closing block of an update
@@ -2653,14 +2702,8 @@ int enqueue_chain_bwd_qt(dsact_handle* h, bool fused, const RideArgs* ride) {
   size_t lds = (size_t)chain_lds(h->cW, h->cW, 4 * rg).total * sizeof(float);
   if (lds < kDw2LdsFloats * sizeof(float)) lds = kDw2LdsFloats * sizeof(float);
   const int grid = a.q.n_chain_blocks + n_riders + a.n_tile_blocks + 1;
-  // (4- and 8-row slices only: the 16-row instantiations spilled 20-92 B under this kernel's three-workgroups-per-CU register
-  //  bound and were reachable only where bqt_ok() is false -- batch >= 1024, pi_merge off; VERDICT r5)
-  if (rg != 1 && rg != 2) return fail(h, DSACT_E_STATE, "k_chain_bwd_qt expects 4- or 8-row critic slices");
-#define CALL_CQT(N, G) return launch(h, "chain_bwd_qt", k_chain_bwd_qt<N, G>, dim3(grid), dim3(kThreads), lds, a)
-  if (rg == 1) { if (h->cNT == 1) { CALL_CQT(1, 1); } else if (h->cNT == 2) { CALL_CQT(2, 1); } else { CALL_CQT(4, 1); } }
-  if (h->cNT == 1) { CALL_CQT(1, 2); } else if (h->cNT == 2) { CALL_CQT(2, 2); }
-  CALL_CQT(4, 2);
-#undef CALL_CQT
+  // (4- and 8-row slices only: the table has no 16-row instances)
+  return kernels().chain_bwd_qt.launch(h, "chain_bwd_qt", {h->cNT, rg}, dim3(grid), dim3(kThreads), lds, a);
 }
 
 // k_chain_bwd_qpt: critics' backward -> policy backward -> every weight-gradient tile -> close, one launch
@@ -2695,15 +2738,8 @@ int enqueue_chain_bwd_qpt(dsact_handle* h, bool fused, const RideArgs* ride) {
   if (lp > lds) lds = lp;
   if (lds < kDw2LdsFloats * sizeof(float)) lds = kDw2LdsFloats * sizeof(float);
   const int grid = a.q.n_chain_blocks + a.pi.n_chain_blocks + n_riders + a.n_tile_blocks + xcd_chunk_grid(a.pi.n_pi_tiles) + 1;
-  if (rg_q != 1 || (rg_pi != 2 && rg_pi != 1)) return fail(h, DSACT_E_STATE, "k_chain_bwd_qpt expects 4-row critic slices and 4- or 8-row policy slices");
-  if (rg_pi == 1) {
-    if (h->cNT == 1) return launch(h, "chain_bwd_qpt", k_chain_bwd_qpt<1, 1, 1>, dim3(grid), dim3(kThreads), lds, a);
-    if (h->cNT == 2) return launch(h, "chain_bwd_qpt", k_chain_bwd_qpt<2, 1, 1>, dim3(grid), dim3(kThreads), lds, a);
-    return launch(h, "chain_bwd_qpt", k_chain_bwd_qpt<4, 1, 1>, dim3(grid), dim3(kThreads), lds, a);
-  }
-  if (h->cNT == 1) return launch(h, "chain_bwd_qpt", k_chain_bwd_qpt<1, 1, 2>, dim3(grid), dim3(kThreads), lds, a);
-  if (h->cNT == 2) return launch(h, "chain_bwd_qpt", k_chain_bwd_qpt<2, 1, 2>, dim3(grid), dim3(kThreads), lds, a);
-  return launch(h, "chain_bwd_qpt", k_chain_bwd_qpt<4, 1, 2>, dim3(grid), dim3(kThreads), lds, a);
+  // (4-row critic slices and 4- or 8-row policy slices only)
+  return kernels().chain_bwd_qpt.launch(h, "chain_bwd_qpt", {h->cNT, rg_q, rg_pi}, dim3(grid), dim3(kThreads), lds, a);
 }
 
 // which part of an update enqueue_grads enqueues
@@ -2851,8 +2887,7 @@ int enqueue_grads(dsact_handle* h, bool actor_backward, bool fused, GradPhase ph
     a.q_out_act = h->cfg.value_out_act; a.pi_out_act = h->cfg.policy_out_act; a.pi_out_n = h->cfg.policy_std_param ? A : 2 * A;
     a.qdmean[0] = h->qdmean[0]; a.qdmean[1] = h->qdmean[1]; a.pi_dact = h->pi_dact;
     a.timeline = tl_for(h, "heads");
-#define CALL_HEADS(N) TRY(launch(h, "heads", k_heads<N>, dim3(h->n_heads_wg, n_heads), dim3(kThreads), 0, a))
-    NCH_DISPATCH(a.W, CALL_HEADS);
+    TRY(kernels().heads.launch(h, "heads", {row_chunks(a.W)}, dim3(h->n_heads_wg, n_heads), dim3(kThreads), 0, a));
   }
   for (size_t l = 0; l < h->fwd2.size(); ++l) TRY(run_stage(h, h->fwd2[l]));
   if (h->use_std_sums || h->auto_std_sums) {
@@ -2891,8 +2926,7 @@ int enqueue_grads(dsact_handle* h, bool actor_backward, bool fused, GradPhase ph
     if (ride) a.ride = *ride;
     a.ride.n_loss_blocks = h->n_loss_wg;
     const int n_riders = ride ? ride->n_gather + (ride->bookkeeping ? 1 : 0) : 0;
-#define CALL_LOSS1(N) TRY(launch(h, "loss", k_loss_v1<N>, dim3(h->n_loss_wg + n_riders), dim3(kThreads), 0, a))
-    NCH_DISPATCH(a.W, CALL_LOSS1);
+    TRY(kernels().loss_v1.launch(h, "loss", {row_chunks(a.W)}, dim3(h->n_loss_wg + n_riders), dim3(kThreads), 0, a));
   } else {
     LossArgs a;
     memset(&a, 0, sizeof(a));
@@ -2924,8 +2958,7 @@ int enqueue_grads(dsact_handle* h, bool actor_backward, bool fused, GradPhase ph
     if (ride) a.ride = *ride;
     a.ride.n_loss_blocks = h->n_loss_wg;
     const int n_riders = ride ? ride->n_gather + (ride->bookkeeping ? 1 : 0) : 0;
-#define CALL_LOSS(N) TRY(launch(h, "loss", k_loss<N>, dim3(h->n_loss_wg + n_riders), dim3(kThreads), 0, a))
-    NCH_DISPATCH(a.W, CALL_LOSS);
+    TRY(kernels().loss.launch(h, "loss", {row_chunks(a.W)}, dim3(h->n_loss_wg + n_riders), dim3(kThreads), 0, a));
   }
   }
   if (!actor_backward) {
@@ -2986,8 +3019,7 @@ actor_part:
     a.fo = fused_opt(h, fused);
     if (ride_hb > 0) { a.extra = h->d_tiles + h->dw_off[0]; a.n_extra = ride_hb; }
     const size_t hb_lds = a.n_extra ? tile_lds_bytes(dw_k(h)) : 0;
-#define CALL_HBWD(N) TRY(launch(h, "heads_bwd", k_heads_bwd<N>, dim3(a.n_row_blocks + a.n_extra), dim3(kThreads), hb_lds, a))
-    NCH_DISPATCH(a.WL, CALL_HBWD);
+    TRY(kernels().heads_bwd.launch(h, "heads_bwd", {row_chunks(a.WL)}, dim3(a.n_row_blocks + a.n_extra), dim3(kThreads), hb_lds, a));
   }
   const size_t np = h->bwdpi.size();
   if (phase == PH_DP_ACTOR) {
@@ -3441,86 +3473,10 @@ int dsact_create(const dsact_config* cfg, int device, dsact_handle** out) {
   }
   HIPCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   h->own_stream = true;
-  {
-    const int max_lds = (int)tile_lds_bytes(BK * kMaxPrefetchTiles);  // 129 KB of the CU's 160 KB
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_stage<false, false, EPI_GELU>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_stage<false, false, EPI_GELU, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_stage<false, false, EPI_GELU, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_stage<false, true, EPI_MULG, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_stage<false, true, EPI_MULG, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_stage<false, true, EPI_MULG>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_stage_table, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_heads_bwd<1>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_heads_bwd<2>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_heads_bwd<3>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_heads_bwd<4>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_stage<false, true, EPI_STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<1, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<1, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<1, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<2, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<2, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<2, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<4, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<4, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd<4, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd2<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd2<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd2<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd2<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd2<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwd2<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdpb<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdpb<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdpb<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdpb<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdpb<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdpb<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdt<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdt<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdt<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdt<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdt<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdt<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdp<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdp<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdp<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdp<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdp<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_fwdp<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_q<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_q<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_q<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_q<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_q<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_q<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_q<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_q<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_q<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_pi<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_pi<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_pi<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_pi<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_pi<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_pi<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_pi<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_pi<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_chain_bwd_pi<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_stage64<false, EPI_GELU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile64_lds_bytes()));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_stage64<true, EPI_MULG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile64_lds_bytes()));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_stage64<true, EPI_STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile64_lds_bytes()));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_conv_fwd64<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile64_lds_bytes()));
-    HIPCHK(h, hipFuncSetAttribute((const void*)k_conv_fwd64<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile64_lds_bytes()));
-  }
+  // every instance of a family that may ask for more than the default 64 KB of dynamic LDS is granted its family's ceiling
+  for (const KernelFamily* f : kernels().all)
+    for (int c = 0; c < f->n_cells; ++c)
+      if (f->max_lds && f->cells[c]) HIPCHK(h, hipFuncSetAttribute(f->cells[c], hipFuncAttributeMaxDynamicSharedMemorySize, f->max_lds));
   HIPCHK(h, hipHostMalloc((void**)&h->handoff_host, 1024, hipHostMallocMapped));
   memset(h->handoff_host, 0, 1024);
   HIPCHK(h, hipHostGetDevicePointer((void**)&h->handoff_dev, h->handoff_host, 0));
@@ -3535,8 +3491,8 @@ int dsact_create(const dsact_config* cfg, int device, dsact_handle** out) {
     // correctness -- consumers only wait for lower block ids, which are always dispatched first)
     int per_cu = 0;
     const size_t la = (size_t)chain_lds(4 * (h->s_obs + h->s_act), h->cW, 4 * chain_rg(h, 6)).total * sizeof(float);
-    const void* fn = h->cNT == 1 ? (const void*)k_chain_fwd2<1> : h->cNT == 2 ? (const void*)k_chain_fwd2<2> : (const void*)k_chain_fwd2<4>;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * h->cNT, la) != hipSuccess || per_cu < 2) h->fwd_merge = false;
+    const void* fn = (const void*)kernels().chain_fwd2.find({h->cNT, false});
+    if (!fn || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * h->cNT, la) != hipSuccess || per_cu < 2) h->fwd_merge = false;
     (void)hipGetLastError();
   }
   for (int i = 0; i < 8; ++i) {
@@ -5766,9 +5722,7 @@ static int enqueue_policy_logits(dsact_handle* h, const float* obs_host, int32_t
   a.bout = net_params(h, N_POL) + h->pd.b_off[h->Lp];
   a.W = h->wp[h->Lp - 1]; a.n = n; a.A = h->A; a.lo_ls = h->cfg.min_log_std; a.hi_ls = h->cfg.max_log_std; a.out = h->act_out;
   a.out_act = h->cfg.policy_out_act; a.out_n = h->cfg.policy_std_param ? h->A : 2 * h->A;
-#define CALL_POUT(N) TRY(launch(h, "policy_out", k_policy_out<N>, dim3((n + 3) / 4), dim3(kThreads), 0, a))
-  NCH_DISPATCH(a.W, CALL_POUT);
-  return DSACT_OK;
+  return kernels().policy_out.launch(h, "policy_out", {row_chunks(a.W)}, dim3((n + 3) / 4), dim3(kThreads), 0, a);
 }
 
 // Evaluator.run_an_episode's acting (training/evaluator.py:50-72) for n environments: dist.mode() of policy(obs) per row
