@@ -47,6 +47,13 @@
 // reads, the conv stack and k_feat_scatter (dsact_conv.h) make the feature rows, and the launches above run the twin trunk
 // (ActBatchHidden::half) and the sample on them. The device-resident forms run the same chunks with kDev = true on frames read in
 // place; k_act_frames_u8 is the ingest for byte frames, codes into the coded ring's table.
+//
+// Exploration noise (dsact_set_explore_noise; training/off_sampler.py:58-65, utils/explore_noise.py:17-23):
+// k_act_batch_out<false, true, true> is the device-resident sampling form with `action + N(mean, std)` in its epilogue. The
+// normal is the acting draw's generator on stream id kExploreStream = 6: counter ((row0 + r) * ceil(A/4) + (shared ? 0 : d/4),
+// step low, step high, 6), key = the acting seed, element shared ? 0 : d % 4 -- never a counter block of eps. Then
+//   noise = __fmaf_rn(std[k], z, mean[k]) (k = shared ? 0 : d);  a = g.a + noise;  action = a;  clipped = min(max(a, lo), hi)
+// with g = tanh_gauss_fwd(...) as ever: logp is that of the un-noised sample, and the ring gets the un-clipped noised action.
 #pragma once
 #include "dsact_kernels.h"
 #include "dsact_conv.h"   // fast_div
@@ -82,8 +89,12 @@ struct ActBatchOut {
   unsigned long long seed;             // the acting seed (eps == nullptr: the draw is made here)
   long long step;                      // the acting-step counter
   int row0;                            // the first row of this launch in the whole call (the chunk offset)
+  // kExplore only (appended likewise): the exploration noise of dsact_set_explore_noise, device arrays the handle owns
+  const float* ex_mean; const float* ex_std;   // [1] (ex_shared) or [A]
+  int ex_shared;                       // one normal per row, added to every action dimension
 };
 constexpr uint32_t kActStream = 5u;
+constexpr uint32_t kExploreStream = 6u;
 
 // frame ingest of the CNN acting forward: n frames as the environment delivers them, src[r][c][pix] (C, H, W), into the
 // pixel-major rows of the conv kernels, dst[r][pix][c]. A pure permutation: no index table, no replay columns, no step
@@ -167,8 +178,9 @@ __global__ void __launch_bounds__(256) k_act_batch_hidden(ActBatchHidden a) {
 
 // 8 rows x 64 outputs (mean | raw log-std, 2A <= 64) per workgroup; thread (tr, tf) = (tid / 32, tid % 32) owns row tr and
 // outputs tf, tf + 32. grid: x = row tiles. kMode: the mode instead of the sample (eps and logp are not touched). kDev: the
-// device-resident form (see the header comment; with kMode it is the mode epilogue on the caller's device arrays)
-template <bool kMode, bool kDev>
+// device-resident form (see the header comment; with kMode it is the mode epilogue on the caller's device arrays). kExplore
+// (<false, true, true> only): exploration noise on the sampled action, before the clip
+template <bool kMode, bool kDev, bool kExplore = false>
 __global__ void __launch_bounds__(256) k_act_batch_out(ActBatchOut a) {
   constexpr int KC = 64;   // (the 64-row weight tile at 128 columns runs out of scalar registers)
   __shared__ float xs[8][KC + 1];
@@ -239,8 +251,17 @@ __global__ void __launch_bounds__(256) k_act_batch_out(ActBatchOut a) {
         e = q == 0 ? z[0] : q == 1 ? z[1] : q == 2 ? z[2] : z[3];
       }
       const TanhGaussFwd g = tanh_gauss_fwd(raw[tr][d], raw[tr][a.A + d], e, a.scale[d], a.center[d], a.lo_ls, a.hi_ls);
-      a.action[(size_t)r * a.A + d] = g.a;
-      a.clipped[(size_t)r * a.A + d] = fminf(fmaxf(g.a, a.lo[d]), a.hi[d]);
+      float act = g.a;
+      if constexpr (kExplore) {
+        float z[4];
+        normal4(a.seed, a.step, kExploreStream,
+                (uint32_t)(a.row0 + r) * (uint32_t)((a.A + 3) >> 2) + (a.ex_shared ? 0u : (uint32_t)(d >> 2)), z);
+        const int q = a.ex_shared ? 0 : d & 3, k = a.ex_shared ? 0 : d;
+        const float zq = q == 0 ? z[0] : q == 1 ? z[1] : q == 2 ? z[2] : z[3];
+        act = g.a + __fmaf_rn(a.ex_std[k], zq, a.ex_mean[k]);
+      }
+      a.action[(size_t)r * a.A + d] = act;
+      a.clipped[(size_t)r * a.A + d] = fminf(fmaxf(act, a.lo[d]), a.hi[d]);
       lps[tr][d] = g.lp;
     }
   } else {
@@ -356,16 +377,18 @@ template __global__ void k_act_batch_out<false, false>(ActBatchOut);
 template __global__ void k_act_batch_out<true, false>(ActBatchOut);
 template __global__ void k_act_batch_out<false, true>(ActBatchOut);
 template __global__ void k_act_batch_out<true, true>(ActBatchOut);
+template __global__ void k_act_batch_out<false, true, true>(ActBatchOut);
 #else
 __global__ void k_act_batch_hidden(ActBatchHidden a);
 __global__ void k_act_frames(ActFramesArgs a);
 __global__ void k_act_frames_u8(ActFramesU8Args a);
-template <bool kMode, bool kDev>
+template <bool kMode, bool kDev, bool kExplore = false>
 __global__ void k_act_batch_out(ActBatchOut a);
 extern template __global__ void k_act_batch_out<false, false>(ActBatchOut);
 extern template __global__ void k_act_batch_out<true, false>(ActBatchOut);
 extern template __global__ void k_act_batch_out<false, true>(ActBatchOut);
 extern template __global__ void k_act_batch_out<true, true>(ActBatchOut);
+extern template __global__ void k_act_batch_out<false, true, true>(ActBatchOut);
 #endif
 
 }  // namespace dsact

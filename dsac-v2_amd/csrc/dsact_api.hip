@@ -317,6 +317,9 @@ struct dsact_handle : BatchBufs {
   unsigned long long ring_commit_rows = 0;   // transitions written by dsact_buffer_add_device
   unsigned long long* digest_dev = nullptr;  // dsact_buffer_digest: the six 64-bit sums k_ring_digest adds into (allocated by the first call)
   unsigned long long act_dev_syncs = 0;  // stream synchronisations made inside those two entry points (stays 0)
+  // exploration noise of the device-resident sampling calls (dsact_set_explore_noise)
+  int explore_n = 0;                     // 0: off, 1: one normal per row (SHARED), act_dim: one per action dimension
+  float* explore_dev = nullptr;          // (mean[32] | std[32]) on the device, allocated by the first call that switches it on
   // device-resident evaluation (dsact_act_mode_device / dsact_eval_*): the episode bookkeeping's state
   int* ev_ep = nullptr; double* ev_acc = nullptr; int* ev_len = nullptr;   // [ev_cap_n]
   double* ev_returns = nullptr; int* ev_lengths = nullptr;                 // [ev_cap_e]
@@ -3528,6 +3531,7 @@ int dsact_destroy(dsact_handle* h) {
   if (h->ev_remaining_host) hipHostFree(h->ev_remaining_host);
   if (h->tk_dev) hipFree(h->tk_dev);
   if (h->digest_dev) hipFree(h->digest_dev);
+  if (h->explore_dev) hipFree(h->explore_dev);
   if (h->tk_host) hipHostFree(h->tk_host);
   for (int i = 0; i < 2; ++i) if (h->ab_h[i]) hipFree(h->ab_h[i]);
   if (h->pol_host) hipHostFree(h->pol_host);
@@ -5402,6 +5406,7 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "act_dev_calls")) *value = (double)h->act_dev_calls;       // dsact_act_sample_device chunks launched
   else if (!strcmp(name, "ring_commit_rows")) *value = (double)h->ring_commit_rows; // transitions written by dsact_buffer_add_device
   else if (!strcmp(name, "act_dev_syncs")) *value = (double)h->act_dev_syncs;       // stream drains inside those two (0)
+  else if (!strcmp(name, "explore_noise")) *value = (double)h->explore_n;           // dsact_set_explore_noise: 0 off, 1 SHARED, act_dim PER-DIMENSION
   else if (!strcmp(name, "act_mode_dev_calls")) *value = (double)h->act_mode_dev_calls;   // dsact_act_mode_device chunks launched
   else if (!strcmp(name, "eval_commit_calls")) *value = (double)h->eval_commit_calls;     // dsact_eval_commit launches
   else if (!strcmp(name, "eval_polls")) *value = (double)h->eval_polls;                   // dsact_eval_poll waits
@@ -5539,11 +5544,13 @@ static int act_batch_ready(dsact_handle* h, const char* who, const char* cnn_rou
   if (h->A > 32) return fail(h, DSACT_E_INVALID, "%s serves act_dim <= 32", who);
   return DSACT_OK;
 }
-// the four forms of the output launch, k_act_batch_out<kMode, kDev> at index kMode + 2 * kDev, under their profile names
-enum { kActOutSample = 0, kActOutMode = 1, kActOutSampleDev = 2, kActOutModeDev = 3 };
-static const struct { const char* name; void (*kernel)(ActBatchOut); } kActOutForms[4] = {
+// the forms of the output launch under their profile names: k_act_batch_out<kMode, kDev> at index kMode + 2 * kDev, then the
+// device-resident sampling form with exploration noise (dsact_set_explore_noise)
+enum { kActOutSample = 0, kActOutMode = 1, kActOutSampleDev = 2, kActOutModeDev = 3, kActOutSampleDevNoise = 4 };
+static const struct { const char* name; void (*kernel)(ActBatchOut); } kActOutForms[5] = {
     {"act_batch_out", k_act_batch_out<false, false>}, {"act_batch_mode", k_act_batch_out<true, false>},
-    {"act_batch_out_dev", k_act_batch_out<false, true>}, {"act_batch_mode_dev", k_act_batch_out<true, true>}};
+    {"act_batch_out_dev", k_act_batch_out<false, true>}, {"act_batch_mode_dev", k_act_batch_out<true, true>},
+    {"act_batch_out_dev_noise", k_act_batch_out<false, true, true>}};
 // policy(X[m][ldx]) for one chunk of m <= kActBatchCap device rows, enqueued on `stream`: one launch per hidden layer (ping-pong
 // through h->ab_h), then output form `form`. base: the policy net's parameters (the live arena, or a held behaviour copy).
 // o: the form's own fields (eps, action, logp; clipped, seed, step, row0) filled in by the caller, the rest zero -- the layer,
@@ -5767,6 +5774,33 @@ int dsact_set_act_rng(dsact_handle* h, uint64_t seed) {
   return DSACT_OK;
 }
 
+// GaussNoise(mean, std) of the reference's OffSampler (training/off_sampler.py:58-65, utils/explore_noise.py:17-23) for the
+// device-resident sampling calls: n = 0 off, 1 one normal per row, act_dim one per action dimension. The parameters go to
+// device memory of the handle's own behind everything enqueued (the way dsact_set_action_limits writes the limits)
+int dsact_set_explore_noise(dsact_handle* h, const float* mean, const float* sd, int32_t n) {
+  if (!h) return DSACT_E_INVALID;
+  if (n != 0 && n != 1 && n != h->A)
+    return fail(h, DSACT_E_INVALID, "dsact_set_explore_noise: n = %d is neither 0 (off), 1 (shared) nor act_dim = %d", (int)n, h->A);
+  if (n > 32) return fail(h, DSACT_E_INVALID, "dsact_set_explore_noise serves act_dim <= 32");
+  if (n > 0 && (!mean || !sd)) return fail(h, DSACT_E_INVALID, "dsact_set_explore_noise: mean and std are required when n > 0");
+  for (int j = 0; j < n; ++j)
+    if (!__builtin_isfinite(mean[j]) || !__builtin_isfinite(sd[j]) || sd[j] < 0.0f)
+      return fail(h, DSACT_E_INVALID, "dsact_set_explore_noise: mean must be finite, std finite and >= 0 (entry %d: %g, %g)", j,
+                  (double)mean[j], (double)sd[j]);
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  HIPCHK(h, hipStreamIsCapturing(h->stream, &cap));
+  if (cap != hipStreamCaptureStatusNone) return fail(h, DSACT_E_STATE, "dsact_set_explore_noise under stream capture");
+  if (n == 0) { h->explore_n = 0; return DSACT_OK; }   // (launches already enqueued keep reading the arrays: they stay)
+  if (!h->explore_dev) HIPCHK(h, hipMalloc((void**)&h->explore_dev, 64 * sizeof(float)));
+  float both[64] = {0};
+  for (int j = 0; j < n; ++j) { both[j] = mean[j]; both[32 + j] = sd[j]; }
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(h->explore_dev, both, sizeof(both), hipMemcpyHostToDevice));
+  h->explore_n = n;
+  return DSACT_OK;
+}
+
 // the device-resident forms: obs is read IN PLACE (no staging copy), the results land in the caller's device arrays, and
 // nothing waits -- per chunk of kActBatchCap rows the launches of enqueue_act_batch on the handle's stream (the live weights,
 // behind every enqueued update; also under a behaviour hold). An enabled CNN handle (dsact_cnn_acting_enable; DESIGN.md section
@@ -5783,6 +5817,10 @@ static int act_device(dsact_handle* h, const char* who, const char* host_form, c
                                   "(hip_obs_codebook / dsact_buffer_create_coded)", who);
   if (!mode && !eps_dev && h->act_seed == 0)
     return fail(h, DSACT_E_STATE, "eps == NULL draws the noise in the kernel: call dsact_set_act_rng with a non-zero seed first");
+  const bool explore = !mode && h->explore_n > 0;
+  if (explore && h->act_seed == 0)
+    return fail(h, DSACT_E_STATE, "exploration noise (dsact_set_explore_noise) is drawn in the kernel: call dsact_set_act_rng with a "
+                                  "non-zero seed first");
   HIPCHK(h, hipSetDevice(h->device));
   bool dev = on_handle_gpu(h, obs_dev) && on_handle_gpu(h, action_dev);
   if (!mode) dev = dev && (!eps_dev || on_handle_gpu(h, eps_dev)) && on_handle_gpu(h, clipped_dev) && on_handle_gpu(h, logp_dev);
@@ -5794,7 +5832,7 @@ static int act_device(dsact_handle* h, const char* who, const char* host_form, c
   const bool cnn = h->cnn_act;
   const int O = h->O, A = h->A, R = cnn ? kActFrameCap : kActBatchCap;
   const size_t elem = u8 ? 1 : sizeof(float);
-  const int form = mode ? kActOutModeDev : kActOutSampleDev;
+  const int form = mode ? kActOutModeDev : explore ? kActOutSampleDevNoise : kActOutSampleDev;
   for (int s = 0; s < n; s += R) {
     const int m = n - s < R ? n - s : R;
     ActBatchOut o = {};
@@ -5803,6 +5841,7 @@ static int act_device(dsact_handle* h, const char* who, const char* host_form, c
       o.eps = eps_dev ? eps_dev + (size_t)s * A : nullptr;
       o.logp = logp_dev + s; o.clipped = clipped_dev + (size_t)s * A;
       o.seed = h->act_seed; o.step = step; o.row0 = s;
+      if (explore) { o.ex_mean = h->explore_dev; o.ex_std = h->explore_dev + 32; o.ex_shared = h->explore_n == 1; }
     }
     const char* rows = (const char*)obs_dev + (size_t)s * O * elem;
     if (cnn) TRY(enqueue_act_cnn(h, rows, u8, m, net_params(h, N_POL), h->stream, o, form));

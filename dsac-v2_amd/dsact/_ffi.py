@@ -130,6 +130,7 @@ SYMBOLS = [
     ("dsact_stream_idle", C.c_int, [_P]),
     ("dsact_cnn_acting_enable", C.c_int, [_P]),
     ("dsact_set_act_rng", C.c_int, [_P, C.c_uint64]),
+    ("dsact_set_explore_noise", C.c_int, [_P, _P, _P, C.c_int32]),
     ("dsact_act_sample_device", C.c_int, [_P, _P, C.c_int32, _P, C.c_int64, _P, _P, _P]),
     ("dsact_buffer_add_device", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_double]),
     ("dsact_act_mode_device", C.c_int, [_P, _P, C.c_int32, _P]),

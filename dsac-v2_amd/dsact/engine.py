@@ -752,6 +752,20 @@ class DsactEngine:
         self._chk(self._lib.dsact_set_act_rng(self._h, int(seed)))
         self.act_seed = int(seed)
 
+    def set_explore_noise(self, mean=None, std=None):
+        """dsact_set_explore_noise: GaussNoise(mean, std) added to act_sample_device's sampled action before the clip, drawn in
+        the kernel on Philox stream 6 (needs set_act_rng). None: off (the default). Scalars or one-element arrays: ONE normal per
+        (row, step) for every action dimension; arrays of length act_dim: one per dimension. The host-returning calls, the
+        mode calls and the evaluators are not affected."""
+        if mean is None and std is None:
+            self._chk(self._lib.dsact_set_explore_noise(self._h, None, None, 0))
+            return
+        if mean is None or std is None:
+            raise ValueError("set_explore_noise takes mean and std together (or neither: off)")
+        m, s = np.broadcast_arrays(_f32(mean).reshape(-1), _f32(std).reshape(-1))
+        m, s = np.ascontiguousarray(m), np.ascontiguousarray(s)
+        self._chk(self._lib.dsact_set_explore_noise(self._h, _ffi.fptr(m), _ffi.fptr(s), int(m.shape[0])))
+
     def act_sample_device(self, obs, eps, step, action, clipped, logp):
         """dsact_act_sample_device: policy(obs[n, O]) on the live weights + the action distribution's sample, written into the
         caller's device tensors action[n, A] (what the ring stores), clipped[n, A] (inside the action limits: what the

@@ -31,9 +31,55 @@ def sample_batch_size(kwargs):
     return kwargs["batch_size_per_sampler"] if "batch_size_per_sampler" in kwargs else kwargs["sample_batch_size"]
 
 
-def refuse_noise(kwargs):
-    if kwargs.get("noise_params") is not None:
-        raise NotImplementedError("exploration noise is not part of the DSAC-T path (default None)")
+def explore_noise(kwargs):
+    """`noise_params` as the reference's OffSampler reads it for continuous actions (off_sampler.py:32-36: GaussNoise(**noise_params);
+    explore_noise.py:17-23: action + np.random.normal(mean, std), before the clip): None, or (mean, std, shared) with mean and std
+    the CALLER'S OWN objects -- the host routes hand them to NumPy as they are, so the global generator is consumed exactly as
+    the reference consumes it. shared: the draw has shape () or (1,) -- one normal for every action dimension; else it has shape
+    (A,): one per dimension (the length is checked against `action_dim` here when the kwargs carry it, and by
+    check_noise_dim as soon as a class knows its A). Everything else is refused, before anything runs."""
+    params = kwargs.get("noise_params")
+    if params is None:
+        return None
+    if kwargs.get("action_type", "continu") != "continu":
+        raise NotImplementedError("exploration noise is served for continuous actions (GaussNoise); the reference's EpsilonGreedy "
+                                  "for action_type %r is not part of this path" % (kwargs.get("action_type"),))
+    missing = [k for k in ("mean", "std") if k not in params]
+    if missing:
+        raise NotImplementedError("exploration noise: noise_params needs the keys 'mean' and 'std' of GaussNoise(mean, std); %s "
+                                  "missing (EpsilonGreedy's keys are not served)" % " and ".join(repr(k) for k in missing))
+    extra = sorted(str(k) for k in params if k not in ("mean", "std"))
+    if extra:
+        raise ValueError("noise_params takes exactly the keys 'mean' and 'std' (got also %s)" % ", ".join(extra))
+    mean, std = params["mean"], params["std"]
+    m, s = np.asarray(mean, np.float64), np.asarray(std, np.float64)
+    if not np.isfinite(m).all():
+        raise ValueError("noise_params['mean'] must be finite (got %r)" % (mean,))
+    if not (np.isfinite(s).all() and (s >= 0).all()):
+        raise ValueError("noise_params['std'] must be finite and >= 0 (got %r)" % (std,))
+    shape = np.broadcast_shapes(m.shape, s.shape)   # np.shape(np.random.normal(mean, std)), without a draw
+    if len(shape) > 1:
+        raise ValueError("np.random.normal(mean, std) has shape %r: exploration noise is a scalar or one value per action "
+                         "dimension" % (shape,))
+    noise = (mean, std, shape in ((), (1,)))
+    if kwargs.get("action_dim") is not None:
+        check_noise_dim(noise, int(kwargs["action_dim"]))
+    return noise
+
+
+def check_noise_dim(noise, act_dim):
+    """the shape rule of explore_noise against a known action dimension"""
+    if noise is None or noise[2]:
+        return
+    n = np.broadcast_shapes(np.shape(noise[0]), np.shape(noise[1]))[0]
+    if n != act_dim:
+        raise ValueError("noise_params: np.random.normal(mean, std) has %d entries, neither 1 nor the action dimension %d"
+                         % (n, act_dim))
+
+
+def noise_shape(noise):
+    """np.shape(np.random.normal(mean, std)): (), (1,) or (A,)"""
+    return tuple(np.broadcast_shapes(np.shape(noise[0]), np.shape(noise[1])))
 
 
 def networks_of(kwargs):

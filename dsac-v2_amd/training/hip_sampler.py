@@ -7,6 +7,15 @@ leave HBM: `networks.policy(obs)` of an attached ApproxContainer runs the fused-
 (dsact_policy_forward) on the batch-1 observation and returns the logits on the host, where the
 tanh-Gaussian draw consumes the torch global generator exactly like TanhGaussDistribution.sample().
 
+Exploration noise (`noise_params={"mean": ..., "std": ...}`, continuous actions; the reference's GaussNoise,
+off_sampler.py:32-36 and 58-65, utils/explore_noise.py:17-23): `action + np.random.normal(mean, std)`
+from the global NumPy generator, between the sample and the clip, in whatever dtype NumPy makes of it (array parameters make
+the action float64, as in the reference). The tuple carries the noised un-clipped action, the environment receives its clip,
+logp is the un-noised sample's. The fast path adds the same expression to the row after dsact_act_sample; its packed float32
+row gets the float32 cast. The draw has shape () or (1,) (one normal for every action dimension) or (A,). Refused before the
+environment is built: a dict without 'mean' / 'std' or a discrete action_type (NotImplementedError); another key, another
+shape, a negative or non-finite std, a non-finite mean (ValueError).
+
 Environment protocol (gym 0.23 style, what the reference's wrappers provide): `reset() -> (obs, info)`
 or `obs`; `step(a) -> (obs, r, done, info)` with `info["TimeLimit.truncated"]` on time-outs;
 `action_space.low/high`.
@@ -17,7 +26,7 @@ import numpy as np
 import torch
 
 from training.hip_acting_common import (ANY_POLICY, MLP_POLICY, _container, _reset, act_fast_ok, attached_engine,  # noqa: F401
-                                        cnn_act_engine, networks_of, refuse_noise, require_env_state, sample_batch_size)
+                                        check_noise_dim, cnn_act_engine, explore_noise, networks_of, require_env_state, sample_batch_size)
 
 __all__ = ["HipOffSampler", "create_sampler"]
 
@@ -36,13 +45,17 @@ class HipOffSampler:
     def __init__(self, index=0, **kwargs):
         from plugin import create_env
 
+        # exploration noise (off_sampler.py:32-36, 58-65; explore_noise.py:17-23): None, or (mean, std, shared) -- parsed and
+        # refused before anything else runs
+        self.noise = explore_noise(kwargs)
+        self.noise_params = kwargs.get("noise_params")
         self.env = kwargs.get("env") or create_env(**kwargs)
+        if self.noise is not None and getattr(self.env, "action_space", None) is not None:
+            check_noise_dim(self.noise, int(np.prod(np.shape(self.env.action_space.low))))
         if kwargs.get("seed") is not None and hasattr(self.env, "seed"):
             self.env.seed(kwargs["seed"])  # reference set_seed(..., env) seeds with the plain seed
         self.obs, self.info = _reset(self.env)
         self.networks = networks_of(kwargs)   # (the reference's throw-away container: built for its use of the torch generator)
-        refuse_noise(kwargs)
-        self.noise_params = None
         self.sample_batch_size = sample_batch_size(kwargs)
         self.action_type = kwargs.get("action_type", "continu")
         self.reward_scale = kwargs.get("reward_scale", 1)
@@ -105,6 +118,8 @@ class HipOffSampler:
         act_into = eng.act_sample_addr
         flat = np.ndim(obs) == 1
         maximum, minimum = np.maximum, np.minimum
+        noise, normal = self.noise, np.random.normal
+        check_noise_dim(noise, A)
         for i in range(n):
             ob = obs_b[i]
             ob[:] = obs if flat else np.reshape(obs, -1)
@@ -112,7 +127,14 @@ class HipOffSampler:
             act_into(obs_a + i * obs_s, eps_a, act_a + i * act_s, logp_a + 4 * i)
             self._fast_started = True     # (an environment step follows: no silent fallback from here on)
             a_i, c_i = act_b[i], clip_b[i]
-            minimum(maximum(a_i, low, out=c_i), high, out=c_i)
+            if noise is not None:
+                # the reference's expression on the row (explore_noise.py:23), in the dtype NumPy gives it: the tuple carries that
+                # value and the clip is taken from it; the packed float32 row gets its float32 cast (ReplayBuffer.store's)
+                a_n = a_i + normal(noise[0], noise[1])
+                a_i[:] = a_n
+                a_i, c_i = a_n, minimum(maximum(a_n, low), high)
+            else:
+                minimum(maximum(a_i, low, out=c_i), high, out=c_i)
             next_obs, reward, done, next_info = step(c_i)
             truncated = bool(next_info.get("TimeLimit.truncated", False))
             next_info["TimeLimit.truncated"] = truncated
@@ -157,6 +179,8 @@ class HipOffSampler:
                 action, logp = dist.sample()
             action = action.detach()[0].cpu().numpy()
             logp = logp.detach()[0].cpu().numpy()
+            if self.noise is not None:
+                action = action + np.random.normal(self.noise[0], self.noise[1])   # (off_sampler.py:58-59, explore_noise.py:23)
             action = np.array(action)
             clipped = action.clip(self.env.action_space.low, self.env.action_space.high)
             next_obs, reward, done, next_info = self.env.step(clipped)

@@ -32,6 +32,16 @@ advances by one per lockstep step and is assignable like the buffer's `index_ite
 pure function of (seed, t, i, action dimension): a run is reproducible from its seeds, and independent of N. It is NOT
 torch.randn's stream, so `strict_rng=True` is refused.
 
+Exploration noise (`noise_params={"mean": ..., "std": ...}`; the reference's GaussNoise, off_sampler.py:58-65 and
+explore_noise.py:17-23): `action + N(mean, std)` before the clip, drawn in the same acting kernel on a
+stream of its own -- Philox stream id 6, same seed, same step counter, so nothing leaves the GPU and nothing waits. The draw of
+np.random.normal(mean, std) has shape () or (1,): ONE normal per (environment, step), added to every action dimension (the
+reference with scalar parameters); shape (A,): one per dimension. The ring stores the noised, un-clipped action, the environment
+receives its clip, logp is the un-noised sample's. _setup hands the parameters to the engine once (set_explore_noise); without
+noise_params no such call is made. It is NOT the global NumPy generator's stream (a run is reproducible from hip_act_seed instead).
+Refused: a missing key or a discrete action_type (NotImplementedError); another key, another shape, a negative or non-finite
+std, a non-finite mean (ValueError).
+
 The clip: the kernel clips to the policy's action limits (dsact_set_action_limits). When the environment's limits are those
 -- the usual case -- its `clipped` output is what the environment receives; otherwise the clip is made with two torch ops on
 the device.
@@ -41,7 +51,7 @@ environment returns [N, C, H, W] frames, float32 or uint8. The [S, C, H, W] buff
 uint8 frame holds codes into the coded ring's codebook (hip_obs_codebook) and the engine's calls dispatch on the dtype.
 
 Refused (NotImplementedError / ValueError, before an environment step or an engine call is made): an unattached policy, a CNN
-policy outside that gate, strict_rng=True, noise_params, S not a multiple of N, an environment on another device than the engine. The overlapped
+policy outside that gate, strict_rng=True, malformed noise_params (above), S not a multiple of N, an environment on another device than the engine. The overlapped
 trainer (hip_off_async_trainer) refuses this sampler as an unknown sampler class: held-behaviour acting is not built for it.
 
 Episode statistics (`hip_episode_stats=True`; default off: exactly the calls above): how the N TRAINING
@@ -65,42 +75,37 @@ import time
 import numpy as np
 import torch
 
-from training.hip_acting_common import (engine_stream, hand_over, networks_of, on_stream, refuse_noise, require_env_state,
-                                        require_tensor_engine, sample_batch_size, tensor_limits)
+from training.hip_acting_common import (check_noise_dim, engine_stream, explore_noise, hand_over, networks_of, on_stream,
+                                        require_env_state, require_tensor_engine, sample_batch_size, tensor_limits)
 from training.hip_replay_buffer import act_seed_from
 from training.hip_sampler import SAMPLER_TIME_KEY
 
-__all__ = ["HipTensorEnvSampler", "DeviceSampleBatch", "act_noise_words", "act_noise_reference", "aggregate_episode_rows",
-           "EPISODE_TB_KEYS"]
+__all__ = ["HipTensorEnvSampler", "DeviceSampleBatch", "act_noise_words", "act_noise_reference", "explore_noise_words",
+           "explore_noise_reference", "aggregate_episode_rows", "EPISODE_TB_KEYS"]
 
 ACT_STREAM = 5    # the acting noise's Philox stream id (include/dsact.h: 1 .. 3 the update noise, 4 the index draw)
+EXPLORE_STREAM = 6   # the exploration noise's (dsact_set_explore_noise)
 _M32 = 0xFFFFFFFF
 
 
-def act_noise_words(seed, step, row, d, act_dim):
-    """(the four Philox4x32-10 words, which of the four normals) behind the in-kernel N(0,1) draw of environment `row`, action
-    dimension `d` at acting step `step` -- include/dsact.h's description in Python integers (no GPU, no library call): counter
-    (row * ceil(A/4) + d // 4, step low, step high, 5), key = the seed's (low, high) words; element d % 4."""
+def _philox_words(seed, step, block, stream=ACT_STREAM):
+    """the four Philox4x32-10 words of counter (block, step low, step high, stream) under key = the seed's (low, high) words"""
     step &= 0xFFFFFFFFFFFFFFFF
-    c0, c1, c2, c3 = (row * ((act_dim + 3) // 4) + d // 4) & _M32, step & _M32, step >> 32, ACT_STREAM
+    c0, c1, c2, c3 = block & _M32, step & _M32, step >> 32, stream
     k0, k1 = seed & _M32, (seed >> 32) & _M32
     for _ in range(10):
         p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
         c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & _M32, (p0 >> 32) ^ c3 ^ k1, p0 & _M32
         k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
-    return (c0, c1, c2, c3), d % 4
+    return c0, c1, c2, c3
 
 
-def act_noise_reference(seed, step, n_rows, act_dim):
-    """float64 [n_rows, act_dim]: the normals the kernel draws for rows 0 .. n_rows - 1 at `step`, by the Box-Muller map of
-    include/dsact.h evaluated in float64 on the same words (u = ((w >> 8) + 0.5) / 2^24; z0, z1 = r(u0) (cos, sin)(2 pi u1);
-    z2, z3 = r(u2) (cos, sin)(2 pi u3); r(u) = sqrt(-2 ln u)). act_noise_words over whole arrays (uint64 lanes holding 32-bit
-    words). The kernel evaluates the map in fp32: DESIGN.md section 15 has the measured distance."""
-    per_row = (act_dim + 3) // 4
+def _philox_normals(seed, step, n_blocks, stream=ACT_STREAM):
+    """float64 [n_blocks, 4]: the Box-Muller normals of counter blocks 0 .. n_blocks - 1 (uint64 lanes holding 32-bit words)"""
     step &= 0xFFFFFFFFFFFFFFFF
     m32 = np.uint64(_M32)
-    c0 = np.arange(n_rows * per_row, dtype=np.uint64) & m32
-    c1, c2, c3 = (np.full_like(c0, v) for v in (step & _M32, step >> 32, ACT_STREAM))
+    c0 = np.arange(n_blocks, dtype=np.uint64) & m32
+    c1, c2, c3 = (np.full_like(c0, v) for v in (step & _M32, step >> 32, stream))
     k0, k1 = seed & _M32, (seed >> 32) & _M32
     s32 = np.uint64(32)
     for _ in range(10):
@@ -109,7 +114,42 @@ def act_noise_reference(seed, step, n_rows, act_dim):
         k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
     u = [((w >> np.uint64(8)).astype(np.float64) + 0.5) / 16777216.0 for w in (c0, c1, c2, c3)]
     ra, rb = np.sqrt(-2.0 * np.log(u[0])), np.sqrt(-2.0 * np.log(u[2]))
-    z = np.stack([ra * np.cos(2 * np.pi * u[1]), ra * np.sin(2 * np.pi * u[1]), rb * np.cos(2 * np.pi * u[3]), rb * np.sin(2 * np.pi * u[3])], axis=1)
+    return np.stack([ra * np.cos(2 * np.pi * u[1]), ra * np.sin(2 * np.pi * u[1]), rb * np.cos(2 * np.pi * u[3]), rb * np.sin(2 * np.pi * u[3])], axis=1)
+
+
+def explore_noise_words(seed, step, row, d, act_dim, shared):
+    """act_noise_words for the exploration normal (dsact_set_explore_noise) of environment `row`, action dimension `d` at acting
+    step `step`: counter (row * ceil(A/4) + (0 if shared else d // 4), step low, step high, 6), the acting seed as the key;
+    element 0 if shared else d % 4 -- SHARED gives every d the normal of d = 0."""
+    if shared:
+        d = 0
+    return _philox_words(seed, step, row * ((act_dim + 3) // 4) + d // 4, EXPLORE_STREAM), d % 4
+
+
+def explore_noise_reference(seed, step, n_rows, act_dim, shared):
+    """float64 [n_rows, act_dim]: act_noise_reference for the exploration normals z of rows 0 .. n_rows - 1 at `step` (the kernel
+    adds fma(std, z, mean) to the sample). shared: every column of a row is that row's element 0."""
+    per_row = (act_dim + 3) // 4
+    z = _philox_normals(seed, step, n_rows * per_row, EXPLORE_STREAM).reshape(n_rows, per_row * 4)
+    if shared:
+        return np.ascontiguousarray(np.repeat(z[:, :1], act_dim, axis=1))
+    return np.ascontiguousarray(z[:, :act_dim])
+
+
+def act_noise_words(seed, step, row, d, act_dim):
+    """(the four Philox4x32-10 words, which of the four normals) behind the in-kernel N(0,1) draw of environment `row`, action
+    dimension `d` at acting step `step` -- include/dsact.h's description in Python integers (no GPU, no library call): counter
+    (row * ceil(A/4) + d // 4, step low, step high, 5), key = the seed's (low, high) words; element d % 4."""
+    return _philox_words(seed, step, row * ((act_dim + 3) // 4) + d // 4), d % 4
+
+
+def act_noise_reference(seed, step, n_rows, act_dim):
+    """float64 [n_rows, act_dim]: the normals the kernel draws for rows 0 .. n_rows - 1 at `step`, by the Box-Muller map of
+    include/dsact.h evaluated in float64 on the same words (u = ((w >> 8) + 0.5) / 2^24; z0, z1 = r(u0) (cos, sin)(2 pi u1);
+    z2, z3 = r(u2) (cos, sin)(2 pi u3); r(u) = sqrt(-2 ln u)). act_noise_words over whole arrays (uint64 lanes holding 32-bit
+    words). The kernel evaluates the map in fp32: DESIGN.md section 15 has the measured distance."""
+    per_row = (act_dim + 3) // 4
+    z = _philox_normals(seed, step, n_rows * per_row)
     return np.ascontiguousarray(z.reshape(n_rows, per_row * 4)[:, :act_dim])
 
 
@@ -202,7 +242,7 @@ class DeviceSampleBatch:
 
 class HipTensorEnvSampler:
     def __init__(self, index=0, **kwargs):
-        refuse_noise(kwargs)
+        self.noise = explore_noise(kwargs)    # None, or (mean, std, shared): drawn in the acting kernel
         if kwargs.get("strict_rng", False):
             raise ValueError("hip_tensor_env_sampler with strict_rng=True: the acting noise is drawn in the kernel (Philox), not "
                              "from torch.randn's stream; a parity run wants hip_vec_off_sampler")
@@ -237,7 +277,7 @@ class HipTensorEnvSampler:
         self._started = False             # env.reset() has been called
         self.networks = networks_of(kwargs)   # (the reference's throw-away container: built for its use of the torch generator)
         if kwargs.get("networks") is not None:
-            self._engine()                # an explicit policy is checked right away
+            check_noise_dim(self.noise, self._engine().act_dim)   # an explicit policy is checked right away
 
     def load_state_dict(self, state_dict):
         self.networks.load_state_dict(state_dict)
@@ -251,8 +291,10 @@ class HipTensorEnvSampler:
         return require_tensor_engine("hip_tensor_env_sampler", self.networks, self.action_type, self.env, self.cnn_act)
 
     def _setup(self, eng):
-        """once per engine: the [S, .] buffers, the acting seed, and whether the kernel's clip is the environment's"""
+        """once per engine: the [S, .] buffers, the acting seed, the exploration noise, and whether the kernel's clip is the
+        environment's"""
         N, S, O, A = self.n_envs, self.sample_batch_size, eng.obs_dim, eng.act_dim
+        check_noise_dim(self.noise, A)
         dev = torch.device(eng.device)
         f = dict(dtype=torch.float32, device=dev)
         # the observation rows: [., O] float32; an image environment on a CNN engine keeps [., C, H, W] rows in the FRAME's dtype
@@ -272,6 +314,8 @@ class HipTensorEnvSampler:
             self._obs = torch.zeros((N,) + row, dtype=odt, device=dev)
         self._low, self._high, self._kernel_clip = tensor_limits(self.env, eng, N)
         eng.set_act_rng(self.act_seed)
+        if self.noise is not None:
+            eng.set_explore_noise(self.noise[0], self.noise[1])   # (without noise_params no call is made: the handle's default is off)
         if self.episode_stats:
             eng.track_begin(N)            # (a new engine starts new statistics)
         if first is not None:
@@ -321,6 +365,13 @@ class HipTensorEnvSampler:
 
     RUN_STATE_FORMAT = "dsact-tensor-sampler-state/1"
 
+    def _noise_state(self):
+        """the parsed noise_params as run_state() carries them: None, or (mean list, std list, shared) in float64"""
+        if self.noise is None:
+            return None
+        return (np.asarray(self.noise[0], np.float64).reshape(-1).tolist(), np.asarray(self.noise[1], np.float64).reshape(-1).tolist(),
+                bool(self.noise[2]))
+
     def run_state(self):
         """What a resumed run needs of this sampler (HipOffSerialTrainer's hip_save_run_state): the counters
         act_step, sample_calls and total_sample_number, the current [N, O] observations as a CPU tensor, and the environment's
@@ -335,7 +386,8 @@ class HipTensorEnvSampler:
             env_sd = env.state_dict()
         eng.sync()
         return {"format": self.RUN_STATE_FORMAT, "act_step": int(self.act_step), "sample_calls": int(self.sample_calls),
-                "total_sample_number": int(self.total_sample_number), "act_seed": int(self.act_seed), "obs": obs, "env": env_sd}
+                "total_sample_number": int(self.total_sample_number), "act_seed": int(self.act_seed), "obs": obs, "env": env_sd,
+                "explore_noise": self._noise_state()}
 
     def load_run_state(self, sd):
         """restores what run_state() saved (named so that it cannot be mistaken for load_state_dict(networks))"""
@@ -345,6 +397,11 @@ class HipTensorEnvSampler:
         if int(sd.get("act_seed", self.act_seed)) != int(self.act_seed):
             raise ValueError("the saved sampler drew its acting noise with hip_act_seed %#x, this one with %#x: the resumed run would "
                              "act differently" % (int(sd["act_seed"]), int(self.act_seed)))
+        saved = sd.get("explore_noise")   # (a state saved before noise_params was served has no such key: no noise)
+        saved = None if saved is None else (list(saved[0]), list(saved[1]), bool(saved[2]))
+        if saved != self._noise_state():
+            raise ValueError("the saved sampler explored with noise_params (mean, std, shared) = %r, this one with %r: the resumed "
+                             "run would act differently" % (saved, self._noise_state()))
         eng = self._engine()
         if self._ready != id(eng):
             self._setup(eng)

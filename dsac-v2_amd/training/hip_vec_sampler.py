@@ -29,7 +29,15 @@ Acting routes (per sample(), one per lockstep step):
 A row's action depends only on its observation and its eps row: environment i's trajectory does not depend on how many
 environments run beside it (given the same draws).
 
-Exploration noise is not supported (as in HipOffSampler).
+Exploration noise (`noise_params={"mean": ..., "std": ...}`, continuous actions; the reference's GaussNoise, off_sampler.py:58-65
+and explore_noise.py:17-23): ONE draw per lockstep step from the global NumPy generator, np.random.normal(mean, std, size=(N,) +
+shape) with shape = np.shape(np.random.normal(mean, std)), made right after the step's acting call and before the clip. Row i is
+environment i's draw -- bit for bit the i-th of N sequential np.random.normal(mean, std) calls, so N = 1 is HipOffSampler's
+trajectory. Row i's action is what `action_i + np.random.normal(mean, std)` gives in NumPy's own arithmetic and dtype (float32
+for scalar parameters, whose draw is a Python float; float64 for array parameters); the tuples carry it un-clipped, the clip
+and the environment see it, the packed float32 rows get its float32 cast. logp is the un-noised sample's. A shape other than
+(), (1,) or (A,), a negative or non-finite std, a non-finite mean or another key: ValueError; a missing key or a discrete
+action_type: NotImplementedError -- all before an environment is built.
 """
 import time
 
@@ -37,7 +45,7 @@ import numpy as np
 import torch
 
 from training.hip_acting_common import (MLP_POLICY, _reset, act_fast_ok, attached_engine, cnn_act_engine, env_count, make_envs,
-                                        networks_of, refuse_noise, sample_batch_size)
+                                        networks_of, check_noise_dim, explore_noise, noise_shape, sample_batch_size)
 from training.hip_sampler import SAMPLER_TIME_KEY, HipOffSampler, SampleBatch
 
 __all__ = ["HipVecOffSampler", "DEFAULT_GPU_MIN_ENVS"]
@@ -53,7 +61,7 @@ class HipVecOffSampler:
         self.sample_batch_size = sample_batch_size(kwargs)
         if self.sample_batch_size % n:
             raise ValueError("the sample batch size %d is not a multiple of vector_env_num %d" % (self.sample_batch_size, n))
-        refuse_noise(kwargs)
+        self.noise = explore_noise(kwargs)
         self.act_mode = kwargs.get("hip_vec_act", "auto")
         if self.act_mode not in ("auto", "gpu", "host"):
             raise ValueError("hip_vec_act must be 'auto', 'gpu' or 'host' (got %r)" % (self.act_mode,))
@@ -83,6 +91,7 @@ class HipVecOffSampler:
         self.low = np.stack([np.asarray(e.action_space.low, np.float32).reshape(-1) for e in envs])
         self.high = np.stack([np.asarray(e.action_space.high, np.float32).reshape(-1) for e in envs])
         self._fast_ok = {}
+        check_noise_dim(self.noise, self.low.shape[1])
 
     # HipOffSampler's surface (the trainer assigns `networks`, the evaluator reads the sample count)
     def __getattr__(self, name):
@@ -153,6 +162,10 @@ class HipVecOffSampler:
         flat = len(self.obs_shape) == 1
         batch = SampleBatch()
         infos = self.infos
+        noise = self.noise
+        if noise is not None:
+            check_noise_dim(noise, A)
+            draw_shape = noise_shape(noise)
         obs_b[0:N] = self.obs
         for t in range(S // N):
             r0, r1 = t * N, (t + 1) * N
@@ -173,8 +186,17 @@ class HipVecOffSampler:
                     act_into = eng.act_sample_addr
                     for i in range(N):
                         act_into(ob[i].ctypes.data, eps_a + 4 * A * i, ac[i].ctypes.data, lp[i:i + 1].ctypes.data)
-            cl = clip_b[r0:r1]
-            minimum(maximum(ac, low, out=cl), high, out=cl)
+            if noise is not None:
+                # ONE draw per lockstep step, row i = the i-th sequential np.random.normal(mean, std); row i's action is
+                # `ac[i] + that draw` as NumPy evaluates it (a scalar draw is a Python float there: float32 arithmetic)
+                draw = np.random.normal(noise[0], noise[1], size=(N,) + draw_shape)
+                ac_t = ac + (draw.astype(np.float32)[:, None] if draw_shape == () else draw)
+                ac[...] = ac_t      # (the packed rows: the float32 cast)
+                cl = minimum(maximum(ac_t, low), high)
+            else:
+                ac_t = ac
+                cl = clip_b[r0:r1]
+                minimum(maximum(ac, low, out=cl), high, out=cl)
             steps = [e.step(cl[i]) for i, e in enumerate(envs)]
             obs2 = obs2_b[r0:r1]
             obs2[...] = [np.reshape(s[0], -1) for s in steps]
@@ -189,9 +211,9 @@ class HipVecOffSampler:
                 ni["TimeLimit.truncated"] = truncs[i]
                 next_infos.append(ni)
                 if flat:
-                    batch.append((ob[i], infos[i], ac[i], float(rew64[i]), obs2[i], dones[i], lp[i], ni))
+                    batch.append((ob[i], infos[i], ac_t[i], float(rew64[i]), obs2[i], dones[i], lp[i], ni))
                 else:
-                    batch.append((ob[i].reshape(self.obs_shape), infos[i], ac[i], float(rew64[i]),
+                    batch.append((ob[i].reshape(self.obs_shape), infos[i], ac_t[i], float(rew64[i]),
                                   obs2[i].reshape(self.obs_shape), dones[i], lp[i], ni))
             # the next step's observations: this step's, with every environment that ended reset on its own
             nxt = obs_b[r1:r1 + N] if r1 < S else self.obs

@@ -304,7 +304,8 @@ int dsact_set_noise(dsact_handle* h, const float* eps_new, const float* eps_2, c
  *   map      u_k = ((float)(w[k] >> 8) + 0.5f) * 2^-24 in fp32 (the add rounds to even once w >> 8 >= 2^23, so the largest u is
  *            1.0 and its normals are 0); r(u) = sqrt(-2 ln u); normals 0, 1 = r(u_0) (cos, sin)(2 pi u_1), normals 2, 3 =
  *            r(u_2) (cos, sin)(2 pi u_3), all in fp32. |normal| <= r(2^-25) = 5.89.
- * Stream ids 4 (dsact_set_index_rng) and 5 (dsact_set_act_rng) belong to the index draw and the acting noise.
+ * Stream ids 4 (dsact_set_index_rng) and 5 (dsact_set_act_rng) belong to the index draw and the acting noise, 6 to the
+ * exploration noise (dsact_set_explore_noise).
  * tests/noise_reference.py restates this; tests/test_update_noise_gpu.py holds every drawing site to it. */
 int dsact_set_device_rng(dsact_handle* h, uint64_t seed);
 
@@ -551,9 +552,27 @@ int dsact_cnn_acting_enable(dsact_handle* h);
  *                                  ASYNCHRONOUS on the handle's stream. fp32 MLP rings (DSACT_E_INVALID on coded rings and
  *                                  CNN handles without dsact_cnn_acting_enable; with it: "Device-resident image environments"
  *                                  below); device pointers of the handle's GPU only.
+ *   dsact_set_explore_noise(h, mean, std, n)   GaussNoise(mean, std) of the reference's OffSampler (training/off_sampler.py:58-65,
+ *                                  utils/explore_noise.py:17-23: action = action + np.random.normal(mean, std) before the clip)
+ *                                  for dsact_act_sample_device and dsact_act_sample_device_u8 ONLY -- the host-returning calls,
+ *                                  the mode calls and the evaluators never add noise (the host samplers add it in Python).
+ *                                  n = 0: off (the default of every handle; mean / std may be NULL). n = 1: SHARED, one normal
+ *                                  per (row, step) added to every action dimension (the reference with scalar parameters).
+ *                                  n = act_dim: PER-DIMENSION. Any other n, a non-finite entry or std < 0: DSACT_E_INVALID.
+ *                                  mean[n], std[n] are host arrays, copied into device memory of the handle's own behind
+ *                                  everything enqueued (the call waits for the stream, like dsact_set_action_limits);
+ *                                  DSACT_E_STATE under stream capture. With noise on, a sampling call without an acting seed
+ *                                  fails with DSACT_E_STATE -- also with eps passed in: this draw is always made in the kernel.
+ *     generator: the acting draw's, on stream id 6 -- philox4x32-10, counter (row * ceil(A/4) + (shared ? 0 : d/4), step low,
+ *                step high, 6), key = the acting seed, the Box-Muller map above, element shared ? 0 : d % 4: a pure function
+ *                of (seed, step, row, d) that never shares a counter block with eps.
+ *     epilogue:  noise = fma(std[k], z, mean[k]) (k = shared ? 0 : d; ONE rounding); a = sample + noise; action = a (what the
+ *                ring stores, un-clipped); clipped = min(max(a, low), high). logp is the un-noised sample's, as in the reference.
  * dsact_debug_get: "act_dev_calls" (chunks launched by dsact_act_sample_device), "ring_commit_rows" (transitions written by
- * dsact_buffer_add_device), "act_dev_syncs" (stream synchronisations made inside the two: 0). */
+ * dsact_buffer_add_device), "act_dev_syncs" (stream synchronisations made inside the two: 0), "explore_noise" (0, 1 or act_dim:
+ * the n of the last dsact_set_explore_noise). */
 int dsact_set_act_rng(dsact_handle* h, uint64_t seed);
+int dsact_set_explore_noise(dsact_handle* h, const float* mean, const float* std, int32_t n);
 int dsact_act_sample_device(dsact_handle* h, const float* obs_dev, int32_t n, const float* eps_dev, int64_t step,
                             float* action_dev, float* clipped_dev, float* logp_dev);
 int dsact_buffer_add_device(dsact_handle* h, int64_t n, const float* obs, const float* act, const float* rew, const float* obs2,

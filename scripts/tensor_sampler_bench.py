@@ -10,6 +10,10 @@ steps) for the baseline. Policy and update are the bench's Humanoid configuratio
         trainer: iterations / s of HipOffSerialTrainer at sample_interval K = 8, hip_device_indices=True
       one warm-up window per leg (which also sizes the windows to about --window seconds), then `pairs` alternating pairs of
       windows. Medians, per-pair ratios (tensor / vec) and each leg's spread over its own windows are recorded.
+  python scripts/tensor_sampler_bench.py --noise [--noise-n 1024] [--out profiles] [--pairs 3] [--window 0.6]
+      opt-in: the sampler-only metric of the tensor route alone, without and with
+      noise_params={"mean": 0.0, "std": 0.1} (the exploration noise drawn in the acting kernel), both legs in ONE fresh child
+      process with alternating windows. Writes DIR/explore_noise_bench.json; nothing else is run.
 Writes DIR/tensor_sampler_bench.json and prints it. The library must have been built (__graft_entry__.build())."""
 import argparse
 import json
@@ -56,7 +60,11 @@ class OneEnv:
         return o2[0].numpy(), float(r), bool(te), {"TimeLimit.truncated": bool(tr)}
 
 
+NOISE = {"mean": 0.0, "std": 0.1}
+
+
 def _leg(leg, N, trainer):
+    """leg: "tensor" | "vec"; "noise": the tensor leg with noise_params=NOISE"""
     import plugin
 
     kw = hip_kwargs(O, A, HID, B, seed=SEED, sample_batch_size=N, buffer_max_size=max(100_000, 4 * N), buffer_warm_size=max(B, N),
@@ -65,8 +73,9 @@ def _leg(leg, N, trainer):
     torch.manual_seed(SEED)
     np.random.seed(SEED)
     alg = plugin.create_alg(**kw)
-    if leg == "tensor":
-        smp = plugin.create_sampler(sampler_name="hip_tensor_env_sampler", env=SynthTensorHumanoid(N, device="cuda", seed=SEED), **kw)
+    if leg in ("tensor", "noise"):
+        smp = plugin.create_sampler(sampler_name="hip_tensor_env_sampler", env=SynthTensorHumanoid(N, device="cuda", seed=SEED),
+                                    **dict(kw, noise_params=NOISE if leg == "noise" else None))
     else:
         smp = plugin.create_sampler(sampler_name="hip_vec_off_sampler", envs=[OneEnv(i) for i in range(N)], hip_vec_act="gpu", **kw)
     smp.networks = alg.networks
@@ -96,7 +105,8 @@ def _window(alg, smp, tr, count):
 def run(N, metric, pairs, window):
     trainer = metric == "trainer"
     unit = K if trainer else 1
-    legs = {leg: _leg(leg, N, trainer) for leg in ("tensor", "vec")}
+    other = "noise" if metric == "noise" else "vec"      # metric "noise": sample() alone, the tensor route without / with noise
+    legs = {leg: _leg(leg, N, trainer) for leg in ("tensor", other)}
     counts = {}
     for leg, h in legs.items():                      # warm-up; its rate sizes the windows
         c = 2 * unit
@@ -108,13 +118,16 @@ def run(N, metric, pairs, window):
         for leg, h in legs.items():
             dt = _window(*h, counts[leg])
             rows[leg].append(counts[leg] * (1 if trainer else N) / dt)
-    ratios = [t / v for t, v in zip(rows["tensor"], rows["vec"])]
+    ratios = [t / v for t, v in zip(rows["tensor"], rows[other])]
     out = {"N": N, "metric": "iterations_per_s" if trainer else "env_steps_per_s", "window_counts": counts, "rows": rows,
            "median": {k: float(np.median(v)) for k, v in rows.items()},
-           "tensor_over_vec": ratios, "tensor_over_vec_median": float(np.median(ratios)),
+           "tensor_over_" + other: ratios, "tensor_over_%s_median" % other: float(np.median(ratios)),
            "spread": {k: (max(v) - min(v)) / float(np.median(v)) for k, v in rows.items()},
            "act_dev_syncs": legs["tensor"][0].engine.debug_get("act_dev_syncs"),
            "handoff_failures": {k: h[0].engine.debug_get("handoff_failures") for k, h in legs.items()}}
+    if other == "noise":
+        out["noise_params"] = NOISE
+        out["explore_noise"] = {k: h[0].engine.debug_get("explore_noise") for k, h in legs.items()}
     for h in legs.values():
         h[0].engine.close()
     return out
@@ -126,14 +139,16 @@ def main():
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--window", type=float, default=0.6)
     ap.add_argument("--only", default="", help="N:metric -- one configuration, in this process")
+    ap.add_argument("--noise", action="store_true", help="only the tensor route's sampler rate without / with exploration noise")
+    ap.add_argument("--noise-n", type=int, default=1024)
     a = ap.parse_args()
     if a.only:
         n, metric = a.only.split(":")
         print("RESULT " + json.dumps(run(int(n), metric, a.pairs, a.window)), flush=True)
         return
     res = {"pairs": a.pairs, "window_s": a.window, "policy": "376-256-256-256-34", "batch": B, "K": K, "configs": []}
-    for n in NS:
-        for metric in ("sampler", "trainer"):
+    for n in [a.noise_n] if a.noise else NS:
+        for metric in ("noise",) if a.noise else ("sampler", "trainer"):
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--only", "%d:%s" % (n, metric), "--pairs", str(a.pairs),
                                 "--window", str(a.window)], capture_output=True, text=True, timeout=420)
             line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
@@ -144,7 +159,7 @@ def main():
             res["configs"].append(r)
             print(json.dumps(r), flush=True)
     os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, "tensor_sampler_bench.json"), "w") as f:
+    with open(os.path.join(a.out, "explore_noise_bench.json" if a.noise else "tensor_sampler_bench.json"), "w") as f:
         json.dump(res, f, indent=1)
 
 
