@@ -54,6 +54,14 @@
 // step low, step high, 6), key = the acting seed, element shared ? 0 : d % 4 -- never a counter block of eps. Then
 //   noise = __fmaf_rn(std[k], z, mean[k]) (k = shared ? 0 : d);  a = g.a + noise;  action = a;  clipped = min(max(a, lo), hi)
 // with g = tanh_gauss_fwd(...) as ever: logp is that of the un-noised sample, and the ring gets the un-clipped noised action.
+//
+// The counted forms (dsact_act_sample_device_counted): k_act_batch_out<false, true, kExplore, true> is the
+// device-resident sampling form whose acting step is `*step_ptr + step` -- the handle's 8-byte counter in device memory plus the
+// launch's offset, one 64-bit add -- instead of the argument alone. A captured graph bakes its kernel arguments; the counter is
+// read when the launch RUNS, so every replay draws the noise of its own steps. Both Philox draws (streams 5 and 6) use the sum;
+// everything else is the uncounted form's instruction for instruction (same bits for the same effective step). The word is read
+// with one ordinary load per lane of the same address (a wave: one request), behind the kernel boundary that orders it with the
+// k_counter_add / k_counter_set launch that wrote it.
 #pragma once
 #include "dsact_kernels.h"
 #include "dsact_conv.h"   // fast_div
@@ -92,6 +100,8 @@ struct ActBatchOut {
   // kExplore only (appended likewise): the exploration noise of dsact_set_explore_noise, device arrays the handle owns
   const float* ex_mean; const float* ex_std;   // [1] (ex_shared) or [A]
   int ex_shared;                       // one normal per row, added to every action dimension
+  // kCounted only (appended likewise): the handle's acting-step counter in device memory (dsact_act_counter_set)
+  const unsigned long long* step_ptr;  // the draws are keyed by *step_ptr + step (64 bits, carry included)
 };
 constexpr uint32_t kActStream = 5u;
 constexpr uint32_t kExploreStream = 6u;
@@ -179,8 +189,9 @@ __global__ void __launch_bounds__(256) k_act_batch_hidden(ActBatchHidden a) {
 // 8 rows x 64 outputs (mean | raw log-std, 2A <= 64) per workgroup; thread (tr, tf) = (tid / 32, tid % 32) owns row tr and
 // outputs tf, tf + 32. grid: x = row tiles. kMode: the mode instead of the sample (eps and logp are not touched). kDev: the
 // device-resident form (see the header comment; with kMode it is the mode epilogue on the caller's device arrays). kExplore
-// (<false, true, true> only): exploration noise on the sampled action, before the clip
-template <bool kMode, bool kDev, bool kExplore = false>
+// (<false, true, true> only): exploration noise on the sampled action, before the clip. kCounted (<false, true, ., true> only): the
+// acting step is *step_ptr + step
+template <bool kMode, bool kDev, bool kExplore = false, bool kCounted = false>
 __global__ void __launch_bounds__(256) k_act_batch_out(ActBatchOut a) {
   constexpr int KC = 64;   // (the 64-row weight tile at 128 columns runs out of scalar registers)
   __shared__ float xs[8][KC + 1];
@@ -241,12 +252,14 @@ __global__ void __launch_bounds__(256) k_act_batch_out(ActBatchOut a) {
   if constexpr (kDev) {
     // eps from the caller's device array or drawn here; then tanh_gauss_fwd as below, plus the clipped copy
     if (r < a.n && d < a.A) {
+      long long step = a.step;
+      if constexpr (kCounted) step = (long long)(*a.step_ptr + (unsigned long long)a.step);
       float e;
       if (a.eps) {
         e = a.eps[(size_t)r * a.A + d];
       } else {
         float z[4];
-        normal4(a.seed, a.step, kActStream, (uint32_t)(a.row0 + r) * (uint32_t)((a.A + 3) >> 2) + (uint32_t)(d >> 2), z);
+        normal4(a.seed, step, kActStream, (uint32_t)(a.row0 + r) * (uint32_t)((a.A + 3) >> 2) + (uint32_t)(d >> 2), z);
         const int q = d & 3;
         e = q == 0 ? z[0] : q == 1 ? z[1] : q == 2 ? z[2] : z[3];
       }
@@ -254,7 +267,7 @@ __global__ void __launch_bounds__(256) k_act_batch_out(ActBatchOut a) {
       float act = g.a;
       if constexpr (kExplore) {
         float z[4];
-        normal4(a.seed, a.step, kExploreStream,
+        normal4(a.seed, step, kExploreStream,
                 (uint32_t)(a.row0 + r) * (uint32_t)((a.A + 3) >> 2) + (a.ex_shared ? 0u : (uint32_t)(d >> 2)), z);
         const int q = a.ex_shared ? 0 : d & 3, k = a.ex_shared ? 0 : d;
         const float zq = q == 0 ? z[0] : q == 1 ? z[1] : q == 2 ? z[2] : z[3];
@@ -378,17 +391,21 @@ template __global__ void k_act_batch_out<true, false>(ActBatchOut);
 template __global__ void k_act_batch_out<false, true>(ActBatchOut);
 template __global__ void k_act_batch_out<true, true>(ActBatchOut);
 template __global__ void k_act_batch_out<false, true, true>(ActBatchOut);
+template __global__ void k_act_batch_out<false, true, false, true>(ActBatchOut);
+template __global__ void k_act_batch_out<false, true, true, true>(ActBatchOut);
 #else
 __global__ void k_act_batch_hidden(ActBatchHidden a);
 __global__ void k_act_frames(ActFramesArgs a);
 __global__ void k_act_frames_u8(ActFramesU8Args a);
-template <bool kMode, bool kDev, bool kExplore = false>
+template <bool kMode, bool kDev, bool kExplore = false, bool kCounted = false>
 __global__ void k_act_batch_out(ActBatchOut a);
 extern template __global__ void k_act_batch_out<false, false>(ActBatchOut);
 extern template __global__ void k_act_batch_out<true, false>(ActBatchOut);
 extern template __global__ void k_act_batch_out<false, true>(ActBatchOut);
 extern template __global__ void k_act_batch_out<true, true>(ActBatchOut);
 extern template __global__ void k_act_batch_out<false, true, true>(ActBatchOut);
+extern template __global__ void k_act_batch_out<false, true, false, true>(ActBatchOut);
+extern template __global__ void k_act_batch_out<false, true, true, true>(ActBatchOut);
 #endif
 
 }  // namespace dsact

@@ -320,6 +320,10 @@ struct dsact_handle : BatchBufs {
   // exploration noise of the device-resident sampling calls (dsact_set_explore_noise)
   int explore_n = 0;                     // 0: off, 1: one normal per row (SHARED), act_dim: one per action dimension
   float* explore_dev = nullptr;          // (mean[32] | std[32]) on the device, allocated by the first call that switches it on
+  // the acting-step counter of a captured sample() (dsact_act_counter_*): one 8-byte device word
+  unsigned long long* act_counter_dev = nullptr;   // allocated by the first dsact_act_counter_set
+  bool act_counter_valid = false;        // ... which has been called
+  unsigned long long step_rows_calls = 0;   // dsact_step_rows_device launches
   // device-resident evaluation (dsact_act_mode_device / dsact_eval_*): the episode bookkeeping's state
   int* ev_ep = nullptr; double* ev_acc = nullptr; int* ev_len = nullptr;   // [ev_cap_n]
   double* ev_returns = nullptr; int* ev_lengths = nullptr;                 // [ev_cap_e]
@@ -3532,6 +3536,7 @@ int dsact_destroy(dsact_handle* h) {
   if (h->tk_dev) hipFree(h->tk_dev);
   if (h->digest_dev) hipFree(h->digest_dev);
   if (h->explore_dev) hipFree(h->explore_dev);
+  if (h->act_counter_dev) hipFree(h->act_counter_dev);
   if (h->tk_host) hipHostFree(h->tk_host);
   for (int i = 0; i < 2; ++i) if (h->ab_h[i]) hipFree(h->ab_h[i]);
   if (h->pol_host) hipHostFree(h->pol_host);
@@ -5412,6 +5417,7 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "eval_polls")) *value = (double)h->eval_polls;                   // dsact_eval_poll waits
   else if (!strcmp(name, "track_commit_calls")) *value = (double)h->track_commit_calls;   // dsact_track_commit launches
   else if (!strcmp(name, "track_reads")) *value = (double)h->track_reads;                 // dsact_track_read waits
+  else if (!strcmp(name, "step_rows_calls")) *value = (double)h->step_rows_calls;         // dsact_step_rows_device launches
   else if (!strcmp(name, "act_fast")) *value = (act_fast_ok(h) || h->cnn_act) ? 1.0 : 0.0;   // dsact_act_sample serves this handle (the one-launch forward, or the enabled CNN acting path)
   else if (!strcmp(name, "cnn_act")) *value = h->cnn_act ? 1.0 : 0.0;          // dsact_cnn_acting_enable has been called
   else if (!strcmp(name, "graph_cache")) *value = (double)h->graph_cache.size();   // inactive captured graphs kept by dsact_run_group
@@ -5545,12 +5551,16 @@ static int act_batch_ready(dsact_handle* h, const char* who, const char* cnn_rou
   return DSACT_OK;
 }
 // the forms of the output launch under their profile names: k_act_batch_out<kMode, kDev> at index kMode + 2 * kDev, then the
-// device-resident sampling form with exploration noise (dsact_set_explore_noise)
-enum { kActOutSample = 0, kActOutMode = 1, kActOutSampleDev = 2, kActOutModeDev = 3, kActOutSampleDevNoise = 4 };
-static const struct { const char* name; void (*kernel)(ActBatchOut); } kActOutForms[5] = {
+// device-resident sampling form with exploration noise (dsact_set_explore_noise), then the two device-resident sampling forms
+// whose acting step comes from the handle's counter (dsact_act_sample_device_counted): without and with exploration noise
+enum { kActOutSample = 0, kActOutMode = 1, kActOutSampleDev = 2, kActOutModeDev = 3, kActOutSampleDevNoise = 4,
+       kActOutSampleDevCounted = 5, kActOutSampleDevNoiseCounted = 6 };
+static const struct { const char* name; void (*kernel)(ActBatchOut); } kActOutForms[7] = {
     {"act_batch_out", k_act_batch_out<false, false>}, {"act_batch_mode", k_act_batch_out<true, false>},
     {"act_batch_out_dev", k_act_batch_out<false, true>}, {"act_batch_mode_dev", k_act_batch_out<true, true>},
-    {"act_batch_out_dev_noise", k_act_batch_out<false, true, true>}};
+    {"act_batch_out_dev_noise", k_act_batch_out<false, true, true>},
+    {"act_batch_out_dev_cnt", k_act_batch_out<false, true, false, true>},
+    {"act_batch_out_dev_noise_cnt", k_act_batch_out<false, true, true, true>}};
 // policy(X[m][ldx]) for one chunk of m <= kActBatchCap device rows, enqueued on `stream`: one launch per hidden layer (ping-pong
 // through h->ab_h), then output form `form`. base: the policy net's parameters (the live arena, or a held behaviour copy).
 // o: the form's own fields (eps, action, logp; clipped, seed, step, row0) filled in by the caller, the rest zero -- the layer,
@@ -5809,7 +5819,11 @@ int dsact_set_explore_noise(dsact_handle* h, const float* mean, const float* sd,
 // last launch (act_batch_gpu: a held call waits for it on the acting stream).
 // mode: dist.mode() (action only) instead of the sample. who / host_form name the entry point and its host-row counterpart
 static int act_device(dsact_handle* h, const char* who, const char* host_form, const char* cnn_route, const void* obs_dev, bool u8,
-                      int32_t n, const float* eps_dev, int64_t step, float* action_dev, float* clipped_dev, float* logp_dev, bool mode) {
+                      int32_t n, const float* eps_dev, int64_t step, float* action_dev, float* clipped_dev, float* logp_dev, bool mode,
+                      bool counted = false) {
+  // counted (dsact_act_sample_device_counted): the acting step is the handle's device counter + `step`, and
+  // the call may be made while the handle's stream is capturing -- then nothing below may allocate or wait
+  if (counted && h->cnn) return fail(h, DSACT_E_INVALID, "%s serves MLP policies (the CNN route records an event per call)", who);
   TRY(act_batch_ready(h, who, h->cnn_act ? nullptr : cnn_route));
   if (u8 && !h->cnn_act) return fail(h, DSACT_E_INVALID, "%s serves CNN policies after dsact_cnn_acting_enable", who);
   if (u8 && !h->rb_code)
@@ -5822,17 +5836,31 @@ static int act_device(dsact_handle* h, const char* who, const char* host_form, c
     return fail(h, DSACT_E_STATE, "exploration noise (dsact_set_explore_noise) is drawn in the kernel: call dsact_set_act_rng with a "
                                   "non-zero seed first");
   HIPCHK(h, hipSetDevice(h->device));
+  bool capturing = false;
+  if (counted) {
+    if (!h->act_counter_valid) return fail(h, DSACT_E_STATE, "%s before dsact_act_counter_set", who);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIPCHK(h, hipStreamIsCapturing(h->stream, &cap));
+    capturing = cap != hipStreamCaptureStatusNone;
+    if (capturing && !h->ab_h[0])
+      return fail(h, DSACT_E_STATE, "%s under stream capture before the batched forward's buffers exist: make one call outside "
+                                    "the capture first (it allocates them)", who);
+    if (capturing && h->profiling) return fail(h, DSACT_E_STATE, "%s under stream capture while profiling", who);
+  }
   bool dev = on_handle_gpu(h, obs_dev) && on_handle_gpu(h, action_dev);
   if (!mode) dev = dev && (!eps_dev || on_handle_gpu(h, eps_dev)) && on_handle_gpu(h, clipped_dev) && on_handle_gpu(h, logp_dev);
   if (!dev) return fail(h, DSACT_E_INVALID, "%s takes device pointers on the handle's GPU (host rows: %s)", who, host_form);
   if (h->cnn_act && !u8 && (uintptr_t)obs_dev % 16)   // (k_act_frames reads 16 bytes per lane, in place)
     return fail(h, DSACT_E_INVALID, "%s: fp32 frames must be 16-byte aligned", who);
-  TRY(check_handoff_counted(h));
+  // (under capture the hand-off check is left to the next entry point outside it: its failure path drains the stream)
+  if (!capturing) TRY(check_handoff_counted(h));
   TRY(alloc_act_batch(h));   // (the hidden layers' two activation buffers; the first call allocates)
   const bool cnn = h->cnn_act;
   const int O = h->O, A = h->A, R = cnn ? kActFrameCap : kActBatchCap;
   const size_t elem = u8 ? 1 : sizeof(float);
-  const int form = mode ? kActOutModeDev : explore ? kActOutSampleDevNoise : kActOutSampleDev;
+  const int form = mode ? kActOutModeDev
+                 : counted ? (explore ? kActOutSampleDevNoiseCounted : kActOutSampleDevCounted)
+                 : explore ? kActOutSampleDevNoise : kActOutSampleDev;
   for (int s = 0; s < n; s += R) {
     const int m = n - s < R ? n - s : R;
     ActBatchOut o = {};
@@ -5841,6 +5869,7 @@ static int act_device(dsact_handle* h, const char* who, const char* host_form, c
       o.eps = eps_dev ? eps_dev + (size_t)s * A : nullptr;
       o.logp = logp_dev + s; o.clipped = clipped_dev + (size_t)s * A;
       o.seed = h->act_seed; o.step = step; o.row0 = s;
+      if (counted) o.step_ptr = h->act_counter_dev;
       if (explore) { o.ex_mean = h->explore_dev; o.ex_std = h->explore_dev + 32; o.ex_shared = h->explore_n == 1; }
     }
     const char* rows = (const char*)obs_dev + (size_t)s * O * elem;
@@ -5852,7 +5881,7 @@ static int act_device(dsact_handle* h, const char* who, const char* host_form, c
     HIPCHK(h, hipEventRecord(h->ca_dev_ev, h->stream));
     h->ca_dev_pending = true;
   }
-  return check_handoff_counted(h);
+  return capturing ? DSACT_OK : check_handoff_counted(h);
 }
 
 int dsact_act_sample_device(dsact_handle* h, const float* obs_dev, int32_t n, const float* eps_dev, int64_t step,
@@ -5866,6 +5895,82 @@ int dsact_act_sample_device_u8(dsact_handle* h, const uint8_t* frames_dev, int32
   if (!h || !frames_dev || !action_dev || !clipped_dev || !logp_dev || n < 1) return DSACT_E_INVALID;
   return act_device(h, "dsact_act_sample_device_u8", "dsact_act_sample_batch", "dsact_policy_forward", frames_dev, true, n, eps_dev,
                     step, action_dev, clipped_dev, logp_dev, false);
+}
+
+// ---- the acting-step counter and the counted acting call ---------------------------------------------
+// A sample() captured into a graph (training/hip_tensor_sampler.py with hip_graph_sample) bakes every kernel argument, the acting
+// step among them; the handle therefore owns ONE 8-byte device word that the counted acting forms add to their `step` argument
+static int stream_capturing(dsact_handle* h, bool* capturing) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  HIPCHK(h, hipStreamIsCapturing(h->stream, &cap));
+  *capturing = cap != hipStreamCaptureStatusNone;
+  return DSACT_OK;
+}
+int dsact_act_counter_set(dsact_handle* h, uint64_t step) {
+  if (!h) return DSACT_E_INVALID;
+  HIPCHK(h, hipSetDevice(h->device));
+  bool capturing = false;
+  TRY(stream_capturing(h, &capturing));
+  if (capturing) return fail(h, DSACT_E_STATE, "dsact_act_counter_set under stream capture (the value would be baked into the graph)");
+  if (!h->act_counter_dev) HIPCHK(h, hipMalloc((void**)&h->act_counter_dev, sizeof(unsigned long long)));
+  TRY(launch(h, "counter_set", k_counter_set, dim3(1), dim3(64), 0, h->act_counter_dev, (unsigned long long)step));
+  h->act_counter_valid = true;
+  return DSACT_OK;
+}
+int dsact_act_counter_add(dsact_handle* h, int64_t k) {
+  if (!h) return DSACT_E_INVALID;
+  if (!h->act_counter_valid) return fail(h, DSACT_E_STATE, "dsact_act_counter_add before dsact_act_counter_set");
+  HIPCHK(h, hipSetDevice(h->device));
+  bool capturing = false;
+  TRY(stream_capturing(h, &capturing));
+  if (capturing && h->profiling) return fail(h, DSACT_E_STATE, "dsact_act_counter_add under stream capture while profiling");
+  return launch(h, "counter_add", k_counter_add, dim3(1), dim3(64), 0, h->act_counter_dev, (long long)k);
+}
+int dsact_act_counter_read(dsact_handle* h, uint64_t* out) {
+  if (!h || !out) return DSACT_E_INVALID;
+  if (!h->act_counter_valid) return fail(h, DSACT_E_STATE, "dsact_act_counter_read before dsact_act_counter_set");
+  HIPCHK(h, hipSetDevice(h->device));
+  bool capturing = false;
+  TRY(stream_capturing(h, &capturing));
+  if (capturing) return fail(h, DSACT_E_STATE, "dsact_act_counter_read under stream capture (it waits for the stream)");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  unsigned long long v = 0;
+  HIPCHK(h, hipMemcpy(&v, h->act_counter_dev, sizeof(v), hipMemcpyDeviceToHost));
+  *out = (uint64_t)v;
+  return check_handoff(h);
+}
+int dsact_act_sample_device_counted(dsact_handle* h, const float* obs_dev, int32_t n, int64_t step_offset, float* action_dev,
+                                    float* clipped_dev, float* logp_dev) {
+  if (!h || !obs_dev || !action_dev || !clipped_dev || !logp_dev || n < 1) return DSACT_E_INVALID;
+  return act_device(h, "dsact_act_sample_device_counted", "dsact_act_sample_batch", "dsact_policy_forward", obs_dev, false, n, nullptr,
+                    step_offset, action_dev, clipped_dev, logp_dev, false, true);
+}
+
+// the row copies of one lockstep step in one launch (k_step_rows, dsact_kernels.h). Legal under stream capture: a launch, no
+// allocation, no wait (the hand-off check is left to the next entry point outside the capture)
+int dsact_step_rows_device(dsact_handle* h, int32_t n, int32_t row_floats, const float* obs2_dev, const float* rew_dev,
+                           const uint8_t* terminated_dev, const uint8_t* truncated_dev, float* obs2_slot, float* rew_slot,
+                           uint8_t* terminated_slot, uint8_t* truncated_slot, uint8_t* ended_dev) {
+  if (!h || !obs2_dev || !rew_dev || !terminated_dev || !truncated_dev || !obs2_slot || !rew_slot || !terminated_slot ||
+      !truncated_slot || !ended_dev)
+    return DSACT_E_INVALID;
+  if (n < 1 || row_floats < 1) return fail(h, DSACT_E_INVALID, "dsact_step_rows_device: n = %d and row_floats = %d must be >= 1", (int)n, (int)row_floats);
+  HIPCHK(h, hipSetDevice(h->device));
+  const void* ptrs[9] = {obs2_dev, rew_dev, terminated_dev, truncated_dev, obs2_slot, rew_slot, terminated_slot, truncated_slot, ended_dev};
+  for (const void* p : ptrs)
+    if (!on_handle_gpu(h, p)) return fail(h, DSACT_E_INVALID, "dsact_step_rows_device takes device pointers on the handle's GPU");
+  bool capturing = false;
+  TRY(stream_capturing(h, &capturing));
+  if (capturing && h->profiling) return fail(h, DSACT_E_STATE, "dsact_step_rows_device under stream capture while profiling");
+  if (!capturing) TRY(check_handoff_counted(h));
+  StepRowsArgs a;
+  a.obs2 = obs2_dev; a.rew = rew_dev; a.term = terminated_dev; a.trunc = truncated_dev;
+  a.obs2_dst = obs2_slot; a.rew_dst = rew_slot; a.term_dst = terminated_slot; a.trunc_dst = truncated_slot; a.ended = ended_dev;
+  a.n = n; a.W = row_floats;
+  a.wide = (row_floats % 4 == 0) && ((uintptr_t)obs2_dev % 16 == 0) && ((uintptr_t)obs2_slot % 16 == 0);
+  TRY(launch(h, "step_rows", k_step_rows, dim3((unsigned)((n + 3) / 4)), dim3(kThreads), 0, a));
+  h->step_rows_calls++;
+  return DSACT_OK;
 }
 
 // ---- device-resident evaluation --------------------------------------------------------------------

@@ -877,6 +877,56 @@ __global__ void __launch_bounds__(kThreads) k_track_init(TrackArgs a, int all) {
 }
 #endif
 
+// The acting-step counter of a captured sample() (dsact_act_counter_set / dsact_act_counter_add): one 8-byte
+// word in device memory that the counted acting forms read (dsact_act_batch.h). A captured graph bakes kernel arguments, so the
+// step its launches draw noise for has to live in memory: k_counter_add is the graph's last node and moves the word on by the
+// lockstep steps of one sample(); k_counter_set writes a value the host chose (never captured: the value would be baked). One
+// lane, one vector load / store; launches on one stream are ordered by their kernel boundaries, so no atomic is needed.
+#ifndef DSACT_FAMILY_UNIT   // plain kernels: compiled in dsact_api.hip only (dsact_tu.h)
+__global__ void __launch_bounds__(64) k_counter_set(unsigned long long* word, unsigned long long value) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *word = value;
+}
+__global__ void __launch_bounds__(64) k_counter_add(unsigned long long* word, long long k) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *word = *word + (unsigned long long)k;
+}
+#endif
+
+// k_step_rows: the row copies of one lockstep step of the device-resident sampler (training/hip_tensor_sampler.py with
+// hip_graph_sample, dsact_step_rows_device) in ONE launch -- what the sampler otherwise issues as four
+// torch copies and one `|` (training/off_sampler.py:66-84 keeps the same five values per step in a Python tuple): the n
+// environments' next observations obs2[n][W], rewards and the two done flags go to their row slots of the [S, .] sample buffers
+// (the caller passes the slots' addresses: row t * n of each buffer), and ended[i] = terminated[i] | truncated[i] -- the mask of
+// env.reset -- is written beside them. Pure moves: every stored bit is a loaded bit (the flags are bytes, non-zero = set;
+// ended is 0 or 1).
+// k_ring_commit's launch shape: one wave per row, four rows per workgroup. `wide` (W % 4 == 0 and 16-byte aligned source and
+// slot): a lane moves 16 bytes per access (a 376-float row: 94 dwordx4, two passes of the wave), else 4 bytes (obs 17). Lane 0
+// moves the row's scalar columns. Vector loads and stores only; every access is inside row i < n of its array.
+struct StepRowsArgs {
+  const float* obs2; const float* rew; const unsigned char* term; const unsigned char* trunc;
+  float* obs2_dst; float* rew_dst; unsigned char* term_dst; unsigned char* trunc_dst; unsigned char* ended;
+  int n, W, wide;
+};
+#ifndef DSACT_FAMILY_UNIT   // plain kernel: compiled in dsact_api.hip only (dsact_tu.h)
+__global__ void __launch_bounds__(kThreads) k_step_rows(StepRowsArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long i = (long long)blockIdx.x * 4 + wave;
+  if (i >= a.n) return;
+  if (a.wide) {
+    const float4* s = reinterpret_cast<const float4*>(a.obs2 + (size_t)i * a.W);
+    float4* d = reinterpret_cast<float4*>(a.obs2_dst + (size_t)i * a.W);
+    for (int k = lane; k < a.W / 4; k += 64) d[k] = s[k];
+  } else {
+    for (int k = lane; k < a.W; k += 64) a.obs2_dst[(size_t)i * a.W + k] = a.obs2[(size_t)i * a.W + k];
+  }
+  if (lane == 0) {
+    const unsigned char t = a.term[i], u = a.trunc[i];   // (both loaded: no load behind a branch)
+    a.rew_dst[i] = a.rew[i];
+    a.term_dst[i] = t; a.trunc_dst[i] = u;
+    a.ended[i] = (t | u) != 0 ? 1 : 0;
+  }
+}
+#endif
+
 // ---------------------------------------------------------------------------------------------
 // k_tiles: C[m][n] (+epilogue) = sum_k P(m,k) * Q(n,k) on 32x32 tiles, BK = 64
 //   operand storage: KC  element (row,k) at base[row*ld + k]   (k contiguous)

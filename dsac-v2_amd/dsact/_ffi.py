@@ -137,6 +137,11 @@ SYMBOLS = [
     ("dsact_act_sample_device_u8", C.c_int, [_P, _P, C.c_int32, _P, C.c_int64, _P, _P, _P]),
     ("dsact_act_mode_device_u8", C.c_int, [_P, _P, C.c_int32, _P]),
     ("dsact_buffer_add_device_u8", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_double]),
+    ("dsact_act_counter_set", C.c_int, [_P, C.c_uint64]),
+    ("dsact_act_counter_add", C.c_int, [_P, C.c_int64]),
+    ("dsact_act_counter_read", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("dsact_act_sample_device_counted", C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P, _P]),
+    ("dsact_step_rows_device", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("dsact_eval_begin", C.c_int, [_P, C.c_int32, C.c_int32]),
     ("dsact_eval_commit", C.c_int, [_P, _P, _P, _P, _P]),
     ("dsact_eval_poll", C.c_int, [_P, _P]),

@@ -783,6 +783,57 @@ class DsactEngine:
         if rc != 0:
             self._chk(rc)
 
+    # ---- a sample() as one captured graph: the acting step lives in device memory --------------------------
+    def act_counter_set(self, step: int):
+        """dsact_act_counter_set: the acting-step counter's device word = step (mod 2^64), written in stream order. Refused under
+        stream capture (the value would be baked into the graph)."""
+        self._chk(self._lib.dsact_act_counter_set(self._h, int(step) & 0xFFFFFFFFFFFFFFFF))
+
+    def act_counter_add(self, k: int):
+        """dsact_act_counter_add: counter += k in stream order. Legal under stream capture: the node that closes a captured
+        sample()."""
+        rc = self._lib.dsact_act_counter_add(self._h, int(k))
+        if rc != 0:
+            self._chk(rc)
+
+    def act_counter_read(self) -> int:
+        """dsact_act_counter_read: the counter behind everything enqueued so far. WAITS for the engine's stream."""
+        v = C.c_uint64()
+        self._chk(self._lib.dsact_act_counter_read(self._h, C.byref(v)))
+        return int(v.value)
+
+    def act_sample_device_counted(self, obs, step_offset, action, clipped, logp):
+        """dsact_act_sample_device_counted: act_sample_device(obs, None, counter + step_offset, ...) with the counter read on the
+        device when the launch runs (act_counter_set first) -- bit for bit that call's action[n, A], clipped[n, A] and logp[n].
+        MLP policies, obs[n, O] float32. Asynchronous, and legal while the engine's stream is being captured into a graph (after
+        one call outside the capture, which makes the library's allocations)."""
+        f32 = (self.torch.float32,)
+        n = self._rows(obs)
+        A = self.act_dim
+        po = self._dev(obs, (n, self.obs_dim), f32, "obs")
+        pa, pc, pl = self._dev(action, (n, A), f32, "action"), self._dev(clipped, (n, A), f32, "clipped"), self._dev(logp, (n,), f32, "logp")
+        rc = self._lib.dsact_act_sample_device_counted(self._h, po, n, int(step_offset), pa, pc, pl)
+        if rc != 0:
+            self._chk(rc)
+
+    def step_rows_device(self, obs2, rew, terminated, truncated, obs2_slot, rew_slot, terminated_slot, truncated_slot, ended):
+        """dsact_step_rows_device: one lockstep step's row copies in one launch -- obs2[n, W] -> obs2_slot, rew[n] -> rew_slot,
+        terminated / truncated [n] -> their slots (the slots: n-row slices of the [S, .] sample buffers), and ended[n] =
+        terminated | truncated. float32 / bool (or uint8) contiguous tensors on this engine's GPU. Asynchronous; legal under
+        stream capture."""
+        torch = self.torch
+        f32, flag = (torch.float32,), (torch.bool, torch.uint8)
+        n = self._rows(rew)
+        W = int(obs2.shape[1]) if hasattr(obs2, "shape") and len(obs2.shape) == 2 else 0
+        ptrs = [self._dev(obs2, (n, W), f32, "obs2"), self._dev(rew, (n,), f32, "rew"),
+                self._dev(terminated, (n,), flag, "terminated"), self._dev(truncated, (n,), flag, "truncated"),
+                self._dev(obs2_slot, (n, W), f32, "obs2_slot"), self._dev(rew_slot, (n,), f32, "rew_slot"),
+                self._dev(terminated_slot, (n,), flag, "terminated_slot"), self._dev(truncated_slot, (n,), flag, "truncated_slot"),
+                self._dev(ended, (n,), flag, "ended")]
+        rc = self._lib.dsact_step_rows_device(self._h, n, W, *ptrs)
+        if rc != 0:
+            self._chk(rc)
+
     def _frames(self, t, n, name):
         """(address, is_uint8) of the observation rows of a device-resident call: [n, O] float32, and on a CNN engine with cnn_act
          also [n, C, H, W] rows and uint8 tensors of either shape -- byte frames, codes into the coded

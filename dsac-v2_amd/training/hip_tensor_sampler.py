@@ -65,6 +65,16 @@ returns: the only case in which sample() waits. The count is `sample_calls` (0 a
 like act_step) and includes the calls a trainer makes to warm the buffer up; a read whose dict nobody writes down is still a
 clearing read. INTEGRATION.md says how to line the reads up with HipOffSerialTrainer's log iterations.
 
+A sample() as one captured graph (`hip_graph_sample=True`; default off: exactly the calls above): the
+environment carries `capture_safe = True` -- step and reset(mask) update their state tensors in place, allocate nothing that
+must outlive the call, never touch the host and stay on torch's current stream. The first sample() after _setup runs eagerly
+through dsact_act_sample_device_counted (the acting step is a counter in device memory + the step's offset; dsact_act_counter_add
+closes the call), the second captures that body on the engine's stream and replays it, every later one is ONE replay();
+dsact_track_commit stays behind the replay. A step's four row copies and the `|` are one launch (dsact_step_rows_device).
+`act_step` stays assignable: the assignment writes the device counter too. `graph_captures` / `graph_replays` count. Refused in
+the constructor: an environment without the attribute, hip_cnn_act=True (NotImplementedError), a non-bool value (ValueError); at
+the first sample(): an engine off the GPU. A capture that raises is ended and re-raised as a RuntimeError naming the environment.
+
 sample() returns (DeviceSampleBatch, {sampler time}). The time is the HOST time of issuing the work. The batch's tensors are the
 sampler's own preallocated [S, .] buffers: they are valid until the next sample() call (add_batch consumes them in stream
 order before that).
@@ -271,7 +281,26 @@ class HipTensorEnvSampler:
         if not 0 < self.act_seed < (1 << 64):
             raise ValueError("hip_act_seed must be in [1, 2^64) (0 switches the in-kernel draw off), got %r" % (seed,))
         self.cnn_act = bool(kwargs.get("hip_cnn_act", False))   # image environments on an engine with the CNN acting path
-        self.act_step = 0                 # the acting-step counter: one per lockstep step (assignable)
+        # hip_graph_sample: sample() as one captured graph. Refused here, before any environment or engine call
+        graph = kwargs.get("hip_graph_sample", False)
+        if not isinstance(graph, (bool, np.bool_)):
+            raise ValueError("hip_graph_sample must be True or False, got %r" % (graph,))
+        self.graph_sample = bool(graph)
+        if self.graph_sample and self.cnn_act:
+            raise NotImplementedError("hip_graph_sample=True with hip_cnn_act=True: the CNN acting route records an event per call "
+                                      "and is not captured; use one of the two")
+        if self.graph_sample and getattr(env, "capture_safe", False) is not True:
+            raise NotImplementedError("hip_graph_sample=True needs an environment with the attribute capture_safe = True (step and "
+                                      "reset(mask) update their state tensors in place, allocate nothing that outlives the call, "
+                                      "never touch the host and stay on torch's current stream); %s does not promise it"
+                                      % type(env).__name__)
+        self.graph_captures = 0           # captures made / replays issued (the capturing call makes the first replay)
+        self.graph_replays = 0
+        self._graph = None                # the captured sample() (torch.cuda.CUDAGraph), dropped with a new engine
+        self._graph_calls = 0             # sample() calls on this engine: 0 -> eager warm-up, 1 -> capture, later -> replay
+        self._graph_eng = None            # the engine whose device counter mirrors act_step
+        self._one_launch_rows = True      # the row copies of a step as one launch (False: the torch copies; measurements)
+        self._act_step = 0                # the acting-step counter behind the `act_step` property: one per lockstep step (assignable)
         self.total_sample_number = 0
         self._ready = None                # id of the engine the buffers / seed / clip route were set up for
         self._started = False             # env.reset() has been called
@@ -290,12 +319,29 @@ class HipTensorEnvSampler:
         setup is refused"""
         return require_tensor_engine("hip_tensor_env_sampler", self.networks, self.action_type, self.env, self.cnn_act)
 
+    @property
+    def act_step(self):
+        """the acting-step counter (host mirror): one per lockstep step. With hip_graph_sample the kernels read its twin in device
+        memory (dsact_act_counter_*); an assignment writes both, in stream order."""
+        return self._act_step
+
+    @act_step.setter
+    def act_step(self, value):
+        self._act_step = int(value)
+        if self.graph_sample and self._graph_eng is not None and self._ready == id(self._graph_eng):   # (else _setup writes it)
+            self._graph_eng.act_counter_set(self._act_step)
+
     def _setup(self, eng):
         """once per engine: the [S, .] buffers, the acting seed, the exploration noise, and whether the kernel's clip is the
         environment's"""
         N, S, O, A = self.n_envs, self.sample_batch_size, eng.obs_dim, eng.act_dim
         check_noise_dim(self.noise, A)
         dev = torch.device(eng.device)
+        if self.graph_sample:
+            if dev.type != "cuda":
+                raise NotImplementedError("hip_graph_sample=True needs an engine on a GPU (a graph is captured from its stream); this "
+                                          "one is on %s" % dev)
+            self._graph, self._graph_calls, self._graph_eng = None, 0, eng   # a new engine: eager, capture, replay again
         f = dict(dtype=torch.float32, device=dev)
         # the observation rows: [., O] float32; an image environment on a CNN engine keeps [., C, H, W] rows in the FRAME's dtype
         # (float32, or uint8: codes into the coded ring's codebook -- DESIGN.md section 20)
@@ -318,11 +364,70 @@ class HipTensorEnvSampler:
             eng.set_explore_noise(self.noise[0], self.noise[1])   # (without noise_params no call is made: the handle's default is off)
         if self.episode_stats:
             eng.track_begin(N)            # (a new engine starts new statistics)
+        if self.graph_sample:
+            self._ended = torch.zeros(N, dtype=torch.bool, device=dev)   # terminated | truncated of a step: the mask of env.reset
+            eng.act_counter_set(self._act_step)                          # the device twin of act_step
         if first is not None:
             self._obs.copy_(first.reshape((N,) + row))
             self._started = True
         hand_over(eng)   # (the only wait this sampler ever makes, once)
         self._ready = id(eng)
+
+    def _graph_body(self, eng):
+        """hip_graph_sample: the S / N lockstep steps of one sample() on torch's current stream -- issued once eagerly, once under
+        capture, and replayed from then on. sample()'s own loop, except that the acting step is the device counter + t
+        (act_sample_device_counted), the four row copies and the `|` are one launch (step_rows_device; the torch copies where
+        the environment hands back anything but contiguous float32 / bool tensors) and act_counter_add(S / N) closes it."""
+        N, S = self.n_envs, self.sample_batch_size
+        env = self.env
+        obs_b, obs2_b, act_b, clip_b = self._obs_b, self._obs2_b, self._act_b, self._clip_b
+        rew_b, logp_b, term_b, trunc_b = self._rew_b, self._logp_b, self._term_b, self._trunc_b
+        obs_b[0:N].copy_(self._obs)
+        for t in range(S // N):
+            r0, r1 = t * N, (t + 1) * N
+            eng.act_sample_device_counted(obs_b[r0:r1], t, act_b[r0:r1], clip_b[r0:r1], logp_b[r0:r1])
+            if not self._kernel_clip:
+                torch.minimum(torch.maximum(act_b[r0:r1], self._low), self._high, out=clip_b[r0:r1])
+            obs2, rew, term, trunc = env.step(clip_b[r0:r1])
+            obs2 = obs2.reshape((N,) + self._row)
+            if (self._one_launch_rows and obs2.dim() == 2 and obs2.dtype == torch.float32 and rew.dtype == torch.float32 and term.dtype == torch.bool
+                    and trunc.dtype == torch.bool and tuple(rew.shape) == tuple(term.shape) == tuple(trunc.shape) == (N,)
+                    and obs2.is_contiguous() and rew.is_contiguous() and term.is_contiguous() and trunc.is_contiguous()):
+                eng.step_rows_device(obs2, rew, term, trunc, obs2_b[r0:r1], rew_b[r0:r1], term_b[r0:r1], trunc_b[r0:r1], self._ended)
+                ended = self._ended
+            else:
+                obs2_b[r0:r1].copy_(obs2)
+                rew_b[r0:r1].copy_(rew)
+                term_b[r0:r1].copy_(term)
+                trunc_b[r0:r1].copy_(trunc)
+                ended = term_b[r0:r1] | trunc_b[r0:r1]
+            nxt = env.reset(ended)
+            (obs_b[r1:r1 + N] if r1 < S else self._obs).copy_(nxt.reshape((N,) + self._row))
+        eng.act_counter_add(S // N)
+
+    def _graph_sample(self, eng, stream):
+        """one sample() of a hip_graph_sample sampler: the first call on an engine runs _graph_body eagerly (the warm-up: it makes
+        the library's lazy allocations), the second captures it into a graph on the engine's stream -- one linear chain -- and
+        replays it, every later call is one replay. A capture that raises is ended and reported; nothing is retried."""
+        if self._graph_calls == 0:
+            self._graph_body(eng)
+        else:
+            if self._graph is None:
+                graph = torch.cuda.CUDAGraph()
+                try:
+                    with torch.cuda.graph(graph, stream=stream, capture_error_mode="relaxed"):   # (its exit ends the capture)
+                        self._graph_body(eng)
+                except Exception as ex:
+                    raise RuntimeError("hip_graph_sample: capturing sample() failed with the environment %s (%s: %s). capture_safe = "
+                                       "True promises that step and reset(mask) update state in place, never touch the host and "
+                                       "stay on torch's current stream; build the sampler without hip_graph_sample for this "
+                                       "environment" % (type(self.env).__name__, type(ex).__name__, ex)) from ex
+                self._graph = graph
+                self.graph_captures += 1
+            self._graph.replay()
+            self.graph_replays += 1
+        self._graph_calls += 1
+        self._act_step += self.sample_batch_size // self.n_envs   # (the device counter moved itself: act_counter_add)
 
     def sample(self):
         eng = self._engine()
@@ -335,8 +440,11 @@ class HipTensorEnvSampler:
         rew_b, logp_b, term_b, trunc_b = self._rew_b, self._logp_b, self._term_b, self._trunc_b
         stream = engine_stream(eng)
         with on_stream(stream), torch.no_grad():
-            obs_b[0:N].copy_(self._obs)
-            for t in range(S // N):
+            if self.graph_sample:
+                self._graph_sample(eng, stream)       # (the steps below as one eager call, then one captured graph)
+            else:
+                obs_b[0:N].copy_(self._obs)
+            for t in range(0 if self.graph_sample else S // N):
                 r0, r1 = t * N, (t + 1) * N
                 eng.act_sample_device(obs_b[r0:r1], None, self.act_step, act_b[r0:r1], clip_b[r0:r1], logp_b[r0:r1])
                 self.act_step += 1

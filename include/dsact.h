@@ -636,6 +636,46 @@ int dsact_act_sample_device_u8(dsact_handle* h, const uint8_t* frames_dev, int32
 int dsact_act_mode_device_u8(dsact_handle* h, const uint8_t* frames_dev, int32_t n, float* action_dev);
 int dsact_buffer_add_device_u8(dsact_handle* h, int64_t n, const uint8_t* obs, const float* act, const float* rew, const uint8_t* obs2,
                                const uint8_t* terminated, const uint8_t* truncated, const float* logp, double reward_scale);
+
+/* ---- A sample() as one captured graph (training/hip_tensor_sampler.py with hip_graph_sample) ------------
+ * The device-resident sampler's lockstep steps (training/off_sampler.py:46-84 for N environments) are about twenty launches
+ * each, issued one at a time; captured into a graph they replay with one host call. A graph bakes every kernel argument, so the
+ * acting step that keys the Philox draws (streams 5 and 6 above) comes from ONE 8-byte word in device memory the handle owns:
+ *   dsact_act_counter_set(h, step)  writes the word in stream order (a one-lane launch that takes the value as its argument).
+ *                                  The first call allocates the word. DSACT_E_STATE under stream capture: the value would be
+ *                                  baked into the graph.
+ *   dsact_act_counter_add(h, k)     word += k in stream order (a one-lane launch); k may be negative. Legal under stream capture:
+ *                                  it is the node that closes a captured sample(), so every replay moves the counter on by the
+ *                                  lockstep steps it made. DSACT_E_STATE before dsact_act_counter_set.
+ *   dsact_act_counter_read(h, out)  WAITS for the handle's stream and copies the word to the host (tests, run_state()).
+ *                                  DSACT_E_STATE before dsact_act_counter_set and under stream capture.
+ *   dsact_act_sample_device_counted dsact_act_sample_device with eps == NULL and step = counter + step_offset (one 64-bit add in
+ *                                  the kernel, carry included): the same checks, the same chunking (a row's noise does not
+ *                                  depend on it), the same exploration-noise switch, bit for bit the same action / clipped /
+ *                                  logp as dsact_act_sample_device(eps = NULL, step = counter + step_offset). The counter is read
+ *                                  when the launch runs, behind every dsact_act_counter_* launch enqueued before it.
+ *                                  DSACT_E_INVALID on CNN handles; DSACT_E_STATE before dsact_act_counter_set and without an
+ *                                  acting seed. LEGAL WHILE THE HANDLE'S STREAM IS CAPTURING: it then allocates nothing
+ *                                  (DSACT_E_STATE if no earlier call has made the batched forward's buffers: make one call outside
+ *                                  the capture first), waits for nothing, and leaves the hand-off check to the next entry point
+ *                                  outside the capture.
+ *   dsact_step_rows_device          the row copies of one lockstep step (training/off_sampler.py:66-84: the step's next
+ *                                  observation, reward and done flags kept for the batch) in ONE launch: obs2[n*row_floats],
+ *                                  rew[n], terminated[n], truncated[n] (one byte each) are copied to the slots the caller names
+ *                                  (row t*n of its [S, .] buffers) and ended[i] = terminated[i] | truncated[i] (0 or 1: the mask
+ *                                  of the environment's reset) is written. Pure moves, 16 bytes per lane where row_floats % 4
+ *                                  == 0 and source and slot are 16-byte aligned. ASYNCHRONOUS, legal under stream capture; device
+ *                                  pointers of the handle's GPU only (DSACT_E_INVALID otherwise).
+ * dsact_debug_get: "step_rows_calls" (dsact_step_rows_device launches); the counted call's chunks count in "act_dev_calls", and
+ * "act_dev_syncs" stays 0 across all of the above but dsact_act_counter_read. */
+int dsact_act_counter_set(dsact_handle* h, uint64_t step);
+int dsact_act_counter_add(dsact_handle* h, int64_t k);
+int dsact_act_counter_read(dsact_handle* h, uint64_t* out);
+int dsact_act_sample_device_counted(dsact_handle* h, const float* obs_dev, int32_t n, int64_t step_offset, float* action_dev,
+                                    float* clipped_dev, float* logp_dev);
+int dsact_step_rows_device(dsact_handle* h, int32_t n, int32_t row_floats, const float* obs2_dev, const float* rew_dev,
+                           const uint8_t* terminated_dev, const uint8_t* truncated_dev, float* obs2_slot, float* rew_slot,
+                           uint8_t* terminated_slot, uint8_t* truncated_slot, uint8_t* ended_dev);
 int dsact_eval_begin(dsact_handle* h, int32_t n_envs, int32_t n_episodes);
 int dsact_eval_commit(dsact_handle* h, const float* reward_dev, const uint8_t* terminated_dev, const uint8_t* truncated_dev,
                       uint8_t* ended_dev);

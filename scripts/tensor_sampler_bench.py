@@ -14,6 +14,15 @@ steps) for the baseline. Policy and update are the bench's Humanoid configuratio
       opt-in: the sampler-only metric of the tensor route alone, without and with
       noise_params={"mean": 0.0, "std": 0.1} (the exploration noise drawn in the acting kernel), both legs in ONE fresh child
       process with alternating windows. Writes DIR/explore_noise_bench.json; nothing else is run.
+  python scripts/tensor_sampler_bench.py --graph [--tree DIR] [--out profiles] [--pairs 3] [--window 0.6]
+      opt-in: the tensor route issued eagerly against the same route with hip_graph_sample=True (sample()
+      as one captured graph, on tests/envs/synth_tensor_humanoid_inplace.py), N in 64, 256, 1024, each configuration in a fresh
+      child process with alternating windows: `sampler` (environment steps / s of sample() alone), `trainer1` / `trainer8`
+      (iterations / s of HipOffSerialTrainer at sample_interval 1 / 8), and `rows`: a hip_graph_sample sampler held on its eager
+      route, its row copies as one launch (dsact_step_rows_device) against the torch copies. --tree DIR runs the EAGER leg alone
+      with the package, helpers and fixtures of another checkout (DIR/dsac-v2_amd with its built library, DIR/tests): the parent
+      commit's numbers, recorded as "parent_eager" beside the others (DIR = this checkout: "eager_alone", the same process
+      layout on this tree -- a leg that shares its process with a second engine issues its launches about a tenth slower). Writes DIR/graph_sample_bench.json; nothing else is run.
 Writes DIR/tensor_sampler_bench.json and prints it. The library must have been built (__graft_entry__.build())."""
 import argparse
 import json
@@ -23,6 +32,9 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT_ROOT = ROOT
+if "--tree" in sys.argv:             # (before the imports below: they come from that checkout)
+    ROOT = os.path.abspath(sys.argv[sys.argv.index("--tree") + 1])
 for p in (ROOT, os.path.join(ROOT, "dsac-v2_amd"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "envs")):
     if p not in sys.path:
         sys.path.insert(0, p)
@@ -88,12 +100,15 @@ def _leg(leg, N, trainer):
     return alg, smp, tr
 
 
-def _window(alg, smp, tr, count):
-    """`count` sample() calls, or `count` trainer iterations; seconds, the stream drained at both ends"""
+def _window(alg, smp, tr, count, hold_eager=False):
+    """`count` sample() calls, or `count` trainer iterations; seconds, the stream drained at both ends. hold_eager: a
+    hip_graph_sample sampler is kept on its first (eager) call"""
     alg.engine.sync()
     t0 = time.perf_counter()
     if tr is None:
         for _ in range(count):
+            if hold_eager:
+                smp._graph_calls = 0
             smp.sample()
     else:
         tr.max_iteration = tr.iteration + count
@@ -133,15 +148,117 @@ def run(N, metric, pairs, window):
     return out
 
 
+GRAPH_NS = [64, 256, 1024]
+GRAPH_METRICS = ("sampler", "trainer1", "trainer8", "rows")
+
+
+def _graph_leg(leg, N, k):
+    """leg: "eager" (the plain tensor route) | "graph" (hip_graph_sample=True) | "rows" / "torch" (hip_graph_sample=True held on
+    its eager route, the row copies as one launch / as torch copies). k: sample_interval of a trainer, 0: sample() alone"""
+    import plugin
+
+    kw = hip_kwargs(O, A, HID, B, seed=SEED, sample_batch_size=N, buffer_max_size=max(100_000, 4 * N), buffer_warm_size=max(B, N),
+                    sample_interval=max(k, 1), max_iteration=0, log_save_interval=10 ** 9, apprfunc_save_interval=10 ** 9,
+                    eval_interval=10 ** 9, save_folder=None, ini_network_dir=None, strict_rng=False, hip_device_indices=True,
+                    hip_pad_widths=True)
+    torch.manual_seed(SEED)
+    np.random.seed(SEED)
+    alg = plugin.create_alg(**kw)
+    if leg == "eager":
+        env, more = SynthTensorHumanoid(N, device="cuda", seed=SEED), {}
+    else:
+        from synth_tensor_humanoid_inplace import SynthTensorHumanoidInplace
+        env, more = SynthTensorHumanoidInplace(N, device="cuda", seed=SEED), {"hip_graph_sample": True}
+    smp = plugin.create_sampler(**dict(kw, sampler_name="hip_tensor_env_sampler", env=env, **more))
+    smp.networks = alg.networks
+    if leg == "torch":
+        smp._one_launch_rows = False
+    tr = None
+    if k:
+        buf = plugin.create_buffer(**kw)
+        tr = plugin.create_trainer(alg, smp, buf, None, **kw)
+    return alg, smp, tr
+
+
+def run_graph(N, metric, pairs, window, parent):
+    k = {"sampler": 0, "rows": 0, "trainer1": 1, "trainer8": 8}[metric]
+    names = ("eager",) if parent else ("rows", "torch") if metric == "rows" else ("eager", "graph")
+    legs = {leg: _graph_leg(leg, N, k) for leg in names}
+    hold = metric == "rows"
+    unit = k or 1
+    counts = {}
+    for leg, h in legs.items():                      # warm-up (eager call, capture, replays); its rate sizes the windows
+        c = 4 * unit
+        dt = _window(*h, c, hold)
+        dt = _window(*h, c, hold)
+        counts[leg] = max(4 * unit, int(round(window / (dt / c) / unit)) * unit)
+    rows = {leg: [] for leg in legs}
+    for _ in range(pairs):
+        for leg, h in legs.items():
+            dt = _window(*h, counts[leg], hold)
+            rows[leg].append(counts[leg] * (N if not k else 1) / dt)
+    out = {"N": N, "metric": metric, "unit": "iterations_per_s" if k else "env_steps_per_s", "window_counts": counts, "rows": rows,
+           "median": {x: float(np.median(v)) for x, v in rows.items()},
+           "spread": {x: (max(v) - min(v)) / float(np.median(v)) for x, v in rows.items()},
+           "act_dev_syncs": {x: h[0].engine.debug_get("act_dev_syncs") for x, h in legs.items()},
+           "handoff_failures": {x: h[0].engine.debug_get("handoff_failures") for x, h in legs.items()}}
+    if len(names) == 2:
+        num, den = ("rows", "torch") if metric == "rows" else ("graph", "eager")
+        ratios = [a / b for a, b in zip(rows[num], rows[den])]
+        out["ratio"] = "%s_over_%s" % (num, den)
+        out["ratios"], out["ratio_median"] = ratios, float(np.median(ratios))
+    if "graph" in legs:
+        out["graph_captures"], out["graph_replays"] = legs["graph"][1].graph_captures, legs["graph"][1].graph_replays
+    for h in legs.values():
+        h[0].engine.close()
+    return out
+
+
+def main_graph(a):
+    parent = a.tree is not None
+    name = os.path.join(a.out, "graph_sample_bench.json")
+    res = {"pairs": a.pairs, "window_s": a.window, "policy": "376-256-256-256-34", "batch": B, "configs": [], "parent_eager": []}
+    if os.path.exists(name):                         # (the two trees are run one after the other into one file)
+        with open(name) as f:
+            res = json.load(f)
+    # (--tree pointing at this checkout: its own eager leg alone, the like-for-like partner of the other checkout's numbers)
+    key = ("eager_alone" if ROOT == OUT_ROOT else "parent_eager") if parent else "configs"
+    res[key] = []
+    for n in GRAPH_NS:
+        for metric in GRAPH_METRICS[:3] if parent else GRAPH_METRICS:
+            cmd = [sys.executable, os.path.abspath(__file__), "--graph", "--only", "%d:%s" % (n, metric), "--pairs", str(a.pairs),
+                   "--window", str(a.window)] + (["--tree", ROOT] if parent else [])
+            p = subprocess.run(cmd, capture_output=True, text=True, timeout=420)
+            line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+            if p.returncode != 0 or not line:
+                sys.stderr.write(p.stdout + p.stderr)
+                raise SystemExit("configuration %d:%s failed (exit status %d)" % (n, metric, p.returncode))
+            r = json.loads(line[-1][len("RESULT "):])
+            res[key].append(r)
+            print(json.dumps(r), flush=True)
+    os.makedirs(a.out, exist_ok=True)
+    with open(name, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
+    ap.add_argument("--out", default=os.path.join(OUT_ROOT, "profiles"))
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--window", type=float, default=0.6)
     ap.add_argument("--only", default="", help="N:metric -- one configuration, in this process")
     ap.add_argument("--noise", action="store_true", help="only the tensor route's sampler rate without / with exploration noise")
     ap.add_argument("--noise-n", type=int, default=1024)
+    ap.add_argument("--graph", action="store_true", help="only the tensor route eager against hip_graph_sample=True")
+    ap.add_argument("--tree", default=None, help="with --graph: the eager leg alone from another checkout (the parent commit)")
     a = ap.parse_args()
+    if a.graph and a.only:
+        n, metric = a.only.split(":")
+        print("RESULT " + json.dumps(run_graph(int(n), metric, a.pairs, a.window, a.tree is not None)), flush=True)
+        return
+    if a.graph:
+        main_graph(a)
+        return
     if a.only:
         n, metric = a.only.split(":")
         print("RESULT " + json.dumps(run(int(n), metric, a.pairs, a.window)), flush=True)
