@@ -331,6 +331,8 @@ struct dsact_handle : BatchBufs {
   int* ev_remaining_host = nullptr;       // its pinned landing place (dsact_eval_poll)
   int ev_cap_n = 0, ev_cap_e = 0;
   int ev_n = 0, ev_e = 0;                 // the running evaluation's N and E (0: no dsact_eval_begin yet)
+  unsigned long long ev_gen = 0;          // +1 whenever dsact_eval_begin (re)allocates an ev_* array: a captured dsact_eval_commit
+                                          // holds their addresses and is valid for the generation it was captured under only
   unsigned long long act_mode_dev_calls = 0;   // dsact_act_mode_device chunks launched
   unsigned long long eval_commit_calls = 0, eval_polls = 0;
   // episode statistics of the training environments (dsact_track_*): ONE device block of tk_n rows laid out
@@ -5415,6 +5417,7 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "act_mode_dev_calls")) *value = (double)h->act_mode_dev_calls;   // dsact_act_mode_device chunks launched
   else if (!strcmp(name, "eval_commit_calls")) *value = (double)h->eval_commit_calls;     // dsact_eval_commit launches
   else if (!strcmp(name, "eval_polls")) *value = (double)h->eval_polls;                   // dsact_eval_poll waits
+  else if (!strcmp(name, "eval_state_gen")) *value = (double)h->ev_gen;                   // (re)allocations of the ev_* arrays
   else if (!strcmp(name, "track_commit_calls")) *value = (double)h->track_commit_calls;   // dsact_track_commit launches
   else if (!strcmp(name, "track_reads")) *value = (double)h->track_reads;                 // dsact_track_read waits
   else if (!strcmp(name, "step_rows_calls")) *value = (double)h->step_rows_calls;         // dsact_step_rows_device launches
@@ -5822,7 +5825,8 @@ static int act_device(dsact_handle* h, const char* who, const char* host_form, c
                       int32_t n, const float* eps_dev, int64_t step, float* action_dev, float* clipped_dev, float* logp_dev, bool mode,
                       bool counted = false) {
   // counted (dsact_act_sample_device_counted): the acting step is the handle's device counter + `step`, and
-  // the call may be made while the handle's stream is capturing -- then nothing below may allocate or wait
+  // the call may be made while the handle's stream is capturing -- then nothing below may allocate or wait. The mode form of an
+  // MLP handle may be captured too (it draws nothing, so it needs no counter)
   if (counted && h->cnn) return fail(h, DSACT_E_INVALID, "%s serves MLP policies (the CNN route records an event per call)", who);
   TRY(act_batch_ready(h, who, h->cnn_act ? nullptr : cnn_route));
   if (u8 && !h->cnn_act) return fail(h, DSACT_E_INVALID, "%s serves CNN policies after dsact_cnn_acting_enable", who);
@@ -5837,11 +5841,15 @@ static int act_device(dsact_handle* h, const char* who, const char* host_form, c
                                   "non-zero seed first");
   HIPCHK(h, hipSetDevice(h->device));
   bool capturing = false;
-  if (counted) {
-    if (!h->act_counter_valid) return fail(h, DSACT_E_STATE, "%s before dsact_act_counter_set", who);
+  if (counted && !h->act_counter_valid) return fail(h, DSACT_E_STATE, "%s before dsact_act_counter_set", who);
+  // the mode call (dsact_act_mode_device) may be made under capture by the same rules. The status query is
+  // made for these two forms only: the uncounted sampling forms make the runtime calls they always made
+  if (counted || mode) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIPCHK(h, hipStreamIsCapturing(h->stream, &cap));
     capturing = cap != hipStreamCaptureStatusNone;
+    if (capturing && h->cnn)
+      return fail(h, DSACT_E_INVALID, "%s under stream capture serves MLP policies (the CNN route records an event per call)", who);
     if (capturing && !h->ab_h[0])
       return fail(h, DSACT_E_STATE, "%s under stream capture before the batched forward's buffers exist: make one call outside "
                                     "the capture first (it allocates them)", who);
@@ -6000,13 +6008,18 @@ int dsact_eval_begin(dsact_handle* h, int32_t n_envs, int32_t n_episodes) {
   if (!h) return DSACT_E_INVALID;
   if (n_envs < 1 || n_episodes < 1) return fail(h, DSACT_E_INVALID, "dsact_eval_begin: n_envs = %d and n_episodes = %d must be >= 1", (int)n_envs, (int)n_episodes);
   HIPCHK(h, hipSetDevice(h->device));
+  bool capturing = false;
+  TRY(stream_capturing(h, &capturing));
+  if (capturing) return fail(h, DSACT_E_STATE, "dsact_eval_begin under stream capture (it allocates and may wait for the stream)");
   if (!h->ev_remaining) {
+    h->ev_gen++;
     HIPCHK(h, hipMalloc(&h->ev_remaining, 64));
     HIPCHK(h, hipHostMalloc((void**)&h->ev_remaining_host, 64, hipHostMallocDefault));
   }
   if (n_envs > h->ev_cap_n || n_episodes > h->ev_cap_e) {
     // the running evaluation's launches (if any) read the old arrays: they finish before the arrays go
     h->ev_n = h->ev_e = 0;
+    h->ev_gen++;
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
   if (n_envs > h->ev_cap_n) {
@@ -6037,7 +6050,12 @@ int dsact_eval_commit(dsact_handle* h, const float* reward_dev, const uint8_t* t
   HIPCHK(h, hipSetDevice(h->device));
   if (!on_handle_gpu(h, reward_dev) || !on_handle_gpu(h, terminated_dev) || !on_handle_gpu(h, truncated_dev) || !on_handle_gpu(h, ended_dev))
     return fail(h, DSACT_E_INVALID, "dsact_eval_commit takes device pointers on the handle's GPU");
-  TRY(check_handoff_counted(h));
+  // legal under stream capture: a launch, no allocation, no wait; the hand-off check is left to the next
+  // entry point outside the capture (its failure path drains the stream)
+  bool capturing = false;
+  TRY(stream_capturing(h, &capturing));
+  if (capturing && h->profiling) return fail(h, DSACT_E_STATE, "dsact_eval_commit under stream capture while profiling");
+  if (!capturing) TRY(check_handoff_counted(h));
   EvalCommitArgs a = eval_args(h);
   a.reward = reward_dev; a.term = terminated_dev; a.trunc = truncated_dev; a.ended = ended_dev;
   TRY(launch(h, "eval_commit", k_eval_commit, dim3((unsigned)((h->ev_n + kThreads - 1) / kThreads)), dim3(kThreads), 0, a));
@@ -6050,6 +6068,9 @@ int dsact_eval_poll(dsact_handle* h, int32_t* remaining) {
   if (!h || !remaining) return DSACT_E_INVALID;
   if (h->ev_n < 1) return fail(h, DSACT_E_STATE, "dsact_eval_poll before dsact_eval_begin");
   HIPCHK(h, hipSetDevice(h->device));
+  bool capturing = false;
+  TRY(stream_capturing(h, &capturing));
+  if (capturing) return fail(h, DSACT_E_STATE, "dsact_eval_poll under stream capture (it waits for the stream)");
   HIPCHK(h, hipMemcpyAsync(h->ev_remaining_host, h->ev_remaining, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->eval_polls++;
@@ -6062,6 +6083,9 @@ int dsact_eval_read(dsact_handle* h, double* returns, int32_t* lengths, int32_t 
   if (h->ev_n < 1) return fail(h, DSACT_E_STATE, "dsact_eval_read before dsact_eval_begin");
   if (n_episodes != h->ev_e) return fail(h, DSACT_E_INVALID, "dsact_eval_read: n_episodes = %d, the evaluation has %d", (int)n_episodes, h->ev_e);
   HIPCHK(h, hipSetDevice(h->device));
+  bool capturing = false;
+  TRY(stream_capturing(h, &capturing));
+  if (capturing) return fail(h, DSACT_E_STATE, "dsact_eval_read under stream capture (it waits for the stream)");
   HIPCHK(h, hipMemcpyAsync(h->ev_remaining_host, h->ev_remaining, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (*h->ev_remaining_host != 0)

@@ -48,6 +48,20 @@ Refused (NotImplementedError / ValueError, before an environment or engine call 
 outside that gate,
 non-continuous actions, an environment on another device than the engine, num_eval_episode < 1, hip_eval_poll_steps < 1.
 
+The poll windows as one captured graph (`hip_graph_eval=True`; default off: exactly the calls above): the
+environment carries `capture_safe = True`, as for the sampler's hip_graph_sample. A window is hip_eval_poll_steps lockstep
+steps -- deterministic acting draws no noise, so it is the same launch sequence every time. Windows are counted per engine,
+across run_evaluation calls: the first runs eagerly (it makes the library's lazy allocations), the second is captured on the
+engine's stream as one linear chain and replayed, every later one is ONE replay(); dsact_eval_begin, the full env.reset() and
+dsact_eval_poll stay outside the graph, and a remainder shorter than a window (hip_eval_max_steps) runs eagerly. On this route
+eval_commit reads the environment's reward / terminated / truncated tensors where they are, and a step's acting call reads the
+previous reset's result in place; the evaluator's observation buffer is written once per window. The graph holds the addresses of
+the library's bookkeeping arrays: it is dropped (and the count restarts) on a new engine and when the engine's
+`eval_state_gen` is no longer the one it was captured under -- another evaluator's larger dsact_eval_begin reallocated them.
+`graph_captures` / `graph_replays` count. Refused in the constructor: an environment without the attribute, hip_cnn_act=True
+(NotImplementedError), a non-bool value (ValueError); at the first run_evaluation: an engine off the GPU. A capture that raises
+is ended and re-raised as a RuntimeError naming the environment.
+
 Evaluation draws nothing from the torch or NumPy generators and enqueues no update: the training state is not touched.
 After run_evaluation, `returns` (float64[E]), `lengths` (int32[E]) and `steps` (lockstep steps made) describe the last run.
 """
@@ -80,6 +94,25 @@ class HipTensorEnvEvaluator:
             raise ValueError("the environment's num_envs must be >= 1 (got %d)" % self.n_envs)
         self.action_type = kwargs.get("action_type", "continu")
         self.cnn_act = bool(kwargs.get("hip_cnn_act", False))   # image environments on an engine with the CNN acting path
+        # hip_graph_eval: the poll windows as one captured graph. Refused here, before any environment or
+        # engine call
+        graph = kwargs.get("hip_graph_eval", False)
+        if not isinstance(graph, (bool, np.bool_)):
+            raise ValueError("hip_graph_eval must be True or False, got %r" % (graph,))
+        self.graph_eval = bool(graph)
+        if self.graph_eval and self.cnn_act:
+            raise NotImplementedError("hip_graph_eval=True with hip_cnn_act=True: the CNN acting route records an event per call "
+                                      "and is not captured; use one of the two")
+        if self.graph_eval and getattr(env, "capture_safe", False) is not True:
+            raise NotImplementedError("hip_graph_eval=True needs an environment with the attribute capture_safe = True (step and "
+                                      "reset(mask) update their state tensors in place, allocate nothing that outlives the call, "
+                                      "never touch the host and stay on torch's current stream); %s does not promise it"
+                                      % type(env).__name__)
+        self.graph_captures = 0   # captures made / replays issued (the capturing call makes the first replay)
+        self.graph_replays = 0
+        self._graph = None        # the captured window of hip_eval_poll_steps steps (torch.cuda.CUDAGraph)
+        self._graph_gen = None    # the engine's eval_state_gen it was captured under: the ev_* addresses it holds
+        self._graph_windows = 0   # full windows run on this engine: 0 -> eager warm-up, 1 -> capture, later -> replay
         self.steps = 0            # lockstep steps of the last run_evaluation
         self.returns = None       # its episode returns, float64[E] in episode-index order
         self.lengths = None       # its episode lengths, int32[E]
@@ -100,6 +133,11 @@ class HipTensorEnvEvaluator:
         """once per engine: the [N, .] buffers and whether the policy's limits are the environment's"""
         N, O, A = self.n_envs, eng.obs_dim, eng.act_dim
         dev = torch.device(eng.device)
+        if self.graph_eval:
+            if dev.type != "cuda":
+                raise NotImplementedError("hip_graph_eval=True needs an engine on a GPU (a graph is captured from its stream); this "
+                                          "one is on %s" % dev)
+            self._graph, self._graph_gen, self._graph_windows = None, None, 0   # a new engine: eager, capture, replay again
         f = dict(dtype=torch.float32, device=dev)
         self._obs, self._act, self._clip = torch.zeros(N, O, **f), torch.zeros(N, A, **f), torch.zeros(N, A, **f)
         if getattr(eng, "conv_type", None):
@@ -110,6 +148,69 @@ class HipTensorEnvEvaluator:
         hand_over(eng)
         self._ready = id(eng)
 
+    def _window(self, eng, count):
+        """`count` lockstep steps on torch's current stream: the acting call, the clip where the environment's limits are not the
+        policy's, env.step, the commit, env.reset(ended) and the observation hand-over. Without hip_graph_eval every step stages
+        reward / terminated / truncated and the next observations in the evaluator's own buffers (the calls this class always
+        made). With it -- issued eagerly, under capture, and replayed -- the staging copies leave the dependent chain: eval_commit
+        reads the environment's own tensors where they are contiguous float32 / bool [N] on the engine's device, the next
+        step's acting call reads the reset's result in place where it is contiguous float32, and self._obs is written once, at
+        the end: the next window (or an eager remainder) starts from a fixed address."""
+        N, env, direct = self.n_envs, self.env, self.graph_eval
+        obs, act, clip, rew, term, trunc, ended = self._obs, self._act, self._clip, self._rew, self._term, self._trunc, self._ended
+        src = obs
+        for _ in range(count):
+            eng.act_mode_device(src, act)
+            if self._policy_clip:
+                a = act
+            else:
+                a = torch.minimum(torch.maximum(act, self._low), self._high, out=clip)
+            obs2, r, te, tr = env.step(a)
+            if (direct and r.dtype == torch.float32 and te.dtype == torch.bool and tr.dtype == torch.bool
+                    and tuple(r.shape) == tuple(te.shape) == tuple(tr.shape) == (N,) and r.device == te.device == tr.device == rew.device
+                    and r.is_contiguous() and te.is_contiguous() and tr.is_contiguous()):
+                eng.eval_commit(r, te, tr, ended)
+            else:
+                rew.copy_(r)
+                term.copy_(te)
+                trunc.copy_(tr)
+                eng.eval_commit(rew, term, trunc, ended)
+            # the next step's observations: this step's, with every environment that ended restarted on its own (rows
+            # without an episode too)
+            nxt = env.reset(ended).reshape(obs.shape)
+            if direct and nxt.dtype == torch.float32 and nxt.device == obs.device and nxt.is_contiguous():
+                src = nxt
+            else:
+                obs.copy_(nxt)
+                src = obs
+        if src is not obs:
+            obs.copy_(src)
+
+    def _graph_window(self, eng, stream):
+        """one full window (hip_eval_poll_steps steps) of a hip_graph_eval evaluator: the first on an engine runs _window eagerly
+        (the warm-up: it makes the library's lazy allocations), the second captures it into a graph on the engine's stream -- one
+        linear chain -- and replays it, every later one is one replay. A capture that raises is ended and reported; nothing is
+        retried."""
+        if self._graph_windows == 0:
+            self._window(eng, self.poll_steps)
+        else:
+            if self._graph is None:
+                graph = torch.cuda.CUDAGraph()
+                gen = eng.debug_get("eval_state_gen")
+                try:
+                    with torch.cuda.graph(graph, stream=stream, capture_error_mode="relaxed"):   # (its exit ends the capture)
+                        self._window(eng, self.poll_steps)
+                except Exception as ex:
+                    raise RuntimeError("hip_graph_eval: capturing an evaluation window failed with the environment %s (%s: %s). "
+                                       "capture_safe = True promises that step and reset(mask) update state in place, never touch "
+                                       "the host and stay on torch's current stream; build the evaluator without hip_graph_eval for "
+                                       "this environment" % (type(self.env).__name__, type(ex).__name__, ex)) from ex
+                self._graph, self._graph_gen = graph, gen
+                self.graph_captures += 1
+            self._graph.replay()
+            self.graph_replays += 1
+        self._graph_windows += 1
+
     def run_evaluation(self, iteration):
         eng = self._engine()
         if self._ready != id(eng):
@@ -118,38 +219,32 @@ class HipTensorEnvEvaluator:
         if hasattr(pol, "parameters"):
             eng.note_torch_writes(pol.parameters())   # (weights written with torch ops since the last call)
         N, E, P, env = self.n_envs, self.num_eval_episode, self.poll_steps, self.env
-        obs, act, clip, rew, term, trunc, ended = self._obs, self._act, self._clip, self._rew, self._term, self._trunc, self._ended
+        obs = self._obs
         self.steps, remaining = 0, E
-        with on_stream(engine_stream(eng)), torch.no_grad():
+        stream = engine_stream(eng)
+        with on_stream(stream), torch.no_grad():
             eng.eval_begin(N, E)
+            if self._graph is not None and eng.debug_get("eval_state_gen") != self._graph_gen:
+                # dsact_eval_begin reallocated the bookkeeping's arrays (another evaluator on this engine asked for more rows or
+                # episodes): the graph's eval_commit nodes hold the freed addresses. Eager, capture, replay again
+                self._graph, self._graph_gen, self._graph_windows = None, None, 0
             first = env.reset()
             if obs is None:
                 row = tuple(getattr(eng, "obs_shape", None) or first.shape[1:])
                 odt = torch.uint8 if first.dtype == torch.uint8 else torch.float32
                 obs = self._obs = torch.zeros((N,) + row, dtype=odt, device=first.device)
             obs.copy_(first.reshape(obs.shape))
+            # windows of P lockstep steps (the last one shorter where hip_eval_max_steps is no multiple of P), one wait behind each
             while self.steps < self.max_steps:
-                eng.act_mode_device(obs, act)
-                if self._policy_clip:
-                    a = act
+                count = min(P, self.max_steps - self.steps)
+                if self.graph_eval and count == P:
+                    self._graph_window(eng, stream)
                 else:
-                    a = torch.minimum(torch.maximum(act, self._low), self._high, out=clip)
-                obs2, r, te, tr = env.step(a)
-                rew.copy_(r)
-                term.copy_(te)
-                trunc.copy_(tr)
-                eng.eval_commit(rew, term, trunc, ended)
-                # the next step's observations: this step's, with every environment that ended restarted on its own (rows
-                # without an episode too)
-                obs.copy_(env.reset(ended).reshape(obs.shape))
-                self.steps += 1
-                if self.steps % P == 0:
-                    remaining = eng.eval_poll()
-                    if remaining == 0:
-                        break
-            else:
-                if self.steps % P:
-                    remaining = eng.eval_poll()   # (drains the stream: the handle is idle when the error is raised)
+                    self._window(eng, count)
+                self.steps += count
+                remaining = eng.eval_poll()   # (drains the stream: the handle is idle when the error below is raised)
+                if remaining == 0:
+                    break
             if remaining != 0:
                 raise RuntimeError("hip_tensor_env_evaluator: %d of %d episodes have not ended after hip_eval_max_steps = %d lockstep "
                                    "steps" % (remaining, E, self.max_steps))

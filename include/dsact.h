@@ -610,7 +610,26 @@ int dsact_buffer_add_device(dsact_handle* h, int64_t n, const float* obs, const 
  *                                  episode returns training/evaluator.py:34-84 averages (lines 77-84). DSACT_E_STATE while an
  *                                  episode has not ended; n_episodes must be dsact_eval_begin's.
  * dsact_debug_get: "act_mode_dev_calls" (chunks launched by dsact_act_mode_device), "eval_commit_calls", "eval_polls";
- * "act_dev_syncs" stays 0 across dsact_act_mode_device and dsact_eval_commit too. */
+ * "act_dev_syncs" stays 0 across dsact_act_mode_device and dsact_eval_commit too.
+ *
+ * UNDER STREAM CAPTURE (training/hip_tensor_evaluator.py with hip_graph_eval): a window of lockstep steps
+ * is the same launch sequence every time -- the mode draws no noise, so no step counter is involved -- and may be captured from
+ * the handle's stream into a graph. The rules are dsact_act_sample_device_counted's:
+ *   dsact_act_mode_device          on an MLP handle is LEGAL WHILE THE HANDLE'S STREAM IS CAPTURING: it then allocates nothing
+ *                                  (DSACT_E_STATE if no earlier call has made the batched forward's buffers: make one call outside
+ *                                  the capture first), waits for nothing and leaves the hand-off check to the next entry point
+ *                                  outside the capture. DSACT_E_STATE while profiling; DSACT_E_INVALID on a CNN handle (that route
+ *                                  records an event per call), dsact_act_mode_device_u8 included.
+ *   dsact_eval_commit              is legal under capture by the same rules (no hand-off check while capturing, DSACT_E_STATE
+ *                                  while profiling). The captured node holds the ADDRESSES of the state dsact_eval_begin
+ *                                  allocated, and dsact_eval_begin frees and reallocates that state when n_envs or n_episodes
+ *                                  grows: dsact_debug_get "eval_state_gen" goes up by one on every (re)allocation, and a graph
+ *                                  that holds a dsact_eval_commit node is valid only for the generation it was captured under
+ *                                  (read it after dsact_eval_begin; replaying it under another one writes freed memory). N and
+ *                                  E are baked as well: a replay serves the (n_envs, n_episodes) of the capture.
+ *   dsact_eval_begin / dsact_eval_poll / dsact_eval_read   DSACT_E_STATE under capture: they allocate or wait.
+ * "act_mode_dev_calls" and "eval_commit_calls" count HOST calls: they move when a graph is captured and not when it is replayed
+ * (as "act_dev_calls" does for the counted sampling call). */
 int dsact_act_mode_device(dsact_handle* h, const float* obs_dev, int32_t n, float* action_dev);
 
 /* ---- Device-resident image environments ----------------------------------------------------------------

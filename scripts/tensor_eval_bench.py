@@ -12,7 +12,17 @@ configuration (3 x 256, untrained). E = N episodes: every environment plays one.
       the poll period (one more child process): hip_eval_poll_steps P in 1, 4, 16, 64 at N = 256, the four periods taken in turn
         inside each of `pairs` rounds.
       Medians, per-pair ratios (vec / tensor) and each leg's spread over its own windows are recorded.
-Writes DIR/tensor_eval_bench.json and prints it. The library must have been built (__graft_entry__.build())."""
+Writes DIR/tensor_eval_bench.json and prints it. The library must have been built (__graft_entry__.build()).
+
+  python scripts/tensor_eval_bench.py --graph [--out profiles] [--pairs 3]
+      hip_graph_eval=True against the eager evaluator, both on tests/envs/synth_tensor_humanoid_inplace.py
+      (the same dynamics with capture_safe = True), the same policy, E = N. Per N in 64, 256, 1024 (a fresh child process each):
+      one warm-up evaluation per leg -- the captured leg's holds its eager window and its capture --, then `pairs` alternating
+      (eager, graph) pairs of windows, the stream drained at each window's end. Medians, each leg's spread over its own windows,
+      per-pair ratios (eager / graph) and the time per lockstep step are recorded. One more child: the captured leg at
+      hip_eval_poll_steps P in 4, 16, 64, N = 256, the periods taken in turn inside each round.
+      Writes DIR/graph_eval_bench.json. `--only eager:N` measures the eager leg of that comparison alone (it needs nothing this
+      kwarg added: the figure to compare across two builds of the library)."""
 import argparse
 import json
 import os
@@ -31,10 +41,12 @@ import torch  # noqa: E402
 
 from helpers import hip_kwargs  # noqa: E402
 from synth_tensor_humanoid import A, O, SynthTensorHumanoid  # noqa: E402
+from synth_tensor_humanoid_inplace import SynthTensorHumanoidInplace  # noqa: E402
 from tensor_sampler_bench import OneEnv  # noqa: E402
 
 NS = [64, 256, 1024]
 PS = [1, 4, 16, 64]
+GRAPH_PS = [4, 16, 64]
 HID, B, SEED, LIMIT = (256, 256, 256), 256, 3, 1000
 
 
@@ -54,12 +66,16 @@ def _alg():
     return plugin.create_alg(**kw)
 
 
-def _tensor(alg, N, P=None):
+def _tensor(alg, N, P=None, graph=None):
+    """graph None: the section-16 leg (the plain fixture). False / True: the in-place fixture without / with hip_graph_eval"""
     import plugin
 
     kw = {} if P is None else {"hip_eval_poll_steps": P}
+    if graph:
+        kw["hip_graph_eval"] = True
+    env = SynthTensorHumanoid if graph is None else SynthTensorHumanoidInplace
     return plugin.create_evaluator(evaluator_name="hip_tensor_env_evaluator", networks=alg.networks, num_eval_episode=N,
-                                   eval_env=SynthTensorHumanoid(N, device="cuda", seed=SEED, episode_limit=LIMIT), **kw)
+                                   eval_env=env(N, device="cuda", seed=SEED, episode_limit=LIMIT), **kw)
 
 
 def _vec(alg, N):
@@ -129,19 +145,87 @@ def run_poll(N, pairs, window):
     return out
 
 
+def run_graph(N, pairs, window, legs=("eager", "graph")):
+    """the eager and the captured evaluator in alternating windows (legs = ("eager",): the eager leg alone)"""
+    alg = _alg()
+    evs = {leg: _tensor(alg, N, graph=leg == "graph") for leg in legs}
+    reps, tars = {}, {}
+    for leg, ev in evs.items():                       # warm-up (the captured leg: eager window + capture), then the sizing run
+        tars[leg] = _window(alg, ev, 1)[1]
+        reps[leg] = max(1, int(round(window / _window(alg, ev, 1)[0])))
+    rows = {leg: [] for leg in evs}
+    for _ in range(pairs):
+        for leg, ev in evs.items():
+            dt, tar = _window(alg, ev, reps[leg])
+            rows[leg].append(dt)
+            assert tar == tars[leg], (leg, tar, tars[leg])
+    e = alg.engine
+    steps = {leg: int(ev.steps) for leg, ev in evs.items()}
+    out = {"N": N, "episodes": N, "metric": "seconds_per_run_evaluation", "repetitions_per_window": reps, "rows": rows,
+           "lockstep_steps": steps, "tar": tars, "poll_steps": evs[legs[0]].poll_steps,
+           "us_per_lockstep_step": {leg: 1e6 * float(np.median(v)) / steps[leg] for leg, v in rows.items()},
+           "act_dev_syncs": e.debug_get("act_dev_syncs"), "handoff_failures": e.debug_get("handoff_failures")}
+    if "graph" in evs:
+        ratios = [a / g for a, g in zip(rows["eager"], rows["graph"])]
+        out.update({"eager_over_graph": ratios, "eager_over_graph_median": float(np.median(ratios)),
+                    "tar_bits_equal": np.float64(tars["eager"]).tobytes() == np.float64(tars["graph"]).tobytes(),
+                    "graph_captures": evs["graph"].graph_captures, "graph_replays": evs["graph"].graph_replays})
+    out.update(_stats(rows))
+    e.close()
+    return out
+
+
+def run_graph_poll(N, pairs, window):
+    """the captured leg at every poll period of GRAPH_PS (a window of the graph is P lockstep steps)"""
+    alg = _alg()
+    evs = {P: _tensor(alg, N, P, graph=True) for P in GRAPH_PS}
+    reps = {}
+    for P, ev in evs.items():
+        _window(alg, ev, 1)
+        reps[P] = max(1, int(round(window / _window(alg, ev, 1)[0])))
+    rows = {P: [] for P in GRAPH_PS}
+    for _ in range(pairs):
+        for P, ev in evs.items():
+            rows[P].append(_window(alg, ev, reps[P])[0])
+    steps = {P: int(ev.steps) for P, ev in evs.items()}
+    out = {"N": N, "episodes": N, "metric": "seconds_per_run_evaluation", "leg": "graph", "repetitions_per_window": reps,
+           "rows": {str(P): v for P, v in rows.items()}, "lockstep_steps": {str(P): steps[P] for P in GRAPH_PS},
+           "us_per_lockstep_step": {str(P): 1e6 * float(np.median(rows[P])) / steps[P] for P in GRAPH_PS},
+           "graph_captures": {str(P): ev.graph_captures for P, ev in evs.items()}}
+    out.update(_stats({str(P): v for P, v in rows.items()}))
+    alg.engine.close()
+    return out
+
+
+def _one(only, pairs, window):
+    if only.startswith("graphpoll:"):
+        return run_graph_poll(int(only[10:]), pairs, window)
+    if only.startswith("graph:"):
+        return run_graph(int(only[6:]), pairs, window)
+    if only.startswith("eager:"):
+        return run_graph(int(only[6:]), pairs, window, legs=("eager",))
+    if only.startswith("poll:"):
+        return run_poll(int(only[5:]), pairs, window)
+    return run_n(int(only), pairs, window)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--window", type=float, default=0.5)
-    ap.add_argument("--only", default="", help="N or poll:N -- one configuration, in this process")
+    ap.add_argument("--only", default="", help="N, poll:N, graph:N, graphpoll:N or eager:N -- one configuration, in this process")
+    ap.add_argument("--graph", action="store_true", help="hip_graph_eval against the eager evaluator -> graph_eval_bench.json")
     a = ap.parse_args()
     if a.only:
-        r = run_poll(int(a.only[5:]), a.pairs, a.window) if a.only.startswith("poll:") else run_n(int(a.only), a.pairs, a.window)
-        print("RESULT " + json.dumps(r), flush=True)
+        print("RESULT " + json.dumps(_one(a.only, a.pairs, a.window)), flush=True)
         return
     res = {"pairs": a.pairs, "window_s": a.window, "policy": "376-256-256-256-34", "episode_limit": LIMIT, "configs": [], "poll": None}
-    for only in [str(n) for n in NS] + ["poll:256"]:
+    todo = [str(n) for n in NS] + ["poll:256"]
+    if a.graph:
+        res["environment"] = "tests/envs/synth_tensor_humanoid_inplace.py"
+        todo = ["graph:%d" % n for n in NS] + ["graphpoll:256"]
+    for only in todo:
         cmd = ["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--only", only, "--pairs", str(a.pairs),
                "--window", str(a.window)]
         p = subprocess.run(cmd, capture_output=True, text=True)
@@ -150,13 +234,13 @@ def main():
             sys.stderr.write(p.stdout + p.stderr)
             raise SystemExit("configuration %s failed (exit status %d)" % (only, p.returncode))
         r = json.loads(line[-1][len("RESULT "):])
-        if only.startswith("poll:"):
+        if only.startswith("poll:") or only.startswith("graphpoll:"):
             res["poll"] = r
         else:
             res["configs"].append(r)
         print(json.dumps(r), flush=True)
     os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, "tensor_eval_bench.json"), "w") as f:
+    with open(os.path.join(a.out, "graph_eval_bench.json" if a.graph else "tensor_eval_bench.json"), "w") as f:
         json.dump(res, f, indent=1)
 
 
