@@ -309,6 +309,11 @@ struct dsact_handle : BatchBufs {
   bool cnn_act = false;
   hipEvent_t ca_dev_ev = nullptr;        // recorded on `stream` behind the last launch of a device-resident CNN acting call
   bool ca_dev_pending = false;           // ... which has been recorded at least once
+  // dsact_cnn_acting_capture (sticky): the device-resident forms record no event any more -- a captured
+  // node could not carry it across replays -- and may run under stream capture; a held call records ca_dev_ev on `stream`
+  // itself and waits for it (act_batch_gpu): behind everything enqueued there so far, graph replays included
+  bool cnn_act_capture = false;
+  unsigned long long step_frames_calls = 0;   // dsact_step_frames_device launches
   float* ca_stage = nullptr; float* ca_frames = nullptr; float* ca_img = nullptr;
   float* ca_act[kMaxConv] = {}; float* ca_feat = nullptr;
   // device-resident sampling (dsact_act_sample_device / dsact_buffer_add_device)
@@ -5422,6 +5427,8 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "track_reads")) *value = (double)h->track_reads;                 // dsact_track_read waits
   else if (!strcmp(name, "step_rows_calls")) *value = (double)h->step_rows_calls;         // dsact_step_rows_device launches
   else if (!strcmp(name, "act_fast")) *value = (act_fast_ok(h) || h->cnn_act) ? 1.0 : 0.0;   // dsact_act_sample serves this handle (the one-launch forward, or the enabled CNN acting path)
+  else if (!strcmp(name, "cnn_act_capture")) *value = h->cnn_act_capture ? 1.0 : 0.0;   // dsact_cnn_acting_capture is on
+  else if (!strcmp(name, "step_frames_calls")) *value = (double)h->step_frames_calls;    // dsact_step_frames_device launches
   else if (!strcmp(name, "cnn_act")) *value = h->cnn_act ? 1.0 : 0.0;          // dsact_cnn_acting_enable has been called
   else if (!strcmp(name, "graph_cache")) *value = (double)h->graph_cache.size();   // inactive captured graphs kept by dsact_run_group
   else if (!strcmp(name, "graph_noise_table")) *value = h->active.noise_table ? 1.0 : 0.0;
@@ -5668,7 +5675,19 @@ static int act_batch_gpu(dsact_handle* h, const float* obs, int32_t n, const flo
   if (stream != h->stream) HIPCHK(h, hipStreamWaitEvent(stream, h->beh_ev, 0));
   // (a device-resident CNN acting call may still have launches on the path's buffers on h->stream: the acting stream waits
   // for the event behind its last launch, the host does not)
-  if (stream != h->stream && h->ca_dev_pending) HIPCHK(h, hipStreamWaitEvent(stream, h->ca_dev_ev, 0));
+  if (stream != h->stream && h->cnn_act_capture) {
+    // dsact_cnn_acting_capture: the device-resident forms record nothing -- a graph replay cannot -- so
+    // the held call records the fence itself: behind everything enqueued on the handle's stream so far, replays included.
+    // Never inside a capture: the graph stays one linear chain
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIPCHK(h, hipStreamIsCapturing(h->stream, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+      return fail(h, DSACT_E_STATE, "a held acting call while the handle's stream is capturing (it would record an event inside the capture)");
+    HIPCHK(h, hipEventRecord(h->ca_dev_ev, h->stream));
+    HIPCHK(h, hipStreamWaitEvent(stream, h->ca_dev_ev, 0));
+  } else if (stream != h->stream && h->ca_dev_pending) {
+    HIPCHK(h, hipStreamWaitEvent(stream, h->ca_dev_ev, 0));
+  }
   // an enabled CNN handle: rows are frames of O = C * H * W floats, chunks of kActFrameCap through the path's own stage
   const bool cnn = h->cnn_act;
   const int O = h->O, A = h->A, R = cnn ? kActFrameCap : kActBatchCap;
@@ -5819,7 +5838,8 @@ int dsact_set_explore_noise(dsact_handle* h, const float* mean, const float* sd,
 // behind every enqueued update; also under a behaviour hold). An enabled CNN handle (dsact_cnn_acting_enable; DESIGN.md section
 // 20): obs is n frames of O = C*H*W elements in the environment's (C, H, W) layout -- floats, or with u8 bytes that are codes
 // into the coded ring's table --, chunks of kActFrameCap frames through enqueue_act_cnn, and ca_dev_ev recorded behind the
-// last launch (act_batch_gpu: a held call waits for it on the acting stream).
+// last launch (act_batch_gpu: a held call waits for it on the acting stream) -- unless dsact_cnn_acting_capture is on: then no
+// event is recorded here and the held call records it itself.
 // mode: dist.mode() (action only) instead of the sample. who / host_form name the entry point and its host-row counterpart
 static int act_device(dsact_handle* h, const char* who, const char* host_form, const char* cnn_route, const void* obs_dev, bool u8,
                       int32_t n, const float* eps_dev, int64_t step, float* action_dev, float* clipped_dev, float* logp_dev, bool mode,
@@ -5827,7 +5847,10 @@ static int act_device(dsact_handle* h, const char* who, const char* host_form, c
   // counted (dsact_act_sample_device_counted): the acting step is the handle's device counter + `step`, and
   // the call may be made while the handle's stream is capturing -- then nothing below may allocate or wait. The mode form of an
   // MLP handle may be captured too (it draws nothing, so it needs no counter)
-  if (counted && h->cnn) return fail(h, DSACT_E_INVALID, "%s serves MLP policies (the CNN route records an event per call)", who);
+  // A CNN handle is served by both after dsact_cnn_acting_capture; without that opt-in it is refused
+  const bool cnn_capture = h->cnn_act && h->cnn_act_capture;
+  if (counted && h->cnn && !cnn_capture)
+    return fail(h, DSACT_E_INVALID, "%s serves MLP policies (the CNN route records an event per call)", who);
   TRY(act_batch_ready(h, who, h->cnn_act ? nullptr : cnn_route));
   if (u8 && !h->cnn_act) return fail(h, DSACT_E_INVALID, "%s serves CNN policies after dsact_cnn_acting_enable", who);
   if (u8 && !h->rb_code)
@@ -5848,7 +5871,7 @@ static int act_device(dsact_handle* h, const char* who, const char* host_form, c
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIPCHK(h, hipStreamIsCapturing(h->stream, &cap));
     capturing = cap != hipStreamCaptureStatusNone;
-    if (capturing && h->cnn)
+    if (capturing && h->cnn && !cnn_capture)
       return fail(h, DSACT_E_INVALID, "%s under stream capture serves MLP policies (the CNN route records an event per call)", who);
     if (capturing && !h->ab_h[0])
       return fail(h, DSACT_E_STATE, "%s under stream capture before the batched forward's buffers exist: make one call outside "
@@ -5885,7 +5908,7 @@ static int act_device(dsact_handle* h, const char* who, const char* host_form, c
     else TRY(enqueue_act_batch(h, (const float*)rows, O, m, net_params(h, N_POL), h->stream, o, form));
     (mode ? h->act_mode_dev_calls : h->act_dev_calls)++;
   }
-  if (cnn) {
+  if (cnn && !h->cnn_act_capture) {   // (with it the held call records the fence itself: act_batch_gpu)
     HIPCHK(h, hipEventRecord(h->ca_dev_ev, h->stream));
     h->ca_dev_pending = true;
   }
@@ -5954,6 +5977,13 @@ int dsact_act_sample_device_counted(dsact_handle* h, const float* obs_dev, int32
                     step_offset, action_dev, clipped_dev, logp_dev, false, true);
 }
 
+int dsact_act_sample_device_counted_u8(dsact_handle* h, const uint8_t* frames_dev, int32_t n, int64_t step_offset, float* action_dev,
+                                       float* clipped_dev, float* logp_dev) {
+  if (!h || !frames_dev || !action_dev || !clipped_dev || !logp_dev || n < 1) return DSACT_E_INVALID;
+  return act_device(h, "dsact_act_sample_device_counted_u8", "dsact_act_sample_batch", "dsact_policy_forward", frames_dev, true, n,
+                    nullptr, step_offset, action_dev, clipped_dev, logp_dev, false, true);
+}
+
 // the row copies of one lockstep step in one launch (k_step_rows, dsact_kernels.h). Legal under stream capture: a launch, no
 // allocation, no wait (the hand-off check is left to the next entry point outside the capture)
 int dsact_step_rows_device(dsact_handle* h, int32_t n, int32_t row_floats, const float* obs2_dev, const float* rew_dev,
@@ -5978,6 +6008,39 @@ int dsact_step_rows_device(dsact_handle* h, int32_t n, int32_t row_floats, const
   a.wide = (row_floats % 4 == 0) && ((uintptr_t)obs2_dev % 16 == 0) && ((uintptr_t)obs2_slot % 16 == 0);
   TRY(launch(h, "step_rows", k_step_rows, dim3((unsigned)((n + 3) / 4)), dim3(kThreads), 0, a));
   h->step_rows_calls++;
+  return DSACT_OK;
+}
+
+// dsact_step_rows_device for image rows (k_step_frames, dsact_kernels.h): a row is row_bytes bytes of any
+// element type, split over several workgroups. Legal under stream capture by the same rules
+int dsact_step_frames_device(dsact_handle* h, int32_t n, int64_t row_bytes, const void* obs2_dev, const float* rew_dev,
+                             const uint8_t* terminated_dev, const uint8_t* truncated_dev, void* obs2_slot, float* rew_slot,
+                             uint8_t* terminated_slot, uint8_t* truncated_slot, uint8_t* ended_dev) {
+  if (!h || !obs2_dev || !rew_dev || !terminated_dev || !truncated_dev || !obs2_slot || !rew_slot || !terminated_slot ||
+      !truncated_slot || !ended_dev)
+    return DSACT_E_INVALID;
+  if (n < 1 || row_bytes < 1)
+    return fail(h, DSACT_E_INVALID, "dsact_step_frames_device: n = %d and row_bytes = %lld must be >= 1", (int)n, (long long)row_bytes);
+  HIPCHK(h, hipSetDevice(h->device));
+  const void* ptrs[9] = {obs2_dev, rew_dev, terminated_dev, truncated_dev, obs2_slot, rew_slot, terminated_slot, truncated_slot, ended_dev};
+  for (const void* p : ptrs)
+    if (!on_handle_gpu(h, p)) return fail(h, DSACT_E_INVALID, "dsact_step_frames_device takes device pointers on the handle's GPU");
+  bool capturing = false;
+  TRY(stream_capturing(h, &capturing));
+  if (capturing && h->profiling) return fail(h, DSACT_E_STATE, "dsact_step_frames_device under stream capture while profiling");
+  if (!capturing) TRY(check_handoff_counted(h));
+  StepFramesArgs a;
+  a.obs2 = (const unsigned char*)obs2_dev; a.rew = rew_dev; a.term = terminated_dev; a.trunc = truncated_dev;
+  a.obs2_dst = (unsigned char*)obs2_slot; a.rew_dst = rew_slot; a.term_dst = terminated_slot; a.trunc_dst = truncated_slot;
+  a.ended = ended_dev;
+  a.n = n; a.row_bytes = row_bytes;
+  const uintptr_t both = (uintptr_t)obs2_dev | (uintptr_t)obs2_slot;
+  a.path = (row_bytes % 16 == 0 && both % 16 == 0) ? 2 : (row_bytes % 4 == 0 && both % 4 == 0) ? 1 : 0;
+  // workgroups per row as enqueue_act_cnn chooses them per frame: one pass of kThreads lanes over the row's 16-byte units each, 16 at most
+  const long long per = (row_bytes / 16 + kThreads - 1) / kThreads;
+  a.chunks = per < 1 ? 1 : (per > 16 ? 16 : (int)per);
+  TRY(launch(h, "step_frames", k_step_frames, dim3((unsigned)((long long)n * a.chunks)), dim3(kThreads), 0, a));
+  h->step_frames_calls++;
   return DSACT_OK;
 }
 
@@ -6241,6 +6304,25 @@ int dsact_cnn_acting_enable(dsact_handle* h) {
   TRY(alloc_act_batch(h));   // the trunk's two activation buffers and the mapped output rows
   if (!h->ca_dev_ev) HIPCHK(h, hipEventCreateWithFlags(&h->ca_dev_ev, hipEventDisableTiming));   // 
   h->cnn_act = true;
+  return DSACT_OK;
+}
+
+// the opt-in that makes the CNN route of the device-resident acting calls capturable. Sticky: a graph
+// captured under it may be replayed at any time, and such a replay records no event -- so the setting cannot be taken back
+int dsact_cnn_acting_capture(dsact_handle* h, int32_t on) {
+  if (!h) return DSACT_E_INVALID;
+  if (!h->cnn_act) return fail(h, DSACT_E_STATE, "dsact_cnn_acting_capture before dsact_cnn_acting_enable");
+  HIPCHK(h, hipSetDevice(h->device));
+  bool capturing = false;
+  TRY(stream_capturing(h, &capturing));
+  if (capturing) return fail(h, DSACT_E_STATE, "dsact_cnn_acting_capture under stream capture");
+  if (!on) {
+    if (h->cnn_act_capture)
+      return fail(h, DSACT_E_STATE, "dsact_cnn_acting_capture(0) after it was switched on: a graph captured since may be replayed at "
+                                    "any time, and its acting nodes record no event");
+    return DSACT_OK;
+  }
+  h->cnn_act_capture = true;
   return DSACT_OK;
 }
 

@@ -927,6 +927,47 @@ __global__ void __launch_bounds__(kThreads) k_step_rows(StepRowsArgs a) {
 }
 #endif
 
+// k_step_frames: k_step_rows for IMAGE rows (dsact_step_frames_device). k_step_rows moves a row with one
+// wave; a (3, 96, 96) fp32 frame is 110 592 bytes, so here a row is split over `chunks` workgroups (grid n * chunks; chunks is
+// chosen the way enqueue_act_cnn chooses its workgroups per frame, from the row's 16-byte units): workgroup (i, c) moves units
+// c * kThreads + tid, then every chunks * kThreads-th one. The semantics are k_step_rows': pure moves of row_bytes bytes per
+// row -- the element type does not matter, byte frames and fp32 frames are the same kernel -- and ended = (term | trunc) != 0.
+// path: 2 = 16 bytes per lane (row_bytes % 16 == 0, source and slot 16-byte aligned: then every row is), 1 = 4 bytes
+// (everything 4-aligned), 0 = bytes. Lane 0 of a row's first workgroup moves the row's scalar columns. Vector loads and stores
+// only; every access is inside row i < n of its array.
+struct StepFramesArgs {
+  const unsigned char* obs2; const float* rew; const unsigned char* term; const unsigned char* trunc;
+  unsigned char* obs2_dst; float* rew_dst; unsigned char* term_dst; unsigned char* trunc_dst; unsigned char* ended;
+  long long row_bytes;
+  int n, chunks, path;
+};
+#ifndef DSACT_FAMILY_UNIT   // plain kernel: compiled in dsact_api.hip only (dsact_tu.h)
+__global__ void __launch_bounds__(kThreads) k_step_frames(StepFramesArgs a) {
+  const int i = (int)blockIdx.x / a.chunks, c = (int)blockIdx.x % a.chunks;
+  if (i >= a.n) return;
+  const unsigned char* s = a.obs2 + (size_t)i * (size_t)a.row_bytes;
+  unsigned char* d = a.obs2_dst + (size_t)i * (size_t)a.row_bytes;
+  const long long first = (long long)c * kThreads + (int)threadIdx.x, stride = (long long)a.chunks * kThreads;
+  if (a.path == 2) {
+    const uint4* s4 = reinterpret_cast<const uint4*>(s);
+    uint4* d4 = reinterpret_cast<uint4*>(d);
+    for (long long k = first; k < a.row_bytes / 16; k += stride) d4[k] = s4[k];
+  } else if (a.path == 1) {
+    const unsigned int* s1 = reinterpret_cast<const unsigned int*>(s);
+    unsigned int* d1 = reinterpret_cast<unsigned int*>(d);
+    for (long long k = first; k < a.row_bytes / 4; k += stride) d1[k] = s1[k];
+  } else {
+    for (long long k = first; k < a.row_bytes; k += stride) d[k] = s[k];
+  }
+  if (c == 0 && threadIdx.x == 0) {
+    const unsigned char t = a.term[i], u = a.trunc[i];   // (both loaded: no load behind a branch)
+    a.rew_dst[i] = a.rew[i];
+    a.term_dst[i] = t; a.trunc_dst[i] = u;
+    a.ended[i] = (t | u) != 0 ? 1 : 0;
+  }
+}
+#endif
+
 // ---------------------------------------------------------------------------------------------
 // k_tiles: C[m][n] (+epilogue) = sum_k P(m,k) * Q(n,k) on 32x32 tiles, BK = 64
 //   operand storage: KC  element (row,k) at base[row*ld + k]   (k contiguous)

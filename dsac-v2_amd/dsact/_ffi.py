@@ -149,6 +149,9 @@ SYMBOLS = [
     ("dsact_track_begin", C.c_int, [_P, C.c_int32]),
     ("dsact_track_commit", C.c_int, [_P, _P, _P, _P, C.c_int32]),
     ("dsact_track_read", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32]),
+    ("dsact_cnn_acting_capture", C.c_int, [_P, C.c_int32]),
+    ("dsact_act_sample_device_counted_u8", C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P, _P]),
+    ("dsact_step_frames_device", C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 ]
 
 _lib = None

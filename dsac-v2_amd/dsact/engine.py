@@ -98,6 +98,13 @@ class DsactEngine:
         self._chk(self._lib.dsact_cnn_acting_enable(self._h))
         self.cnn_act = True
 
+    def cnn_acting_capture(self):
+        """dsact_cnn_acting_capture(on=1): the device-resident acting calls of this CNN engine (act_sample_device_counted,
+        act_mode_device) become legal while the engine's stream is captured into a graph. They record no
+        event any more; a held act_sample_batch records its fence itself, behind everything enqueued on the engine's stream.
+        Needs enable_cnn_acting first; sticky (it cannot be switched off); idempotent."""
+        self._chk(self._lib.dsact_cnn_acting_capture(self._h, 1))
+
     @staticmethod
     def _pad_width(hidden, policy_hidden, batch, obs_dim, *, conv_type=None, algo="DSAC_V2", policy_std_type="mlp_shared", value_act=0,
                    policy_act=0, **_):
@@ -805,14 +812,37 @@ class DsactEngine:
     def act_sample_device_counted(self, obs, step_offset, action, clipped, logp):
         """dsact_act_sample_device_counted: act_sample_device(obs, None, counter + step_offset, ...) with the counter read on the
         device when the launch runs (act_counter_set first) -- bit for bit that call's action[n, A], clipped[n, A] and logp[n].
-        MLP policies, obs[n, O] float32. Asynchronous, and legal while the engine's stream is being captured into a graph (after
-        one call outside the capture, which makes the library's allocations)."""
+        MLP policies, obs[n, O] float32; a CNN engine after cnn_acting_capture: frames as act_sample_device takes them, float32
+        or uint8 (the call dispatches on the dtype). Asynchronous, and legal while the engine's stream is being captured into a
+        graph (after one call outside the capture, which makes the library's allocations)."""
         f32 = (self.torch.float32,)
         n = self._rows(obs)
         A = self.act_dim
-        po = self._dev(obs, (n, self.obs_dim), f32, "obs")
+        po, u8 = self._frames(obs, n, "obs")
         pa, pc, pl = self._dev(action, (n, A), f32, "action"), self._dev(clipped, (n, A), f32, "clipped"), self._dev(logp, (n,), f32, "logp")
-        rc = self._lib.dsact_act_sample_device_counted(self._h, po, n, int(step_offset), pa, pc, pl)
+        fn = self._lib.dsact_act_sample_device_counted_u8 if u8 else self._lib.dsact_act_sample_device_counted
+        rc = fn(self._h, po, n, int(step_offset), pa, pc, pl)
+        if rc != 0:
+            self._chk(rc)
+
+    def step_frames_device(self, obs2, rew, terminated, truncated, obs2_slot, rew_slot, terminated_slot, truncated_slot, ended):
+        """dsact_step_frames_device: step_rows_device for image rows -- obs2[n, C, H, W] (or any [n, ...] rows) uint8 or float32
+        -> obs2_slot of the same shape and dtype, a row split over several workgroups; the scalar columns and ended as there.
+        Contiguous tensors on this engine's GPU. Asynchronous; legal under stream capture."""
+        torch = self.torch
+        f32, flag, img = (torch.float32,), (torch.bool, torch.uint8), (torch.float32, torch.uint8)
+        n = self._rows(rew)
+        shape = tuple(obs2.shape) if hasattr(obs2, "shape") else ()
+        if len(shape) < 2 or shape[0] != n or getattr(obs2_slot, "dtype", None) != obs2.dtype:
+            raise ValueError("obs2 must be [n, ...] rows with n = %d and obs2_slot of its dtype (got %r, %s and %s)"
+                             % (n, shape, getattr(obs2, "dtype", None), getattr(obs2_slot, "dtype", None)))
+        ptrs = [self._dev(obs2, shape, img, "obs2"), self._dev(rew, (n,), f32, "rew"),
+                self._dev(terminated, (n,), flag, "terminated"), self._dev(truncated, (n,), flag, "truncated"),
+                self._dev(obs2_slot, shape, img, "obs2_slot"), self._dev(rew_slot, (n,), f32, "rew_slot"),
+                self._dev(terminated_slot, (n,), flag, "terminated_slot"), self._dev(truncated_slot, (n,), flag, "truncated_slot"),
+                self._dev(ended, (n,), flag, "ended")]
+        row_bytes = int(obs2[0].numel()) * int(obs2.element_size())
+        rc = self._lib.dsact_step_frames_device(self._h, n, row_bytes, *ptrs)
         if rc != 0:
             self._chk(rc)
 

@@ -189,6 +189,30 @@ def require_tensor_engine(who, networks, action_type, env, hip_cnn_act=False):
     return eng
 
 
+def image_graph_engine(eng):
+    """an image engine with the CNN acting path (`conv_type` and `cnn_act`): the only engine on which `hip_graph_sample=True` /
+    `hip_graph_eval=True` goes together with `hip_cnn_act=True`. Attribute reads only."""
+    return bool(getattr(eng, "conv_type", None) and getattr(eng, "cnn_act", False))
+
+
+def require_graph_cnn_pair(kwarg, networks):
+    """`kwarg`=True with hip_cnn_act=True: accepted on an image engine with the CNN acting path, refused on every other ATTACHED
+    engine -- there hip_cnn_act does nothing. Reads attributes only (no environment call, no engine method call); an unattached
+    policy is left to require_tensor_engine, which refuses it in its own words."""
+    eng = getattr(getattr(networks, "policy", None), "_engine", None)
+    if eng is not None and not image_graph_engine(eng):
+        raise NotImplementedError("%s=True with hip_cnn_act=True needs an image (CNN) policy whose engine has the CNN acting path "
+                                  "(hip_cnn_act=True on the algorithm); on this %s engine hip_cnn_act does nothing: drop it"
+                                  % (kwarg, "CNN" if getattr(eng, "conv_type", None) else "MLP"))
+
+
+def require_graph_device(kwarg, dev):
+    """a graph is captured from the engine's stream: `kwarg`=True needs an engine on a GPU"""
+    if dev.type != "cuda":
+        raise NotImplementedError("%s=True needs an engine on a GPU (a graph is captured from its stream); this one is on %s"
+                                  % (kwarg, dev))
+
+
 def tensor_limits(env, eng, n):
     """(low[n, A], high[n, A], same): the environment's action limits as device rows, and whether they are the policy's own
     (dsact_set_action_limits) -- then what the library clips to is what the environment accepts"""

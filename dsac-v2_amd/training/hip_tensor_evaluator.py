@@ -58,9 +58,15 @@ eval_commit reads the environment's reward / terminated / truncated tensors wher
 previous reset's result in place; the evaluator's observation buffer is written once per window. The graph holds the addresses of
 the library's bookkeeping arrays: it is dropped (and the count restarts) on a new engine and when the engine's
 `eval_state_gen` is no longer the one it was captured under -- another evaluator's larger dsact_eval_begin reallocated them.
-`graph_captures` / `graph_replays` count. Refused in the constructor: an environment without the attribute, hip_cnn_act=True
-(NotImplementedError), a non-bool value (ValueError); at the first run_evaluation: an engine off the GPU. A capture that raises
-is ended and re-raised as a RuntimeError naming the environment.
+`graph_captures` / `graph_replays` count. Image environments under the kwarg: with hip_cnn_act=True on an
+image engine with the CNN acting path, _setup opts the engine's CNN route into capture once (dsact_cnn_acting_capture) and a
+window holds the CNN acting forward of every step; the acting call reads the previous reset's frames in place where they are
+contiguous uint8, or contiguous float32 at a 16-byte aligned address. A captured CNN acting node holds only addresses that live
+as long as the handle (no generation to watch beside eval_state_gen). Refused in the constructor: an environment without the
+attribute (NotImplementedError), a non-bool value (ValueError), hip_cnn_act=True on an attached engine that is no image engine
+with the CNN acting path (NotImplementedError: hip_cnn_act does nothing there, drop it) -- for a policy attached later, at the
+first run_evaluation, before an environment or engine call; at the first run_evaluation: an engine off the GPU. A capture that
+raises is ended and re-raised as a RuntimeError naming the environment.
 
 Evaluation draws nothing from the torch or NumPy generators and enqueues no update: the training state is not touched.
 After run_evaluation, `returns` (float64[E]), `lengths` (int32[E]) and `steps` (lockstep steps made) describe the last run.
@@ -68,7 +74,8 @@ After run_evaluation, `returns` (float64[E]), `lengths` (int32[E]) and `steps` (
 import numpy as np
 import torch
 
-from training.hip_acting_common import engine_stream, hand_over, networks_of, on_stream, require_tensor_engine, tensor_limits
+from training.hip_acting_common import (engine_stream, hand_over, image_graph_engine, networks_of, on_stream, require_graph_cnn_pair,
+                                        require_graph_device, require_tensor_engine, tensor_limits)
 
 __all__ = ["HipTensorEnvEvaluator"]
 
@@ -100,9 +107,10 @@ class HipTensorEnvEvaluator:
         if not isinstance(graph, (bool, np.bool_)):
             raise ValueError("hip_graph_eval must be True or False, got %r" % (graph,))
         self.graph_eval = bool(graph)
-        if self.graph_eval and self.cnn_act:
-            raise NotImplementedError("hip_graph_eval=True with hip_cnn_act=True: the CNN acting route records an event per call "
-                                      "and is not captured; use one of the two")
+        if self.graph_eval and self.cnn_act and kwargs.get("networks") is not None:
+            # the pair is for image engines with the CNN acting path; a policy attached later is checked
+            # at the first run_evaluation, before anything runs
+            require_graph_cnn_pair("hip_graph_eval", kwargs["networks"])
         if self.graph_eval and getattr(env, "capture_safe", False) is not True:
             raise NotImplementedError("hip_graph_eval=True needs an environment with the attribute capture_safe = True (step and "
                                       "reset(mask) update their state tensors in place, allocate nothing that outlives the call, "
@@ -127,6 +135,8 @@ class HipTensorEnvEvaluator:
     def _engine(self):
         """the engine behind the ATTACHED MLP policy (hip_cnn_act=True: or CNN policy with the CNN acting path); every other
         setup is refused"""
+        if self.graph_eval and self.cnn_act:
+            require_graph_cnn_pair("hip_graph_eval", self.networks)
         return require_tensor_engine("hip_tensor_env_evaluator", self.networks, self.action_type, self.env, self.cnn_act)
 
     def _setup(self, eng):
@@ -134,10 +144,10 @@ class HipTensorEnvEvaluator:
         N, O, A = self.n_envs, eng.obs_dim, eng.act_dim
         dev = torch.device(eng.device)
         if self.graph_eval:
-            if dev.type != "cuda":
-                raise NotImplementedError("hip_graph_eval=True needs an engine on a GPU (a graph is captured from its stream); this "
-                                          "one is on %s" % dev)
+            require_graph_device("hip_graph_eval", dev)
             self._graph, self._graph_gen, self._graph_windows = None, None, 0   # a new engine: eager, capture, replay again
+            if self.cnn_act and image_graph_engine(eng):
+                eng.cnn_acting_capture()   # the CNN route's opt-in to capture
         f = dict(dtype=torch.float32, device=dev)
         self._obs, self._act, self._clip = torch.zeros(N, O, **f), torch.zeros(N, A, **f), torch.zeros(N, A, **f)
         if getattr(eng, "conv_type", None):
@@ -154,8 +164,8 @@ class HipTensorEnvEvaluator:
         reward / terminated / truncated and the next observations in the evaluator's own buffers (the calls this class always
         made). With it -- issued eagerly, under capture, and replayed -- the staging copies leave the dependent chain: eval_commit
         reads the environment's own tensors where they are contiguous float32 / bool [N] on the engine's device, the next
-        step's acting call reads the reset's result in place where it is contiguous float32, and self._obs is written once, at
-        the end: the next window (or an eager remainder) starts from a fixed address."""
+        step's acting call reads the reset's result in place where it is contiguous float32 (image rows: contiguous uint8, or
+        float32 at a 16-byte aligned address), and self._obs is written once, at the end: the next window (or an eager remainder) starts from a fixed address."""
         N, env, direct = self.n_envs, self.env, self.graph_eval
         obs, act, clip, rew, term, trunc, ended = self._obs, self._act, self._clip, self._rew, self._term, self._trunc, self._ended
         src = obs
@@ -178,8 +188,11 @@ class HipTensorEnvEvaluator:
             # the next step's observations: this step's, with every environment that ended restarted on its own (rows
             # without an episode too)
             nxt = env.reset(ended).reshape(obs.shape)
-            if direct and nxt.dtype == torch.float32 and nxt.device == obs.device and nxt.is_contiguous():
-                src = nxt
+            if direct and nxt.device == obs.device and nxt.is_contiguous() and (
+                    (nxt.dtype == torch.float32 and obs.dim() == 2)
+                    or (obs.dim() == 4 and nxt.dtype == obs.dtype
+                        and (nxt.dtype == torch.uint8 or (nxt.dtype == torch.float32 and nxt.data_ptr() % 16 == 0)))):
+                src = nxt     # (image rows: byte frames as they are, float32 frames where the kernel's 16-byte reads are aligned)
             else:
                 obs.copy_(nxt)
                 src = obs

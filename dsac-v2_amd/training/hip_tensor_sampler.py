@@ -70,10 +70,17 @@ environment carries `capture_safe = True` -- step and reset(mask) update their s
 must outlive the call, never touch the host and stay on torch's current stream. The first sample() after _setup runs eagerly
 through dsact_act_sample_device_counted (the acting step is a counter in device memory + the step's offset; dsact_act_counter_add
 closes the call), the second captures that body on the engine's stream and replays it, every later one is ONE replay();
-dsact_track_commit stays behind the replay. A step's four row copies and the `|` are one launch (dsact_step_rows_device).
-`act_step` stays assignable: the assignment writes the device counter too. `graph_captures` / `graph_replays` count. Refused in
-the constructor: an environment without the attribute, hip_cnn_act=True (NotImplementedError), a non-bool value (ValueError); at
-the first sample(): an engine off the GPU. A capture that raises is ended and re-raised as a RuntimeError naming the environment.
+dsact_track_commit stays behind the replay. A step's four row copies and the `|` are one launch (dsact_step_rows_device; for
+[N, C, H, W] image rows dsact_step_frames_device, which splits a frame over several workgroups).
+`act_step` stays assignable: the assignment writes the device counter too. `graph_captures` / `graph_replays` count.
+Image environments under the kwarg: with hip_cnn_act=True on an image engine with the CNN acting path,
+_setup opts the engine's CNN route into capture once (dsact_cnn_acting_capture: its device-resident acting calls record no event
+any more, a held acting call fences itself) and the graph holds the chunks of 64 frames -- ingest, conv stack, feature scatter,
+trunk, output -- of every step. Refused in the constructor: an environment without the attribute (NotImplementedError), a non-bool
+value (ValueError), hip_cnn_act=True on an attached engine that is no image engine with the CNN acting path (NotImplementedError:
+hip_cnn_act does nothing there, drop it) -- for a policy attached later, at the first sample(), before an environment or engine
+call; at the first sample(): an engine off the GPU. A capture that raises is ended and re-raised as a RuntimeError naming the
+environment.
 
 sample() returns (DeviceSampleBatch, {sampler time}). The time is the HOST time of issuing the work. The batch's tensors are the
 sampler's own preallocated [S, .] buffers: they are valid until the next sample() call (add_batch consumes them in stream
@@ -85,8 +92,9 @@ import time
 import numpy as np
 import torch
 
-from training.hip_acting_common import (check_noise_dim, engine_stream, explore_noise, hand_over, networks_of, on_stream,
-                                        require_env_state, require_tensor_engine, sample_batch_size, tensor_limits)
+from training.hip_acting_common import (check_noise_dim, engine_stream, explore_noise, hand_over, image_graph_engine, networks_of,
+                                        on_stream, require_env_state, require_graph_cnn_pair, require_graph_device, require_tensor_engine,
+                                        sample_batch_size, tensor_limits)
 from training.hip_replay_buffer import act_seed_from
 from training.hip_sampler import SAMPLER_TIME_KEY
 
@@ -286,9 +294,10 @@ class HipTensorEnvSampler:
         if not isinstance(graph, (bool, np.bool_)):
             raise ValueError("hip_graph_sample must be True or False, got %r" % (graph,))
         self.graph_sample = bool(graph)
-        if self.graph_sample and self.cnn_act:
-            raise NotImplementedError("hip_graph_sample=True with hip_cnn_act=True: the CNN acting route records an event per call "
-                                      "and is not captured; use one of the two")
+        if self.graph_sample and self.cnn_act and kwargs.get("networks") is not None:
+            # the pair is for image engines with the CNN acting path; a policy attached later is checked
+            # at the first sample(), before anything runs
+            require_graph_cnn_pair("hip_graph_sample", kwargs["networks"])
         if self.graph_sample and getattr(env, "capture_safe", False) is not True:
             raise NotImplementedError("hip_graph_sample=True needs an environment with the attribute capture_safe = True (step and "
                                       "reset(mask) update their state tensors in place, allocate nothing that outlives the call, "
@@ -317,6 +326,8 @@ class HipTensorEnvSampler:
     def _engine(self):
         """the engine behind the ATTACHED MLP policy (hip_cnn_act=True: or CNN policy with the CNN acting path); every other
         setup is refused"""
+        if self.graph_sample and self.cnn_act:
+            require_graph_cnn_pair("hip_graph_sample", self.networks)
         return require_tensor_engine("hip_tensor_env_sampler", self.networks, self.action_type, self.env, self.cnn_act)
 
     @property
@@ -338,9 +349,7 @@ class HipTensorEnvSampler:
         check_noise_dim(self.noise, A)
         dev = torch.device(eng.device)
         if self.graph_sample:
-            if dev.type != "cuda":
-                raise NotImplementedError("hip_graph_sample=True needs an engine on a GPU (a graph is captured from its stream); this "
-                                          "one is on %s" % dev)
+            require_graph_device("hip_graph_sample", dev)
             self._graph, self._graph_calls, self._graph_eng = None, 0, eng   # a new engine: eager, capture, replay again
         f = dict(dtype=torch.float32, device=dev)
         # the observation rows: [., O] float32; an image environment on a CNN engine keeps [., C, H, W] rows in the FRAME's dtype
@@ -366,6 +375,8 @@ class HipTensorEnvSampler:
             eng.track_begin(N)            # (a new engine starts new statistics)
         if self.graph_sample:
             self._ended = torch.zeros(N, dtype=torch.bool, device=dev)   # terminated | truncated of a step: the mask of env.reset
+            if self.cnn_act and image_graph_engine(eng):
+                eng.cnn_acting_capture()                                 # the CNN route's opt-in to capture
             eng.act_counter_set(self._act_step)                          # the device twin of act_step
         if first is not None:
             self._obs.copy_(first.reshape((N,) + row))
@@ -376,8 +387,9 @@ class HipTensorEnvSampler:
     def _graph_body(self, eng):
         """hip_graph_sample: the S / N lockstep steps of one sample() on torch's current stream -- issued once eagerly, once under
         capture, and replayed from then on. sample()'s own loop, except that the acting step is the device counter + t
-        (act_sample_device_counted), the four row copies and the `|` are one launch (step_rows_device; the torch copies where
-        the environment hands back anything but contiguous float32 / bool tensors) and act_counter_add(S / N) closes it."""
+        (act_sample_device_counted), the four row copies and the `|` are one launch (step_rows_device; step_frames_device for
+        [N, C, H, W] image rows, uint8 or float32; the torch copies where the environment hands back anything but contiguous
+        tensors of those dtypes / bool) and act_counter_add(S / N) closes it."""
         N, S = self.n_envs, self.sample_batch_size
         env = self.env
         obs_b, obs2_b, act_b, clip_b = self._obs_b, self._obs2_b, self._act_b, self._clip_b
@@ -390,10 +402,15 @@ class HipTensorEnvSampler:
                 torch.minimum(torch.maximum(act_b[r0:r1], self._low), self._high, out=clip_b[r0:r1])
             obs2, rew, term, trunc = env.step(clip_b[r0:r1])
             obs2 = obs2.reshape((N,) + self._row)
-            if (self._one_launch_rows and obs2.dim() == 2 and obs2.dtype == torch.float32 and rew.dtype == torch.float32 and term.dtype == torch.bool
-                    and trunc.dtype == torch.bool and tuple(rew.shape) == tuple(term.shape) == tuple(trunc.shape) == (N,)
-                    and obs2.is_contiguous() and rew.is_contiguous() and term.is_contiguous() and trunc.is_contiguous()):
+            one = (self._one_launch_rows and rew.dtype == torch.float32 and term.dtype == torch.bool
+                   and trunc.dtype == torch.bool and tuple(rew.shape) == tuple(term.shape) == tuple(trunc.shape) == (N,)
+                   and obs2.is_contiguous() and rew.is_contiguous() and term.is_contiguous() and trunc.is_contiguous())
+            if one and obs2.dim() == 2 and obs2.dtype == torch.float32:
                 eng.step_rows_device(obs2, rew, term, trunc, obs2_b[r0:r1], rew_b[r0:r1], term_b[r0:r1], trunc_b[r0:r1], self._ended)
+                ended = self._ended
+            elif one and obs2.dim() == 4 and obs2.dtype in (torch.uint8, torch.float32) and obs2.dtype == obs2_b.dtype:
+                # image rows: a frame is split over several workgroups (row_bytes = the frame's byte size)
+                eng.step_frames_device(obs2, rew, term, trunc, obs2_b[r0:r1], rew_b[r0:r1], term_b[r0:r1], trunc_b[r0:r1], self._ended)
                 ended = self._ended
             else:
                 obs2_b[r0:r1].copy_(obs2)

@@ -619,7 +619,8 @@ int dsact_buffer_add_device(dsact_handle* h, int64_t n, const float* obs, const 
  *                                  (DSACT_E_STATE if no earlier call has made the batched forward's buffers: make one call outside
  *                                  the capture first), waits for nothing and leaves the hand-off check to the next entry point
  *                                  outside the capture. DSACT_E_STATE while profiling; DSACT_E_INVALID on a CNN handle (that route
- *                                  records an event per call), dsact_act_mode_device_u8 included.
+ *                                  records an event per call), dsact_act_mode_device_u8 included -- unless the handle opted in
+ *                                  with dsact_cnn_acting_capture (below).
  *   dsact_eval_commit              is legal under capture by the same rules (no hand-off check while capturing, DSACT_E_STATE
  *                                  while profiling). The captured node holds the ADDRESSES of the state dsact_eval_begin
  *                                  allocated, and dsact_eval_begin frees and reallocates that state when n_envs or n_episodes
@@ -673,7 +674,7 @@ int dsact_buffer_add_device_u8(dsact_handle* h, int64_t n, const uint8_t* obs, c
  *                                  depend on it), the same exploration-noise switch, bit for bit the same action / clipped /
  *                                  logp as dsact_act_sample_device(eps = NULL, step = counter + step_offset). The counter is read
  *                                  when the launch runs, behind every dsact_act_counter_* launch enqueued before it.
- *                                  DSACT_E_INVALID on CNN handles; DSACT_E_STATE before dsact_act_counter_set and without an
+ *                                  DSACT_E_INVALID on CNN handles (served after dsact_cnn_acting_capture, below); DSACT_E_STATE before dsact_act_counter_set and without an
  *                                  acting seed. LEGAL WHILE THE HANDLE'S STREAM IS CAPTURING: it then allocates nothing
  *                                  (DSACT_E_STATE if no earlier call has made the batched forward's buffers: make one call outside
  *                                  the capture first), waits for nothing, and leaves the hand-off check to the next entry point
@@ -700,6 +701,51 @@ int dsact_eval_commit(dsact_handle* h, const float* reward_dev, const uint8_t* t
                       uint8_t* ended_dev);
 int dsact_eval_poll(dsact_handle* h, int32_t* remaining);
 int dsact_eval_read(dsact_handle* h, double* returns, int32_t* lengths, int32_t n_episodes);
+
+/* ---- Image environments inside sample / eval graphs -----------------------------------------------------
+ * The two capture sections above refuse a CNN handle: its device-resident acting calls record an event behind their last launch
+ * (the fence a held dsact_act_sample_batch waits for), and a captured node cannot carry that event across replays.
+ *   dsact_cnn_acting_capture(h, on)  the PER-HANDLE OPT-IN that lifts the refusal. Legal after dsact_cnn_acting_enable
+ *                                  (DSACT_E_STATE otherwise) and outside a capture (DSACT_E_STATE). Default off: every call makes
+ *                                  the runtime calls and gives the answers described above, both refusals and their messages
+ *                                  included. STICKY: on = 0 after it was switched on is DSACT_E_STATE (on = 0 while off is a
+ *                                  no-op) -- a graph captured under it may be replayed at any time. While on:
+ *                                    - dsact_act_sample_device_counted, dsact_act_sample_device_counted_u8, dsact_act_mode_device
+ *                                      and dsact_act_mode_device_u8 on this CNN handle are LEGAL WHILE THE HANDLE'S STREAM IS
+ *                                      CAPTURING, by the MLP rules: DSACT_E_STATE "make one call outside the capture first"
+ *                                      while the forward's lazily allocated buffers are missing, DSACT_E_STATE while profiling,
+ *                                      no hand-off check under capture (left to the next entry point outside it).
+ *                                    - NO device-resident CNN acting call records the event any more, captured or not.
+ *                                    - a held host-row call (dsact_act_sample_batch / dsact_act_sample under
+ *                                      dsact_behaviour_hold, on the acting stream) records the event ON THE HANDLE'S STREAM ITSELF
+ *                                      and makes the acting stream wait for it. DSACT_E_STATE if that stream is capturing.
+ *                                    - nothing records or waits for an event inside a capture and nothing forks: the graph
+ *                                      is one linear chain on the handle's stream.
+ *                                  WHY OPT-IN: the held call's fence moves from "behind the last device-resident acting call" to
+ *                                  "behind EVERYTHING enqueued on the handle's stream at the held call" -- updates enqueued after
+ *                                  that acting call included. The held call's results are the same bits (it reads the held
+ *                                  copy of the weights); it may start later than it does without the switch.
+ *   dsact_act_sample_device_counted  on an enabled CNN handle WITH the switch on: fp32 frames, 16-byte aligned, read in place; bit
+ *                                  for bit dsact_act_sample_device(eps = NULL, step = counter + step_offset). Switch off:
+ *                                  DSACT_E_INVALID as ever.
+ *   dsact_act_sample_device_counted_u8  its byte-frame form (dsact_act_sample_device_u8's counted form): needs the switch and a
+ *                                  coded ring -- DSACT_E_INVALID without the switch or off a CNN handle, DSACT_E_STATE naming
+ *                                  hip_obs_codebook without a coded ring.
+ *   dsact_step_frames_device        dsact_step_rows_device for IMAGE rows: a row is row_bytes bytes of any element type (a byte
+ *                                  frame, an fp32 frame), split over several workgroups (k_step_rows moves a row with one
+ *                                  wave). The same pure moves and ended[i] = (terminated[i] | truncated[i]) != 0. 16 bytes per
+ *                                  lane where row_bytes % 16 == 0 and source and slot are 16-byte aligned, 4 bytes where
+ *                                  everything is 4-aligned, bytes otherwise. ASYNCHRONOUS, legal under stream capture
+ *                                  (DSACT_E_STATE while profiling); device pointers of the handle's GPU only. Any handle.
+ * A captured CNN acting node holds the addresses of the path's buffers, the codebook and the limit arrays; none of them is ever
+ * freed or reallocated before dsact_destroy (DESIGN.md section 24 has the lines), so there is no generation to watch.
+ * dsact_debug_get: "cnn_act_capture" (the switch), "step_frames_calls" (dsact_step_frames_device launches). */
+int dsact_cnn_acting_capture(dsact_handle* h, int32_t on);
+int dsact_act_sample_device_counted_u8(dsact_handle* h, const uint8_t* frames_dev, int32_t n, int64_t step_offset, float* action_dev,
+                                       float* clipped_dev, float* logp_dev);
+int dsact_step_frames_device(dsact_handle* h, int32_t n, int64_t row_bytes, const void* obs2_dev, const float* rew_dev,
+                             const uint8_t* terminated_dev, const uint8_t* truncated_dev, void* obs2_slot, float* rew_slot,
+                             uint8_t* terminated_slot, uint8_t* truncated_slot, uint8_t* ended_dev);
 
 /* ---- Episode statistics of the training environments (training/hip_tensor_sampler.py) ------------------
  * Returns and lengths of the episodes the device-resident sampler's N TRAINING environments play, kept on the device across

@@ -16,7 +16,17 @@ tests/envs/synth_tensor_blob.py (3 x 96 x 96, act 3). Policy and update are type
       windows. Medians, per-round ratios (f32 / vec, u8 / vec, u8 / f32), each leg's spread over its own windows and the
       library's launches per sample() (acting chunks x launches per chunk + the ring write's; the environment's torch ops are
       not counted) are recorded.
-Writes DIR/tensor_image_sampler_bench.json and prints it. The library must have been built (__graft_entry__.build())."""
+Writes DIR/tensor_image_sampler_bench.json and prints it. The library must have been built (__graft_entry__.build()).
+
+  python scripts/tensor_image_sampler_bench.py --graph [--out profiles] [--pairs 3] [--window 0.6]
+      the opt-in of DESIGN.md section 24: the tensor sampler issued eagerly (tests/envs/synth_tensor_blob.py) against the same
+      sampler with hip_graph_sample=True (sample() as one captured graph, on tests/envs/synth_tensor_blob_inplace.py), per N in
+      64, 256, 1024, per frame dtype (u8: byte frames, coded ring; f32: float32 frames, fp32 ring) and per metric -- `sampler`
+      (environment steps / s of sample() alone, one lockstep step per call) and `trainer1` / `trainer8` (iterations / s of
+      HipOffSerialTrainer at sample_interval 1 / 8). Each configuration runs in a fresh child process under its own
+      `timeout -k 10`; the first child that fails ends the run. One warm-up per leg (eager call, capture, replays), then `pairs`
+      alternating rounds of an eager and a captured window, the stream drained at each window's end. Writes
+      DIR/graph_image_bench.json; nothing else is run."""
 import argparse
 import json
 import os
@@ -106,6 +116,93 @@ def _library_launches(eng, smp, leg):
     return {"acting_chunks": chunks, "launches_per_chunk": per_chunk, "ring_launches": 2, "total": chunks * per_chunk + 2}
 
 
+GRAPH_NS = [64, 256, 1024]
+GRAPH_METRICS = ("sampler", "trainer1", "trainer8")
+GRAPH_FRAMES = ("u8", "f32")
+
+
+def _graph_leg(leg, frames, N, k):
+    """leg: "eager" (the plain tensor route) | "graph" (hip_graph_sample=True on the in-place fixture). frames: "u8" | "f32".
+    k: sample_interval of a trainer, 0: sample() alone"""
+    import plugin
+    from synth_tensor_blob_inplace import SynthTensorBlobInplace
+
+    kw = cnn_kwargs(SHAPE, A, "type_2", B, seed=SEED, sample_batch_size=N, buffer_max_size=max(CAP, 2 * N), buffer_warm_size=max(B, N),
+                    sample_interval=max(k, 1), max_iteration=0, log_save_interval=10 ** 9, apprfunc_save_interval=10 ** 9,
+                    eval_interval=10 ** 9, save_folder=None, ini_network_dir=None, strict_rng=False, hip_device_indices=True,
+                    hip_cnn_act=True)
+    if frames == "u8":
+        kw["hip_obs_codebook"] = BOOK
+    torch.manual_seed(SEED)
+    np.random.seed(SEED)
+    alg = plugin.create_alg(**kw)
+    cls, more = (SynthTensorBlob, {}) if leg == "eager" else (SynthTensorBlobInplace, {"hip_graph_sample": True})
+    env = cls(N, device="cuda", seed=SEED, act_dim=A, frames="uint8" if frames == "u8" else "float32")
+    smp = plugin.create_sampler(sampler_name="hip_tensor_env_sampler", env=env, **dict(kw, **more))
+    smp.networks = alg.networks
+    buf = plugin.create_buffer(**kw)     # (always: byte frames are codes into the ring's codebook)
+    tr = plugin.create_trainer(alg, smp, buf, None, **kw) if k else None
+    return alg, smp, tr
+
+
+def run_graph(N, frames, metric, pairs, window):
+    k = {"sampler": 0, "trainer1": 1, "trainer8": 8}[metric]
+    legs = {leg: _graph_leg(leg, frames, N, k) for leg in ("eager", "graph")}
+    unit = k or 1
+    counts = {}
+    for leg, h in legs.items():                      # warm-up (eager call, capture, replays); its rate sizes the windows
+        c = 4 * unit
+        dt = _window(*h, c)
+        dt = _window(*h, c)
+        counts[leg] = max(4 * unit, int(round(window / (dt / c) / unit)) * unit)
+    rows = {leg: [] for leg in legs}
+    for _ in range(pairs):
+        for leg, h in legs.items():
+            dt = _window(*h, counts[leg])
+            rows[leg].append(counts[leg] * (N if not k else 1) / dt)
+    ratios = [g / e for g, e in zip(rows["graph"], rows["eager"])]
+    eng = legs["graph"][0].engine
+    out = {"N": N, "frames": frames, "metric": metric, "unit": "iterations_per_s" if k else "env_steps_per_s", "window_counts": counts,
+           "rows": rows, "median": {x: float(np.median(v)) for x, v in rows.items()},
+           "spread": {x: (max(v) - min(v)) / float(np.median(v)) for x, v in rows.items()},
+           "ratio": "graph_over_eager", "ratios": ratios, "ratio_median": float(np.median(ratios)),
+           "graph_captures": legs["graph"][1].graph_captures, "graph_replays": legs["graph"][1].graph_replays,
+           "launches_per_step": -(-N // 64) * (1 + len(eng.layout.geom) + 1 + len(eng.layout.hidden) + 1) + 1,
+           "act_dev_syncs": {x: h[0].engine.debug_get("act_dev_syncs") for x, h in legs.items()},
+           "handoff_failures": {x: h[0].engine.debug_get("handoff_failures") for x, h in legs.items()}}
+    if not k:                                        # host time per lockstep step (= per sample() here), from the medians
+        out["us_per_step"] = {x: 1e6 * N / out["median"][x] for x in rows}
+    for h in legs.values():
+        h[0].engine.close()
+    return out
+
+
+def main_graph(a):
+    res = {"pairs": a.pairs, "window_s": a.window, "policy": "type_2 3x96x96, act 3", "batch": B, "ring_rows": CAP,
+           "legs": {"eager": "HipTensorEnvSampler on SynthTensorBlob", "graph": "hip_graph_sample=True on SynthTensorBlobInplace"},
+           "launches_per_step": "library launches of one lockstep step: acting chunks x (ingest + conv layers + feature scatter + "
+                                "trunk layers + output) + the row move; the environment's torch ops are not counted",
+           "configs": []}
+    for n in GRAPH_NS:
+        for frames in GRAPH_FRAMES:
+            for metric in GRAPH_METRICS:
+                what = "%d:%s:%s" % (n, frames, metric)
+                # every GPU step under a time limit of its own; a child that fails ends the run: nothing more is started
+                cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--graph", "--only", what,
+                       "--pairs", str(a.pairs), "--window", str(a.window)]
+                p = subprocess.run(cmd, capture_output=True, text=True)
+                line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+                if p.returncode != 0 or not line:
+                    sys.stderr.write(p.stdout + p.stderr)
+                    raise SystemExit("configuration %s failed (exit status %d)" % (what, p.returncode))
+                r = json.loads(line[-1][len("RESULT "):])
+                res["configs"].append(r)
+                print(json.dumps(r), flush=True)
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "graph_image_bench.json"), "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def run(N, metric, pairs, window):
     trainer = metric == "trainer"
     unit = K if trainer else 1
@@ -143,7 +240,15 @@ def main():
     ap.add_argument("--window", type=float, default=0.6)
     ap.add_argument("--only", default="", help="N:metric -- one configuration, in this process")
     ap.add_argument("--limit", type=int, default=240, help="seconds a configuration's child process may take")
+    ap.add_argument("--graph", action="store_true", help="only the tensor sampler eager against hip_graph_sample=True")
     a = ap.parse_args()
+    if a.graph and a.only:
+        n, frames, metric = a.only.split(":")
+        print("RESULT " + json.dumps(run_graph(int(n), frames, metric, a.pairs, a.window)), flush=True)
+        return
+    if a.graph:
+        main_graph(a)
+        return
     if a.only:
         n, metric = a.only.split(":")
         print("RESULT " + json.dumps(run(int(n), metric, a.pairs, a.window)), flush=True)
