@@ -340,6 +340,15 @@ struct dsact_handle : BatchBufs {
                                           // holds their addresses and is valid for the generation it was captured under only
   unsigned long long act_mode_dev_calls = 0;   // dsact_act_mode_device chunks launched
   unsigned long long eval_commit_calls = 0, eval_polls = 0;
+  // the evaluation trace (dsact_eval_trace_* / dsact_eval_record): the first tr_saved episodes' observation,
+  // action and reward rows, tr_max_steps slots each. The arrays are kept across evaluations and grow only (ev_gen goes up)
+  unsigned char* tr_obs = nullptr; float* tr_act = nullptr; float* tr_rew = nullptr;
+  unsigned long long* tr_dropped = nullptr;   // one 64-bit word on the device: (row, step) pairs past tr_max_steps
+  size_t tr_cap_obs = 0, tr_cap_act = 0, tr_cap_rew = 0;   // bytes allocated
+  int tr_saved = 0, tr_max_steps = 0;
+  long long tr_row_bytes = 0;
+  bool tr_active = false;
+  unsigned long long eval_record_calls = 0;
   // episode statistics of the training environments (dsact_track_*): ONE device block of tk_n rows laid out
   // as eight 8-byte columns (cur_ret, episodes, terminated, ret_sum, ret_min, ret_max, len_sum, last_ret) and two 4-byte
   // columns (cur_len, last_len), kTrackRowBytes per row, and its pinned landing place (dsact_track_read)
@@ -3540,6 +3549,7 @@ int dsact_destroy(dsact_handle* h) {
   for (void* p : {(void*)h->ev_ep, (void*)h->ev_acc, (void*)h->ev_len, (void*)h->ev_returns, (void*)h->ev_lengths, (void*)h->ev_remaining})
     if (p) hipFree(p);
   if (h->ev_remaining_host) hipHostFree(h->ev_remaining_host);
+  for (void* p : {(void*)h->tr_obs, (void*)h->tr_act, (void*)h->tr_rew, (void*)h->tr_dropped}) if (p) hipFree(p);
   if (h->tk_dev) hipFree(h->tk_dev);
   if (h->digest_dev) hipFree(h->digest_dev);
   if (h->explore_dev) hipFree(h->explore_dev);
@@ -5422,7 +5432,19 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "act_mode_dev_calls")) *value = (double)h->act_mode_dev_calls;   // dsact_act_mode_device chunks launched
   else if (!strcmp(name, "eval_commit_calls")) *value = (double)h->eval_commit_calls;     // dsact_eval_commit launches
   else if (!strcmp(name, "eval_polls")) *value = (double)h->eval_polls;                   // dsact_eval_poll waits
-  else if (!strcmp(name, "eval_state_gen")) *value = (double)h->ev_gen;                   // (re)allocations of the ev_* arrays
+  else if (!strcmp(name, "eval_state_gen")) *value = (double)h->ev_gen;                   // (re)allocations of the ev_* / tr_* arrays
+  else if (!strcmp(name, "eval_record_calls")) *value = (double)h->eval_record_calls;     // dsact_eval_record launches
+  else if (!strcmp(name, "eval_trace_dropped")) {   // (row, step) pairs past max_steps since the last dsact_eval_trace_begin. Read
+    // BEHIND THE STREAM BY THE CALLER: a blocking copy of the word as it stands (after dsact_eval_read: final)
+    unsigned long long v = 0;
+    if (h->tr_dropped) {
+      if (hipSetDevice(h->device) != hipSuccess || hipMemcpy(&v, h->tr_dropped, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError();
+        return DSACT_E_HIP;
+      }
+    }
+    *value = (double)v;
+  }
   else if (!strcmp(name, "track_commit_calls")) *value = (double)h->track_commit_calls;   // dsact_track_commit launches
   else if (!strcmp(name, "track_reads")) *value = (double)h->track_reads;                 // dsact_track_read waits
   else if (!strcmp(name, "step_rows_calls")) *value = (double)h->step_rows_calls;         // dsact_step_rows_device launches
@@ -6063,6 +6085,7 @@ static EvalCommitArgs eval_args(const dsact_handle* h) {
   memset(&a, 0, sizeof(a));
   a.ep = h->ev_ep; a.acc = h->ev_acc; a.len = h->ev_len; a.returns = h->ev_returns; a.lengths = h->ev_lengths;
   a.remaining = h->ev_remaining; a.N = h->ev_n; a.E = h->ev_e;
+  if (h->tr_active) { a.tr_rew = h->tr_rew; a.n_saved = h->tr_saved; a.max_steps = h->tr_max_steps; }
   return a;
 }
 
@@ -6101,6 +6124,7 @@ int dsact_eval_begin(dsact_handle* h, int32_t n_envs, int32_t n_episodes) {
     h->ev_cap_e = n_episodes;
   }
   h->ev_n = n_envs; h->ev_e = n_episodes;
+  h->tr_active = false;   // an evaluation starts without a trace (dsact_eval_trace_begin follows where one is wanted)
   *h->ev_remaining_host = n_episodes;
   const int m = n_envs > n_episodes ? n_envs : n_episodes;
   return launch(h, "eval_init", k_eval_init, dim3((unsigned)((m + kThreads - 1) / kThreads)), dim3(kThreads), 0, eval_args(h));
@@ -6121,7 +6145,9 @@ int dsact_eval_commit(dsact_handle* h, const float* reward_dev, const uint8_t* t
   if (!capturing) TRY(check_handoff_counted(h));
   EvalCommitArgs a = eval_args(h);
   a.reward = reward_dev; a.term = terminated_dev; a.trunc = truncated_dev; a.ended = ended_dev;
-  TRY(launch(h, "eval_commit", k_eval_commit, dim3((unsigned)((h->ev_n + kThreads - 1) / kThreads)), dim3(kThreads), 0, a));
+  // (with an active trace the step's reward goes to its slot as well: DESIGN.md section 25)
+  TRY(launch(h, "eval_commit", h->tr_active ? k_eval_commit<true> : k_eval_commit<false>,
+             dim3((unsigned)((h->ev_n + kThreads - 1) / kThreads)), dim3(kThreads), 0, a));
   h->eval_commit_calls++;
   return DSACT_OK;
 }
@@ -6155,6 +6181,126 @@ int dsact_eval_read(dsact_handle* h, double* returns, int32_t* lengths, int32_t 
     return fail(h, DSACT_E_STATE, "dsact_eval_read: %d of %d episodes have not ended", *h->ev_remaining_host, h->ev_e);
   HIPCHK(h, hipMemcpy(returns, h->ev_returns, (size_t)n_episodes * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(h, hipMemcpy(lengths, h->ev_lengths, (size_t)n_episodes * sizeof(int), hipMemcpyDeviceToHost));
+  return check_handoff(h);
+}
+
+// ---- the evaluation trace -----------------------------------------------------------------------------
+// training/evaluator.py:40-42, 53-54, 62-73 (obs_list / action_list / reward_list and the saved dict) for the first n_saved
+// episodes of the running evaluation, kept on the device until dsact_eval_trace_read
+int dsact_eval_trace_begin(dsact_handle* h, int32_t n_saved, int32_t max_steps, int64_t obs_row_bytes) {
+  if (!h) return DSACT_E_INVALID;
+  if (h->ev_n < 1) return fail(h, DSACT_E_STATE, "dsact_eval_trace_begin before dsact_eval_begin");
+  if (n_saved < 1 || n_saved > h->ev_e || max_steps < 1)
+    return fail(h, DSACT_E_INVALID, "dsact_eval_trace_begin: n_saved = %d must be 1 .. %d (the evaluation's episodes) and max_steps = %d >= 1",
+                (int)n_saved, h->ev_e, (int)max_steps);
+  const long long fp32_row = 4ll * h->O;
+  if (h->cnn && !h->cnn_act)
+    return fail(h, DSACT_E_INVALID, "dsact_eval_trace_begin serves CNN policies after dsact_cnn_acting_enable");
+  if (obs_row_bytes != fp32_row && !(h->cnn && obs_row_bytes == (long long)h->O))
+    return fail(h, DSACT_E_INVALID, "dsact_eval_trace_begin: obs_row_bytes = %lld is not the handle's observation row (%lld%s)",
+                (long long)obs_row_bytes, fp32_row, h->cnn ? " for fp32 frames, a quarter of it for byte frames" : "");
+  HIPCHK(h, hipSetDevice(h->device));
+  bool capturing = false;
+  TRY(stream_capturing(h, &capturing));
+  if (capturing) return fail(h, DSACT_E_STATE, "dsact_eval_trace_begin under stream capture (it allocates and may wait for the stream)");
+  const size_t slots = (size_t)n_saved * (size_t)max_steps;
+  const size_t need_obs = slots * (size_t)obs_row_bytes, need_act = slots * (size_t)h->A * sizeof(float), need_rew = slots * sizeof(float);
+  h->tr_active = false;
+  if (!h->tr_dropped) {
+    h->ev_gen++;
+    HIPCHK(h, hipMalloc((void**)&h->tr_dropped, 64));
+  }
+  if (need_obs > h->tr_cap_obs || need_act > h->tr_cap_act || need_rew > h->tr_cap_rew) {
+    // launches enqueued earlier (an evaluation that was given up) may still write the old arrays: they finish before the arrays go
+    h->ev_gen++;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  if (need_obs > h->tr_cap_obs) {
+    if (h->tr_obs) HIPCHK(h, hipFree(h->tr_obs));
+    h->tr_obs = nullptr; h->tr_cap_obs = 0;
+    HIPCHK(h, hipMalloc((void**)&h->tr_obs, need_obs));
+    h->tr_cap_obs = need_obs;
+  }
+  if (need_act > h->tr_cap_act) {
+    if (h->tr_act) HIPCHK(h, hipFree(h->tr_act));
+    h->tr_act = nullptr; h->tr_cap_act = 0;
+    HIPCHK(h, hipMalloc((void**)&h->tr_act, need_act));
+    h->tr_cap_act = need_act;
+  }
+  if (need_rew > h->tr_cap_rew) {
+    if (h->tr_rew) HIPCHK(h, hipFree(h->tr_rew));
+    h->tr_rew = nullptr; h->tr_cap_rew = 0;
+    HIPCHK(h, hipMalloc((void**)&h->tr_rew, need_rew));
+    h->tr_cap_rew = need_rew;
+  }
+  HIPCHK(h, hipMemsetAsync(h->tr_dropped, 0, sizeof(unsigned long long), h->stream));   // (stream order: behind the last evaluation's records)
+  h->tr_saved = n_saved; h->tr_max_steps = max_steps; h->tr_row_bytes = obs_row_bytes;
+  h->tr_active = true;
+  return DSACT_OK;
+}
+
+int dsact_eval_trace_end(dsact_handle* h) {
+  if (!h) return DSACT_E_INVALID;
+  h->tr_active = false;   // (the arrays stay for the next dsact_eval_trace_begin)
+  return DSACT_OK;
+}
+
+int dsact_eval_record(dsact_handle* h, const void* obs_dev, const float* action_dev) {
+  if (!h || !obs_dev || !action_dev) return DSACT_E_INVALID;
+  if (!h->tr_active) return fail(h, DSACT_E_STATE, "dsact_eval_record without an active trace (dsact_eval_trace_begin)");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!on_handle_gpu(h, obs_dev) || !on_handle_gpu(h, action_dev))
+    return fail(h, DSACT_E_INVALID, "dsact_eval_record takes device pointers on the handle's GPU");
+  // legal under stream capture by dsact_eval_commit's rules: a launch, no allocation, no wait
+  bool capturing = false;
+  TRY(stream_capturing(h, &capturing));
+  if (capturing && h->profiling) return fail(h, DSACT_E_STATE, "dsact_eval_record under stream capture while profiling");
+  if (!capturing) TRY(check_handoff_counted(h));
+  EvalRecordArgs a;
+  memset(&a, 0, sizeof(a));
+  a.obs = (const unsigned char*)obs_dev; a.act = action_dev;
+  a.tr_obs = h->tr_obs; a.tr_act = h->tr_act; a.dropped = h->tr_dropped;
+  a.ep = h->ev_ep; a.len = h->ev_len;
+  a.row_bytes = h->tr_row_bytes;
+  a.N = h->ev_n; a.A = h->A; a.n_saved = h->tr_saved; a.max_steps = h->tr_max_steps;
+  // (the trace base comes from hipMalloc: 16-byte aligned, so every slot is where row_bytes % 16 == 0)
+  const uintptr_t both = (uintptr_t)obs_dev | (uintptr_t)h->tr_obs;
+  a.path = (a.row_bytes % 16 == 0 && both % 16 == 0) ? 2 : (a.row_bytes % 4 == 0 && both % 4 == 0) ? 1 : 0;
+  // workgroups per row as dsact_step_frames_device chooses them: one pass of kThreads lanes over the row's 16-byte units each, 16 at most
+  const long long per = (a.row_bytes / 16 + kThreads - 1) / kThreads;
+  a.chunks = per < 1 ? 1 : (per > 16 ? 16 : (int)per);
+  TRY(launch(h, "eval_record", k_eval_record, dim3((unsigned)((long long)a.N * a.chunks)), dim3(kThreads), 0, a));
+  h->eval_record_calls++;
+  return DSACT_OK;
+}
+
+int dsact_eval_trace_read(dsact_handle* h, int32_t episode, void* obs_host, float* act_host, float* rew_host, int32_t capacity_rows,
+                          int32_t* rows) {
+  if (!h || !obs_host || !act_host || !rew_host || !rows) return DSACT_E_INVALID;
+  if (h->ev_n < 1) return fail(h, DSACT_E_STATE, "dsact_eval_trace_read before dsact_eval_begin");
+  if (!h->tr_active) return fail(h, DSACT_E_STATE, "dsact_eval_trace_read without an active trace (dsact_eval_trace_begin)");
+  if (episode < 0 || episode >= h->tr_saved)
+    return fail(h, DSACT_E_INVALID, "dsact_eval_trace_read: episode = %d, the trace holds episodes 0 .. %d", (int)episode, h->tr_saved - 1);
+  HIPCHK(h, hipSetDevice(h->device));
+  bool capturing = false;
+  TRY(stream_capturing(h, &capturing));
+  if (capturing) return fail(h, DSACT_E_STATE, "dsact_eval_trace_read under stream capture (it waits for the stream)");
+  HIPCHK(h, hipMemcpyAsync(h->ev_remaining_host, h->ev_remaining, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (*h->ev_remaining_host != 0)
+    return fail(h, DSACT_E_STATE, "dsact_eval_trace_read: %d of %d episodes have not ended", *h->ev_remaining_host, h->ev_e);
+  int len = 0;
+  HIPCHK(h, hipMemcpy(&len, h->ev_lengths + episode, sizeof(int), hipMemcpyDeviceToHost));
+  const int n = len < h->tr_max_steps ? len : h->tr_max_steps;
+  if (capacity_rows < n)
+    return fail(h, DSACT_E_INVALID, "dsact_eval_trace_read: capacity_rows = %d, episode %d holds %d rows", (int)capacity_rows, (int)episode, n);
+  const size_t slot = (size_t)episode * (size_t)h->tr_max_steps;
+  if (n > 0) {
+    HIPCHK(h, hipMemcpy(obs_host, h->tr_obs + slot * (size_t)h->tr_row_bytes, (size_t)n * (size_t)h->tr_row_bytes, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(act_host, h->tr_act + slot * (size_t)h->A, (size_t)n * (size_t)h->A * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(rew_host, h->tr_rew + slot, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  *rows = n;
   return check_handoff(h);
 }
 

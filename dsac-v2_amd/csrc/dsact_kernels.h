@@ -779,12 +779,18 @@ __global__ void __launch_bounds__(kThreads) k_ring_digest(RingDigestArgs a) {
 //     well, so the simulator is never stepped past a terminal state;
 //   * each row writes its own slots (episodes of different rows are different indices); only `remaining` is shared, by atomicAdd.
 // Plain C++, vector loads / stores and one vector atomic; no LDS.
+// kTrace (dsact_eval_trace_begin is active): the step's reward is also stored at slot (e, len - 1) of
+// tr_rew[n_saved][max_steps] -- the reward_list.append of training/evaluator.py:62 -- where the episode is a saved one and the
+// step lies inside the trace; `len` is the value this launch counts, so the slot is the one k_eval_record filled before the
+// environment stepped. <false> is the body above, unchanged: it never reads the three trace fields.
 struct EvalCommitArgs {
   const float* reward; const unsigned char* term; const unsigned char* trunc; unsigned char* ended;
   int* ep; double* acc; int* len; double* returns; int* lengths; int* remaining;
   int N, E;
+  float* tr_rew; int n_saved, max_steps;
 };
 #ifndef DSACT_FAMILY_UNIT   // plain kernel: compiled in dsact_api.hip only (dsact_tu.h)
+template <bool kTrace>
 __global__ void __launch_bounds__(kThreads) k_eval_commit(EvalCommitArgs a) {
   const int i = (int)blockIdx.x * kThreads + (int)threadIdx.x;
   if (i >= a.N) return;
@@ -794,6 +800,9 @@ __global__ void __launch_bounds__(kThreads) k_eval_commit(EvalCommitArgs a) {
   if (e < 0) return;
   const double acc = a.acc[i] + (double)a.reward[i];
   const int len = a.len[i] + 1;
+  if constexpr (kTrace) {
+    if (e < a.n_saved && len - 1 < a.max_steps) a.tr_rew[(long long)e * a.max_steps + (len - 1)] = a.reward[i];
+  }
   if (end) {
     a.returns[e] = acc; a.lengths[e] = len;
     a.acc[i] = 0.0; a.len[i] = 0;
@@ -809,6 +818,58 @@ __global__ void __launch_bounds__(kThreads) k_eval_init(EvalCommitArgs a) {
   if (i < a.N) { a.ep[i] = i < a.E ? i : -1; a.acc[i] = 0.0; a.len[i] = 0; }
   if (i < a.E) { a.returns[i] = 0.0; a.lengths[i] = 0; }
   if (i == 0) *a.remaining = a.E;
+}
+#endif
+
+// k_eval_record: the obs_list.append / action_list.append of training/evaluator.py:53-54 for the device-resident evaluator
+// (dsact_eval_record) -- one launch per lockstep step, issued BEFORE the environment steps, so ep[i] /
+// len[i] are the episode row i is playing and the number of steps it has made: the slot of this step is (ep[i], len[i]) of
+//   tr_obs[n_saved][max_steps][row_bytes] (raw bytes: fp32 rows, fp32 frames and byte frames are the same kernel)
+//   tr_act[n_saved][max_steps][A]         (fp32)
+// A row is split over `chunks` workgroups the way k_step_frames splits a frame (grid N * chunks): workgroup (i, c) moves units
+// c * kThreads + tid, then every chunks * kThreads-th one; path 2 = 16 bytes per lane (row_bytes % 16 == 0, source and trace
+// base 16-byte aligned: then every row and every slot is), 1 = 4 bytes (everything 4-aligned), 0 = bytes. The first workgroup of
+// a row moves the action row. A row without an episode or with an episode >= n_saved does nothing; a step at len[i] >= max_steps
+// stores nothing and adds 1 to `dropped`, once per (row, step): lane 0 of the row's first workgroup, one vector atomicAdd. Every slot
+// offset is 64-bit. Plain C++, vector loads / stores and that one vector atomic; no LDS. Every store is inside slot
+// (e, t) with e < n_saved and t < max_steps.
+struct EvalRecordArgs {
+  const unsigned char* obs; const float* act;
+  unsigned char* tr_obs; float* tr_act; unsigned long long* dropped;
+  const int* ep; const int* len;
+  long long row_bytes;
+  int N, A, n_saved, max_steps, chunks, path;
+};
+#ifndef DSACT_FAMILY_UNIT   // plain kernel: compiled in dsact_api.hip only (dsact_tu.h)
+__global__ void __launch_bounds__(kThreads) k_eval_record(EvalRecordArgs a) {
+  const int i = (int)blockIdx.x / a.chunks, c = (int)blockIdx.x % a.chunks;
+  if (i >= a.N) return;
+  const int e = a.ep[i], t = a.len[i];
+  if (e < 0 || e >= a.n_saved) return;
+  if (t >= a.max_steps) {
+    if (c == 0 && threadIdx.x == 0) atomicAdd(a.dropped, 1ull);
+    return;
+  }
+  const long long slot = (long long)e * a.max_steps + t;
+  const unsigned char* s = a.obs + (long long)i * a.row_bytes;
+  unsigned char* d = a.tr_obs + slot * a.row_bytes;
+  const long long first = (long long)c * kThreads + (int)threadIdx.x, stride = (long long)a.chunks * kThreads;
+  if (a.path == 2) {
+    const uint4* s4 = reinterpret_cast<const uint4*>(s);
+    uint4* d4 = reinterpret_cast<uint4*>(d);
+    for (long long k = first; k < a.row_bytes / 16; k += stride) d4[k] = s4[k];
+  } else if (a.path == 1) {
+    const unsigned int* s1 = reinterpret_cast<const unsigned int*>(s);
+    unsigned int* d1 = reinterpret_cast<unsigned int*>(d);
+    for (long long k = first; k < a.row_bytes / 4; k += stride) d1[k] = s1[k];
+  } else {
+    for (long long k = first; k < a.row_bytes; k += stride) d[k] = s[k];
+  }
+  if (c == 0) {
+    const float* sa = a.act + (long long)i * a.A;
+    float* da = a.tr_act + slot * a.A;
+    for (int k = (int)threadIdx.x; k < a.A; k += kThreads) da[k] = sa[k];
+  }
 }
 #endif
 

@@ -152,6 +152,10 @@ SYMBOLS = [
     ("dsact_cnn_acting_capture", C.c_int, [_P, C.c_int32]),
     ("dsact_act_sample_device_counted_u8", C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P, _P]),
     ("dsact_step_frames_device", C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("dsact_eval_trace_begin", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64]),
+    ("dsact_eval_trace_end", C.c_int, [_P]),
+    ("dsact_eval_record", C.c_int, [_P, _P, _P]),
+    ("dsact_eval_trace_read", C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P]),
 ]
 
 _lib = None

@@ -944,6 +944,43 @@ class DsactEngine:
         self._chk(self._lib.dsact_eval_read(self._h, returns.ctypes.data_as(C.c_void_p), lengths.ctypes.data_as(C.c_void_p), E))
         return returns, lengths
 
+    # ---- the evaluation trace: eval_save's lists of the first episodes, kept on the device ----------------
+    def eval_trace_begin(self, n_saved: int, max_steps: int, obs_row_bytes: int):
+        """dsact_eval_trace_begin (after eval_begin): record the first n_saved episodes of the running evaluation, up to max_steps
+        steps each; obs_row_bytes is one observation row in bytes (4 * obs_dim; image engines: C*H*W bytes of uint8 frames or
+        4*C*H*W of float32 frames). Allocates on growth only (eval_state_gen then goes up)."""
+        self._chk(self._lib.dsact_eval_trace_begin(self._h, int(n_saved), int(max_steps), int(obs_row_bytes)))
+        self._trace_row_bytes = int(obs_row_bytes)
+
+    def eval_trace_end(self):
+        """dsact_eval_trace_end: the trace goes inactive (its arrays are kept for the next eval_trace_begin)"""
+        self._chk(self._lib.dsact_eval_trace_end(self._h))
+
+    def eval_record(self, obs, action):
+        """dsact_eval_record: one lockstep step of the trace, BEFORE the environment steps -- obs[N, O] float32 (image engines:
+        frames as act_mode_device takes them, float32 or uint8) and action[N, A] float32, the action the environment receives.
+        Contiguous tensors on this engine's GPU. Asynchronous; legal under stream capture."""
+        n = getattr(self, "_eval_n", None)
+        if n is None:
+            n = self._rows(obs)   # (the library refuses: E_STATE)
+        (po, _), pa = self._frames(obs, n, "obs"), self._dev(action, (n, self.act_dim), (self.torch.float32,), "action")
+        rc = self._lib.dsact_eval_record(self._h, po, pa)
+        if rc != 0:
+            self._chk(rc)
+
+    def eval_trace_read(self, episode: int, capacity_rows: int):
+        """dsact_eval_trace_read: (obs uint8[rows, obs_row_bytes] -- the raw bytes of the rows --, act float32[rows, A], rew
+        float32[rows]) of one saved episode, rows = min(its length, max_steps) <= capacity_rows. WAITS; DsactError E_STATE while
+        an episode has not ended."""
+        cap = max(int(capacity_rows), 0)
+        rb = getattr(self, "_trace_row_bytes", 4 * self.obs_dim)
+        obs, act, rew = np.empty((cap, rb), np.uint8), np.empty((cap, self.act_dim), np.float32), np.empty(cap, np.float32)
+        rows = C.c_int32()
+        self._chk(self._lib.dsact_eval_trace_read(self._h, int(episode), obs.ctypes.data_as(C.c_void_p), act.ctypes.data_as(C.c_void_p),
+                                                  rew.ctypes.data_as(C.c_void_p), cap, C.byref(rows)))
+        n = int(rows.value)
+        return obs[:n], act[:n], rew[:n]
+
     # ---- episode statistics of the training environments (DESIGN.md section 17): one launch per commit, one wait in track_read ---
     TRACK_COLUMNS = (("episodes", np.int64), ("terminated", np.int64), ("ret_sum", np.float64), ("ret_min", np.float64),
                      ("ret_max", np.float64), ("len_sum", np.int64), ("last_ret", np.float64), ("last_len", np.int32),

@@ -4,6 +4,7 @@ consumes the torch generator), the question "which engine stands behind this pol
 Nothing here runs per environment step.
 """
 import contextlib
+import os
 
 import numpy as np
 import torch
@@ -24,6 +25,44 @@ def _reset(env):
     if isinstance(out, tuple) and len(out) == 2 and isinstance(out[1], dict):
         return out
     return out, {}
+
+
+# ---- eval_save: the evaluation episodes on disk -----------------------------------------------------
+def eval_save_kwargs(kwargs):
+    """(eval_save, save_folder) as the three evaluators take them (training/evaluator.py:25-26): eval_save a bool, default
+    False; with it save_folder is required. Refused with ValueError before anything runs and before anything is written."""
+    save = kwargs.get("eval_save", False)
+    if not isinstance(save, (bool, np.bool_)):
+        raise ValueError("eval_save must be True or False, got %r" % (save,))
+    folder = kwargs.get("save_folder")
+    if save and (folder is None or not isinstance(folder, (str, os.PathLike)) or not str(folder)):
+        raise ValueError("eval_save=True writes save_folder/evaluator/iter{iteration}_ep{k}.npy: pass save_folder (got %r)" % (folder,))
+    return bool(save), (os.fspath(folder) if save else folder)
+
+
+class EvalEpisodeCounter:
+    """the k of iter{iteration}_ep{k}: the reference's print_time (training/evaluator.py:28-29, 35-39) -- episodes counted from 0
+    within one `iteration` value, across run_evaluation calls that pass the same value"""
+
+    def __init__(self):
+        self.print_time, self.print_iteration = 0, -1
+
+    def next(self, iteration):
+        if self.print_iteration != iteration:
+            self.print_iteration, self.print_time = iteration, 0
+        else:
+            self.print_time += 1
+        return self.print_time
+
+
+def write_eval_episode(save_folder, iteration, k, reward_list, action_list, obs_list):
+    """np.save(save_folder/evaluator/iter{iteration}_ep{k}, {"reward_list", "action_list", "obs_list"}) -- training/
+    evaluator.py:63-73's dict and file name; the directory is created. Returns the path written (np.save adds .npy)."""
+    folder = os.path.join(save_folder, "evaluator")
+    os.makedirs(folder, exist_ok=True)
+    path = os.path.join(folder, "iter{}_ep{}".format(iteration, k))
+    np.save(path, {"reward_list": reward_list, "action_list": action_list, "obs_list": obs_list})
+    return path + ".npy"
 
 
 # ---- constructor steps ------------------------------------------------------------------------------------------------------

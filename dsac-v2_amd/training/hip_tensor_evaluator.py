@@ -70,12 +70,32 @@ raises is ended and re-raised as a RuntimeError naming the environment.
 
 Evaluation draws nothing from the torch or NumPy generators and enqueues no update: the training state is not touched.
 After run_evaluation, `returns` (float64[E]), `lengths` (int32[E]) and `steps` (lockstep steps made) describe the last run.
+
+Recording the episodes (`eval_save=True` with `save_folder`; default off: exactly the calls above): the
+reference's eval_save (training/evaluator.py:26, 40-73) -- every evaluation episode written to
+save_folder/evaluator/iter{iteration}_ep{k}.npy as the dict {"reward_list", "action_list", "obs_list"}, one entry per step; load
+one with np.load(path, allow_pickle=True).item(). The rows never leave the GPU during the evaluation: dsact_eval_trace_begin
+follows dsact_eval_begin, every lockstep step issues ONE more launch (dsact_eval_record, between the clip and env.step: the
+observation rows the acting call read and the action the environment receives) and dsact_eval_commit also stores the reward;
+after dsact_eval_read the first `hip_eval_save_episodes` episodes (default: all) are read back one by one and written.
+reward_list holds Python floats (the float32 rewards, exactly), action_list float32[A] rows, obs_list rows in the shape and dtype
+the environment returned (byte frames stay uint8[C, H, W]). k counts the episodes of one `iteration` value from 0 and keeps
+counting when run_evaluation is called again with the same value (the reference's print_time, evaluator.py:35-39).
+`hip_eval_save_max_steps` (default: the environment's max_episode_steps attribute; required where it has none) is the number of
+steps kept per episode: a longer episode's file holds its first steps, `trace_dropped` counts the (row, step) pairs left out and
+one RuntimeWarning per evaluation names them; TAR, returns and lengths are not affected. The trace takes
+episodes * steps * (observation row + 4 A + 4) bytes of device memory; above `hip_eval_save_max_bytes` (default 1 << 30) the
+first run_evaluation refuses, before any call is made. Under hip_graph_eval the record is a node of the captured window.
 """
+import os
+import warnings
+
 import numpy as np
 import torch
 
-from training.hip_acting_common import (engine_stream, hand_over, image_graph_engine, networks_of, on_stream, require_graph_cnn_pair,
-                                        require_graph_device, require_tensor_engine, tensor_limits)
+from training.hip_acting_common import (EvalEpisodeCounter, engine_stream, eval_save_kwargs, hand_over, image_graph_engine, networks_of,
+                                        on_stream, require_graph_cnn_pair, require_graph_device, require_tensor_engine, tensor_limits,
+                                        write_eval_episode)
 
 __all__ = ["HipTensorEnvEvaluator"]
 
@@ -85,6 +105,17 @@ class HipTensorEnvEvaluator:
         self.num_eval_episode = int(kwargs.get("num_eval_episode", 5))
         if self.num_eval_episode < 1:
             raise ValueError("num_eval_episode must be >= 1 (got %d)" % self.num_eval_episode)
+        # eval_save: refused here, before an environment is made or touched
+        self.eval_save, self.save_folder = eval_save_kwargs(kwargs)
+        self.save_episodes = kwargs.get("hip_eval_save_episodes")
+        self.save_episodes = self.num_eval_episode if self.save_episodes is None else int(self.save_episodes)
+        if self.eval_save and not 1 <= self.save_episodes <= self.num_eval_episode:
+            raise ValueError("hip_eval_save_episodes must be 1 .. num_eval_episode = %d (got %d)" % (self.num_eval_episode, self.save_episodes))
+        self.save_max_bytes = int(kwargs.get("hip_eval_save_max_bytes", 1 << 30))
+        self.trace_dropped = 0                  # (row, step) pairs past hip_eval_save_max_steps in the last run_evaluation
+        self.saved_files = []                   # the files the last run_evaluation wrote, in episode-index order
+        self._episode_counter = EvalEpisodeCounter()
+        self._trace_on = False                  # an eval_trace_begin of the running evaluation has been made
         self.poll_steps = int(kwargs.get("hip_eval_poll_steps", 16))
         if self.poll_steps < 1:
             raise ValueError("hip_eval_poll_steps must be >= 1 (got %d)" % self.poll_steps)
@@ -99,6 +130,16 @@ class HipTensorEnvEvaluator:
         self.n_envs = int(env.num_envs)
         if self.n_envs < 1:
             raise ValueError("the environment's num_envs must be >= 1 (got %d)" % self.n_envs)
+        self.save_max_steps = kwargs.get("hip_eval_save_max_steps")
+        if self.save_max_steps is None and self.eval_save:
+            self.save_max_steps = getattr(env, "max_episode_steps", None)
+            if self.save_max_steps is None:
+                raise ValueError("eval_save=True keeps a fixed number of steps per episode and %s has no max_episode_steps attribute: "
+                                 "pass hip_eval_save_max_steps" % type(env).__name__)
+        if self.eval_save:
+            self.save_max_steps = int(self.save_max_steps)
+            if self.save_max_steps < 1:
+                raise ValueError("hip_eval_save_max_steps must be >= 1 (got %d)" % self.save_max_steps)
         self.action_type = kwargs.get("action_type", "continu")
         self.cnn_act = bool(kwargs.get("hip_cnn_act", False))   # image environments on an engine with the CNN acting path
         # hip_graph_eval: the poll windows as one captured graph. Refused here, before any environment or
@@ -175,6 +216,8 @@ class HipTensorEnvEvaluator:
                 a = act
             else:
                 a = torch.minimum(torch.maximum(act, self._low), self._high, out=clip)
+            if self.eval_save:
+                eng.eval_record(src, a)   # what the acting call read and what the environment receives (evaluator.py:53-54)
             obs2, r, te, tr = env.step(a)
             if (direct and r.dtype == torch.float32 and te.dtype == torch.bool and tr.dtype == torch.bool
                     and tuple(r.shape) == tuple(te.shape) == tuple(tr.shape) == (N,) and r.device == te.device == tr.device == rew.device
@@ -224,8 +267,47 @@ class HipTensorEnvEvaluator:
             self.graph_replays += 1
         self._graph_windows += 1
 
+    def _trace_bytes(self, eng, row_bytes):
+        """the device memory of the trace for observation rows of row_bytes bytes; above hip_eval_save_max_bytes: ValueError"""
+        per_step = row_bytes + 4 * eng.act_dim + 4
+        total = self.save_episodes * self.save_max_steps * per_step
+        if total > self.save_max_bytes:
+            raise ValueError("eval_save: the trace takes %d episodes x %d steps x %d bytes per step (a %d-byte observation row, "
+                             "the action row and the reward) = %d bytes, above hip_eval_save_max_bytes = %d: lower "
+                             "hip_eval_save_episodes or hip_eval_save_max_steps, or raise the bound"
+                             % (self.save_episodes, self.save_max_steps, per_step, row_bytes, total, self.save_max_bytes))
+        return total
+
+    def _trace_begin(self, eng, obs):
+        """eval_trace_begin for rows like obs[N, ...] and, under hip_graph_eval, the generation check over the trace's arrays"""
+        row_bytes = int(obs[0].numel()) * int(obs.element_size())
+        self._trace_bytes(eng, row_bytes)
+        eng.eval_trace_begin(self.save_episodes, self.save_max_steps, row_bytes)
+        self._trace_on = True
+        if self._graph is not None and eng.debug_get("eval_state_gen") != self._graph_gen:
+            self._graph, self._graph_gen, self._graph_windows = None, None, 0   # (the trace's arrays were reallocated)
+
+    def _write_trace(self, eng, iteration):
+        """the files of the evaluation that has just been read (evaluator.py:63-73): episode e < hip_eval_save_episodes goes to
+        iter{iteration}_ep{k0 + e}; every episode of the evaluation counts in k"""
+        ks = [self._episode_counter.next(iteration) for _ in range(self.num_eval_episode)]
+        obs_dtype = np.uint8 if self._obs.dtype == torch.uint8 else np.float32
+        self.saved_files = []
+        for e in range(self.save_episodes):
+            raw, act, rew = eng.eval_trace_read(e, min(int(self.lengths[e]), self.save_max_steps))
+            rows = np.ascontiguousarray(raw).view(obs_dtype).reshape((raw.shape[0],) + self._row_shape)
+            self.saved_files.append(write_eval_episode(self.save_folder, iteration, ks[e], [float(x) for x in rew],
+                                                       [a.copy() for a in act], [o.copy() for o in rows]))
+        self.trace_dropped = int(eng.debug_get("eval_trace_dropped"))   # (behind eval_read's wait: final)
+        if self.trace_dropped:
+            warnings.warn("eval_save: %d (episode, step) pairs lie past hip_eval_save_max_steps = %d and are not in the files of "
+                          "iteration %s (trace_dropped); returns and lengths are complete"
+                          % (self.trace_dropped, self.save_max_steps, iteration), RuntimeWarning, stacklevel=3)
+
     def run_evaluation(self, iteration):
         eng = self._engine()
+        if self.eval_save and not getattr(eng, "conv_type", None):
+            self._trace_bytes(eng, 4 * eng.obs_dim)   # refused before any call is made (image rows: once their dtype is known)
         if self._ready != id(eng):
             self._setup(eng)
         pol = self.networks.policy
@@ -241,11 +323,17 @@ class HipTensorEnvEvaluator:
                 # dsact_eval_begin reallocated the bookkeeping's arrays (another evaluator on this engine asked for more rows or
                 # episodes): the graph's eval_commit nodes hold the freed addresses. Eager, capture, replay again
                 self._graph, self._graph_gen, self._graph_windows = None, None, 0
+            self.trace_dropped, self._trace_on = 0, False
+            if self.eval_save and obs is not None:
+                self._trace_begin(eng, obs)
             first = env.reset()
             if obs is None:
                 row = tuple(getattr(eng, "obs_shape", None) or first.shape[1:])
                 odt = torch.uint8 if first.dtype == torch.uint8 else torch.float32
                 obs = self._obs = torch.zeros((N,) + row, dtype=odt, device=first.device)
+            self._row_shape = tuple(first.shape[1:])   # a saved observation row keeps the shape the environment returns
+            if self.eval_save and not self._trace_on:
+                self._trace_begin(eng, obs)            # (image rows on a new engine: the frames' dtype is known only now)
             obs.copy_(first.reshape(obs.shape))
             # windows of P lockstep steps (the last one shorter where hip_eval_max_steps is no multiple of P), one wait behind each
             while self.steps < self.max_steps:
@@ -259,7 +347,14 @@ class HipTensorEnvEvaluator:
                 if remaining == 0:
                     break
             if remaining != 0:
+                if self.eval_save:
+                    eng.eval_trace_end()
                 raise RuntimeError("hip_tensor_env_evaluator: %d of %d episodes have not ended after hip_eval_max_steps = %d lockstep "
                                    "steps" % (remaining, E, self.max_steps))
             self.returns, self.lengths = eng.eval_read(E)
+            if self.eval_save:
+                try:
+                    self._write_trace(eng, iteration)
+                finally:
+                    eng.eval_trace_end()
         return np.mean(self.returns)   # episode-index order (evaluator.py:77-81)

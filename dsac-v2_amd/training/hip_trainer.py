@@ -28,7 +28,7 @@ import time
 
 import torch
 
-from training.hip_acting_common import _reset, networks_of
+from training.hip_acting_common import EvalEpisodeCounter, _reset, eval_save_kwargs, networks_of, write_eval_episode
 
 __all__ = ["HipOffSerialTrainer", "HipEvaluator", "create_trainer", "create_evaluator", "save_tb_to_csv", "TB_TAGS"]
 
@@ -122,33 +122,44 @@ class _Scalars:
 
 class HipEvaluator:
     """Deterministic-mode rollouts (reference training/evaluator.py:34-84): mean episode return of
-    `num_eval_episode` episodes acting with dist.mode()."""
+    `num_eval_episode` episodes acting with dist.mode(). eval_save=True with save_folder (evaluator.py:26, 40-73; DESIGN.md
+    section 25): every episode is written to save_folder/evaluator/iter{iteration}_ep{k}.npy as the reference writes it -- the
+    observations before each step, the actions handed to env.step and the rewards as the environment returned them."""
 
     def __init__(self, index=0, **kwargs):
         from plugin import create_env
 
+        self.eval_save, self.save_folder = eval_save_kwargs(kwargs)   # (refused before an environment is made)
+        self._episode_counter = EvalEpisodeCounter()
         self.env = kwargs.get("eval_env") or kwargs.get("env") or create_env(**kwargs)
         if kwargs.get("seed") is not None and hasattr(self.env, "seed"):
             self.env.seed(kwargs["seed"])  # reference evaluator.py:15: set_seed(..., env) seeds with the plain seed
         self.networks = networks_of(kwargs)   # evaluator.py:16-20: consumes the torch generator like the reference
         self.num_eval_episode = kwargs.get("num_eval_episode", 5)
 
-    def run_an_episode(self):
+    def run_an_episode(self, iteration=None):
         obs = _reset(self.env)[0]
         rewards, done = [], False
+        save = self.eval_save and iteration is not None
+        obs_list, action_list = [], []
         while not done:
             with torch.no_grad():
                 logits = self.networks.policy(torch.from_numpy(obs.astype("float32")[None]))
                 act = self.networks.create_action_distributions(logits).mode()[0].cpu().numpy()
+            if save:   # evaluator.py:53-54: the observation the policy saw, the action env.step receives
+                obs_list.append(obs)
+                action_list.append(act)
             obs, r, done, info = self.env.step(act)
             rewards.append(r)
             done = bool(done) or bool(info.get("TimeLimit.truncated", False))
+        if save:
+            write_eval_episode(self.save_folder, iteration, self._episode_counter.next(iteration), rewards, action_list, obs_list)
         return sum(rewards)   # the reference's own reduction (evaluator.py:71): same value to the last bit
 
     def run_evaluation(self, iteration):
         import numpy as np
 
-        return np.mean([self.run_an_episode() for _ in range(self.num_eval_episode)])   # evaluator.py:74-78
+        return np.mean([self.run_an_episode(iteration) for _ in range(self.num_eval_episode)])   # evaluator.py:74-78
 
 
 class HipOffSerialTrainer:

@@ -19,17 +19,25 @@ Acting routes (per step, over the live rows):
   * an unattached container or a shape the library does not serve (act_dim > 32): the module forward over the live batch
     plus create_action_distributions(...).mode().
 Evaluation draws nothing from the torch generator and enqueues no update: the training state is not touched.
+
+eval_save=True with save_folder (training/evaluator.py:26, 40-73): episode e of a call is written to
+save_folder/evaluator/iter{iteration}_ep{k0 + e}.npy -- k0 the episode counter at the start of the call (the reference's
+print_time rule) -- whatever order the episodes finish in, with the dict HipEvaluator writes for that episode on environment
+e % N's own copy. The files are written after the loop, in episode-index order.
 """
 import numpy as np
 import torch
 
-from training.hip_acting_common import ANY_POLICY, _reset, attached_engine, env_count, make_envs, networks_of
+from training.hip_acting_common import (ANY_POLICY, EvalEpisodeCounter, _reset, attached_engine, env_count, eval_save_kwargs, make_envs,
+                                        networks_of, write_eval_episode)
 
 __all__ = ["HipVecEvaluator"]
 
 
 class HipVecEvaluator:
     def __init__(self, index=0, **kwargs):
+        self.eval_save, self.save_folder = eval_save_kwargs(kwargs)   # (refused before an environment is made)
+        self._episode_counter = EvalEpisodeCounter()
         envs, self.n_envs = env_count(kwargs, "eval_envs", "hip_eval_env_num", noun="evaluation environments")
         self.envs = make_envs(kwargs, envs, self.n_envs)
         self.networks = networks_of(kwargs)   # evaluator.py:16-20: the generator is consumed as HipEvaluator's
@@ -62,9 +70,13 @@ class HipVecEvaluator:
             eng.note_torch_writes(self.networks.policy.parameters())   # (weights written with torch ops since the last call)
         returns = [None] * E
         episode, rewards, obs = {}, {}, {}
+        save = self.eval_save
+        ks = [self._episode_counter.next(iteration) for _ in range(E)] if save else None   # episode e -> file k0 + e
+        seen, acted, traces = {}, {}, [None] * E   # per live environment: obs_list / action_list; per episode: the three lists
 
         def begin(i, e):
             episode[i], rewards[i], obs[i] = e, [], _reset(envs[i])[0]
+            seen[i], acted[i] = [], []
 
         for i in range(min(N, E)):
             begin(i, i)
@@ -87,6 +99,9 @@ class HipVecEvaluator:
             self.steps += 1
             ended = []
             for j, i in enumerate(live):
+                if save:   # evaluator.py:53-54: the observation before the step, the action env.step receives (its own row)
+                    seen[i].append(obs[i])
+                    acted[i].append(act[j].copy())
                 o, r, done, info = envs[i].step(act[j])
                 rewards[i].append(r)
                 obs[i] = o
@@ -95,11 +110,15 @@ class HipVecEvaluator:
             for i in ended:
                 e = episode[i]
                 returns[e] = sum(rewards[i])   # the reference's own reduction (evaluator.py:71)
+                traces[e] = (rewards[i], acted[i], seen[i])
                 if e + N < E:
                     begin(i, e + N)
                 else:
                     del episode[i], rewards[i], obs[i]
             if ended:
                 live = sorted(episode)
+        if save:
+            for e in range(E):
+                write_eval_episode(self.save_folder, iteration, ks[e], *traces[e])
         self.returns = returns
         return np.mean(returns)   # episode-index order (evaluator.py:74-78)

@@ -747,6 +747,53 @@ int dsact_step_frames_device(dsact_handle* h, int32_t n, int64_t row_bytes, cons
                              const uint8_t* terminated_dev, const uint8_t* truncated_dev, void* obs2_slot, float* rew_slot,
                              uint8_t* terminated_slot, uint8_t* truncated_slot, uint8_t* ended_dev);
 
+/* ---- The evaluation trace: eval_save on the device (training/hip_tensor_evaluator.py) -------------------
+ * The reference's Evaluator with eval_save keeps every evaluation episode's observations, actions and rewards and writes them
+ * to save_folder/evaluator/iter{iteration}_ep{k}.npy. A device-resident evaluation never brings a row to the host, so the
+ * handle keeps the lists of the FIRST n_saved episodes beside dsact_eval_begin's bookkeeping and hands them over at the end:
+ *   tr_obs[n_saved][max_steps][obs_row_bytes] raw bytes, tr_act[n_saved][max_steps][act_dim] fp32, tr_rew[n_saved][max_steps]
+ *   fp32, and one 64-bit `dropped` counter. The handle owns them; dsact_destroy frees them.
+ *   dsact_eval_trace_begin         training/evaluator.py:40-42 (obs_list = [], action_list = [], reward_list = []) for episodes
+ *                                  0 .. n_saved - 1 of the running evaluation (1 <= n_saved <= n_episodes), max_steps >= 1 slots
+ *                                  each. Call it after dsact_eval_begin (DSACT_E_STATE before one). Allocates only on growth,
+ *                                  after draining the handle's stream as dsact_eval_begin does; "eval_state_gen" goes up on
+ *                                  every (re)allocation, so the guard of a graph with dsact_eval_commit nodes covers the trace's
+ *                                  addresses too. `dropped` is zeroed in stream order by every call. obs_row_bytes must be the
+ *                                  handle's observation row: 4 * obs_dim for MLP handles; C*H*W (byte frames) or 4*C*H*W (fp32
+ *                                  frames) for image handles after dsact_cnn_acting_enable -- anything else DSACT_E_INVALID.
+ *                                  DSACT_E_STATE under stream capture. n_saved and max_steps are baked into captured nodes.
+ *   dsact_eval_trace_end           the trace goes inactive: later commits and records behave as without one (training/
+ *                                  evaluator.py:62-73 is over: the dict has been handed out). The arrays are kept for the next
+ *                                  begin. dsact_eval_begin is no substitute for this call, but every evaluation starts WITHOUT
+ *                                  a trace: after dsact_eval_begin the trace is inactive until the next dsact_eval_trace_begin.
+ *   dsact_eval_record              training/evaluator.py:53-54 (obs_list.append(obs); action_list.append(action)) for every row
+ *                                  in ONE launch, issued BEFORE the environment steps: a row i that plays a saved episode
+ *                                  (0 <= ep[i] < n_saved) copies its observation row (obs_row_bytes bytes of obs_dev, row-major)
+ *                                  and its action row (act_dim floats of action_dev: the action the environment receives) into
+ *                                  slot (ep[i], len[i]) when len[i] < max_steps; at len[i] >= max_steps it stores nothing and adds
+ *                                  1 to `dropped`, once per (row, step). Every other row does nothing. A row is split over
+ *                                  several workgroups like dsact_step_frames_device's; 16 bytes per lane where obs_row_bytes %
+ *                                  16 == 0 and obs_dev is 16-byte aligned, 4 bytes where everything is 4-aligned, bytes
+ *                                  otherwise; slot offsets are 64-bit. By dsact_eval_commit's rules: device pointers of the
+ *                                  handle's GPU only (DSACT_E_INVALID), ASYNCHRONOUS, legal under stream capture (DSACT_E_STATE
+ *                                  while profiling). DSACT_E_STATE without an active trace.
+ *   dsact_eval_commit              with an active trace also stores the step's reward (training/evaluator.py:62:
+ *                                  reward_list.append(reward)) at slot (e, len - 1), len the step count this commit reaches,
+ *                                  when e < n_saved and len - 1 < max_steps. Everything else it does is unchanged.
+ *   dsact_eval_trace_read          training/evaluator.py:62-73 (the dict of the three lists): WAITS, then copies rows =
+ *                                  min(lengths[episode], max_steps) rows of one saved episode to obs_host (rows * obs_row_bytes
+ *                                  bytes), act_host (rows * act_dim floats) and rew_host (rows floats). DSACT_E_STATE while an
+ *                                  episode of the evaluation has not ended and without an active trace; DSACT_E_INVALID when
+ *                                  episode is not 0 .. n_saved - 1 or capacity_rows < rows.
+ * dsact_debug_get: "eval_record_calls" (dsact_eval_record launches, host calls as "eval_commit_calls"), "eval_trace_dropped" (the
+ * counter AS IT STANDS, a blocking copy that does not wait for the handle's stream: read it after dsact_eval_read);
+ * "act_dev_syncs" stays 0 across dsact_eval_record too. */
+int dsact_eval_trace_begin(dsact_handle* h, int32_t n_saved, int32_t max_steps, int64_t obs_row_bytes);
+int dsact_eval_trace_end(dsact_handle* h);
+int dsact_eval_record(dsact_handle* h, const void* obs_dev, const float* action_dev);
+int dsact_eval_trace_read(dsact_handle* h, int32_t episode, void* obs_host, float* act_host, float* rew_host, int32_t capacity_rows,
+                          int32_t* rows);
+
 /* ---- Episode statistics of the training environments (training/hip_tensor_sampler.py) ------------------
  * Returns and lengths of the episodes the device-resident sampler's N TRAINING environments play, kept on the device across
  * sample() calls: one launch per sample(), no wait unless the numbers are asked for. Per environment row i < n_envs the handle

@@ -22,7 +22,17 @@ Writes DIR/tensor_eval_bench.json and prints it. The library must have been buil
       per-pair ratios (eager / graph) and the time per lockstep step are recorded. One more child: the captured leg at
       hip_eval_poll_steps P in 4, 16, 64, N = 256, the periods taken in turn inside each round.
       Writes DIR/graph_eval_bench.json. `--only eager:N` measures the eager leg of that comparison alone (it needs nothing this
-      kwarg added: the figure to compare across two builds of the library)."""
+      kwarg added: the figure to compare across two builds of the library).
+
+  python scripts/tensor_eval_bench.py --save [--parent DIR] [--out profiles] [--pairs 3]
+      eval_save=True against the evaluator without it, N = E = 256, a fresh child process per route: eager
+      (tests/envs/synth_tensor_humanoid.py) and hip_graph_eval (its in-place twin). Legs, taken in turn inside each of `pairs`
+      rounds: "off" (no kwarg), "save_1" (hip_eval_save_episodes=1: the extra launch per lockstep step, one file) and "save" (all
+      256 episodes read back and written to a temporary folder, which is emptied between windows, outside the timing).
+      --parent DIR: the one timing claim of the feature -- eval_save absent costs what it cost before. DIR is a built checkout of
+      the commit to compare with; 2 * `pairs` pairs of fresh child processes, the order swapped from pair to pair, run
+      `--only eager:256` from DIR and from this tree, and the ratio this / parent is recorded per pair with each side's spread.
+      Writes DIR/tensor_eval_save_bench.json."""
 import argparse
 import json
 import os
@@ -66,11 +76,11 @@ def _alg():
     return plugin.create_alg(**kw)
 
 
-def _tensor(alg, N, P=None, graph=None):
+def _tensor(alg, N, P=None, graph=None, **more):
     """graph None: the section-16 leg (the plain fixture). False / True: the in-place fixture without / with hip_graph_eval"""
     import plugin
 
-    kw = {} if P is None else {"hip_eval_poll_steps": P}
+    kw = dict(more) if P is None else dict(more, hip_eval_poll_steps=P)
     if graph:
         kw["hip_graph_eval"] = True
     env = SynthTensorHumanoid if graph is None else SynthTensorHumanoidInplace
@@ -197,7 +207,99 @@ def run_graph_poll(N, pairs, window):
     return out
 
 
+def run_save(N, pairs, window, graph):
+    """eval_save against the evaluator without it: legs off / save_1 / save in turn, `pairs` rounds"""
+    import shutil
+    import tempfile
+
+    alg = _alg()
+    root = tempfile.mkdtemp(prefix="tensor_eval_save_bench_")
+    try:
+        saved = {"off": 0, "save_1": 1, "save": N}
+        evs = {leg: _tensor(alg, N, graph=True if graph else None,
+                            **({} if not n else dict(eval_save=True, save_folder=os.path.join(root, leg), hip_eval_save_episodes=n,
+                                                     hip_eval_save_max_steps=LIMIT)))
+               for leg, n in saved.items()}
+
+        def clean():
+            alg.engine.sync()
+            size = sum(os.path.getsize(os.path.join(d, f)) for d, _, fs in os.walk(root) for f in fs)
+            for leg in saved:
+                shutil.rmtree(os.path.join(root, leg), ignore_errors=True)
+            return size
+
+        reps, tars, written = {}, {}, {}
+        for leg, ev in evs.items():                   # warm-up (the captured route: eager window + capture), then the sizing run
+            tars[leg] = _window(alg, ev, 1)[1]
+            clean()
+            dt = _window(alg, ev, 1)[0]
+            written[leg] = clean()                    # bytes one evaluation writes
+            reps[leg] = max(1, int(round(window / dt))) if leg == "off" else 1
+        rows = {leg: [] for leg in evs}
+        for _ in range(pairs):
+            for leg, ev in evs.items():
+                dt, tar = _window(alg, ev, reps[leg])
+                clean()
+                rows[leg].append(dt)
+                assert tar == tars[leg] == tars["off"], (leg, tar, tars)
+        e = alg.engine
+        steps = {leg: int(ev.steps) for leg, ev in evs.items()}
+        out = {"route": "graph" if graph else "eager", "N": N, "episodes": N, "metric": "seconds_per_run_evaluation",
+               "repetitions_per_window": reps, "rows": rows, "lockstep_steps": steps, "tar": tars, "poll_steps": evs["off"].poll_steps,
+               "mean_episode_length": float(np.mean(evs["off"].lengths)), "bytes_written_per_evaluation": written,
+               "trace_bytes": {leg: n * LIMIT * (4 * O + 4 * A + 4) for leg, n in saved.items()},
+               "trace_dropped": {leg: int(ev.trace_dropped) for leg, ev in evs.items()},
+               "us_per_lockstep_step": {leg: 1e6 * float(np.median(v)) / steps[leg] for leg, v in rows.items()},
+               "over_off": {leg: [a / b for a, b in zip(rows[leg], rows["off"])] for leg in ("save_1", "save")},
+               "eval_record_calls": e.debug_get("eval_record_calls"), "act_dev_syncs": e.debug_get("act_dev_syncs"),
+               "handoff_failures": e.debug_get("handoff_failures")}
+        if graph:
+            out["graph_captures"] = {leg: ev.graph_captures for leg, ev in evs.items()}
+        out.update(_stats(rows))
+        e.close()
+        return out
+    finally:
+        shutil.rmtree(root, ignore_errors=True)
+
+
+def _child(script, only, pairs, window):
+    cmd = ["timeout", "-k", "10", "300", sys.executable, script, "--only", only, "--pairs", str(pairs), "--window", str(window)]
+    p = subprocess.run(cmd, capture_output=True, text=True, cwd=os.path.dirname(os.path.dirname(script)))
+    line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+    if p.returncode != 0 or not line:
+        sys.stderr.write(p.stdout + p.stderr)
+        raise SystemExit("configuration %s of %s failed (exit status %d)" % (only, script, p.returncode))
+    return json.loads(line[-1][len("RESULT "):])
+
+
+def save_main(a):
+    res = {"pairs": a.pairs, "window_s": a.window, "policy": "376-256-256-256-34", "episode_limit": LIMIT, "N": 256, "configs": [],
+           "off_against_parent": None}
+    for only in ("save:256", "savegraph:256"):
+        r = _child(os.path.abspath(__file__), only, a.pairs, a.window)
+        res["configs"].append(r)
+        print(json.dumps(r), flush=True)
+    if a.parent:
+        scripts = {"parent": os.path.join(os.path.abspath(a.parent), "scripts", "tensor_eval_bench.py"), "this": os.path.abspath(__file__)}
+        rows = {k: [] for k in scripts}
+        for i in range(2 * a.pairs):                  # pairs of fresh processes, the order swapped from pair to pair (a process that
+            for k in (("parent", "this") if i % 2 == 0 else ("this", "parent")):     # follows another one starts on a warm device)
+                rows[k].append(_child(scripts[k], "eager:256", a.pairs, a.window)["median"]["eager"])   # the child's median window
+        ratios = [t / p for p, t in zip(rows["parent"], rows["this"])]
+        res["off_against_parent"] = dict({"configuration": "eager:256 (no eval_save kwarg), seconds per run_evaluation, one fresh "
+                                          "process per entry", "rows": rows, "this_over_parent": ratios,
+                                          "this_over_parent_median": float(np.median(ratios))}, **_stats(rows))
+        print(json.dumps(res["off_against_parent"]), flush=True)
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "tensor_eval_save_bench.json"), "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def _one(only, pairs, window):
+    if only.startswith("savegraph:"):
+        return run_save(int(only[10:]), pairs, window, True)
+    if only.startswith("save:"):
+        return run_save(int(only[5:]), pairs, window, False)
     if only.startswith("graphpoll:"):
         return run_graph_poll(int(only[10:]), pairs, window)
     if only.startswith("graph:"):
@@ -216,10 +318,14 @@ def main():
     ap.add_argument("--window", type=float, default=0.5)
     ap.add_argument("--only", default="", help="N, poll:N, graph:N, graphpoll:N or eager:N -- one configuration, in this process")
     ap.add_argument("--graph", action="store_true", help="hip_graph_eval against the eager evaluator -> graph_eval_bench.json")
+    ap.add_argument("--save", action="store_true", help="eval_save against the evaluator without it -> tensor_eval_save_bench.json")
+    ap.add_argument("--parent", default="", help="with --save: a built checkout of the commit to compare the kwarg-less evaluator with")
     a = ap.parse_args()
     if a.only:
         print("RESULT " + json.dumps(_one(a.only, a.pairs, a.window)), flush=True)
         return
+    if a.save:
+        return save_main(a)
     res = {"pairs": a.pairs, "window_s": a.window, "policy": "376-256-256-256-34", "episode_limit": LIMIT, "configs": [], "poll": None}
     todo = [str(n) for n in NS] + ["poll:256"]
     if a.graph:
