@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -96,6 +97,44 @@ constexpr int kChainFlagInts = kChainFlags + 128 + kChainCounters;
 // Everything that exists once per staged minibatch. The handle derives from it: h->X0, h->fwd1 ... are the SELECTED set's
 // (select_set copies one of dsact_handle::sets over them), so every enqueue function and args builder reads the handle.
 // A field a set has no storage of its own for holds the workspace's pointer (carve).
+// The shadow of a background snapshot (dsact_buffer_shadow_*) -- the ONLY handle state that two threads
+// touch. The owning thread takes and releases; one reader thread exports rows and digests in between. Every field is read and
+// written under `mu`; a reader copies what it needs out of the struct, counts itself in `readers` and works without the lock.
+// The reader never touches anything else of the handle: not its stream, not h->err (its text goes to `err` here).
+struct ShadowShared {
+  mutable std::mutex mu;
+  int state = 0;                        // 0: free, 1: taken and not released
+  int readers = 0;                      // reader calls in flight (a release while one runs is refused)
+  char* base = nullptr;                 // the six columns, each on a 256-byte boundary: column k starts at base + col_off[k]
+  size_t alloc_bytes = 0;
+  long long layout_rows = 0;            // rows the column offsets were laid out for (>= size of every take that uses them)
+  size_t col_off[6] = {};
+  size_t row_bytes[6] = {};
+  unsigned long long* dig = nullptr;    // [n_chunks][6]
+  size_t dig_words = 0;                 // allocated 64-bit words
+  long long size = 0, ptr = 0, chunk_rows = 0, n_chunks = 0;   // of the take
+  unsigned long long bytes = 0;         // what the take needed: the padded columns of `size` rows + the digest words
+  unsigned long long takes = 0;
+  hipEvent_t ev = nullptr;              // recorded behind the take's launch: all a reader waits for
+  hipStream_t copy_stream = nullptr;    // the reader's own stream
+  std::vector<void*> retired;           // allocations a growing take replaced: freed by a release (hipFree waits, a take must not)
+  char err[512] = {0};                  // the reader's error text (dsact_buffer_shadow_error)
+};
+// frees the shadow's device memory (owning thread; hipFree waits for the device). The copy stream and the event stay.
+static void shadow_free_memory(ShadowShared& s) {
+  for (void* p : s.retired) hipFree(p);
+  s.retired.clear();
+  if (s.base) hipFree(s.base);
+  if (s.dig) hipFree(s.dig);
+  s.base = nullptr; s.dig = nullptr;
+  s.alloc_bytes = 0; s.dig_words = 0; s.layout_rows = 0;
+}
+static void shadow_destroy(ShadowShared& s) {
+  if (s.copy_stream) { hipStreamSynchronize(s.copy_stream); hipStreamDestroy(s.copy_stream); s.copy_stream = nullptr; }
+  if (s.ev) { hipEventDestroy(s.ev); s.ev = nullptr; }
+  shadow_free_memory(s);
+}
+
 struct BatchBufs {
   float *X0 = nullptr, *XP = nullptr, *X2 = nullptr, *rew = nullptr, *done = nullptr;
   float *eps_new = nullptr, *eps_2 = nullptr, *z5 = nullptr, *z6 = nullptr;
@@ -322,6 +361,7 @@ struct dsact_handle : BatchBufs {
   unsigned long long ring_commit_rows = 0;   // transitions written by dsact_buffer_add_device
   unsigned long long* digest_dev = nullptr;  // dsact_buffer_digest: the six 64-bit sums k_ring_digest adds into (allocated by the first call)
   unsigned long long act_dev_syncs = 0;  // stream synchronisations made inside those two entry points (stays 0)
+  ShadowShared shadow;                   // the device shadow of background snapshots (dsact_buffer_shadow_*)
   // exploration noise of the device-resident sampling calls (dsact_set_explore_noise)
   int explore_n = 0;                     // 0: off, 1: one normal per row (SHARED), act_dim: one per action dimension
   float* explore_dev = nullptr;          // (mean[32] | std[32]) on the device, allocated by the first call that switches it on
@@ -3552,6 +3592,7 @@ int dsact_destroy(dsact_handle* h) {
   for (void* p : {(void*)h->tr_obs, (void*)h->tr_act, (void*)h->tr_rew, (void*)h->tr_dropped}) if (p) hipFree(p);
   if (h->tk_dev) hipFree(h->tk_dev);
   if (h->digest_dev) hipFree(h->digest_dev);
+  shadow_destroy(h->shadow);
   if (h->explore_dev) hipFree(h->explore_dev);
   if (h->act_counter_dev) hipFree(h->act_counter_dev);
   if (h->tk_host) hipHostFree(h->tk_host);
@@ -4159,6 +4200,208 @@ int dsact_buffer_digest(dsact_handle* h, int64_t row0, int64_t n, uint64_t out[6
   HIPCHK(h, hipStreamSynchronize(h->stream));
   for (int k = 0; k < 6; ++k) out[k] = (uint64_t)got[k];
   return check_handoff(h);
+}
+
+// ---- background snapshots: a consistent device copy of the live rows, taken in stream order --------
+namespace {
+size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+// bytes of six columns of `rows` rows, each padded to a 256-byte boundary; off[k] (optional) receives column k's offset
+size_t shadow_layout(const RingColumn c[6], long long rows, size_t off[6]) {
+  size_t at = 0;
+  for (int k = 0; k < 6; ++k) {
+    if (off) off[k] = at;
+    at += up256((size_t)rows * c[k].row_bytes);
+  }
+  return at;
+}
+// the reader's failure: its own text, never h->err
+int shadow_fail(dsact_handle* h, int code, const char* fmt, ...) {
+  std::lock_guard<std::mutex> lk(h->shadow.mu);
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(h->shadow.err, sizeof(h->shadow.err), fmt, ap);
+  va_end(ap);
+  return code;
+}
+#define SHADOW_HIPCHK(h, call)                                                                   \
+  do {                                                                                           \
+    hipError_t e_ = (call);                                                                      \
+    if (e_ != hipSuccess) { rc = shadow_fail(h, DSACT_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); goto done; } \
+  } while (0)
+// a reader call's entry and exit: a copy of the shared fields, and the in-flight count
+struct ShadowView { char* base; size_t col_off[6], row_bytes[6]; unsigned long long* dig; long long size, n_chunks; hipEvent_t ev; hipStream_t cs; };
+int shadow_reader_enter(dsact_handle* h, const char* what, ShadowView* v) {
+  std::lock_guard<std::mutex> lk(h->shadow.mu);
+  const ShadowShared& s = h->shadow;
+  if (s.state != 1) {
+    snprintf(h->shadow.err, sizeof(h->shadow.err), "%s: no shadow is taken (dsact_buffer_shadow_take first)", what);
+    return DSACT_E_STATE;
+  }
+  v->base = s.base; v->dig = s.dig; v->size = s.size; v->n_chunks = s.n_chunks; v->ev = s.ev; v->cs = s.copy_stream;
+  for (int k = 0; k < 6; ++k) { v->col_off[k] = s.col_off[k]; v->row_bytes[k] = s.row_bytes[k]; }
+  h->shadow.readers += 1;
+  return DSACT_OK;
+}
+void shadow_reader_exit(dsact_handle* h) {
+  std::lock_guard<std::mutex> lk(h->shadow.mu);
+  h->shadow.readers -= 1;
+}
+}  // namespace
+
+int dsact_buffer_shadow_take(dsact_handle* h, int64_t chunk_rows, uint64_t max_bytes, dsact_shadow_info* info_out) {
+  if (!h) return DSACT_E_INVALID;
+  TRY(ring_entry(h, "dsact_buffer_shadow_take"));   // no ring, or the stream is capturing
+  ShadowShared& s = h->shadow;
+  {
+    std::lock_guard<std::mutex> lk(s.mu);
+    if (s.state != 0) return fail(h, DSACT_E_STATE, "dsact_buffer_shadow_take: a shadow has been taken and not released");
+  }
+  // (from here on this thread is the only one that touches the struct: a reader is admitted in state 1 only)
+  if (!info_out) return fail(h, DSACT_E_INVALID, "dsact_buffer_shadow_take: info_out is NULL");
+  if (chunk_rows < 1) return fail(h, DSACT_E_INVALID, "dsact_buffer_shadow_take: chunk_rows must be >= 1 (got %lld)", (long long)chunk_rows);
+  RingColumn c[6];
+  ring_columns(h, c);
+  const long long size = h->size;
+  const long long n_chunks = (size + chunk_rows - 1) / chunk_rows;
+  const size_t dig_words = (size_t)n_chunks * 6;
+  const unsigned long long need = (unsigned long long)shadow_layout(c, size, nullptr) + (unsigned long long)dig_words * 8;
+  if (max_bytes != 0 && need > max_bytes)
+    return fail(h, DSACT_E_INVALID, "dsact_buffer_shadow_take: the shadow of %lld rows needs %llu bytes, max_bytes is %llu", size, need,
+                (unsigned long long)max_bytes);
+  for (int k = 0; k < 6; ++k)
+    if (((uintptr_t)c[k].base & 15u) != 0)
+      return fail(h, DSACT_E_STATE, "dsact_buffer_shadow_take: ring column %d does not start on a 16-byte boundary", k);
+  TRY(check_codes(h));
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!s.ev) HIPCHK(h, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming | hipEventBlockingSync));   // (the reader sleeps in its wait)
+  if (!s.copy_stream) HIPCHK(h, hipStreamCreateWithFlags(&s.copy_stream, hipStreamNonBlocking));
+  if (size > 0 && (!s.base || s.layout_rows < size)) {
+    // grow: to the ring's capacity when the bound allows (a filling ring then never grows again), else to what this take needs.
+    // The old allocation is retired, not freed: hipFree waits for the device, and a take never waits
+    const unsigned long long full = (unsigned long long)shadow_layout(c, h->cap, nullptr) + (unsigned long long)((h->cap + chunk_rows - 1) / chunk_rows) * 48;
+    const long long rows = (max_bytes == 0 || full <= max_bytes) ? h->cap : size;
+    const size_t bytes = shadow_layout(c, rows, nullptr);
+    char* fresh = nullptr;
+    HIPCHK(h, hipMalloc(&fresh, bytes));
+    std::lock_guard<std::mutex> lk(s.mu);
+    if (s.base) s.retired.push_back(s.base);
+    s.base = fresh; s.alloc_bytes = bytes; s.layout_rows = rows;
+    shadow_layout(c, rows, s.col_off);
+  }
+  if (dig_words > s.dig_words) {
+    unsigned long long* fresh = nullptr;
+    HIPCHK(h, hipMalloc(&fresh, dig_words * 8));
+    std::lock_guard<std::mutex> lk(s.mu);
+    if (s.dig) s.retired.push_back(s.dig);
+    s.dig = fresh; s.dig_words = dig_words;
+  }
+  if (size > 0) {
+    RingShadowArgs a;
+    unsigned long long most = 0;
+    const unsigned long long rows0 = (unsigned long long)(size < chunk_rows ? size : chunk_rows);   // rows of the longest chunk
+    for (int k = 0; k < 6; ++k) {
+      const int eb = (k < 2 && h->rb_code) ? 1 : 4;
+      a.col[k].src = c[k].base;
+      a.col[k].dst = s.base + s.col_off[k];
+      a.col[k].w = (unsigned long long)(c[k].row_bytes / (size_t)eb);
+      a.col[k].elem_bytes = eb;
+      const unsigned long long loads = rows0 * a.col[k].w / (eb == 4 ? 4u : 16u);
+      if (loads > most) most = loads;
+    }
+    a.dig = s.dig;
+    a.size = (unsigned long long)size;
+    a.chunk_rows = (unsigned long long)chunk_rows;
+    // workgroups per (chunk, column) pair: one 16-byte access per lane of the widest column's chunk, capped so that a column
+    // gets about eight workgroups per compute unit over all chunks (k_ring_digest's cap; the kernel strides over the rest)
+    unsigned long long bpp = (most + kThreads - 1) / kThreads;
+    const unsigned long long cap_bpp = std::max<unsigned long long>(1, (unsigned long long)(h->n_cu > 0 ? h->n_cu : 256) * 8 / (unsigned long long)n_chunks);
+    bpp = std::min(std::max<unsigned long long>(bpp, 1), cap_bpp);
+    a.bpp = (unsigned)bpp;
+    const unsigned long long per_launch = 0x7FFFFFFFull / (6 * bpp);   // chunks whose workgroups fit one grid's x dimension
+    HIPCHK(h, hipMemsetAsync(s.dig, 0, dig_words * 8, h->stream));
+    for (unsigned long long k0 = 0; k0 < (unsigned long long)n_chunks; k0 += per_launch) {
+      const unsigned long long nk = std::min(per_launch, (unsigned long long)n_chunks - k0);
+      a.chunk0 = k0;
+      TRY(launch(h, "ring_shadow", k_ring_shadow, dim3((unsigned)(nk * 6 * bpp)), dim3(kThreads), 0, a));
+    }
+  }
+  HIPCHK(h, hipEventRecord(s.ev, h->stream));
+  {
+    std::lock_guard<std::mutex> lk(s.mu);
+    for (int k = 0; k < 6; ++k) s.row_bytes[k] = c[k].row_bytes;
+    s.size = size; s.ptr = h->ptr; s.chunk_rows = chunk_rows; s.n_chunks = n_chunks; s.bytes = need;
+    s.takes += 1;
+    s.err[0] = 0;
+    s.state = 1;
+  }
+  info_out->size = size; info_out->ptr = h->ptr; info_out->chunk_rows = chunk_rows; info_out->n_chunks = n_chunks; info_out->bytes = need;
+  return DSACT_OK;
+}
+
+int dsact_buffer_shadow_export(dsact_handle* h, int64_t row0, int64_t n, void* obs, void* obs2, float* act, float* rew, float* done,
+                               float* logp) {
+  if (!h) return DSACT_E_INVALID;
+  ShadowView v;
+  TRY(shadow_reader_enter(h, "dsact_buffer_shadow_export", &v));
+  int rc = DSACT_OK;
+  void* dst[6] = {obs, obs2, act, rew, done, logp};
+  if (row0 < 0 || n < 0 || row0 > v.size || n > v.size - row0) {
+    rc = shadow_fail(h, DSACT_E_INVALID, "dsact_buffer_shadow_export: rows [%lld, %lld + %lld) are not inside the %lld rows taken", (long long)row0,
+                     (long long)row0, (long long)n, v.size);
+    goto done;
+  }
+  SHADOW_HIPCHK(h, hipSetDevice(h->device));
+  SHADOW_HIPCHK(h, hipEventSynchronize(v.ev));
+  if (n > 0) {
+    for (int k = 0; k < 6; ++k)
+      if (dst[k])
+        SHADOW_HIPCHK(h, hipMemcpyAsync(dst[k], v.base + v.col_off[k] + (size_t)row0 * v.row_bytes[k], (size_t)n * v.row_bytes[k],
+                                        hipMemcpyDeviceToHost, v.cs));
+    SHADOW_HIPCHK(h, hipStreamSynchronize(v.cs));
+  }
+done:
+  shadow_reader_exit(h);
+  return rc;
+}
+
+int dsact_buffer_shadow_digests(dsact_handle* h, uint64_t* out, int64_t n_chunks) {
+  if (!h) return DSACT_E_INVALID;
+  ShadowView v;
+  TRY(shadow_reader_enter(h, "dsact_buffer_shadow_digests", &v));
+  int rc = DSACT_OK;
+  if (n_chunks != v.n_chunks || (n_chunks > 0 && !out)) {
+    rc = shadow_fail(h, DSACT_E_INVALID, "dsact_buffer_shadow_digests: %lld chunks asked for (out %s), the take made %lld", (long long)n_chunks,
+                     out ? "given" : "NULL", v.n_chunks);
+    goto done;
+  }
+  SHADOW_HIPCHK(h, hipSetDevice(h->device));
+  SHADOW_HIPCHK(h, hipEventSynchronize(v.ev));
+  if (n_chunks > 0) {
+    SHADOW_HIPCHK(h, hipMemcpyAsync(out, v.dig, (size_t)n_chunks * 48, hipMemcpyDeviceToHost, v.cs));
+    SHADOW_HIPCHK(h, hipStreamSynchronize(v.cs));
+  }
+done:
+  shadow_reader_exit(h);
+  return rc;
+}
+
+const char* dsact_buffer_shadow_error(const dsact_handle* h) { return h ? h->shadow.err : "null handle"; }
+
+int dsact_buffer_shadow_release(dsact_handle* h, int32_t free_memory) {
+  if (!h) return DSACT_E_INVALID;
+  ShadowShared& s = h->shadow;
+  {
+    std::lock_guard<std::mutex> lk(s.mu);
+    if (s.readers != 0) return fail(h, DSACT_E_STATE, "dsact_buffer_shadow_release: a reader call is still running");
+    s.state = 0;
+  }
+  // (state 0 admits no reader: the rest is this thread's alone)
+  if (free_memory || !s.retired.empty()) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (free_memory) shadow_free_memory(s);
+    else { for (void* p : s.retired) hipFree(p); s.retired.clear(); }
+  }
+  return DSACT_OK;
 }
 
 int dsact_gather(dsact_handle* h, const int64_t* idx_host, int32_t batch) {
@@ -5428,6 +5671,11 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "act_dev_calls")) *value = (double)h->act_dev_calls;       // dsact_act_sample_device chunks launched
   else if (!strcmp(name, "ring_commit_rows")) *value = (double)h->ring_commit_rows; // transitions written by dsact_buffer_add_device
   else if (!strcmp(name, "act_dev_syncs")) *value = (double)h->act_dev_syncs;       // stream drains inside those two (0)
+  else if (!strcmp(name, "shadow_state") || !strcmp(name, "shadow_bytes") || !strcmp(name, "shadow_takes")) {
+    // the background-snapshot shadow: 1 while taken and not released; device bytes allocated for it (rows + digests); takes made
+    std::lock_guard<std::mutex> lk(h->shadow.mu);
+    *value = name[7] == 's' ? (double)h->shadow.state : name[7] == 'b' ? (double)(h->shadow.alloc_bytes + h->shadow.dig_words * 8) : (double)h->shadow.takes;
+  }
   else if (!strcmp(name, "explore_noise")) *value = (double)h->explore_n;           // dsact_set_explore_noise: 0 off, 1 SHARED, act_dim PER-DIMENSION
   else if (!strcmp(name, "act_mode_dev_calls")) *value = (double)h->act_mode_dev_calls;   // dsact_act_mode_device chunks launched
   else if (!strcmp(name, "eval_commit_calls")) *value = (double)h->eval_commit_calls;     // dsact_eval_commit launches

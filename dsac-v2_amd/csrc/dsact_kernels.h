@@ -767,6 +767,125 @@ __global__ void __launch_bounds__(kThreads) k_ring_digest(RingDigestArgs a) {
 }
 #endif
 
+// k_ring_shadow: the device half of a background snapshot (dsact_buffer_shadow_take) -- ONE launch copies
+// rows [0, size) of the six ring columns into the handle's shadow (same SoA order, same stored form) and digests every chunk
+// of `chunk_rows` rows of every column over the bytes it copies: dig[k][c] is what dsact_buffer_digest(k * chunk_rows, rows of
+// chunk k) returns for column c. The ring is read once and the digests cost no second pass over it.
+//   work:   a (chunk, column) pair is one contiguous run of elements, exactly k_ring_digest's run (g0 = k * chunk_rows * w_c,
+//           count = rows * w_c, both 64-bit products of the host's 64-bit operands), and is treated exactly like it: single
+//           elements in front of the first 16-byte boundary and behind the last whole 16 bytes, 16-byte loads for the body.
+//           `bpp` workgroups share a pair and stride over its body. The pair and the slice are folded into blockIdx.x =
+//           ((chunk - chunk0) * 6 + column) * bpp + slice, so the number of chunks is not bounded by a grid dimension's
+//           65,535 (70,000 one-row chunks are 420,000 workgroups of one launch); the host splits the chunk range over several
+//           launches only if that product would pass 2^31 - 1.
+//   stores: every loaded element goes to the same element offset of the shadow column, with a store of the load's width. The
+//           host lays the shadow columns out on 256-byte boundaries and every ring column starts on one too (its own
+//           allocation, or capacity * O code bytes into one with O % 16 == 0), so source and destination always have the same
+//           16-byte phase and the body's stores are aligned dwordx4 like its loads (dsact_buffer_shadow_take refuses a pair of
+//           bases that differ mod 16 instead of running an unaligned variant nobody could reach).
+//   cache:  both sides are non-temporal. The ring run is read once and the shadow is never read by a kernel (the copy engine
+//           takes it to the host), so neither has reuse for L1 or L2 to serve, while the update kernels that run right behind
+//           this launch want their weights to stay in L2. Loads: on gfx950 an `nt` load bypasses L1 only and is served from L2
+//           at the plain rate to within a few percent, and read-once streams are the case the hint exists for. Stores: an `nt`
+//           store keeps its line in L2 exactly like a plain one, so it is not slower, and it marks the line as streaming for the
+//           eviction policy instead of letting 3 GB of shadow displace the resident set (nt_store4 above has the same reason).
+//           Measured with both hints on: 3.09 GB copied and digested in 1.22 ms, 5.05 TB/s of read + written bytes (DESIGN.md
+//           section 26); the plain form (-DDSACT_SHADOW_NT=0) was not timed.
+//   sums:   as k_ring_digest -- one 64-bit partial per lane, six shuffles per wave, one 64-bit vector atomic add per wave into
+//           the pair's word, which the host zeroed in stream order. No LDS, no scratch.
+#ifndef DSACT_SHADOW_NT
+#define DSACT_SHADOW_NT 1
+#endif
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+struct ShadowCol {
+  const void* src;                  // the ring column's first element (row 0)
+  void* dst;                        // the shadow column's first element: dst % 16 == src % 16
+  unsigned long long w;             // elements per row: O, O, A, 1, 1, 1
+  int elem_bytes;                   // 4 (float32 bits) or 1 (code byte)
+};
+struct RingShadowArgs {
+  ShadowCol col[6];
+  unsigned long long* dig;          // [n_chunks][6], zero before the launch
+  unsigned long long size;          // rows to copy: the ring's live rows at the take
+  unsigned long long chunk_rows;
+  unsigned long long chunk0;        // first chunk of this launch
+  unsigned bpp;                     // workgroups per (chunk, column) pair
+};
+template <typename T>
+__device__ __forceinline__ T shadow_ld(const T* p) {
+#if DSACT_SHADOW_NT
+  return __builtin_nontemporal_load(p);
+#else
+  return *p;
+#endif
+}
+template <typename T>
+__device__ __forceinline__ void shadow_st(T* p, T v) {
+#if DSACT_SHADOW_NT
+  __builtin_nontemporal_store(v, p);
+#else
+  *p = v;
+#endif
+}
+#ifndef DSACT_FAMILY_UNIT   // plain kernel: compiled in dsact_api.hip only (dsact_tu.h)
+__global__ void __launch_bounds__(kThreads) k_ring_shadow(RingShadowArgs a) {
+  const unsigned slice = blockIdx.x % a.bpp;
+  const unsigned pair = blockIdx.x / a.bpp;
+  const unsigned c = pair % 6u;
+  const unsigned long long chunk = a.chunk0 + pair / 6u;
+  const unsigned long long row0 = chunk * a.chunk_rows;
+  if (row0 >= a.size) return;                                               // (never: the host sizes the grid by the chunk count)
+  const unsigned long long rows = a.size - row0 < a.chunk_rows ? a.size - row0 : a.chunk_rows;
+  const ShadowCol col = a.col[c];
+  const unsigned long long g0 = row0 * col.w, count = rows * col.w;
+  const unsigned per = col.elem_bytes == 4 ? 4u : 16u;                      // elements per 16-byte access
+  const unsigned long long addr = (unsigned long long)(uintptr_t)col.src + g0 * (unsigned)col.elem_bytes;
+  unsigned long long head = ((16u - (unsigned)(addr & 15u)) & 15u) / (unsigned)col.elem_bytes;   // elements in front of the first 16-byte boundary
+  if (head > count) head = count;
+  const unsigned long long wide = (count - head) / per;                     // whole 16-byte accesses
+  const unsigned long long tail0 = head + wide * per, tail = count - tail0;
+  const unsigned long long tid = (unsigned long long)slice * kThreads + threadIdx.x;
+  const unsigned long long nthreads = (unsigned long long)a.bpp * kThreads;
+  if ((unsigned long long)slice * kThreads >= (wide > 16 ? wide : 16)) return;   // (workgroup-uniform: nothing left for it)
+  const unsigned c1 = c + 1;
+  unsigned long long sum = 0;
+  if (col.elem_bytes == 4) {
+    const unsigned* p = reinterpret_cast<const unsigned*>(col.src) + g0;
+    unsigned* d = reinterpret_cast<unsigned*>(col.dst) + g0;
+    if (tid < head) { const unsigned v = shadow_ld(p + tid); shadow_st(d + tid, v); sum += digest_mix(g0 + tid, c1, v); }
+    if (tid < tail) { const unsigned v = shadow_ld(p + tail0 + tid); shadow_st(d + tail0 + tid, v); sum += digest_mix(g0 + tail0 + tid, c1, v); }
+    const u32x4* q = reinterpret_cast<const u32x4*>(p + head);
+    u32x4* dq = reinterpret_cast<u32x4*>(d + head);
+    for (unsigned long long k = tid; k < wide; k += nthreads) {
+      const u32x4 v = shadow_ld(q + k);
+      shadow_st(dq + k, v);
+      const unsigned long long g = g0 + head + 4 * k;
+      sum += digest_mix(g, c1, v.x) + digest_mix(g + 1, c1, v.y) + digest_mix(g + 2, c1, v.z) + digest_mix(g + 3, c1, v.w);
+    }
+  } else {
+    const unsigned char* p = reinterpret_cast<const unsigned char*>(col.src) + g0;
+    unsigned char* d = reinterpret_cast<unsigned char*>(col.dst) + g0;
+    if (tid < head) { const unsigned char v = shadow_ld(p + tid); shadow_st(d + tid, v); sum += digest_mix(g0 + tid, c1, v); }
+    if (tid < tail) { const unsigned char v = shadow_ld(p + tail0 + tid); shadow_st(d + tail0 + tid, v); sum += digest_mix(g0 + tail0 + tid, c1, v); }
+    const u32x4* q = reinterpret_cast<const u32x4*>(p + head);
+    u32x4* dq = reinterpret_cast<u32x4*>(d + head);
+    for (unsigned long long k = tid; k < wide; k += nthreads) {
+      const u32x4 v = shadow_ld(q + k);
+      shadow_st(dq + k, v);
+      const unsigned long long g = g0 + head + 16 * k;
+      const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) sum += digest_mix(g + 4 * i + b, c1, (w[i] >> (8 * b)) & 0xFFu);   // little-endian: byte b of word i
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+  if ((threadIdx.x & 63) == 0 && sum != 0) atomicAdd(a.dig + chunk * 6u + c, sum);
+}
+#endif
+
 // k_eval_commit: the episode bookkeeping of the device-resident evaluator (training/hip_tensor_evaluator.py, dsact_eval_commit)
 // -- what Evaluator.run_an_episode / run_n_episodes keep in Python lists (training/evaluator.py:34-84: reward_list.append,
 // sum(reward_list), the episode counter) for N environments that step in lockstep, one launch per lockstep step, one thread per

@@ -46,6 +46,10 @@ class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_float), ("blocks", C.c_int32)]
 
 
+class ShadowInfo(C.Structure):   # dsact_shadow_info: what dsact_buffer_shadow_take captured
+    _fields_ = [("size", C.c_int64), ("ptr", C.c_int64), ("chunk_rows", C.c_int64), ("n_chunks", C.c_int64), ("bytes", C.c_uint64)]
+
+
 # every symbol include/dsact.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 _FP = C.POINTER(C.c_float)
@@ -80,6 +84,11 @@ SYMBOLS = [
     ("dsact_buffer_import", C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P]),
     ("dsact_buffer_set_cursor", C.c_int, [_P, C.c_int64, C.c_int64]),
     ("dsact_buffer_digest", C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(C.c_uint64)]),
+    ("dsact_buffer_shadow_take", C.c_int, [_P, C.c_int64, C.c_uint64, C.POINTER(ShadowInfo)]),
+    ("dsact_buffer_shadow_export", C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    ("dsact_buffer_shadow_digests", C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int64]),
+    ("dsact_buffer_shadow_error", C.c_char_p, [_P]),
+    ("dsact_buffer_shadow_release", C.c_int, [_P, C.c_int32]),
     ("dsact_gather", C.c_int, [_P, _I64P, C.c_int32]),
     ("dsact_read_batch", C.c_int, [_P, _FP, _FP, _FP, _FP, _FP, _FP]),
     ("dsact_load_batch", C.c_int, [_P, _FP, _FP, _FP, _FP, _FP]),

@@ -351,6 +351,41 @@ class DsactEngine:
         self._chk(self._lib.dsact_buffer_digest(self._h, int(row0), int(n), out))
         return tuple(int(v) for v in out)
 
+    # ---- background snapshots: take / release on the owning thread, export / digests on ONE other thread ---
+    def buffer_shadow_take(self, chunk_rows: int, max_bytes: int = 0) -> Dict[str, int]:
+        """dsact_buffer_shadow_take: a consistent device copy of ring rows [0, buffer_size) with the digests of its chunks, in
+        stream order and without a wait. Returns what was captured: {size, ptr, chunk_rows, n_chunks, bytes}. Rows added after
+        the call do not reach the copy. max_bytes 0: no bound. One shadow at a time (DsactError until buffer_shadow_release)."""
+        info = _ffi.ShadowInfo()
+        self._chk(self._lib.dsact_buffer_shadow_take(self._h, int(chunk_rows), int(max_bytes or 0), C.byref(info)))
+        self._shadow_info = {k: int(getattr(info, k)) for k in ("size", "ptr", "chunk_rows", "n_chunks", "bytes")}
+        return dict(self._shadow_info)
+
+    def _chk_shadow(self, rc):
+        if rc != 0:   # the reader calls keep their own error text: dsact_last_error belongs to the owning thread
+            raise DsactError("%s: %s" % (_ffi.E_NAMES.get(rc, rc), self._lib.dsact_buffer_shadow_error(self._h).decode()))
+
+    def buffer_shadow_export(self, row0: int, n: int) -> Dict[str, np.ndarray]:
+        """dsact_buffer_shadow_export: rows [row0, row0 + n) of the shadow in buffer_export's form. Callable from one other
+        thread while the owning thread goes on using the engine; waits for the take only."""
+        rows = max(int(n), 0)
+        out = {k: np.empty((rows, w) if i < 3 else (rows,), dt)
+               for i, (k, w, dt) in enumerate(zip(RING_COLUMNS, self.ring_widths, self._ring_dtypes()))}
+        self._chk_shadow(self._lib.dsact_buffer_shadow_export(self._h, int(row0), int(n), *[a.ctypes.data_as(C.c_void_p) for a in out.values()]))
+        return out
+
+    def buffer_shadow_digests(self) -> np.ndarray:
+        """dsact_buffer_shadow_digests: uint64 [n_chunks, 6] -- row k is buffer_digest(k * chunk_rows, rows of chunk k) as it was
+        at the take. Reader side, like buffer_shadow_export."""
+        n = int(getattr(self, "_shadow_info", {}).get("n_chunks", 0))
+        out = np.zeros((n, 6), np.uint64)
+        self._chk_shadow(self._lib.dsact_buffer_shadow_digests(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64)), n))
+        return out
+
+    def buffer_shadow_release(self, free: bool = False):
+        """dsact_buffer_shadow_release: owning thread, after the reader is done; free=True also frees the shadow's device memory"""
+        self._chk(self._lib.dsact_buffer_shadow_release(self._h, 1 if free else 0))
+
     def buffer_check(self):
         """dsact_buffer_check: drains the stream; raises if a value missing from the codebook was written"""
         self._chk(self._lib.dsact_buffer_check(self._h))

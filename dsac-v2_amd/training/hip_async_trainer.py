@@ -70,7 +70,7 @@ def _check_supported(alg, sampler, kwargs=None):
 
 class HipOffAsyncTrainer(HipOffSerialTrainer):
     def __init__(self, alg, sampler, buffer, evaluator, **kwargs):
-        for k in ("hip_save_run_state", "ini_run_state_dir"):
+        for k in ("hip_save_run_state", "ini_run_state_dir", "hip_run_state_async"):
             if kwargs.get(k):
                 raise NotImplementedError("hip_off_async_trainer: %s is not supported -- between two groups this trainer holds a "
                                           "behaviour policy one group old, state the run-state format does not carry; use "

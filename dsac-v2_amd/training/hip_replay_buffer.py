@@ -32,18 +32,24 @@ one little-endian file per column -- rows [0, size) in the ring's stored form (f
 and a meta.json holding the cursor, the shapes, the codebook's bit patterns, the per-chunk device digests and the state of the
 device index draw. load() refuses a snapshot of another capacity, shape, coded-ness or codebook before it touches the ring, and
 leaves the ring EMPTY when the digests the device computes over the restored rows are not the saved ones.
+
+`save_async(path)` writes the same snapshot without holding the caller: one launch takes a consistent copy
+of the live rows, with its digests, inside HBM in stream order, and a writer thread moves that copy to disk while the caller goes
+on adding and sampling. It returns a RingSaveJob; the files are the ones save() would have written at the moment of the call.
 """
 import json
 import os
 import shutil
 import sys
 import tempfile
+import threading
+import time
 
 import numpy as np
 
 from dsact.engine import RING_COLUMNS, DsactEngine, current_engine, ring_digest_reference
 
-__all__ = ["HipReplayBuffer", "parse_obs_codebook", "index_seed_from", "act_seed_from"]
+__all__ = ["HipReplayBuffer", "RingSaveJob", "parse_obs_codebook", "index_seed_from", "act_seed_from"]
 
 MAX_CODES = 256
 RING_FORMAT = "dsact-ring-1"
@@ -91,6 +97,50 @@ def parse_obs_codebook(table, obs_shape):
     return f
 
 
+class RingSaveJob:
+    """A background snapshot in flight (HipReplayBuffer.save_async). `path` is where the snapshot appears, `size` the rows it
+    holds, `seconds` the writer's wall time once it is done (None before). done() asks without waiting; wait() joins the writer,
+    releases the device copy and re-raises what the writer raised -- it is called on the thread that owns the buffer."""
+
+    def __init__(self, buffer, path, info, index_seed, index_iteration, keep_shadow, on_chunk, on_done=None):
+        self.path, self.size, self.seconds = path, int(info["size"]), None
+        self._buffer, self._keep_shadow, self._error, self._released = buffer, keep_shadow, None, False
+        eng, chunk_rows, digs = buffer.engine, int(info["chunk_rows"]), []
+
+        def digest(r0, n):
+            if not digs:
+                digs.append(eng.buffer_shadow_digests())
+            return tuple(int(v) for v in digs[0][r0 // chunk_rows])
+
+        def run():
+            t0 = time.perf_counter()
+            try:
+                buffer._write_snapshot(path, self.size, int(info["ptr"]), chunk_rows, index_seed, index_iteration,
+                                       eng.buffer_shadow_export, digest, on_chunk)
+                if on_done is not None:
+                    on_done()
+            except BaseException as e:      # (kept for wait(): a thread has nobody to raise to)
+                self._error = e
+            self.seconds = time.perf_counter() - t0
+
+        # (not a daemon: an interpreter that exits with a job pending lets the snapshot finish instead of cutting it off)
+        self._thread = threading.Thread(target=run, name="dsact-ring-snapshot")
+
+    def done(self):
+        return not self._thread.is_alive()
+
+    def wait(self):
+        self._thread.join()
+        if not self._released:
+            self._released = True
+            if self._buffer._snapshot_job is self:
+                self._buffer._snapshot_job = None
+            self._buffer.engine.buffer_shadow_release(free=not self._keep_shadow)
+        if self._error is not None:
+            raise self._error
+        return self.path
+
+
 class HipReplayBuffer:
     def __init__(self, index=0, **kwargs):
         self.obsv_dim = kwargs["obsv_dim"]   # int, or the (C, H, W) tuple of the CNN configs (replay_buffer.py:22-31)
@@ -123,6 +173,8 @@ class HipReplayBuffer:
         self.engine = eng
         self.engine.buffer_create(self.max_size, codebook=self.codebook)
         self.index_seed, self.index_iteration = 0, 0
+        self._snapshot_job = None     # the pending RingSaveJob of save_async, if any
+        self.snapshot_waits = 0       # save_async calls that first had to wait for the one before
         if self.device_indices:
             seed = kwargs.get("hip_index_seed")
             self.index_seed = int(seed) if seed is not None else index_seed_from(kwargs.get("seed"))
@@ -176,20 +228,26 @@ class HipReplayBuffer:
             raise NotImplementedError("dsact-ring-1 files are little-endian; this host is not")
         if os.path.lexists(path) and not overwrite:
             raise FileExistsError("%s exists (pass overwrite=True to replace it)" % path)
+        self._wait_snapshot()
         eng = self.engine
         if hasattr(eng, "sync"):
             eng.sync()
-        size, ptr = int(self.size), int(self.ptr)
+        return self._write_snapshot(path, int(self.size), int(self.ptr), chunk_rows, int(self.index_seed), int(self.index_iteration),
+                                    eng.buffer_export, eng.buffer_digest)
+
+    def _write_snapshot(self, path, size, ptr, chunk_rows, index_seed, index_iteration, export, digest, on_chunk=None):
+        """the file side of save() and of save_async()'s writer thread: `export(row0, n)` gives a chunk's columns in stored form and
+        `digest(row0, n)` its six digests -- from the ring, or from the shadow of a background snapshot"""
         os.makedirs(os.path.dirname(path), exist_ok=True)
         tmp = tempfile.mkdtemp(prefix=os.path.basename(path) + ".tmp-", dir=os.path.dirname(path))
         try:
             files = {k: open(os.path.join(tmp, k + ".bin"), "wb") for k in RING_COLUMNS}
             chunks, total = [], [0] * 6
             try:
-                for r0 in range(0, size, chunk_rows):
+                for i, r0 in enumerate(range(0, size, chunk_rows)):
                     n = min(chunk_rows, size - r0)
-                    cols = eng.buffer_export(r0, n)
-                    dig = eng.buffer_digest(r0, n)
+                    cols = export(r0, n)
+                    dig = digest(r0, n)
                     for k, _, dt in self._ring_columns():
                         a = np.ascontiguousarray(cols[k])
                         if a.dtype != dt:
@@ -197,12 +255,16 @@ class HipReplayBuffer:
                         a.tofile(files[k])
                     chunks.append(["%016x" % v for v in dig])
                     total = [(t + v) & _M64 for t, v in zip(total, dig)]
+                    if on_chunk is not None:
+                        for f in files.values():
+                            f.flush()
+                        on_chunk(i)
             finally:
                 for f in files.values():
                     f.close()
             meta = dict(self._snapshot_identity(), format=RING_FORMAT, size=size, ptr=ptr, chunk_rows=chunk_rows,
                         digests={"chunks": chunks, "total": ["%016x" % v for v in total]},
-                        index_seed=int(self.index_seed), index_iteration=int(self.index_iteration))
+                        index_seed=index_seed, index_iteration=index_iteration)
             with open(os.path.join(tmp, "meta.json"), "w") as f:      # last: a directory without it is not a snapshot
                 json.dump(meta, f, indent=1)
                 f.flush()
@@ -218,6 +280,52 @@ class HipReplayBuffer:
             shutil.rmtree(tmp, ignore_errors=True)
             raise
         return path
+
+    # ---- background snapshots ---------------------------------------------------------------------------
+    def save_async(self, path, chunk_rows=65536, overwrite=False, max_bytes=None, keep_shadow=True, on_chunk=None, on_done=None):
+        """save() without the wait: the files that save(path, chunk_rows, overwrite) would write AT THE MOMENT OF THIS CALL, byte
+        for byte, written by a second thread while this one goes on adding and sampling. The calling thread refuses what save()
+        refuses, takes ONE consistent copy of the live rows inside HBM (engine.buffer_shadow_take: one launch in stream order that
+        also digests every chunk, no wait) and captures size, ptr, index_seed and index_iteration; the writer thread then exports
+        the copy chunk by chunk -- the host still holds one chunk -- and writes the six column files, meta.json and the rename as
+        save() does. Returns the RingSaveJob at once.
+          max_bytes    refuse (DsactError) a copy that needs more device bytes than this; None: no bound
+          keep_shadow  False frees the copy's device memory when the job is waited for (True keeps it for the next snapshot)
+          on_chunk(i)  called on the WRITER thread after chunk i is on disk (progress reporting)
+          on_done()    called on the WRITER thread once the snapshot is in place (the trainer completes its run state there);
+                       what it raises is the job's error
+        One job at a time: a second save_async, save(), load() and dropping the buffer first wait for a pending job
+        (`snapshot_waits` counts the save_async calls that had to). job.wait() belongs to the thread that owns the buffer."""
+        path = os.path.abspath(os.fspath(path))
+        chunk_rows = int(chunk_rows)
+        if chunk_rows < 1:
+            raise ValueError("chunk_rows must be >= 1 (got %d)" % chunk_rows)
+        if sys.byteorder != "little":
+            raise NotImplementedError("dsact-ring-1 files are little-endian; this host is not")
+        if os.path.lexists(path) and not overwrite:
+            raise FileExistsError("%s exists (pass overwrite=True to replace it)" % path)
+        if not callable(getattr(self.engine, "buffer_shadow_take", None)):
+            raise NotImplementedError("save_async: the engine %s has no buffer_shadow_take()" % type(self.engine).__name__)
+        if self._snapshot_job is not None:
+            self.snapshot_waits += 1          # back-pressure: one shadow, one writer
+            self._wait_snapshot()
+        info = self.engine.buffer_shadow_take(chunk_rows, int(max_bytes or 0))
+        job = RingSaveJob(self, path, info, int(self.index_seed), int(self.index_iteration), bool(keep_shadow), on_chunk, on_done)
+        self._snapshot_job = job
+        job._thread.start()
+        return job
+
+    def _wait_snapshot(self):
+        """joins a pending background snapshot, releases its shadow and raises what its writer raised"""
+        job = getattr(self, "_snapshot_job", None)
+        if job is not None:
+            job.wait()
+
+    def __del__(self):
+        try:
+            self._wait_snapshot()
+        except Exception:
+            pass
 
     def _read_snapshot_meta(self, path):
         """meta.json of a snapshot this ring can take, or ValueError -- nothing here touches the ring"""
@@ -263,6 +371,7 @@ class HipReplayBuffer:
         on. Then the rows go up chunk by chunk, and the device's digest of every chunk is compared with the file's: on a mismatch
         the ring is left EMPTY and the ValueError names the chunk and the column. Synchronous."""
         path = os.path.abspath(os.fspath(path))
+        self._wait_snapshot()
         meta = self._read_snapshot_meta(path)
         eng = self.engine
         size, ptr, chunk = int(meta["size"]), int(meta["ptr"]), int(meta["chunk_rows"])

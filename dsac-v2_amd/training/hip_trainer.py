@@ -15,6 +15,9 @@ Whole-run snapshots (additive): `hip_save_run_state=True` 
 apprfunc/run_state_{it}/ -- the replay ring (HipReplayBuffer.save), the networks, the optimiser sidecar and run.pkl (iteration,
 best / last TAR, the sampler's run_state(), the NumPy and torch generator states, a fingerprint of the run) -- and
 `ini_run_state_dir=<such a directory>` makes a new trainer continue that run bit for bit from the iteration after the save.
+`hip_run_state_async=True` writes the ring of those directories in the background: the save point takes one
+consistent device copy of the ring (HipReplayBuffer.save_async) and training continues while a writer thread moves it to disk,
+then writes run.pkl and prunes; the next save point, _finish() and the end of train() join it.
 
 tensorboard is optional (not installed in every image): scalars always go to <save_folder>/scalars.jsonl,
 and to a SummaryWriter too when one can be imported.
@@ -190,6 +193,17 @@ class HipOffSerialTrainer:
             self._check_run_state_support("hip_save_run_state" if self.save_run_state else "ini_run_state_dir")
             if self.run_state_keep < 1:
                 raise ValueError("hip_run_state_keep must be >= 1 (got %d)" % self.run_state_keep)
+        # additive: `hip_run_state_async=True` writes the ring of every run state in the background
+        self.run_state_async = bool(kwargs.get("hip_run_state_async", False))
+        self._snapshot_kwargs = {"max_bytes": kwargs.get("hip_snapshot_max_bytes"),
+                                 "keep_shadow": bool(kwargs.get("hip_snapshot_keep_shadow", True))}
+        self._run_state_job = None       # the RingSaveJob of the run state being written, if any
+        if self.run_state_async:
+            if not self.save_run_state:
+                raise ValueError("hip_run_state_async=True writes the run states of hip_save_run_state=True in the background; "
+                                 "that kwarg is not set")
+            if not callable(getattr(buffer, "save_async", None)):
+                raise NotImplementedError("hip_run_state_async: %s has no save_async()" % type(buffer).__name__)
         self.replay_batch_size = kwargs["replay_batch_size"]
         self.max_iteration = kwargs["max_iteration"]
         self.sample_interval = kwargs.get("sample_interval", 1)
@@ -251,32 +265,58 @@ class HipOffSerialTrainer:
     def _save_run_state(self, next_iteration):
         import numpy as np
 
+        self.wait_run_state()     # (background snapshots: the one before is whole, or its error is raised here)
         root = os.path.join(self.save_folder, "apprfunc")
         d = os.path.join(root, "run_state_{}".format(self.iteration))
         if os.path.lexists(d):
             shutil.rmtree(d)      # (left by an earlier run in this folder: a directory is written whole)
         os.makedirs(d)
-        self.buffer.save(os.path.join(d, "ring"))
+        if not self.run_state_async:
+            self.buffer.save(os.path.join(d, "ring"))
         torch.save(self.networks.state_dict(), os.path.join(d, "networks.pkl"))
         torch.save(self.alg.optimizer_state_dict(), os.path.join(d, "optstate.pkl"))
         run = {"format": self.RUN_STATE_FORMAT, "next_iteration": int(next_iteration), "best_tar": self.best_tar,
                "last_tar": self.last_tar, "sampler": self.sampler.run_state() if self.sampler is not None else None,
                "evaluator": self.evaluator.run_state() if callable(getattr(self.evaluator, "run_state", None)) else None,
                "numpy_rng": np.random.get_state(), "torch_rng": torch.get_rng_state(), "fingerprint": dict(self._fingerprint)}
+        # run.pkl's BYTES are made here: nothing the run changes from now on can reach them
+        blob = pickle.dumps(run, protocol=pickle.HIGHEST_PROTOCOL)
+        if not self.run_state_async:
+            self._complete_run_state(root, d, self.iteration, self.run_state_keep, blob)
+            return
+        # the ring goes last and in the background: one consistent device copy is taken now, a writer thread moves it to disk
+        # while training goes on, and the same thread then completes the directory. The next save point, _finish() and the end
+        # of train() join it (wait_run_state)
+        done = (lambda root=root, d=d, it=self.iteration, keep=self.run_state_keep: self._complete_run_state(root, d, it, keep, blob))
+        self._run_state_job = self.buffer.save_async(os.path.join(d, "ring"), on_done=done, **self._snapshot_kwargs)
+
+    @staticmethod
+    def _complete_run_state(root, d, iteration, keep, blob):
+        """run.pkl, last and renamed into place -- it is what makes the directory complete -- and only then the pruning. Runs on
+        the training thread, or on the writer thread of a background snapshot once the ring directory is whole: it touches
+        files only, and everything it needs was captured at the save point."""
         tmp = os.path.join(d, "run.pkl.tmp")
-        with open(tmp, "wb") as f:      # last, and renamed into place: run.pkl is what makes the directory complete
-            pickle.dump(run, f, protocol=pickle.HIGHEST_PROTOCOL)
+        with open(tmp, "wb") as f:
+            f.write(blob)
             f.flush()
             os.fsync(f.fileno())
         os.rename(tmp, os.path.join(d, "run.pkl"))
-        # a ring is gigabytes: once this directory is complete, only the newest `hip_run_state_keep` stay
+        # a ring is gigabytes: once this directory is complete, only the newest `hip_run_state_keep` stay. A run killed while a
+        # snapshot is being written still has the complete one before it: nothing is removed before this point
         found = []
         for fn in os.listdir(root):
             m = re.fullmatch(r"run_state_(\d+)", fn)
-            if m and int(m.group(1)) <= self.iteration and os.path.isdir(os.path.join(root, fn)):
+            if m and int(m.group(1)) <= iteration and os.path.isdir(os.path.join(root, fn)):
                 found.append((int(m.group(1)), fn))
-        for _, fn in sorted(found)[:-self.run_state_keep]:
+        for _, fn in sorted(found)[:-keep]:
             shutil.rmtree(os.path.join(root, fn), ignore_errors=True)
+
+    def wait_run_state(self):
+        """joins the background snapshot in flight, if any (hip_run_state_async), and raises what its writer raised; afterwards
+        every directory with a run.pkl is whole and no thread is left"""
+        job, self._run_state_job = self._run_state_job, None
+        if job is not None:
+            job.wait()
 
     def _restore_run_state(self, d):
         """everything of run_state_{it}/ but the generator states (returned with run.pkl's dict: they are set last)"""
@@ -372,12 +412,19 @@ class HipOffSerialTrainer:
 
     def train(self):
         self._grouping = True
+        completed = False
         try:
             while self.iteration < self.max_iteration:
                 self.step()
                 self.iteration += 1
+            completed = True
         finally:
             self._grouping = False
+            try:
+                self.wait_run_state()      # no thread outlives train(), however it ends
+            except Exception:
+                if completed:              # (else the loop's own error is the one to report)
+                    raise
         self._finish()
 
     def _finish(self):
@@ -386,6 +433,7 @@ class HipOffSerialTrainer:
         self.writer.flush()
         if self.save_folder:
             save_tb_to_csv(self.save_folder)   # what the reference's example scripts do right after train()
+        self.wait_run_state()
 
     def save_apprfunc(self, final=False):
         """final: called after train()'s last iteration (self.iteration == max_iteration, no update of that number was made)

@@ -251,6 +251,44 @@ int dsact_buffer_import(dsact_handle* h, int64_t row0, int64_t n, const void* ob
                         const float* rew, const float* done, const float* logp);
 int dsact_buffer_set_cursor(dsact_handle* h, int64_t size, int64_t ptr);
 int dsact_buffer_digest(dsact_handle* h, int64_t row0, int64_t n, uint64_t out[6]);
+/* Background snapshots (training/hip_replay_buffer.py save_async): a consistent copy of the live rows is
+ * taken INSIDE HBM in stream order -- one launch (k_ring_shadow) copies rows [0, size) of the six columns into a library-owned
+ * "shadow" with the same SoA order and stored form, and digests every chunk of chunk_rows rows over the same bytes -- and a
+ * second host thread moves the shadow to the host while the owning thread goes on issuing work on the handle.
+ *
+ * WHICH THREAD CALLS WHAT. The OWNING thread is the one that makes every other call on the handle; it alone calls take and
+ * release. ONE OTHER thread (the reader) may call export, digests and error between a take and its release, concurrently with
+ * anything the owning thread does on the handle. The two share one small struct behind a mutex and nothing else: the reader
+ * calls never touch the handle's stream, its hand-over words, its graph cache or the text of dsact_last_error.
+ *   take     (owning thread) stream-ordered, NEVER waits: validates, grows the shadow and digest allocations if needed (an
+ *            allocation it replaces is kept until the next release: freeing waits for the device), zeroes the digests,
+ *            launches k_ring_shadow on the handle's stream and records an event behind it. What it captured -- size, ptr,
+ *            chunk_rows, n_chunks = ceil(size / chunk_rows) and bytes (the padded columns of `size` rows plus 48 bytes per
+ *            chunk) -- is remembered and returned in *info_out. Rows written to the ring after the call do not reach the
+ *            shadow. Refused before anything is allocated or enqueued: DSACT_E_STATE without a ring, under stream capture,
+ *            or while a shadow is taken and not released; DSACT_E_INVALID for chunk_rows < 1 or bytes > max_bytes (0: no
+ *            bound). An empty ring gives an empty shadow with n_chunks = 0. A first take allocates for the ring's CAPACITY
+ *            when max_bytes allows it, so that a ring that is still filling does not grow its shadow again.
+ *   export   (reader) rows [row0, row0 + n) of the shadow to HOST arrays, as the synchronous export does from the ring: any
+ *            destination may be NULL, 0 <= row0, 0 <= n, row0 + n <= the size TAKEN. Waits for the take's event only, copies on
+ *            a private copy stream and synchronises that stream only.
+ *   digests  (reader) out[n_chunks][6]: word [k][c] equals what the synchronous digest of rows [k * chunk_rows, + rows of
+ *            chunk k) gave for column c at the take. n_chunks must be the take's.
+ *   error    (reader) the text of the reader calls' last failure (they return the same codes as every other call).
+ *   release  (owning thread, after the reader is done; DSACT_E_STATE while a reader call runs) marks the shadow free for the
+ *            next take; free_memory != 0 also frees its device memory (that waits for the device). The destroy call
+ *            synchronises the copy stream and frees whatever is left.
+ * dsact_debug_get: "shadow_state" (1 between take and release), "shadow_bytes" (device bytes allocated), "shadow_takes". */
+typedef struct dsact_shadow_info {
+  int64_t size, ptr, chunk_rows, n_chunks;
+  uint64_t bytes;
+} dsact_shadow_info;
+int dsact_buffer_shadow_take(dsact_handle* h, int64_t chunk_rows, uint64_t max_bytes, dsact_shadow_info* info_out);
+int dsact_buffer_shadow_export(dsact_handle* h, int64_t row0, int64_t n, void* obs, void* obs2, float* act, float* rew, float* done,
+                               float* logp);
+int dsact_buffer_shadow_digests(dsact_handle* h, uint64_t* out, int64_t n_chunks);
+const char* dsact_buffer_shadow_error(const dsact_handle* h);
+int dsact_buffer_shadow_release(dsact_handle* h, int32_t free_memory);
 /* gather rows idx[0..batch) into the handle's minibatch staging area (== sample_batch + .cuda()). idx_host == NULL (an
  * index seed is set, DSACT_E_STATE otherwise): the rows of index-table row 0 as dsact_draw_indices left it, copied device to
  * device behind the draw -- replay_buffer.py:86-90 with no host index at all. */
