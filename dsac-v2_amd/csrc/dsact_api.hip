@@ -369,6 +369,7 @@ struct dsact_handle : BatchBufs {
   unsigned long long* act_counter_dev = nullptr;   // allocated by the first dsact_act_counter_set
   bool act_counter_valid = false;        // ... which has been called
   unsigned long long step_rows_calls = 0;   // dsact_step_rows_device launches
+  unsigned long long env_wrap_calls = 0;    // dsact_env_wrap_step / dsact_env_wrap_reset launches
   // device-resident evaluation (dsact_act_mode_device / dsact_eval_*): the episode bookkeeping's state
   int* ev_ep = nullptr; double* ev_acc = nullptr; int* ev_len = nullptr;   // [ev_cap_n]
   double* ev_returns = nullptr; int* ev_lengths = nullptr;                 // [ev_cap_e]
@@ -5696,6 +5697,7 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "track_commit_calls")) *value = (double)h->track_commit_calls;   // dsact_track_commit launches
   else if (!strcmp(name, "track_reads")) *value = (double)h->track_reads;                 // dsact_track_read waits
   else if (!strcmp(name, "step_rows_calls")) *value = (double)h->step_rows_calls;         // dsact_step_rows_device launches
+  else if (!strcmp(name, "env_wrap_calls")) *value = (double)h->env_wrap_calls;           // dsact_env_wrap_step / _reset launches
   else if (!strcmp(name, "act_fast")) *value = (act_fast_ok(h) || h->cnn_act) ? 1.0 : 0.0;   // dsact_act_sample serves this handle (the one-launch forward, or the enabled CNN acting path)
   else if (!strcmp(name, "cnn_act_capture")) *value = h->cnn_act_capture ? 1.0 : 0.0;   // dsact_cnn_acting_capture is on
   else if (!strcmp(name, "step_frames_calls")) *value = (double)h->step_frames_calls;    // dsact_step_frames_device launches
@@ -6312,6 +6314,77 @@ int dsact_step_frames_device(dsact_handle* h, int32_t n, int64_t row_bytes, cons
   TRY(launch(h, "step_frames", k_step_frames, dim3((unsigned)((long long)n * a.chunks)), dim3(kThreads), 0, a));
   h->step_frames_calls++;
   return DSACT_OK;
+}
+
+// the reference's environment wrappers behind a tensor environment's step / reset in one launch each (k_env_wrap_step /
+// k_env_wrap_reset, dsact_kernels.h). dsact_step_rows_device's rules: a launch, no allocation, no wait,
+// legal under stream capture (the hand-off check is left to the next entry point outside it). No state is kept in the handle.
+static int env_wrap_launch(dsact_handle* h, const char* who, bool step, EnvWrapArgs& a, const void* const* ptrs, int n_ptrs) {
+  HIPCHK(h, hipSetDevice(h->device));
+  for (int k = 0; k < n_ptrs; ++k)
+    if (ptrs[k] && !on_handle_gpu(h, ptrs[k])) return fail(h, DSACT_E_INVALID, "%s takes device pointers on the handle's GPU", who);
+  bool capturing = false;
+  TRY(stream_capturing(h, &capturing));
+  if (capturing && h->profiling) return fail(h, DSACT_E_STATE, "%s under stream capture while profiling", who);
+  if (!capturing) TRY(check_handoff_counted(h));
+  const uintptr_t all = (uintptr_t)a.obs | (uintptr_t)a.obs_out | (uintptr_t)a.shift | (uintptr_t)a.scale;
+  a.wide = (a.W > 0 && a.W % 4 == 0 && all % 16 == 0) ? 1 : 0;
+  // one wave per row up to 1024 units (16 passes); longer rows are split like dsact_step_frames_device's: one pass of kThreads
+  // lanes over the row's units per workgroup, 16 workgroups at most
+  const long long units = a.wide ? a.W / 4 : a.W;
+  const long long per = (units + kThreads - 1) / kThreads;
+  a.chunks = units <= 1024 ? 0 : (per > 16 ? 16 : (int)per);
+  const long long grid = a.chunks ? (long long)a.n * a.chunks : ((long long)a.n + 3) / 4;
+  if (grid > 0x7fffffffLL) return fail(h, DSACT_E_INVALID, "%s: n = %d rows of %d floats need %lld workgroups", who, a.n, a.W, grid);
+  if (step) TRY(launch(h, "env_wrap_step", k_env_wrap_step, dim3((unsigned)grid), dim3(kThreads), 0, a));
+  else TRY(launch(h, "env_wrap_reset", k_env_wrap_reset, dim3((unsigned)grid), dim3(kThreads), 0, a));
+  h->env_wrap_calls++;
+  return DSACT_OK;
+}
+
+int dsact_env_wrap_step(dsact_handle* h, int32_t n, int32_t row_floats, const float* obs2_dev, const float* rew_dev,
+                        const uint8_t* terminated_dev, const uint8_t* truncated_dev, const float* obs_shift_dev,
+                        const float* obs_scale_dev, float reward_shift, float reward_scale, int32_t reward_on,
+                        int32_t max_episode_steps, int32_t* elapsed_dev, float* obs2_out, float* rew_out, uint8_t* truncated_out) {
+  if (!h) return DSACT_E_INVALID;
+  if (n < 1 || row_floats < 0 || max_episode_steps < 0)
+    return fail(h, DSACT_E_INVALID, "dsact_env_wrap_step: n = %d must be >= 1, row_floats = %d and max_episode_steps = %d >= 0", (int)n,
+                (int)row_floats, (int)max_episode_steps);
+  const bool obs_on = row_floats > 0, rew_on = reward_on != 0, lim_on = max_episode_steps > 0;
+  if (!obs_on && !rew_on && !lim_on) return fail(h, DSACT_E_INVALID, "dsact_env_wrap_step: every part is off");
+  if ((obs2_out != nullptr) != obs_on || (rew_out != nullptr) != rew_on || (truncated_out != nullptr) != lim_on)
+    return fail(h, DSACT_E_INVALID, "dsact_env_wrap_step: obs2_out / rew_out / truncated_out must be NULL exactly when its part is off");
+  if ((obs_on && (!obs2_dev || !obs_shift_dev || !obs_scale_dev)) || (rew_on && !rew_dev) ||
+      (lim_on && (!terminated_dev || !truncated_dev || !elapsed_dev)))
+    return fail(h, DSACT_E_INVALID, "dsact_env_wrap_step: a part that is on has a NULL input");
+  EnvWrapArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n; a.W = row_floats; a.M = max_episode_steps; a.rew_on = rew_on ? 1 : 0;
+  a.rshift = reward_shift; a.rscale = reward_scale;
+  if (obs_on) { a.obs = obs2_dev; a.shift = obs_shift_dev; a.scale = obs_scale_dev; a.obs_out = obs2_out; }
+  if (rew_on) { a.rew = rew_dev; a.rew_out = rew_out; }
+  if (lim_on) { a.term = terminated_dev; a.trunc = truncated_dev; a.elapsed = elapsed_dev; a.trunc_out = truncated_out; }
+  const void* ptrs[11] = {a.obs, a.shift, a.scale, a.obs_out, a.rew, a.rew_out, a.term, a.trunc, a.elapsed, a.trunc_out, nullptr};
+  return env_wrap_launch(h, "dsact_env_wrap_step", true, a, ptrs, 10);
+}
+
+int dsact_env_wrap_reset(dsact_handle* h, int32_t n, int32_t row_floats, const float* obs_dev, const uint8_t* mask_dev,
+                         const float* obs_shift_dev, const float* obs_scale_dev, int32_t* elapsed_dev, float* obs_out) {
+  if (!h) return DSACT_E_INVALID;
+  if (n < 1 || row_floats < 0)
+    return fail(h, DSACT_E_INVALID, "dsact_env_wrap_reset: n = %d must be >= 1 and row_floats = %d >= 0", (int)n, (int)row_floats);
+  const bool obs_on = row_floats > 0;
+  if (!obs_on && !elapsed_dev) return fail(h, DSACT_E_INVALID, "dsact_env_wrap_reset: every part is off");
+  if ((obs_out != nullptr) != obs_on) return fail(h, DSACT_E_INVALID, "dsact_env_wrap_reset: obs_out must be NULL exactly when row_floats is 0");
+  if (obs_on && (!obs_dev || !obs_shift_dev || !obs_scale_dev))
+    return fail(h, DSACT_E_INVALID, "dsact_env_wrap_reset: the observation part is on and has a NULL input");
+  EnvWrapArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n; a.W = row_floats;
+  if (obs_on) { a.obs = obs_dev; a.shift = obs_shift_dev; a.scale = obs_scale_dev; a.obs_out = obs_out; }
+  a.elapsed = elapsed_dev; a.mask = elapsed_dev ? mask_dev : nullptr;
+  const void* ptrs[6] = {a.obs, a.shift, a.scale, a.obs_out, a.elapsed, a.mask};
+  return env_wrap_launch(h, "dsact_env_wrap_reset", false, a, ptrs, 6);
 }
 
 // ---- device-resident evaluation --------------------------------------------------------------------

@@ -1148,6 +1148,83 @@ __global__ void __launch_bounds__(kThreads) k_step_frames(StepFramesArgs a) {
 }
 #endif
 
+// k_env_wrap_step / k_env_wrap_reset: the reference's environment wrappers (utils/wrapping_env.py: TimeLimit, ShapingRewardData,
+// ScaleObservationData) behind a batched tensor environment's step and reset in ONE launch each (dsact_env_wrap_step /
+// dsact_env_wrap_reset, training/hip_tensor_env_wrappers.py). Every part is optional:
+//   observation (W > 0)  obs_out[i][k] = (obs[i][k] + shift[k]) * scale[k]: one add and one multiply, each rounded to fp32
+//                        (__fadd_rn / __fmul_rn: never contracted), shift / scale one row of W floats
+//   reward (rew_on)      rew_out[i] = (rew[i] + rshift) * rscale, the same two operations
+//   time limit (M > 0)   e = min(elapsed[i] + 1, M) (saturating: written as e >= M ? M : e + 1, no overflow); elapsed[i] = e;
+//                        trunc_out[i] = trunc[i] | (e >= M & ~term[i]) as 0 / 1 (flags are bytes, non-zero = set)
+//   reset                every row goes through the observation part; elapsed[i] = 0 where mask[i] is set (mask == NULL: all)
+// Launch shapes: chunks == 0 is k_step_rows' -- one wave per row, four rows per workgroup, lane 0 does the row's scalars;
+// chunks > 0 is k_step_frames' for long rows (fp32 frames) -- workgroup (i, c) of a grid n * chunks takes units c * kThreads +
+// tid, then every chunks * kThreads-th one, and the scalars go in the row's first workgroup. `wide` (W % 4 == 0 and source,
+// output and both parameter rows 16-byte aligned): 16 bytes per lane and access, else 4. An element is loaded and stored by
+// the same lane, so out == in is correct. Vector loads and stores only; every access is inside row i < n of its array or
+// inside the W floats of a parameter row.
+struct EnvWrapArgs {
+  const float* obs; const float* rew; const unsigned char* term; const unsigned char* trunc; const unsigned char* mask;
+  const float* shift; const float* scale;
+  int* elapsed; float* obs_out; float* rew_out; unsigned char* trunc_out;
+  float rshift, rscale;
+  int n, W, wide, chunks, M, rew_on;
+};
+#ifndef DSACT_FAMILY_UNIT   // plain kernels: compiled in dsact_api.hip only (dsact_tu.h)
+__device__ __forceinline__ void env_wrap_row(const EnvWrapArgs& a, long long i, long long first, long long stride) {
+  const float* s = a.obs + (size_t)i * (size_t)a.W;
+  float* d = a.obs_out + (size_t)i * (size_t)a.W;
+  if (a.wide) {
+    const float4* s4 = reinterpret_cast<const float4*>(s);
+    const float4* sh4 = reinterpret_cast<const float4*>(a.shift);
+    const float4* sc4 = reinterpret_cast<const float4*>(a.scale);
+    float4* d4 = reinterpret_cast<float4*>(d);
+    for (long long k = first; k < a.W / 4; k += stride) {
+      const float4 v = s4[k], sh = sh4[k], sc = sc4[k];
+      float4 o;
+      o.x = __fmul_rn(__fadd_rn(v.x, sh.x), sc.x); o.y = __fmul_rn(__fadd_rn(v.y, sh.y), sc.y);
+      o.z = __fmul_rn(__fadd_rn(v.z, sh.z), sc.z); o.w = __fmul_rn(__fadd_rn(v.w, sh.w), sc.w);
+      d4[k] = o;
+    }
+  } else {
+    for (long long k = first; k < a.W; k += stride) d[k] = __fmul_rn(__fadd_rn(s[k], a.shift[k]), a.scale[k]);
+  }
+}
+// (row, first unit, unit stride, whether this lane does the row's scalars) of a lane under either launch shape; false: no row
+__device__ __forceinline__ bool env_wrap_lane(const EnvWrapArgs& a, long long* i, long long* first, long long* stride, bool* scalars) {
+  if (a.chunks == 0) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    *i = (long long)blockIdx.x * 4 + wave; *first = lane; *stride = 64; *scalars = lane == 0;
+  } else {
+    const int c = (int)(blockIdx.x % (unsigned)a.chunks);
+    *i = (long long)(blockIdx.x / (unsigned)a.chunks);
+    *first = (long long)c * kThreads + (int)threadIdx.x; *stride = (long long)a.chunks * kThreads;
+    *scalars = c == 0 && threadIdx.x == 0;
+  }
+  return *i < a.n;
+}
+__global__ void __launch_bounds__(kThreads) k_env_wrap_step(EnvWrapArgs a) {
+  long long i, first, stride; bool scalars;
+  if (!env_wrap_lane(a, &i, &first, &stride, &scalars)) return;
+  if (a.W > 0) env_wrap_row(a, i, first, stride);
+  if (!scalars) return;
+  if (a.rew_on) a.rew_out[i] = __fmul_rn(__fadd_rn(a.rew[i], a.rshift), a.rscale);
+  if (a.M > 0) {
+    const unsigned char t = a.term[i], u = a.trunc[i];   // (both loaded: no load behind a branch)
+    int e = a.elapsed[i];
+    e = e >= a.M ? a.M : e + 1;
+    a.elapsed[i] = e;
+    a.trunc_out[i] = (u != 0 || (e >= a.M && t == 0)) ? 1 : 0;
+  }
+}
+__global__ void __launch_bounds__(kThreads) k_env_wrap_reset(EnvWrapArgs a) {
+  long long i, first, stride; bool scalars;
+  if (!env_wrap_lane(a, &i, &first, &stride, &scalars)) return;
+  if (a.W > 0) env_wrap_row(a, i, first, stride);
+  if (scalars && a.elapsed && (!a.mask || a.mask[i] != 0)) a.elapsed[i] = 0;
+}
+#endif
+
 // ---------------------------------------------------------------------------------------------
 // k_tiles: C[m][n] (+epilogue) = sum_k P(m,k) * Q(n,k) on 32x32 tiles, BK = 64
 //   operand storage: KC  element (row,k) at base[row*ld + k]   (k contiguous)

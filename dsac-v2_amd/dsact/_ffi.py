@@ -165,6 +165,8 @@ SYMBOLS = [
     ("dsact_eval_trace_end", C.c_int, [_P]),
     ("dsact_eval_record", C.c_int, [_P, _P, _P]),
     ("dsact_eval_trace_read", C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P]),
+    ("dsact_env_wrap_step", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    ("dsact_env_wrap_reset", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
 ]
 
 _lib = None

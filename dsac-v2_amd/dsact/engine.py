@@ -899,6 +899,55 @@ class DsactEngine:
         if rc != 0:
             self._chk(rc)
 
+    def env_wrap_step(self, n, obs2=None, rew=None, terminated=None, truncated=None, obs_shift=None, obs_scale=None,
+                      reward_shift=0.0, reward_scale=1.0, reward_on=False, max_episode_steps=0, elapsed=None, obs2_out=None,
+                      rew_out=None, truncated_out=None):
+        """dsact_env_wrap_step: the reference's environment wrappers behind a tensor environment's step in one launch (DESIGN.md
+        section 27). A part is on when its output is given: obs2_out[n, ...] = (obs2 + obs_shift) * obs_scale (float32 rows of
+        any shape, obs_shift / obs_scale one flat row), rew_out[n] = (rew + reward_shift) * reward_scale (reward_on),
+        truncated_out[n] = truncated | (elapsed >= M & ~terminated) after elapsed = min(elapsed + 1, M) (int32 [n], M =
+        max_episode_steps > 0). Contiguous tensors on this engine's GPU; an output may be its input. Asynchronous; legal under
+        stream capture."""
+        torch = self.torch
+        f32, flag, i32 = (torch.float32,), (torch.bool, torch.uint8), (torch.int32,)
+        n, W, M = int(n), 0, int(max_episode_steps)
+        po = ps = pc = pr = pt = pu = pe = poo = pro = puo = None
+        if obs2_out is not None:
+            shape = tuple(obs2.shape) if hasattr(obs2, "shape") else ()
+            W = int(obs2[0].numel()) if len(shape) >= 2 and shape[0] == n else 0
+            po, poo = self._dev(obs2, shape, f32, "obs2"), self._dev(obs2_out, shape, f32, "obs2_out")
+            ps, pc = self._dev(obs_shift, (W,), f32, "obs_shift"), self._dev(obs_scale, (W,), f32, "obs_scale")
+        if reward_on:
+            pr, pro = self._dev(rew, (n,), f32, "rew"), self._dev(rew_out, (n,), f32, "rew_out")
+        if M > 0:
+            pt, pu = self._dev(terminated, (n,), flag, "terminated"), self._dev(truncated, (n,), flag, "truncated")
+            pe, puo = self._dev(elapsed, (n,), i32, "elapsed"), self._dev(truncated_out, (n,), flag, "truncated_out")
+        rc = self._lib.dsact_env_wrap_step(self._h, n, W, po, pr, pt, pu, ps, pc, float(reward_shift), float(reward_scale),
+                                           1 if reward_on else 0, M, pe, poo, pro, puo)
+        if rc != 0:
+            self._chk(rc)
+
+    def env_wrap_reset(self, n, obs=None, mask=None, obs_shift=None, obs_scale=None, elapsed=None, obs_out=None):
+        """dsact_env_wrap_reset: the wrappers behind a tensor environment's reset in one launch -- obs_out[n, ...] = (obs +
+        obs_shift) * obs_scale for EVERY row (on when obs_out is given) and elapsed[i] = 0 where the bool / uint8 mask[n] is set
+        (mask None: every row; on when elapsed is given). Contiguous tensors on this engine's GPU. Asynchronous; legal under
+        stream capture."""
+        torch = self.torch
+        f32, flag, i32 = (torch.float32,), (torch.bool, torch.uint8), (torch.int32,)
+        n, W = int(n), 0
+        po = ps = pc = poo = pe = pm = None
+        if obs_out is not None:
+            shape = tuple(obs.shape) if hasattr(obs, "shape") else ()
+            W = int(obs[0].numel()) if len(shape) >= 2 and shape[0] == n else 0
+            po, poo = self._dev(obs, shape, f32, "obs"), self._dev(obs_out, shape, f32, "obs_out")
+            ps, pc = self._dev(obs_shift, (W,), f32, "obs_shift"), self._dev(obs_scale, (W,), f32, "obs_scale")
+        if elapsed is not None:
+            pe = self._dev(elapsed, (n,), i32, "elapsed")
+            pm = None if mask is None else self._dev(mask, (n,), flag, "mask")
+        rc = self._lib.dsact_env_wrap_reset(self._h, n, W, po, pm, ps, pc, pe, poo)
+        if rc != 0:
+            self._chk(rc)
+
     def _frames(self, t, n, name):
         """(address, is_uint8) of the observation rows of a device-resident call: [n, O] float32, and on a CNN engine with cnn_act
          also [n, C, H, W] rows and uint8 tensors of either shape -- byte frames, codes into the coded

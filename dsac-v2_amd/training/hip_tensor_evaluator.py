@@ -86,6 +86,13 @@ steps kept per episode: a longer episode's file holds its first steps, `trace_dr
 one RuntimeWarning per evaluation names them; TAR, returns and lengths are not affected. The trace takes
 episodes * steps * (observation row + 4 A + 4) bytes of device memory; above `hip_eval_save_max_bytes` (default 1 << 30) the
 first run_evaluation refuses, before any call is made. Under hip_graph_eval the record is a node of the captured window.
+
+The reference's environment wrappers (`hip_env_wrap=True`; default off: exactly the calls above): the
+constructor puts the environment it resolved through training/hip_tensor_env_wrappers.wrap_tensor_env with `max_episode_steps`,
+`reward_shift`, `obs_shift` and `obs_scale` from the flat argument dict (the reference's Evaluator clears reward_scale only, so
+the shift stays and returns sum the shifted reward). Refused (ValueError): a non-bool value, and True with none of the four set.
+The per-engine set-up hands the engine to an environment that has `bind_engine`; a wrapped environment's `max_episode_steps` is
+eval_save's default step bound.
 """
 import os
 import warnings
@@ -96,6 +103,7 @@ import torch
 from training.hip_acting_common import (EvalEpisodeCounter, engine_stream, eval_save_kwargs, hand_over, image_graph_engine, networks_of,
                                         on_stream, require_graph_cnn_pair, require_graph_device, require_tensor_engine, tensor_limits,
                                         write_eval_episode)
+from training.hip_tensor_env_wrappers import env_wrap_kwargs, wrap_tensor_env
 
 __all__ = ["HipTensorEnvEvaluator"]
 
@@ -126,6 +134,9 @@ class HipTensorEnvEvaluator:
         if env is None:
             from plugin import create_env
             env = create_env(**kwargs)
+        wrap = env_wrap_kwargs(kwargs, "hip_tensor_env_evaluator")   # hip_env_wrap; None: off, the default
+        if wrap is not None:
+            env = wrap_tensor_env(env, **wrap)
         self.env = env
         self.n_envs = int(env.num_envs)
         if self.n_envs < 1:
@@ -184,6 +195,8 @@ class HipTensorEnvEvaluator:
         """once per engine: the [N, .] buffers and whether the policy's limits are the environment's"""
         N, O, A = self.n_envs, eng.obs_dim, eng.act_dim
         dev = torch.device(eng.device)
+        if callable(getattr(self.env, "bind_engine", None)):
+            self.env.bind_engine(eng)     # a wrapped environment's step / reset as one launch each (DESIGN.md section 27)
         if self.graph_eval:
             require_graph_device("hip_graph_eval", dev)
             self._graph, self._graph_gen, self._graph_windows = None, None, 0   # a new engine: eager, capture, replay again

@@ -82,6 +82,12 @@ hip_cnn_act does nothing there, drop it) -- for a policy attached later, at the 
 call; at the first sample(): an engine off the GPU. A capture that raises is ended and re-raised as a RuntimeError naming the
 environment.
 
+The reference's environment wrappers (`hip_env_wrap=True`; default off: exactly the calls above): the
+constructor puts the environment it resolved through training/hip_tensor_env_wrappers.wrap_tensor_env with `max_episode_steps`,
+`reward_shift`, `obs_shift` and `obs_scale` from the flat argument dict -- NOT `reward_scale`, which this sampler multiplies by
+once at the ring write. Refused (ValueError): a non-bool value, and True with none of the four set. _setup hands the engine to an
+environment that has `bind_engine` (a wrapped one: its step and reset are then one launch each).
+
 sample() returns (DeviceSampleBatch, {sampler time}). The time is the HOST time of issuing the work. The batch's tensors are the
 sampler's own preallocated [S, .] buffers: they are valid until the next sample() call (add_batch consumes them in stream
 order before that).
@@ -97,6 +103,7 @@ from training.hip_acting_common import (check_noise_dim, engine_stream, explore_
                                         sample_batch_size, tensor_limits)
 from training.hip_replay_buffer import act_seed_from
 from training.hip_sampler import SAMPLER_TIME_KEY
+from training.hip_tensor_env_wrappers import env_wrap_kwargs, wrap_tensor_env
 
 __all__ = ["HipTensorEnvSampler", "DeviceSampleBatch", "act_noise_words", "act_noise_reference", "explore_noise_words",
            "explore_noise_reference", "aggregate_episode_rows", "EPISODE_TB_KEYS"]
@@ -276,6 +283,9 @@ class HipTensorEnvSampler:
         if env is None:
             from plugin import create_env
             env = create_env(**kwargs)
+        wrap = env_wrap_kwargs(kwargs, "hip_tensor_env_sampler")   # hip_env_wrap; None: off, the default
+        if wrap is not None:
+            env = wrap_tensor_env(env, **wrap)
         self.env = env
         self.n_envs = int(env.num_envs)
         self.sample_batch_size = sample_batch_size(kwargs)
@@ -381,6 +391,10 @@ class HipTensorEnvSampler:
         if first is not None:
             self._obs.copy_(first.reshape((N,) + row))
             self._started = True
+        if callable(getattr(self.env, "bind_engine", None)):
+            # a wrapped environment's step / reset as one launch each on the engine's stream -- bound behind
+            # the first reset(), which ran on torch's current stream
+            self.env.bind_engine(eng)
         hand_over(eng)   # (the only wait this sampler ever makes, once)
         self._ready = id(eng)
 

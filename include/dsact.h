@@ -867,6 +867,39 @@ int dsact_track_read(dsact_handle* h, int32_t n_envs, int64_t* episodes, int64_t
                      double* ret_max, int64_t* len_sum, double* last_ret, int32_t* last_len, double* cur_ret, int32_t* cur_len,
                      int32_t clear);
 
+/* ---- The reference's environment wrappers on tensor environments (training/hip_tensor_env_wrappers.py) ---
+ * utils/wrapping_env.py puts every environment behind gym's TimeLimit, ShapingRewardData ((r + shift) * scale) and
+ * ScaleObservationData ((obs + shift) * scale). For a batched tensor environment the three are ONE launch behind step and ONE
+ * behind reset. The handle keeps NO state: elapsed, the two parameter rows and the outputs are the caller's device arrays.
+ *   dsact_env_wrap_step            n >= 1 rows. Each of the three parts is on or off:
+ *                                    observation  row_floats > 0: obs2_out[i][k] = (obs2[i][k] + obs_shift[k]) * obs_scale[k], two
+ *                                                 separately rounded fp32 operations; obs_shift_dev / obs_scale_dev hold one row of
+ *                                                 row_floats floats. row_floats == 0: off.
+ *                                    reward       reward_on != 0: rew_out[i] = (rew[i] + reward_shift) * reward_scale, likewise.
+ *                                    time limit   max_episode_steps = M > 0: elapsed[i] = min(elapsed[i] + 1, M) (int32, saturating)
+ *                                                 and truncated_out[i] = truncated[i] | (elapsed[i] >= M & ~terminated[i]), written
+ *                                                 as 0 or 1 (flags are one byte each, non-zero = set) -- gym 0.23's
+ *                                                 info["TimeLimit.truncated"] = not done, OR the environment's own truncation.
+ *                                                 M == 0: off.
+ *                                  obs2_out / rew_out / truncated_out must be NULL exactly when its part is off, an input of a part
+ *                                  that is on must not be NULL, and at least one part must be on (DSACT_E_INVALID otherwise);
+ *                                  inputs of a part that is off are ignored. An output may be its input (in place).
+ *   dsact_env_wrap_reset           the observation part for EVERY row of obs_dev[n][row_floats] (row_floats == 0 and obs_out ==
+ *                                  NULL: off) and, where elapsed_dev != NULL, elapsed[i] = 0 for the rows whose mask byte is
+ *                                  non-zero (mask_dev == NULL: every row). At least one of the two must be on.
+ * Both follow dsact_step_rows_device's rules: ASYNCHRONOUS on the handle's stream; legal under stream capture (no allocation, no
+ * wait, the hand-off check left to the next entry point outside it; DSACT_E_STATE while profiling); device pointers of the
+ * handle's GPU only (DSACT_E_INVALID otherwise). One wave per row and four rows per workgroup, rows above 1024 access units
+ * split over up to 16 workgroups like dsact_step_frames_device's; 16 bytes per lane where row_floats % 4 == 0 and source, output
+ * and both parameter rows are 16-byte aligned, 4 bytes otherwise. Any handle.
+ * dsact_debug_get: "env_wrap_calls" (launches of either entry point). */
+int dsact_env_wrap_step(dsact_handle* h, int32_t n, int32_t row_floats, const float* obs2_dev, const float* rew_dev,
+                        const uint8_t* terminated_dev, const uint8_t* truncated_dev, const float* obs_shift_dev,
+                        const float* obs_scale_dev, float reward_shift, float reward_scale, int32_t reward_on,
+                        int32_t max_episode_steps, int32_t* elapsed_dev, float* obs2_out, float* rew_out, uint8_t* truncated_out);
+int dsact_env_wrap_reset(dsact_handle* h, int32_t n, int32_t row_floats, const float* obs_dev, const uint8_t* mask_dev,
+                         const float* obs_shift_dev, const float* obs_scale_dev, int32_t* elapsed_dev, float* obs_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,14 @@ steps) for the baseline. Policy and update are the bench's Humanoid configuratio
       with the package, helpers and fixtures of another checkout (DIR/dsac-v2_amd with its built library, DIR/tests): the parent
       commit's numbers, recorded as "parent_eager" beside the others (DIR = this checkout: "eager_alone", the same process
       layout on this tree -- a leg that shares its process with a second engine issues its launches about a tenth slower). Writes DIR/graph_sample_bench.json; nothing else is run.
+  python scripts/tensor_sampler_bench.py --wrap none torch fused [--graph] [--out profiles] [--pairs 3] [--window 0.6]
+      opt-in: sample() alone at S = N, N in 64, 1024, with the reference's three environment wrappers
+      (training/hip_tensor_env_wrappers.py: max_episode_steps=1000, reward shift and scale, a per-element observation shift and
+      scale) on the torch route / on the fused route (one launch behind step and reset each), against `none`: the bare
+      environment, whose own limit is the same 1000 steps. The legs named share ONE fresh child process per N with alternating
+      windows; --graph: every leg with hip_graph_sample=True on the in-place fixture. Recorded per leg: environment steps / s and
+      the library's launches per lockstep step from the debug counters (act_dev_calls, step_rows_calls, env_wrap_calls; torch's
+      own launches are not counted there). Writes DIR/env_wrap_bench.json ("eager" / "graph"); nothing else is run.
 Writes DIR/tensor_sampler_bench.json and prints it. The library must have been built (__graft_entry__.build())."""
 import argparse
 import json
@@ -214,6 +222,93 @@ def run_graph(N, metric, pairs, window, parent):
     return out
 
 
+WRAP_NS = [64, 1024]
+WRAP_COUNTERS = ("act_dev_calls", "step_rows_calls", "env_wrap_calls")
+
+
+def _wrap_leg(leg, N, graph):
+    """leg: "none" (the bare environment, its own limit 1000) | "torch" / "fused" (no limit of its own, the three wrappers on)"""
+    import plugin
+    from training.hip_tensor_env_wrappers import wrap_tensor_env
+
+    kw = hip_kwargs(O, A, HID, B, seed=SEED, sample_batch_size=N, buffer_max_size=max(100_000, 4 * N), buffer_warm_size=max(B, N),
+                    sample_interval=1, max_iteration=0, log_save_interval=10 ** 9, apprfunc_save_interval=10 ** 9,
+                    eval_interval=10 ** 9, save_folder=None, ini_network_dir=None, strict_rng=False, hip_device_indices=True,
+                    hip_pad_widths=True)
+    torch.manual_seed(SEED)
+    np.random.seed(SEED)
+    alg = plugin.create_alg(**kw)
+    cls = SynthTensorHumanoid
+    if graph:
+        from synth_tensor_humanoid_inplace import SynthTensorHumanoidInplace as cls
+    env = cls(N, device="cuda", seed=SEED, episode_limit=1000 if leg == "none" else 1 << 30)
+    if leg != "none":
+        env = wrap_tensor_env(env, max_episode_steps=1000, reward_shift=0.1, reward_scale=0.5,
+                              obs_shift=np.linspace(-0.1, 0.1, O).astype(np.float32), obs_scale=np.linspace(0.5, 1.5, O).astype(np.float32))
+        env.use_fused = leg == "fused"
+    smp = plugin.create_sampler(**dict(kw, sampler_name="hip_tensor_env_sampler", env=env, **({"hip_graph_sample": True} if graph else {})))
+    smp.networks = alg.networks
+    return alg, smp, None
+
+
+def run_wrap(N, names, graph, pairs, window):
+    legs = {leg: _wrap_leg(leg, N, graph) for leg in names}
+    counts, launches = {}, {}
+    for leg, h in legs.items():                      # warm-up (eager call, capture, replays); its rate sizes the windows
+        before = {k: h[0].engine.debug_get(k) for k in WRAP_COUNTERS}
+        _window(*h, 1)                               # the first sample(): always issued eagerly, one lockstep step (S = N)
+        launches[leg] = {k: h[0].engine.debug_get(k) - before[k] for k in WRAP_COUNTERS}
+        dt = _window(*h, 4)
+        dt = _window(*h, 4)
+        counts[leg] = max(4, int(round(window / (dt / 4))))
+    rows = {leg: [] for leg in legs}
+    for _ in range(pairs):
+        for leg, h in legs.items():
+            dt = _window(*h, counts[leg])
+            rows[leg].append(counts[leg] * N / dt)
+    out = {"N": N, "graph": bool(graph), "unit": "env_steps_per_s", "window_counts": counts, "rows": rows,
+           "median": {x: float(np.median(v)) for x, v in rows.items()},
+           "spread": {x: (max(v) - min(v)) / float(np.median(v)) for x, v in rows.items()},
+           "library_launches_per_lockstep_step": launches,
+           "fused": {x: bool(getattr(h[1].env, "fused", False)) for x, h in legs.items()},
+           "act_dev_syncs": {x: h[0].engine.debug_get("act_dev_syncs") for x, h in legs.items()},
+           "handoff_failures": {x: h[0].engine.debug_get("handoff_failures") for x, h in legs.items()}}
+    for num, den in (("fused", "torch"), ("fused", "none"), ("torch", "none")):
+        if num in rows and den in rows:
+            ratios = [a / b for a, b in zip(rows[num], rows[den])]
+            out["%s_over_%s" % (num, den)] = {"ratios": ratios, "median": float(np.median(ratios))}
+    if graph:
+        out["graph_captures"] = {x: h[1].graph_captures for x, h in legs.items()}
+        out["graph_replays"] = {x: h[1].graph_replays for x, h in legs.items()}
+    for h in legs.values():
+        h[0].engine.close()
+    return out
+
+
+def main_wrap(a):
+    name = os.path.join(a.out, "env_wrap_bench.json")
+    res = {"pairs": a.pairs, "window_s": a.window, "policy": "376-256-256-256-34", "max_episode_steps": 1000}
+    if os.path.exists(name):                         # (the eager and the --graph run go into one file)
+        with open(name) as f:
+            res = json.load(f)
+    key = "graph" if a.graph else "eager"
+    res[key] = []
+    for n in WRAP_NS:
+        cmd = [sys.executable, os.path.abspath(__file__), "--wrap"] + a.wrap + ["--only", "%d:wrap" % n, "--pairs", str(a.pairs),
+                                                                                "--window", str(a.window)] + (["--graph"] if a.graph else [])
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=420)
+        line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+        if p.returncode != 0 or not line:
+            sys.stderr.write(p.stdout + p.stderr)
+            raise SystemExit("configuration %d:wrap failed (exit status %d)" % (n, p.returncode))
+        r = json.loads(line[-1][len("RESULT "):])
+        res[key].append(r)
+        print(json.dumps(r), flush=True)
+    os.makedirs(a.out, exist_ok=True)
+    with open(name, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main_graph(a):
     parent = a.tree is not None
     name = os.path.join(a.out, "graph_sample_bench.json")
@@ -251,7 +346,15 @@ def main():
     ap.add_argument("--noise-n", type=int, default=1024)
     ap.add_argument("--graph", action="store_true", help="only the tensor route eager against hip_graph_sample=True")
     ap.add_argument("--tree", default=None, help="with --graph: the eager leg alone from another checkout (the parent commit)")
+    ap.add_argument("--wrap", nargs="+", choices=("none", "torch", "fused"), default=None,
+                    help="only sample() alone with the reference's environment wrappers: the legs to run (with --graph: captured)")
     a = ap.parse_args()
+    if a.wrap and a.only:
+        print("RESULT " + json.dumps(run_wrap(int(a.only.split(":")[0]), a.wrap, a.graph, a.pairs, a.window)), flush=True)
+        return
+    if a.wrap:
+        main_wrap(a)
+        return
     if a.graph and a.only:
         n, metric = a.only.split(":")
         print("RESULT " + json.dumps(run_graph(int(n), metric, a.pairs, a.window, a.tree is not None)), flush=True)
