@@ -370,6 +370,7 @@ struct dsact_handle : BatchBufs {
   bool act_counter_valid = false;        // ... which has been called
   unsigned long long step_rows_calls = 0;   // dsact_step_rows_device launches
   unsigned long long env_wrap_calls = 0;    // dsact_env_wrap_step / dsact_env_wrap_reset launches
+  unsigned long long frame_pipe_calls = 0;  // dsact_frame_pipe_step / dsact_frame_pipe_reset launches
   // device-resident evaluation (dsact_act_mode_device / dsact_eval_*): the episode bookkeeping's state
   int* ev_ep = nullptr; double* ev_acc = nullptr; int* ev_len = nullptr;   // [ev_cap_n]
   double* ev_returns = nullptr; int* ev_lengths = nullptr;                 // [ev_cap_e]
@@ -5698,6 +5699,7 @@ int dsact_debug_get(const dsact_handle* h, const char* name, double* value) {
   else if (!strcmp(name, "track_reads")) *value = (double)h->track_reads;                 // dsact_track_read waits
   else if (!strcmp(name, "step_rows_calls")) *value = (double)h->step_rows_calls;         // dsact_step_rows_device launches
   else if (!strcmp(name, "env_wrap_calls")) *value = (double)h->env_wrap_calls;           // dsact_env_wrap_step / _reset launches
+  else if (!strcmp(name, "frame_pipe_calls")) *value = (double)h->frame_pipe_calls;       // dsact_frame_pipe_step / _reset launches
   else if (!strcmp(name, "act_fast")) *value = (act_fast_ok(h) || h->cnn_act) ? 1.0 : 0.0;   // dsact_act_sample serves this handle (the one-launch forward, or the enabled CNN acting path)
   else if (!strcmp(name, "cnn_act_capture")) *value = h->cnn_act_capture ? 1.0 : 0.0;   // dsact_cnn_acting_capture is on
   else if (!strcmp(name, "step_frames_calls")) *value = (double)h->step_frames_calls;    // dsact_step_frames_device launches
@@ -6385,6 +6387,75 @@ int dsact_env_wrap_reset(dsact_handle* h, int32_t n, int32_t row_floats, const f
   a.elapsed = elapsed_dev; a.mask = elapsed_dev ? mask_dev : nullptr;
   const void* ptrs[6] = {a.obs, a.shift, a.scale, a.obs_out, a.elapsed, a.mask};
   return env_wrap_launch(h, "dsact_env_wrap_reset", false, a, ptrs, 6);
+}
+
+// the reference's image pipeline behind a tensor environment's inner step / reset in one launch each (k_frame_pipe_step /
+// k_frame_pipe_reset, dsact_kernels.h): env_gym/gym_carracing_data.py:34-51 (the repeat loop, the reward
+// sum, the early stop, the stack's pop / append) and :23-32 (reset's K copies), with :63-69 (rgb2gray) in both.
+// dsact_env_wrap_*'s rules: a launch on the handle's stream, no allocation, no wait, legal under stream capture. No state is
+// kept in the handle.
+static int frame_pipe_launch(dsact_handle* h, const char* who, bool step, FramePipeArgs& a, const void* const* ptrs, int n_ptrs) {
+  if (a.n < 1 || a.K < 1 || a.P < 1)
+    return fail(h, DSACT_E_INVALID, "%s: n = %d, frame_stack = %d and slot_elems = %lld must be >= 1", who, a.n, a.K, a.P);
+  if (a.gray < 0 || a.gray > 2) return fail(h, DSACT_E_INVALID, "%s: gray = %d is not 0 (off), 1 (chw) or 2 (hwc)", who, a.gray);
+  if (a.esize != 1 && a.esize != 4) return fail(h, DSACT_E_INVALID, "%s: elem_size = %d is not 1 or 4", who, a.esize);
+  if (a.P > (1LL << 40) / a.K) return fail(h, DSACT_E_INVALID, "%s: a stack of %d x %lld elements is out of range", who, a.K, a.P);
+  HIPCHK(h, hipSetDevice(h->device));
+  for (int k = 0; k < n_ptrs; ++k)
+    if (ptrs[k] && !on_handle_gpu(h, ptrs[k])) return fail(h, DSACT_E_INVALID, "%s takes device pointers on the handle's GPU", who);
+  bool capturing = false;
+  TRY(stream_capturing(h, &capturing));
+  if (capturing && h->profiling) return fail(h, DSACT_E_STATE, "%s under stream capture while profiling", who);
+  if (!capturing) TRY(check_handoff_counted(h));
+  // a unit is 16 bytes of a slot where counts and pointers allow: with gray 4 pixels (source: 4 bytes per plane / 12 bytes per
+  // group for bytes, 16-byte accesses for fp32), without 16 bytes of the row; else one element
+  const uintptr_t dst = (uintptr_t)a.stack | (uintptr_t)a.out, src = (uintptr_t)a.raw;
+  if (a.gray) a.wide = (a.P % 4 == 0 && dst % 16 == 0 && src % (a.esize == 4 ? 16 : 4) == 0) ? 1 : 0;
+  else a.wide = ((a.P * a.esize) % 16 == 0 && (dst | src) % 16 == 0) ? 1 : 0;
+  const long long units = a.gray ? (a.wide ? a.P / 4 : a.P) : (a.wide ? a.P * a.esize / 16 : a.P);
+  // one wave per row up to 1024 units; longer rows are split like dsact_env_wrap_step's: 16 workgroups at most
+  const long long per = (units + kThreads - 1) / kThreads;
+  a.chunks = units <= 1024 ? 0 : (per > 16 ? 16 : (int)per);
+  const long long grid = a.chunks ? (long long)a.n * a.chunks : ((long long)a.n + 3) / 4;
+  if (grid > 0x7fffffffLL) return fail(h, DSACT_E_INVALID, "%s: n = %d rows of %lld units need %lld workgroups", who, a.n, units, grid);
+  if (step) TRY(launch(h, "frame_pipe_step", k_frame_pipe_step, dim3((unsigned)grid), dim3(kThreads), 0, a));
+  else TRY(launch(h, "frame_pipe_reset", k_frame_pipe_reset, dim3((unsigned)grid), dim3(kThreads), 0, a));
+  h->frame_pipe_calls++;
+  return DSACT_OK;
+}
+
+int dsact_frame_pipe_step(dsact_handle* h, int32_t n, int64_t slot_elems, int32_t frame_stack, int32_t action_repeat, int32_t j,
+                          int32_t gray, int32_t elem_size, const void* raw_dev, const float* rew_dev, const uint8_t* terminated_dev,
+                          const uint8_t* truncated_dev, void* stack_dev, float* acc_dev, int32_t* ended_at_dev, uint8_t* flags_dev,
+                          void* obs2_out, float* rew_out, uint8_t* terminated_out, uint8_t* truncated_out) {
+  if (!h) return DSACT_E_INVALID;
+  if (action_repeat < 1 || j < 0 || j >= action_repeat)
+    return fail(h, DSACT_E_INVALID, "dsact_frame_pipe_step: action_repeat = %d must be >= 1 and j = %d in [0, action_repeat)",
+                (int)action_repeat, (int)j);
+  if (!raw_dev || !rew_dev || !terminated_dev || !truncated_dev || !stack_dev || !acc_dev || !ended_at_dev || !flags_dev || !obs2_out ||
+      !rew_out || !terminated_out || !truncated_out)
+    return fail(h, DSACT_E_INVALID, "dsact_frame_pipe_step: a NULL pointer");
+  FramePipeArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n; a.P = slot_elems; a.K = frame_stack; a.R = action_repeat; a.j = j; a.gray = gray; a.esize = elem_size;
+  a.raw = (const unsigned char*)raw_dev; a.rew = rew_dev; a.term = terminated_dev; a.trunc = truncated_dev;
+  a.stack = (unsigned char*)stack_dev; a.out = (unsigned char*)obs2_out; a.acc = acc_dev; a.ended_at = ended_at_dev; a.flags = flags_dev;
+  a.rew_out = rew_out; a.term_out = terminated_out; a.trunc_out = truncated_out;
+  const void* ptrs[12] = {raw_dev, rew_dev, terminated_dev, truncated_dev, stack_dev, acc_dev, ended_at_dev, flags_dev, obs2_out, rew_out,
+                          terminated_out, truncated_out};
+  return frame_pipe_launch(h, "dsact_frame_pipe_step", true, a, ptrs, 12);
+}
+
+int dsact_frame_pipe_reset(dsact_handle* h, int32_t n, int64_t slot_elems, int32_t frame_stack, int32_t gray, int32_t elem_size,
+                           const void* raw_dev, const uint8_t* mask_dev, void* stack_dev, void* obs_out) {
+  if (!h) return DSACT_E_INVALID;
+  if (!raw_dev || !stack_dev || !obs_out) return fail(h, DSACT_E_INVALID, "dsact_frame_pipe_reset: a NULL pointer");
+  FramePipeArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n; a.P = slot_elems; a.K = frame_stack; a.R = 1; a.gray = gray; a.esize = elem_size;
+  a.raw = (const unsigned char*)raw_dev; a.mask = mask_dev; a.stack = (unsigned char*)stack_dev; a.out = (unsigned char*)obs_out;
+  const void* ptrs[4] = {raw_dev, mask_dev, stack_dev, obs_out};
+  return frame_pipe_launch(h, "dsact_frame_pipe_reset", false, a, ptrs, 4);
 }
 
 // ---- device-resident evaluation --------------------------------------------------------------------

@@ -1225,6 +1225,203 @@ __global__ void __launch_bounds__(kThreads) k_env_wrap_reset(EnvWrapArgs a) {
 }
 #endif
 
+// k_frame_pipe_step / k_frame_pipe_reset: the reference's image pipeline (env_gym/gym_carracing_data.py:23-69: rgb2gray, the
+// stack of the last img_stack frames, action_repeat inner steps per action) behind a batched tensor environment in ONE launch
+// per inner step and ONE per reset (dsact_frame_pipe_step / dsact_frame_pipe_reset, training/hip_tensor_frame_pipe.py;
+// DESIGN.md section 28). Row i owns a stack S[i][K][P] of K slots; a slot is P output elements: P pixels of fp32 with gray, P
+// elements of the row's own type (esize 1 or 4 bytes, moved as bits) without.
+//   gray   out = float( ((R*0.299 + G*0.587) + B*0.114) / 128 - 1 ) in fp64, every operation rounded on its own (__dmul_rn /
+//          __dadd_rn: never contracted); / 128 is written as * 2^-7, the same correctly rounded value for every input. gray 1:
+//          the row is three planes [3][P] (chw), gray 2: P groups of three [P][3] (hwc); elements are bytes 0..255 or fp32.
+//   step   launch j of R behind inner step j. For a row ALIVE at the start of j: j == 0 shifts S[i][k] = S[i][k+1] and writes
+//          the newest slot from the inner frame, j > 0 overwrites the newest slot (the frame of the row's last live inner step
+//          stays). At j == R-1 every row, alive or not, copies its stack to out[i]. The scalar lane: acc = r_0, then
+//          acc = __fadd_rn(acc, r_j) while alive; the step at which term | trunc is set ends the row and keeps its two flags;
+//          at j == R-1 rew_out = acc and term_out / trunc_out = the kept flags (0 for a row that did not end).
+//   alive  ended_at[i] is -1 while alive and j once the row ended at j. At j == 0 every row is alive: nobody reads the array
+//          and the scalar lane writes 0 or -1 outright. At j > 0 a thread takes `e < 0 || e == j` as alive at the start of j:
+//          the only value the scalar lane of the SAME launch can store is j (and only over -1), so either value a thread can
+//          observe means the same and no thread depends on another thread's write. The scalar lane loads e before it stores.
+//   reset  rows whose mask byte is set (mask == NULL: all) fill all K slots with f(raw[i]); every row copies its stack to out.
+// A thread owns unit q of a row across all K slots (the in-place shift of its own column needs no second buffer and no
+// barrier; what it copies to `out` it wrote itself or nobody writes in this launch). Launch shapes are k_env_wrap_step's:
+// chunks == 0 one wave per row and four rows per workgroup, chunks > 0 workgroup (i, c) of a grid n * chunks. `wide`: a unit
+// is 16 bytes of a slot (4 gray pixels: 4 bytes / one float4 per plane for chw, 12 bytes / three float4 for hwc), else one
+// element. Plain vector loads and stores only; every access is inside row i < n of its array.
+struct FramePipeArgs {
+  const unsigned char* raw; const float* rew; const unsigned char* term; const unsigned char* trunc; const unsigned char* mask;
+  unsigned char* stack; unsigned char* out;
+  float* acc; int* ended_at; unsigned char* flags;
+  float* rew_out; unsigned char* term_out; unsigned char* trunc_out;
+  long long P;
+  int n, K, R, j, gray, esize, wide, chunks;
+};
+#ifndef DSACT_FAMILY_UNIT   // plain kernels: compiled in dsact_api.hip only (dsact_tu.h)
+__device__ __forceinline__ float frame_pipe_gray(double r, double g, double b) {
+  const double s = __dadd_rn(__dadd_rn(__dmul_rn(r, 0.299), __dmul_rn(g, 0.587)), __dmul_rn(b, 0.114));
+  return __double2float_rn(__dadd_rn(__dmul_rn(s, 0.0078125), -1.0));
+}
+// the newest slot's unit q of a row: Gray* read the row's three colours, Copy moves bits
+struct FramePipeCopy16 { const uint4* s; __device__ uint4 operator()(long long q) const { return s[q]; } };
+struct FramePipeCopy4 { const unsigned int* s; __device__ unsigned int operator()(long long q) const { return s[q]; } };
+struct FramePipeCopy1 { const unsigned char* s; __device__ unsigned char operator()(long long q) const { return s[q]; } };
+struct FramePipeGray1 {   // one pixel; sr / sg / sb: the pixel's colours are at [q * step]
+  const unsigned char* sr; const unsigned char* sg; const unsigned char* sb; int step, f32;
+  __device__ float operator()(long long q) const {
+    if (f32) {
+      const float* r = reinterpret_cast<const float*>(sr); const float* g = reinterpret_cast<const float*>(sg);
+      const float* b = reinterpret_cast<const float*>(sb);
+      return frame_pipe_gray((double)r[q * step], (double)g[q * step], (double)b[q * step]);
+    }
+    return frame_pipe_gray((double)sr[q * step], (double)sg[q * step], (double)sb[q * step]);
+  }
+};
+struct FramePipeGray4 {   // four pixels 4q .. 4q+3
+  const unsigned char* s; long long P; int hwc, f32;
+  __device__ float4 operator()(long long q) const {
+    float c[12];   // [pixel][colour]
+    if (f32) {
+      const float4* s4 = reinterpret_cast<const float4*>(s);
+      if (hwc) {
+        const float4 u = s4[3 * q], v = s4[3 * q + 1], w = s4[3 * q + 2];
+        c[0] = u.x; c[1] = u.y; c[2] = u.z; c[3] = u.w; c[4] = v.x; c[5] = v.y; c[6] = v.z; c[7] = v.w;
+        c[8] = w.x; c[9] = w.y; c[10] = w.z; c[11] = w.w;
+      } else {
+        const long long plane = P / 4;
+        const float4 r = s4[q], g = s4[plane + q], b = s4[2 * plane + q];
+        c[0] = r.x; c[1] = g.x; c[2] = b.x; c[3] = r.y; c[4] = g.y; c[5] = b.y; c[6] = r.z; c[7] = g.z; c[8] = b.z;
+        c[9] = r.w; c[10] = g.w; c[11] = b.w;
+      }
+    } else {
+      const unsigned int* s1 = reinterpret_cast<const unsigned int*>(s);
+      if (hwc) {
+        const unsigned int u = s1[3 * q], v = s1[3 * q + 1], w = s1[3 * q + 2];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          c[e] = (float)((u >> (8 * e)) & 255u); c[4 + e] = (float)((v >> (8 * e)) & 255u); c[8 + e] = (float)((w >> (8 * e)) & 255u);
+        }
+      } else {
+        const long long plane = P / 4;
+        const unsigned int r = s1[q], g = s1[plane + q], b = s1[2 * plane + q];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          c[3 * e] = (float)((r >> (8 * e)) & 255u); c[3 * e + 1] = (float)((g >> (8 * e)) & 255u);
+          c[3 * e + 2] = (float)((b >> (8 * e)) & 255u);
+        }
+      }
+    }
+    float4 o;
+    o.x = frame_pipe_gray((double)c[0], (double)c[1], (double)c[2]); o.y = frame_pipe_gray((double)c[3], (double)c[4], (double)c[5]);
+    o.z = frame_pipe_gray((double)c[6], (double)c[7], (double)c[8]); o.w = frame_pipe_gray((double)c[9], (double)c[10], (double)c[11]);
+    return o;
+  }
+};
+// one row's units first, first + stride, ... of a step (alive: shift where `shift`, then the newest slot from f; `last`: copy
+// the stack out) or, with `reset`, of a reset (alive = restarted: every slot from f; the stack is always copied out)
+template <typename U, typename F>
+__device__ __forceinline__ void frame_pipe_cols(U* S, U* out, long long units, int K, long long first, long long stride, bool alive,
+                                                bool shift, bool last, bool reset, F f) {
+  for (long long q = first; q < units; q += stride) {
+    if (reset) {
+      if (alive) {
+        const U v = f(q);
+        for (int k = 0; k < K; ++k) { S[(long long)k * units + q] = v; out[(long long)k * units + q] = v; }
+      } else {
+        for (int k = 0; k < K; ++k) out[(long long)k * units + q] = S[(long long)k * units + q];
+      }
+      continue;
+    }
+    if (alive && shift) {
+      for (int k = 0; k + 1 < K; ++k) {
+        const U v = S[(long long)(k + 1) * units + q];
+        S[(long long)k * units + q] = v;
+        if (last) out[(long long)k * units + q] = v;
+      }
+    } else if (last) {
+      for (int k = 0; k + 1 < K; ++k) out[(long long)k * units + q] = S[(long long)k * units + q];
+    }
+    const long long top = (long long)(K - 1) * units + q;
+    if (alive) {
+      const U v = f(q);
+      S[top] = v;
+      if (last) out[top] = v;
+    } else if (last) {
+      out[top] = S[top];
+    }
+  }
+}
+__device__ __forceinline__ void frame_pipe_row(const FramePipeArgs& a, long long i, long long first, long long stride, bool alive,
+                                               bool shift, bool last, bool reset) {
+  const size_t osize = a.gray ? 4 : (size_t)a.esize;
+  const size_t in_row = (a.gray ? 3 : 1) * (size_t)a.P * (size_t)a.esize, slot_row = (size_t)a.K * (size_t)a.P * osize;
+  const unsigned char* s = a.raw + (size_t)i * in_row;
+  unsigned char* S = a.stack + (size_t)i * slot_row;
+  unsigned char* o = a.out + (size_t)i * slot_row;
+  if (a.gray) {
+    if (a.wide) {
+      FramePipeGray4 f{s, a.P, a.gray == 2, a.esize == 4};
+      frame_pipe_cols(reinterpret_cast<float4*>(S), reinterpret_cast<float4*>(o), a.P / 4, a.K, first, stride, alive, shift, last, reset, f);
+    } else {
+      const size_t e = (size_t)a.esize;
+      FramePipeGray1 f{s, a.gray == 2 ? s + e : s + (size_t)a.P * e, a.gray == 2 ? s + 2 * e : s + 2 * (size_t)a.P * e,
+                       a.gray == 2 ? 3 : 1, a.esize == 4};
+      frame_pipe_cols(reinterpret_cast<float*>(S), reinterpret_cast<float*>(o), a.P, a.K, first, stride, alive, shift, last, reset, f);
+    }
+  } else if (a.wide) {
+    FramePipeCopy16 f{reinterpret_cast<const uint4*>(s)};
+    frame_pipe_cols(reinterpret_cast<uint4*>(S), reinterpret_cast<uint4*>(o), a.P * (long long)a.esize / 16, a.K, first, stride, alive, shift,
+                    last, reset, f);
+  } else if (a.esize == 4) {
+    FramePipeCopy4 f{reinterpret_cast<const unsigned int*>(s)};
+    frame_pipe_cols(reinterpret_cast<unsigned int*>(S), reinterpret_cast<unsigned int*>(o), a.P, a.K, first, stride, alive, shift, last, reset, f);
+  } else {
+    FramePipeCopy1 f{s};
+    frame_pipe_cols(S, o, a.P, a.K, first, stride, alive, shift, last, reset, f);
+  }
+}
+// env_wrap_lane's launch shapes: (row, first unit, unit stride, whether this lane does the row's scalars); false: no row
+__device__ __forceinline__ bool frame_pipe_lane(const FramePipeArgs& a, long long* i, long long* first, long long* stride, bool* scalars) {
+  if (a.chunks == 0) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    *i = (long long)blockIdx.x * 4 + wave; *first = lane; *stride = 64; *scalars = lane == 0;
+  } else {
+    const int c = (int)(blockIdx.x % (unsigned)a.chunks);
+    *i = (long long)(blockIdx.x / (unsigned)a.chunks);
+    *first = (long long)c * kThreads + (int)threadIdx.x; *stride = (long long)a.chunks * kThreads;
+    *scalars = c == 0 && threadIdx.x == 0;
+  }
+  return *i < a.n;
+}
+__global__ void __launch_bounds__(kThreads) k_frame_pipe_step(FramePipeArgs a) {
+  long long i, first, stride; bool scalars;
+  if (!frame_pipe_lane(a, &i, &first, &stride, &scalars)) return;
+  const int e = a.j > 0 ? a.ended_at[i] : -1;          // (loaded before the scalar lane's store below)
+  const bool alive = e < 0 || e == a.j, last = a.j == a.R - 1;
+  if (!alive && !last) return;                         // an ended row before the last launch: nothing to move, no scalar to write
+  frame_pipe_row(a, i, first, stride, alive, a.j == 0, last, false);
+  if (!scalars) return;
+  const float r = a.rew[i];
+  const unsigned char t = a.term[i], u = a.trunc[i];   // (all loaded: no load behind a branch)
+  float acc = a.j > 0 ? a.acc[i] : 0.0f;
+  unsigned char fl = a.j > 0 ? a.flags[i] : (unsigned char)0;
+  if (e < 0) {                                           // alive and not yet ended: this step counts
+    acc = a.j == 0 ? r : __fadd_rn(acc, r);
+    const bool ends = (t | u) != 0;
+    if (ends) fl = (unsigned char)((t != 0 ? 1 : 0) | (u != 0 ? 2 : 0));
+    if (a.j == 0) a.ended_at[i] = ends ? 0 : -1;
+    else if (ends) a.ended_at[i] = a.j;
+    a.acc[i] = acc; a.flags[i] = fl;
+  }
+  if (last) { a.rew_out[i] = acc; a.term_out[i] = fl & 1; a.trunc_out[i] = (fl >> 1) & 1; }
+}
+__global__ void __launch_bounds__(kThreads) k_frame_pipe_reset(FramePipeArgs a) {
+  long long i, first, stride; bool scalars;
+  if (!frame_pipe_lane(a, &i, &first, &stride, &scalars)) return;
+  const bool restarted = !a.mask || a.mask[i] != 0;
+  frame_pipe_row(a, i, first, stride, restarted, false, true, true);
+}
+#endif
+
 // ---------------------------------------------------------------------------------------------
 // k_tiles: C[m][n] (+epilogue) = sum_k P(m,k) * Q(n,k) on 32x32 tiles, BK = 64
 //   operand storage: KC  element (row,k) at base[row*ld + k]   (k contiguous)

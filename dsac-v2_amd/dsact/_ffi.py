@@ -167,6 +167,8 @@ SYMBOLS = [
     ("dsact_eval_trace_read", C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P]),
     ("dsact_env_wrap_step", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("dsact_env_wrap_reset", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    ("dsact_frame_pipe_step", C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("dsact_frame_pipe_reset", C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
 ]
 
 _lib = None

@@ -948,6 +948,59 @@ class DsactEngine:
         if rc != 0:
             self._chk(rc)
 
+    def _frame_pipe_rows(self, n, raw, stack, out, frame_stack, gray, out_name):
+        """(slot_elems, gray flag, elem_size, the three addresses) of a frame-pipe call: raw[n, ...] uint8 or float32 (with gray
+        [n, 3, H, W] for "chw", [n, H, W, 3] for "hwc"), stack / out [n, frame_stack * slot] of the slot's dtype"""
+        torch = self.torch
+        n, K = int(n), int(frame_stack)
+        flag = {None: 0, "chw": 1, "hwc": 2}.get(gray, -1)
+        shape = tuple(raw.shape) if hasattr(raw, "shape") else ()
+        pr = self._dev(raw, shape, (torch.uint8, torch.float32), "raw")
+        if len(shape) < 2 or shape[0] != n:
+            raise ValueError("raw must have shape [%d, ...] (got %r)" % (n, shape))
+        elems = int(raw[0].numel())
+        if flag > 0:
+            if len(shape) != 4 or shape[1 if flag == 1 else 3] != 3:
+                raise ValueError("raw must be 3-channel %s frames (got %r)" % (gray, shape))
+            elems //= 3
+        odt = (torch.float32,) if flag > 0 else (raw.dtype,)
+        want = (n, max(K, 0) * elems)
+        ps = self._dev(stack.view(n, -1) if hasattr(stack, "view") else stack, want, odt, "stack")
+        po = self._dev(out.view(n, -1) if hasattr(out, "view") else out, want, odt, out_name)
+        return elems, flag, int(raw.element_size()), pr, ps, po
+
+    def frame_pipe_step(self, n, j, action_repeat, frame_stack, gray, raw, rew, terminated, truncated, stack, acc, ended_at, flags,
+                        obs2_out, rew_out, terminated_out, truncated_out):
+        """dsact_frame_pipe_step: launch j of action_repeat of the reference's image pipeline behind a tensor environment's inner
+        step -- gray (None, "chw", "hwc") of raw[n, ...], the stack[n, frame_stack * slot] shifted at
+        j == 0 and its newest slot overwritten while the row is alive, the reward summed into acc[n], the ending step's flags
+        kept in flags[n] / ended_at[n] (int32), and at j == action_repeat - 1 the four outputs written. Contiguous tensors on
+        this engine's GPU. Asynchronous; legal under stream capture."""
+        torch = self.torch
+        f32, flag, i32 = (torch.float32,), (torch.bool, torch.uint8), (torch.int32,)
+        n = int(n)
+        elems, g, esize, pr, ps, po = self._frame_pipe_rows(n, raw, stack, obs2_out, frame_stack, gray, "obs2_out")
+        rc = self._lib.dsact_frame_pipe_step(
+            self._h, n, elems, int(frame_stack), int(action_repeat), int(j), g, esize, pr, self._dev(rew, (n,), f32, "rew"),
+            self._dev(terminated, (n,), flag, "terminated"), self._dev(truncated, (n,), flag, "truncated"), ps,
+            self._dev(acc, (n,), f32, "acc"), self._dev(ended_at, (n,), i32, "ended_at"), self._dev(flags, (n,), (torch.uint8,), "flags"),
+            po, self._dev(rew_out, (n,), f32, "rew_out"), self._dev(terminated_out, (n,), flag, "terminated_out"),
+            self._dev(truncated_out, (n,), flag, "truncated_out"))
+        if rc != 0:
+            self._chk(rc)
+
+    def frame_pipe_reset(self, n, frame_stack, gray, raw, mask, stack, obs_out):
+        """dsact_frame_pipe_reset: rows whose bool / uint8 mask[n] is set (None: every row) fill all frame_stack slots of
+        stack[n, frame_stack * slot] from (the gray of) raw[n, ...]; every row's stack is then copied to obs_out. Contiguous
+        tensors on this engine's GPU. Asynchronous; legal under stream capture."""
+        torch = self.torch
+        n = int(n)
+        elems, g, esize, pr, ps, po = self._frame_pipe_rows(n, raw, stack, obs_out, frame_stack, gray, "obs_out")
+        pm = None if mask is None else self._dev(mask, (n,), (torch.bool, torch.uint8), "mask")
+        rc = self._lib.dsact_frame_pipe_reset(self._h, n, elems, int(frame_stack), g, esize, pr, pm, ps, po)
+        if rc != 0:
+            self._chk(rc)
+
     def _frames(self, t, n, name):
         """(address, is_uint8) of the observation rows of a device-resident call: [n, O] float32, and on a CNN engine with cnn_act
          also [n, C, H, W] rows and uint8 tensors of either shape -- byte frames, codes into the coded

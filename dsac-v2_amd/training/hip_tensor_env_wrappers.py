@@ -143,8 +143,11 @@ class WrappedTensorEnv:
     # ---- routes --------------------------------------------------------------------------------------------------------------
     def bind_engine(self, engine):
         """the DsactEngine whose stream the environment's ops run on: from here on step and reset are one launch each (None: the
-        torch route again)"""
+        torch route again). An inner environment that has `bind_engine` (training/hip_tensor_frame_pipe.py: the pipeline sits inside
+        this wrapper) is handed the engine too."""
         self._engine = engine
+        if callable(getattr(self.env, "bind_engine", None)):
+            self.env.bind_engine(engine)
 
     @property
     def fused(self):

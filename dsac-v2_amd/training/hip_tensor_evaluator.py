@@ -93,6 +93,12 @@ constructor puts the environment it resolved through training/hip_tensor_env_wra
 the shift stays and returns sum the shifted reward). Refused (ValueError): a non-bool value, and True with none of the four set.
 The per-engine set-up hands the engine to an environment that has `bind_engine`; a wrapped environment's `max_episode_steps` is
 eval_save's default step bound.
+
+The reference's image pipeline (`hip_frame_pipe=True`; default off): the constructor puts the environment
+through training/hip_tensor_frame_pipe.frame_pipe_tensor_env with `frame_gray`, `frame_stack` and `action_repeat` from the flat
+argument dict, before hip_env_wrap. The evaluator KEEPS the repeat (the reference's Evaluator drops only the generic repeat_num
+wrapper; CarRacing's built-in repeat stays): lengths count outer steps, returns sum the summed rewards, eval_save records the
+stacks. Refused (ValueError): a non-bool value, and True with none of the three set.
 """
 import os
 import warnings
@@ -104,6 +110,7 @@ from training.hip_acting_common import (EvalEpisodeCounter, engine_stream, eval_
                                         on_stream, require_graph_cnn_pair, require_graph_device, require_tensor_engine, tensor_limits,
                                         write_eval_episode)
 from training.hip_tensor_env_wrappers import env_wrap_kwargs, wrap_tensor_env
+from training.hip_tensor_frame_pipe import frame_pipe_kwargs, frame_pipe_tensor_env
 
 __all__ = ["HipTensorEnvEvaluator"]
 
@@ -134,6 +141,9 @@ class HipTensorEnvEvaluator:
         if env is None:
             from plugin import create_env
             env = create_env(**kwargs)
+        pipe = frame_pipe_kwargs(kwargs, "hip_tensor_env_evaluator")   # hip_frame_pipe; None: off, the default
+        if pipe is not None:
+            env = frame_pipe_tensor_env(env, **pipe)                # (inside hip_env_wrap, as the reference's Env sits inside wrapping_env)
         wrap = env_wrap_kwargs(kwargs, "hip_tensor_env_evaluator")   # hip_env_wrap; None: off, the default
         if wrap is not None:
             env = wrap_tensor_env(env, **wrap)

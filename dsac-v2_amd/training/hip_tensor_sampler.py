@@ -88,6 +88,12 @@ constructor puts the environment it resolved through training/hip_tensor_env_wra
 once at the ring write. Refused (ValueError): a non-bool value, and True with none of the four set. _setup hands the engine to an
 environment that has `bind_engine` (a wrapped one: its step and reset are then one launch each).
 
+The reference's image pipeline (`hip_frame_pipe=True`; default off): the constructor puts the environment
+through training/hip_tensor_frame_pipe.frame_pipe_tensor_env with `frame_gray` ("chw" / "hwc"), `frame_stack` and `action_repeat`
+from the flat argument dict, BEFORE hip_env_wrap (the pipeline sits inside the wrappers). A batch row is then one held action: the
+stacked observation, the reward summed over the repeat. Refused (ValueError): a non-bool value, and True with none of the three
+set. Bound like a wrapped environment: one launch behind every inner step and one behind a reset.
+
 sample() returns (DeviceSampleBatch, {sampler time}). The time is the HOST time of issuing the work. The batch's tensors are the
 sampler's own preallocated [S, .] buffers: they are valid until the next sample() call (add_batch consumes them in stream
 order before that).
@@ -104,6 +110,7 @@ from training.hip_acting_common import (check_noise_dim, engine_stream, explore_
 from training.hip_replay_buffer import act_seed_from
 from training.hip_sampler import SAMPLER_TIME_KEY
 from training.hip_tensor_env_wrappers import env_wrap_kwargs, wrap_tensor_env
+from training.hip_tensor_frame_pipe import frame_pipe_kwargs, frame_pipe_tensor_env
 
 __all__ = ["HipTensorEnvSampler", "DeviceSampleBatch", "act_noise_words", "act_noise_reference", "explore_noise_words",
            "explore_noise_reference", "aggregate_episode_rows", "EPISODE_TB_KEYS"]
@@ -283,6 +290,9 @@ class HipTensorEnvSampler:
         if env is None:
             from plugin import create_env
             env = create_env(**kwargs)
+        pipe = frame_pipe_kwargs(kwargs, "hip_tensor_env_sampler")   # hip_frame_pipe; None: off, the default
+        if pipe is not None:
+            env = frame_pipe_tensor_env(env, **pipe)                # (inside hip_env_wrap, as the reference's Env sits inside wrapping_env)
         wrap = env_wrap_kwargs(kwargs, "hip_tensor_env_sampler")   # hip_env_wrap; None: off, the default
         if wrap is not None:
             env = wrap_tensor_env(env, **wrap)

@@ -900,6 +900,40 @@ int dsact_env_wrap_step(dsact_handle* h, int32_t n, int32_t row_floats, const fl
 int dsact_env_wrap_reset(dsact_handle* h, int32_t n, int32_t row_floats, const float* obs_dev, const uint8_t* mask_dev,
                          const float* obs_shift_dev, const float* obs_scale_dev, int32_t* elapsed_dev, float* obs_out);
 
+/* ---- The reference's image pipeline on tensor environments (training/hip_tensor_frame_pipe.py) ----------
+ * env_gym/gym_carracing_data.py feeds its networks the last img_stack gray frames and holds every action for action_repeat
+ * simulator steps. For a batched tensor environment that is ONE launch behind each inner step and ONE behind a reset. The
+ * handle keeps NO state: the stack, the scratch and the outputs are the caller's device arrays.
+ * Row i owns a stack stack_dev[i][frame_stack][slot_elems]; a slot holds slot_elems output elements:
+ *   gray == 0   the inner row raw_dev[i][slot_elems] in its own type, elem_size 1 or 4 bytes, moved as bits;
+ *   gray == 1   raw_dev[i][3][slot_elems] (chw), gray == 2: raw_dev[i][slot_elems][3] (hwc); elements are bytes holding 0..255
+ *               (elem_size 1) or fp32 (elem_size 4); a slot is slot_elems fp32 pixels
+ *               float( ((R*0.299 + G*0.587) + B*0.114) / 128 - 1 ), computed in fp64 with every operation rounded on its own
+ *               (gym_carracing_data.py:63-69).
+ *   dsact_frame_pipe_step   launch j of action_repeat, issued behind inner step j (gym_carracing_data.py:34-51). A row is
+ *                           alive until an inner step sets terminated | truncated for it. For a row alive at the start of j:
+ *                           j == 0 shifts the stack by one slot and writes the newest slot from raw_dev, j > 0 overwrites the
+ *                           newest slot; acc = rew (j == 0) or acc + rew, one rounded fp32 add; the step that ends the row
+ *                           keeps its two flags and sets ended_at[i] = j (ended_at is -1 while alive; j == 0 writes it
+ *                           outright, so the three scratch arrays acc_dev[n] / ended_at_dev[n] / flags_dev[n] need no
+ *                           initialisation). At j == action_repeat - 1 every row copies its stack to obs2_out and
+ *                           rew_out / terminated_out / truncated_out (0 or 1) are written. No pointer may be NULL.
+ *   dsact_frame_pipe_reset  rows whose mask byte is non-zero (mask_dev == NULL: every row) fill all frame_stack slots from
+ *                           raw_dev[i] (gym_carracing_data.py:23-32); every row then copies its stack to obs_out.
+ * DSACT_E_INVALID with a message and no launch: n < 1, frame_stack < 1, slot_elems < 1, action_repeat < 1, j outside
+ * [0, action_repeat), a NULL pointer other than mask_dev, gray outside {0, 1, 2}, elem_size outside {1, 4}, a pointer off the
+ * handle's GPU. Both follow dsact_env_wrap_step's rules: ASYNCHRONOUS on the handle's stream; legal under stream capture (no
+ * allocation, no wait; DSACT_E_STATE while profiling). One wave per row and four rows per workgroup, rows above 1024 access
+ * units split over up to 16 workgroups; a unit is 16 bytes of a slot where the element counts and the pointers' alignment
+ * allow, one element otherwise. Any handle.
+ * dsact_debug_get: "frame_pipe_calls" (launches of either entry point). */
+int dsact_frame_pipe_step(dsact_handle* h, int32_t n, int64_t slot_elems, int32_t frame_stack, int32_t action_repeat, int32_t j,
+                          int32_t gray, int32_t elem_size, const void* raw_dev, const float* rew_dev, const uint8_t* terminated_dev,
+                          const uint8_t* truncated_dev, void* stack_dev, float* acc_dev, int32_t* ended_at_dev, uint8_t* flags_dev,
+                          void* obs2_out, float* rew_out, uint8_t* terminated_out, uint8_t* truncated_out);
+int dsact_frame_pipe_reset(dsact_handle* h, int32_t n, int64_t slot_elems, int32_t frame_stack, int32_t gray, int32_t elem_size,
+                           const void* raw_dev, const uint8_t* mask_dev, void* stack_dev, void* obs_out);
+
 #ifdef __cplusplus
 }
 #endif

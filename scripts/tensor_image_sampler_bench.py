@@ -26,7 +26,18 @@ Writes DIR/tensor_image_sampler_bench.json and prints it. The library must have 
       HipOffSerialTrainer at sample_interval 1 / 8). Each configuration runs in a fresh child process under its own
       `timeout -k 10`; the first child that fails ends the run. One warm-up per leg (eager call, capture, replays), then `pairs`
       alternating rounds of an eager and a captured window, the stream drained at each window's end. Writes
-      DIR/graph_image_bench.json; nothing else is run."""
+      DIR/graph_image_bench.json; nothing else is run.
+
+  python scripts/tensor_image_sampler_bench.py --pipe [--graph] [--out profiles] [--pairs 3] [--window 0.6]
+      the reference's image pipeline of DESIGN.md section 28 (training/hip_tensor_frame_pipe.py): tests/envs/synth_tensor_rgb.py
+      renders (3, 84, 84) uint8 RGB, hip_frame_pipe=True turns it into the (4, 84, 84) float32 gray stack with action_repeat 4
+      for a type_1 policy. Two legs on twin handles: `torch` (the wrapper's torch route, use_fused = False) and `fused` (one
+      launch behind every inner step and one behind the reset), per N in 64, 256, 1024, issued eagerly and with
+      hip_graph_sample=True (--graph: the captured mode only). The metric is sample() alone, one lockstep step per call:
+      OUTER environment steps / s and the host's microseconds per lockstep step. `frame_pipe_calls_per_step` is read from the
+      debug counter: action_repeat + 1 on the fused leg, 0 on the torch leg. Each configuration runs in a fresh child process
+      under its own `timeout -k 10`; the first child that fails ends the run. Writes DIR/frame_pipe_bench.json; nothing else is
+      run."""
 import argparse
 import json
 import os
@@ -203,6 +214,86 @@ def main_graph(a):
         json.dump(res, f, indent=1)
 
 
+PIPE_NS = [64, 256, 1024]
+PIPE_SHAPE, PIPE_A, PIPE_K, PIPE_R = (4, 84, 84), 2, 4, 4
+
+
+def _pipe_leg(leg, N, graph):
+    """leg: "torch" | "fused" -- the same wrapped environment on either route of training/hip_tensor_frame_pipe.py"""
+    import plugin
+    from synth_tensor_rgb import SynthTensorRgb
+
+    kw = cnn_kwargs(PIPE_SHAPE, PIPE_A, "type_1", B, seed=SEED, sample_batch_size=N, buffer_max_size=max(CAP, 2 * N),
+                    buffer_warm_size=max(B, N), strict_rng=False, hip_cnn_act=True)
+    torch.manual_seed(SEED)
+    np.random.seed(SEED)
+    alg = plugin.create_alg(**kw)
+    env = SynthTensorRgb(N, device="cuda", height=84, width=84, layout="chw", frames="uint8", act_dim=PIPE_A, act_limit=1.0)
+    more = {"hip_graph_sample": True} if graph else {}
+    smp = plugin.create_sampler(sampler_name="hip_tensor_env_sampler", env=env, hip_frame_pipe=True, frame_gray="chw",
+                                frame_stack=PIPE_K, action_repeat=PIPE_R, **dict(kw, **more))
+    smp.networks = alg.networks
+    if leg == "torch":
+        smp.env.use_fused = False
+    return alg, smp, None
+
+
+def run_pipe(N, mode, pairs, window):
+    graph = mode == "graph"
+    legs = {leg: _pipe_leg(leg, N, graph) for leg in ("torch", "fused")}
+    counts, calls = {}, {}
+    for leg, h in legs.items():                      # warm-up (eager call, capture, replays); its rate sizes the windows
+        dt = _window(*h, 4)
+        eng = h[0].engine
+        before = eng.debug_get("frame_pipe_calls")
+        dt = _window(*h, 4)
+        # (a replayed graph makes no library call: the count is taken from the eager mode, where every launch is one)
+        calls[leg] = None if graph else (eng.debug_get("frame_pipe_calls") - before) / 4.0
+        counts[leg] = max(4, int(round(window / (dt / 4))))
+    rows = {leg: [] for leg in legs}
+    for _ in range(pairs):
+        for leg, h in legs.items():
+            dt = _window(*h, counts[leg])
+            rows[leg].append(counts[leg] * N / dt)
+    ratios = [f / t for f, t in zip(rows["fused"], rows["torch"])]
+    out = {"N": N, "mode": mode, "unit": "outer_env_steps_per_s", "window_counts": counts, "rows": rows,
+           "median": {x: float(np.median(v)) for x, v in rows.items()},
+           "spread": {x: (max(v) - min(v)) / float(np.median(v)) for x, v in rows.items()},
+           "us_per_step": {x: 1e6 * N / float(np.median(v)) for x, v in rows.items()},
+           "ratio": "fused_over_torch", "ratios": ratios, "ratio_median": float(np.median(ratios)),
+           "frame_pipe_calls_per_step": calls, "fused": {x: bool(h[1].env.fused) for x, h in legs.items()},
+           "graph_replays": {x: h[1].graph_replays for x, h in legs.items()},
+           "act_dev_syncs": {x: h[0].engine.debug_get("act_dev_syncs") for x, h in legs.items()},
+           "handoff_failures": {x: h[0].engine.debug_get("handoff_failures") for x, h in legs.items()}}
+    for h in legs.values():
+        h[0].engine.close()
+    return out
+
+
+def main_pipe(a):
+    res = {"pairs": a.pairs, "window_s": a.window, "policy": "type_1 4x84x84, act 2", "batch": B,
+           "pipeline": "uint8 RGB (3, 84, 84) -> gray, frame_stack %d, action_repeat %d" % (PIPE_K, PIPE_R),
+           "legs": {"torch": "FramePipeTensorEnv on its torch route", "fused": "one launch per inner step and one per reset"},
+           "configs": []}
+    for n in PIPE_NS:
+        for mode in (("graph",) if a.graph else ("eager", "graph")):
+            what = "%d:%s" % (n, mode)
+            # every GPU step under a time limit of its own; a child that fails ends the run: nothing more is started
+            cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--pipe", "--only", what,
+                   "--pairs", str(a.pairs), "--window", str(a.window)]
+            p = subprocess.run(cmd, capture_output=True, text=True)
+            line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+            if p.returncode != 0 or not line:
+                sys.stderr.write(p.stdout + p.stderr)
+                raise SystemExit("configuration %s failed (exit status %d)" % (what, p.returncode))
+            r = json.loads(line[-1][len("RESULT "):])
+            res["configs"].append(r)
+            print(json.dumps(r), flush=True)
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "frame_pipe_bench.json"), "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def run(N, metric, pairs, window):
     trainer = metric == "trainer"
     unit = K if trainer else 1
@@ -241,7 +332,15 @@ def main():
     ap.add_argument("--only", default="", help="N:metric -- one configuration, in this process")
     ap.add_argument("--limit", type=int, default=240, help="seconds a configuration's child process may take")
     ap.add_argument("--graph", action="store_true", help="only the tensor sampler eager against hip_graph_sample=True")
+    ap.add_argument("--pipe", action="store_true", help="only the frame pipeline: its torch route against its fused route")
     a = ap.parse_args()
+    if a.pipe and a.only:
+        n, mode = a.only.split(":")
+        print("RESULT " + json.dumps(run_pipe(int(n), mode, a.pairs, a.window)), flush=True)
+        return
+    if a.pipe:
+        main_pipe(a)
+        return
     if a.graph and a.only:
         n, frames, metric = a.only.split(":")
         print("RESULT " + json.dumps(run_graph(int(n), frames, metric, a.pairs, a.window)), flush=True)
