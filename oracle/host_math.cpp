@@ -7,6 +7,9 @@ extern "C" {
 void hm_gelu(const float* z, int n, float* h, float* g) {
   for (int i = 0; i < n; ++i) dsact::gelu_fwd_grad(z[i], h[i], g[i]);
 }
+void hm_act(int act, const float* z, int n, float* h, float* g) {   // every hidden activation (ACT_*) and its derivative
+  for (int i = 0; i < n; ++i) dsact::act_fwd_grad(act, z[i], h[i], g[i]);
+}
 void hm_softplus(const float* x, int n, float* y, float* dy) {
   for (int i = 0; i < n; ++i) { y[i] = dsact::softplus(x[i]); dy[i] = dsact::softplus_grad(x[i]); }
 }
